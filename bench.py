@@ -8,8 +8,13 @@ HBM, per-GPU batch 65,536 items (throughput shape; the config's B=64 latency is 
 beside it): encoder MLP -> fused HIP L-level quantize -> decoder MLP -> losses -> backward
 (HIP quantize VJP) -> RCCL gradient all-reduce (N>1) -> AdamW.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--no-cpu-baseline] [--no-extras]
-                  [--no-pmc]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR]
+  python bench.py --full [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline] [--no-extras] [--no-pmc] ...
+
+A plain run sets up, warms up, times the K steps and prints the JSON line (headline items/s, ms_per_step);
+--dump-outputs DIR also writes what the last timed step returned as DIR/<name>.npy. Everything below that
+is not the headline figure (kernel statistics and rooflines, PMC traffic, the exact-fp32 step, the decoder
+lines, the secondary rows, the trainers, the CPU baselines) runs only with --full.
 
 N>1 is launched by torch.distributed.run (one process per GPU); every rank processes its own
 disjoint 65,536-item shard ("weak" scaling) and rank 0 prints ONE JSON line.
@@ -18,8 +23,8 @@ Matmul precision follows the reference: it sets torch.set_float32_matmul_precisi
 import (modules/rqvae.py:19), so the MLP matmuls run on the split-bf16 GEMM (rq_gemm_bf16x3);
 the same step at 'highest' (exact fp32) is reported beside it (exact_fp32_highest).
 
-The timed region carries no instrumentation; kernel statistics come from an untimed pass of 5 more
-steps of the same loop with HIP events on the launching stream.
+With --full: the timed region carries no instrumentation; kernel statistics come from an untimed pass of
+5 more steps of the same loop with HIP events on the launching stream.
 roofline: the dominant kernel — the split-bf16 GEMM at its largest-time launch shape (fp32-matmul
 FLOPs 2MNK / mean device time, peak = bf16 dense MFMA / 3 products); roofline_quantize: the fused quantize forward
 (rq_quantize_fwd), algorithmic FLOPs 2*K*D*L per item, peak = fp32 MFMA 157.3
@@ -73,6 +78,12 @@ def parse():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=65536, help="items per GPU per step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0) as DIR/<name>.npy, float32")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: kernel statistics and rooflines, PMC "
+                         "traffic, the exact-fp32 step, the decoder lines, secondary rows, trainers, CPU baselines "
+                         "(the --no-* switches below trim this set)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 PMC traffic passes")
@@ -106,6 +117,24 @@ def build_model(device, seed=0):
             cb = res[l * CFG["K"]:(l + 1) * CFG["K"]].clone()
             layer.embedding.weight.copy_(cb)
     return m
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, out):
+    """What one step of the timed path returned (the RqVaeComputedLosses fields), each as
+    out_dir/<field>.npy in float32. The arrays share a 64 MB budget: one that exceeds its share is
+    written as a fixed, seeded sample of its flattened elements (ascending indices, seed 0)."""
+    os.makedirs(out_dir, exist_ok=True)
+    fields = out._asdict()
+    cap = DUMP_BUDGET_BYTES // (4 * len(fields))
+    for name, t in fields.items():
+        a = t.detach().to(torch.float32).cpu().numpy()
+        if a.size > cap:
+            idx = np.sort(np.random.Generator(np.random.PCG64(0)).choice(a.size, size=cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def time_region(fn, steps, warmup, sync_all):
@@ -366,18 +395,15 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
     loss = float(last.loss.detach())
+    if args.dump_outputs and rk == 0:
+        dump_outputs(args.dump_outputs, last)
     del last
-    # kernel statistics from an untimed pass of the same step (HIP events on the launching stream)
-    ops.TIMER.reset()
-    ops.TIMER.enabled = True
-    for _ in range(5):
-        step()
-    sync_all()
-    ops.TIMER.enabled = False
-    q_ms, q_n = ops.TIMER.mean_ms("rq_quantize_fwd")
-    gemm = gemm_launch_stats(ops.TIMER, 5)
+    full = args.full   # everything beside the headline figure
+    q_ms = q_n = gemm = None
+    if full:
+        q_ms, q_n, gemm = kernel_stats_pass(step, sync_all)
     exact = None
-    if not args.no_extras and ws == 1 and torch.get_float32_matmul_precision() != "highest":
+    if full and not args.no_extras and ws == 1 and torch.get_float32_matmul_precision() != "highest":
         # the same step with exact-fp32 matmuls ('highest': library fp32 GEMMs + split-K wgrad kernel)
         prev = torch.get_float32_matmul_precision()
         torch.set_float32_matmul_precision("highest")
@@ -389,7 +415,7 @@ def main():
 
     # decoder-train tokens/s (BASELINE metric, second half): data parallel over the same ranks
     dec = dec_dm = None
-    if not args.no_decoder:
+    if full and not args.no_decoder:
         _log("decoder amazon")
         dec = measure_decoder(device, ws, rk, DEC, graphs=not args.no_graph,
                               cpu_seconds=0.0 if args.no_cpu_baseline else 8.0)
@@ -404,7 +430,7 @@ def main():
                 dec_dm[f"per_gpu_batch_{b}"] = measure_decoder(device, ws, rk, DEC_DM, B=b, steps=10, warmup=5,
                                                                graphs=not args.no_graph, stats=(b == 64))
     extras = {}
-    if not args.no_extras and rk == 0 and ws == 1:
+    if full and not args.no_extras and rk == 0 and ws == 1:
         _log("extras")
         extras = measure_extras(model, device, pool[0])
         extras["trainers"] = measure_trainers()
@@ -414,35 +440,9 @@ def main():
             dist.barrier()
         return
     flops_per_item = 2 * CFG["K"] * CFG["D"] * CFG["L"]
-    achieved = flops_per_item * B / (q_ms * 1e-3) / 1e12
-    alg_bytes = quantize_algorithmic_bytes(B, CFG["D"], CFG["K"], CFG["L"])
-    traffic, traffic_note = (None, "skipped (--no-pmc or N>1)")
-    gtraffic, gtraffic_note = (None, "skipped (--no-pmc or N>1)")
-    if not args.no_pmc and ws == 1 and B == 65536:
-        traffic, traffic_note = pmc_traffic()
-        if gemm is not None:
-            M, N, K, akc, bkc = gemm["shape"]
-            asp, bsp = gemm["operands_split"]
-            gtraffic, gtraffic_note = pmc_traffic(   # the GEMM kernel alone (its slab reduction is deferred)
-                regex="gemm_bf16x3_kernel|gemm_x3w_kernel", launches=5, script=(
-                    "pmc_gemm.py", str(M), str(N), str(K), str(akc), str(bkc), "5", str(asp), str(bsp)))
-    q_roof = {"kernel": "rq_quantize_fwd", "bound": "mfma", "achieved": round(achieved, 3),
-              "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / FP32_MFMA_PEAK_TFLOPS, 4),
-              "traffic": round(traffic["bytes"]) if traffic else None, "launch_ms": round(q_ms, 4),
-              "launches": q_n, "flops_per_launch": flops_per_item * B, "algorithmic_bytes": alg_bytes,
-              "traffic_detail": traffic if traffic else traffic_note,
-              "hbm_GBps_at_algorithmic_bytes": round(alg_bytes / (q_ms * 1e-3) / 1e9, 1)}
-    roof = q_roof
-    if gemm is not None:   # the split-bf16 GEMM is the dominant kernel at 'high' precision
-        roof = {"kernel": "gemm_bf16x3 (rq_gemm_bf16x3_run: the step's largest-time plain-epilogue launch, M x N x K)",
-                "bound": "mfma",
-                "achieved": gemm["achieved_tflops"], "peak": round(BF16_MFMA_PEAK_TFLOPS / 3, 1), "unit": "TFLOP/s",
-                "frac": round(gemm["achieved_tflops"] / (BF16_MFMA_PEAK_TFLOPS / 3), 4),
-                "traffic": round(gtraffic["bytes"]) if gtraffic else None,
-                "peak_note": "fp32-matmul FLOPs; the split runs 3 bf16 MFMA products per fp32 product, so the "
-                             "ceiling is the bf16 dense MFMA peak (2.5 PFLOP/s) / 3",
-                **{k: v for k, v in gemm.items() if k != "achieved_tflops"},
-                "traffic_detail": gtraffic if gtraffic else gtraffic_note}
+    roof = q_roof = None
+    if full:
+        roof, q_roof = kernel_rooflines(args, ws, B, q_ms, q_n, gemm)
     # the whole step against its roofline (6 P_mlp + 2 K D L FLOP per item; MLP matmuls on the
     # split-bf16 ceiling, the quantize distances on fp32 MFMA) and its achieved HBM % (PMC bytes of every
     # dispatch of whole steps, tools/pmc_rqstep.py)
@@ -456,7 +456,7 @@ def main():
                  "frac_of_step_roofline": round((mlp_flops / (BF16_MFMA_PEAK_TFLOPS / 3 * 1e12) +
                                                  q_flops / (FP32_MFMA_PEAK_TFLOPS * 1e12)) / (ms_step * 1e-3), 4),
                  "note": "frac_of_step_roofline = (MLP matmul FLOPs / 833 TF + quantize FLOPs / 157.3 TF) / step time"}
-    if not args.no_pmc and ws == 1 and B == 65536:
+    if full and not args.no_pmc and ws == 1 and B == 65536:
         st_traffic, st_note = pmc_traffic(timeout_s=120, regex=".*", script=("pmc_rqstep.py", "6"), launches=6)
         if st_traffic:
             step_roof.update(hbm_bytes_per_step=round(st_traffic["bytes"]),
@@ -495,7 +495,9 @@ def main():
         "loss_last": round(loss, 5),
         "gemm_selection": "default heuristic" if args.no_tunable else "TunableOp (rqvae_hip.gemm_tuning)",
     }
-    if roof is not q_roof:
+    if roof is None:   # plain run: no kernel-statistics pass
+        del line["roofline"]
+    elif roof is not q_roof:
         line["roofline_quantize"] = q_roof
     if exact is not None:
         line["exact_fp32_highest"] = exact
@@ -504,11 +506,62 @@ def main():
     if dec_dm is not None:
         line["decoder_ml32m"] = dec_dm
     line.update(extras)
-    if not args.no_cpu_baseline and ws == 1:
+    if full and not args.no_cpu_baseline and ws == 1:
         line["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
     print(json.dumps(line), flush=True)
     if ws > 1:
         dist.barrier()
+
+
+def kernel_stats_pass(step, sync_all):
+    """--full: kernel statistics from an untimed pass of 5 more steps of the timed loop (HIP events on the
+    launching stream): the quantize forward's mean launch time and count, and the GEMM launch statistics."""
+    from rqvae_hip import ops
+    ops.TIMER.reset()
+    ops.TIMER.enabled = True
+    for _ in range(5):
+        step()
+    sync_all()
+    ops.TIMER.enabled = False
+    q_ms, q_n = ops.TIMER.mean_ms("rq_quantize_fwd")
+    gemm = gemm_launch_stats(ops.TIMER, 5)
+    return q_ms, q_n, gemm
+
+
+def kernel_rooflines(args, ws, B, q_ms, q_n, gemm):
+    """--full: the rooflines of the dominant kernel (the split-bf16 GEMM, when the step ran any) and of the
+    fused quantize forward, from the kernel-statistics pass, with their PMC traffic (child processes)."""
+    flops_per_item = 2 * CFG["K"] * CFG["D"] * CFG["L"]
+    achieved = flops_per_item * B / (q_ms * 1e-3) / 1e12
+    alg_bytes = quantize_algorithmic_bytes(B, CFG["D"], CFG["K"], CFG["L"])
+    traffic, traffic_note = (None, "skipped (--no-pmc or N>1)")
+    gtraffic, gtraffic_note = (None, "skipped (--no-pmc or N>1)")
+    if not args.no_pmc and ws == 1 and B == 65536:
+        traffic, traffic_note = pmc_traffic()
+        if gemm is not None:
+            M, N, K, akc, bkc = gemm["shape"]
+            asp, bsp = gemm["operands_split"]
+            gtraffic, gtraffic_note = pmc_traffic(   # the GEMM kernel alone (its slab reduction is deferred)
+                regex="gemm_bf16x3_kernel|gemm_x3w_kernel", launches=5, script=(
+                    "pmc_gemm.py", str(M), str(N), str(K), str(akc), str(bkc), "5", str(asp), str(bsp)))
+    q_roof = {"kernel": "rq_quantize_fwd", "bound": "mfma", "achieved": round(achieved, 3),
+              "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / FP32_MFMA_PEAK_TFLOPS, 4),
+              "traffic": round(traffic["bytes"]) if traffic else None, "launch_ms": round(q_ms, 4),
+              "launches": q_n, "flops_per_launch": flops_per_item * B, "algorithmic_bytes": alg_bytes,
+              "traffic_detail": traffic if traffic else traffic_note,
+              "hbm_GBps_at_algorithmic_bytes": round(alg_bytes / (q_ms * 1e-3) / 1e9, 1)}
+    roof = q_roof
+    if gemm is not None:   # the split-bf16 GEMM is the dominant kernel at 'high' precision
+        roof = {"kernel": "gemm_bf16x3 (rq_gemm_bf16x3_run: the step's largest-time plain-epilogue launch, M x N x K)",
+                "bound": "mfma",
+                "achieved": gemm["achieved_tflops"], "peak": round(BF16_MFMA_PEAK_TFLOPS / 3, 1), "unit": "TFLOP/s",
+                "frac": round(gemm["achieved_tflops"] / (BF16_MFMA_PEAK_TFLOPS / 3), 4),
+                "traffic": round(gtraffic["bytes"]) if gtraffic else None,
+                "peak_note": "fp32-matmul FLOPs; the split runs 3 bf16 MFMA products per fp32 product, so the "
+                             "ceiling is the bf16 dense MFMA peak (2.5 PFLOP/s) / 3",
+                **{k: v for k, v in gemm.items() if k != "achieved_tflops"},
+                "traffic_detail": gtraffic if gtraffic else gtraffic_note}
+    return roof, q_roof
 
 
 def measure_trainers(iters=30):

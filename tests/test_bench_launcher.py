@@ -20,6 +20,42 @@ def test_launcher_cmd_is_the_driver_form():
     assert cmd[-5:] == [os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "3"]
 
 
+def test_dump_outputs_writes_float32_within_budget(tmp_path, monkeypatch):
+    """--dump-outputs: one float32 .npy per field of the step's result; an array over its share of the
+    budget is written as the same seeded sample every time."""
+    import collections
+    import numpy as np
+    import torch
+    import bench
+    Out = collections.namedtuple("Out", ["loss", "embs_norm"])
+    out = Out(torch.tensor(1.5, dtype=torch.float64), torch.arange(1000, dtype=torch.float32).reshape(250, 4))
+    bench.dump_outputs(str(tmp_path / "a"), out)
+    loss, norms = np.load(tmp_path / "a" / "loss.npy"), np.load(tmp_path / "a" / "embs_norm.npy")
+    assert loss.dtype == np.float32 and loss.shape == () and float(loss) == 1.5
+    assert norms.dtype == np.float32 and np.array_equal(norms, out.embs_norm.numpy())
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 2 * 4 * 100)   # 100 elements per array
+    bench.dump_outputs(str(tmp_path / "b"), out)
+    bench.dump_outputs(str(tmp_path / "c"), out)
+    s1, s2 = np.load(tmp_path / "b" / "embs_norm.npy"), np.load(tmp_path / "c" / "embs_norm.npy")
+    assert s1.shape == (100,) and np.array_equal(s1, s2) and np.all(np.diff(s1) > 0)
+    assert np.load(tmp_path / "b" / "loss.npy").shape == ()
+
+
+def test_plain_run_options():
+    """--full is off by default and --dump-outputs takes a directory."""
+    import bench
+    old = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"]
+        a = bench.parse()
+        assert not a.full and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+        sys.argv = ["bench.py", "--full", "--dump-outputs", "d"]
+        a = bench.parse()
+        assert a.full and a.dump_outputs == "d"
+    finally:
+        sys.argv = old
+
+
 def test_gpus_2_starts_two_ranks_and_propagates_failure():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(RQVAE_DIST_BACKEND="gloo", CUDA_VISIBLE_DEVICES="", PYTHONUNBUFFERED="1")

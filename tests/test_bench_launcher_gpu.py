@@ -12,7 +12,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ARGS = ["--gpus", "2", "--no-extras", "--no-pmc", "--no-cpu-baseline", "--no-dm", "--steps", "3", "--warmup", "2"]
+ARGS = ["--gpus", "2", "--full", "--no-extras", "--no-pmc", "--no-cpu-baseline", "--no-dm", "--steps", "3", "--warmup", "2"]
 
 
 def _run(env):
