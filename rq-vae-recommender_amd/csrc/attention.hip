@@ -46,13 +46,8 @@
 // (row c = lane % 16, columns 16 (lane / 16) + 4 i): with 256-byte rows all 16 rows hit the same banks
 // (16-way conflicts on every ds_write_b128: 8-17 conflict cycles per LDS instruction in the Amazon SQ
 // pass). 4 floats of row padding put the 16 rows on disjoint 4-bank groups; same values, same order.
-#ifndef RQ_ATTN_PART_PAD
-#define RQ_ATTN_PART_PAD 1
-#endif
-constexpr int kPartPad = RQ_ATTN_PART_PAD ? 4 : 0;
-#ifndef RQ_ATTN_BWD_GROUP
-#define RQ_ATTN_BWD_GROUP 2
-#endif
+constexpr int kPartPad = 4;
+constexpr int kBwdGroup = 2;   // key tiles per group of the backward tile loops
 
 namespace rqhip {
 
@@ -523,9 +518,9 @@ struct DqChunk {
   f32x4* acc;
   template <int NTT, bool MASK>
   __device__ __forceinline__ void run() { groups<NTT, MASK>(0); }
-  template <int N, bool MASK>   // tiles [tb, tb + N) in groups of RQ_ATTN_BWD_GROUP
+  template <int N, bool MASK>   // tiles [tb, tb + N) in groups of kBwdGroup
   __device__ __forceinline__ void groups(int tb) {
-    constexpr int NG = N < RQ_ATTN_BWD_GROUP ? N : RQ_ATTN_BWD_GROUP;
+    constexpr int NG = N < kBwdGroup ? N : kBwdGroup;
     group<NG, MASK>(tb);
     if constexpr (N > NG) groups<N - NG, MASK>(tb + NG);
   }
@@ -631,9 +626,9 @@ struct DkdvChunk {
   f32x4* dva;
   template <int NTT, bool MASK>
   __device__ __forceinline__ void run() { groups<NTT, MASK>(t0); }
-  template <int N, bool MASK>   // tiles [tb, tb + N) in groups of RQ_ATTN_BWD_GROUP
+  template <int N, bool MASK>   // tiles [tb, tb + N) in groups of kBwdGroup
   __device__ __forceinline__ void groups(int tb) {
-    constexpr int NG = N < RQ_ATTN_BWD_GROUP ? N : RQ_ATTN_BWD_GROUP;
+    constexpr int NG = N < kBwdGroup ? N : kBwdGroup;
     group<NG, MASK>(tb);
     if constexpr (N > NG) groups<N - NG, MASK>(tb + NG);
   }
@@ -968,7 +963,7 @@ struct FusedChunk {
   __device__ __forceinline__ void run() { groups<NTT, MASK>(t0); }
   template <int N, bool MASK>
   __device__ __forceinline__ void groups(int tb) {
-    constexpr int NG = N < RQ_ATTN_BWD_GROUP ? N : RQ_ATTN_BWD_GROUP;
+    constexpr int NG = N < kBwdGroup ? N : kBwdGroup;
     group<NG, MASK>(tb);
     if constexpr (N > NG) groups<N - NG, MASK>(tb + NG);
   }
@@ -2333,11 +2328,9 @@ __global__ void __launch_bounds__(64 * NW) attn_bwd_dq_fewq_kernel(
 // feeds dQ^T += K^T dS^T. The waves' partial dQ^T sum through LDS in wave order (deterministic). 5 products
 // + the transpose per tile pair; keys are read once. delta = rowsum(dO * O) per query comes in by lane
 // shuffles from the lanes that computed it (lane & 15 = query).
+constexpr int kFewqBwdMinWg = 1;   // workgroups per CU the 4-wave few-query backward is compiled for (register budget)
 template <int NW>
-#ifndef RQ_FEWQ_BWD_MINWG
-#define RQ_FEWQ_BWD_MINWG 1   // workgroups per CU the 4-wave few-query backward is compiled for (register budget)
-#endif
-__global__ void __launch_bounds__(64 * NW, NW == 4 ? RQ_FEWQ_BWD_MINWG : 1) attn_bwd_fewq_fused_kernel(
+__global__ void __launch_bounds__(64 * NW, NW == 4 ? kFewqBwdMinWg : 1) attn_bwd_fewq_fused_kernel(
     const float* __restrict__ q, int64_t sq, const float* __restrict__ k, int64_t sk, const float* __restrict__ v,
     int64_t sv, const float* __restrict__ out, int64_t so, const float* __restrict__ dout, int64_t sdo,
     const float* __restrict__ lse, int64_t Tq, const int64_t* __restrict__ cu_q, const int64_t* __restrict__ cu_k,
@@ -2764,9 +2757,6 @@ __global__ void __launch_bounds__(256, R <= 96 ? 2 : 1) attn_bwd_fewq_stream_ker
 // summed in wave order (deterministic) by the whole workgroup. delta = rowsum(dO * O) and lse per query are
 // staged in LDS first. 5 products + the transpose per tile pair (the two-pass form: 7), Q / dO / K / V read
 // once.
-#ifndef RQ_ATTN_SHORT_PAIR
-#define RQ_ATTN_SHORT_PAIR 1   // 0: a wave's two key tiles one after the other (A/B: same bits)
-#endif
 template <int NW, int R>
 __global__ void __launch_bounds__(64 * NW, 2) attn_bwd_short_fused_kernel(
     const float* __restrict__ q, int64_t sq, const float* __restrict__ k, int64_t sk, const float* __restrict__ v,
@@ -2857,7 +2847,7 @@ __global__ void __launch_bounds__(64 * NW, 2) attn_bwd_short_fused_kernel(
     // both key tiles of this wave live for this query tile (wave-uniform): their S / dP, dV / dK and dS^T chains
     // interleaved, each Q / dO chunk read from LDS once for both — the same products in the same per-
     // accumulator order as the tile-by-tile loop below (dQ^T: tile 0's terms, then tile 1's), so the same bits
-    const bool two = RQ_ATTN_SHORT_PAIR && TPW == 2 && wave + NW < nkt && (!causal || wave + NW <= qt);
+    const bool two = TPW == 2 && wave + NW < nkt && (!causal || wave + NW <= qt);
     if constexpr (TPW == 2) {
       if (two) {
         f32x4 st0 = f32x4{0.f, 0.f, 0.f, 0.f}, st1 = st0, dp0 = st0, dp1 = st0;
@@ -3026,25 +3016,20 @@ __global__ void __launch_bounds__(64 * NW, 2) attn_bwd_short_fused_kernel(
   }
 }
 
-#ifndef RQ_ATTN_SHORT
-#define RQ_ATTN_SHORT 1   // 0: the chunked kernels for every length (A/B switch)
-#endif
-#ifndef RQ_ATTN_SHORT_MAX_STAGED
-#define RQ_ATTN_SHORT_MAX_STAGED 32   // longest staged range served by the short forms (A/B: 32 / 128)
-#endif
+constexpr int kShortMaxStaged = 32;   // longest staged range served by the short forms (A/B: 32 / 128)
 constexpr int kShortMax = 128;   // longest staged range of the short forms
 
 // (waves, staged rows) of a short-form launch whose tiles run over `rows` (queries for fwd / dQ, keys
 // for dK/dV) against a staged range of `staged` rows; false when the chunked kernels serve it
 static bool short_plan(int64_t rows, int64_t staged, int* nw, int* ch) {
-  if (!RQ_ATTN_SHORT || rows > kShortMax || staged > kShortMax) return false;
+  if (rows > kShortMax || staged > kShortMax) return false;
   // Measured on MI355X (decoder Amazon step, rocprofv3): the short forms win where the staged range
   // is one 32-row chunk (decoder self-attention 5 x 5: fwd 11.6 -> 6.4 us, dQ 15.6 -> 8.9 us; the
   // cross-attention dK/dV over 5 staged queries 41 -> 24 us) and lose at 96 staged rows (encoder
   // self-attention, n <= 81: fwd 35 -> 39 us, dQ 54 -> 59 us, dK/dV 41 -> 64 us: 52 KB of LDS per
   // workgroup leaves 3 workgroups per CU, and a one-wave workgroup would hold it alone), so longer
   // staged ranges keep the chunked kernels.
-  if (staged > RQ_ATTN_SHORT_MAX_STAGED) return false;
+  if (staged > kShortMaxStaged) return false;
   *nw = rows <= 16 ? 1 : 4;
   *ch = staged <= 32 ? 32 : (staged <= 64 ? 64 : (staged <= 96 ? 96 : 128));
   return true;
@@ -3069,19 +3054,12 @@ static bool short_plan(int64_t rows, int64_t staged, int* nw, int* ch) {
 // on padding, long ones (ML-32M <= 801, C5 <= 1281) share each staged 64-row chunk between 4 waves.
 static int waves_for(int64_t rows) { return rows <= 16 ? 1 : (rows <= 96 ? 2 : 4); }
 
-#ifndef RQ_ATTN_LPT
-#define RQ_ATTN_LPT 1   // longest-first sequence order for long ranges (A/B switch)
-#endif
 // LPT order where a workgroup's run time varies enough with the sequence to leave a straggler tail
-static bool lpt_plan(int64_t B, int64_t max_len) { return RQ_ATTN_LPT && B >= 2 && B <= kOrderMax && max_len > 128; }
+static bool lpt_plan(int64_t B, int64_t max_len) { return B >= 2 && B <= kOrderMax && max_len > 128; }
 
-#ifndef RQ_ATTN_SPLIT
-#define RQ_ATTN_SPLIT 1   // split-key forward for <= 16 queries over > 128 keys (A/B switch)
-#endif
-// split-key forward: one query tile per sequence, non-causal, long key ranges (cross-attention)
-#ifndef RQ_ATTN_SPLIT_MIN_K
-#define RQ_ATTN_SPLIT_MIN_K 129   // key ranges from here use the split-key forward (A/B: at the Amazon
-#endif                            // contexts, <= 81 keys in 32-key blocks, it ties the chunked form)
+// split-key forward: one query tile per sequence (<= 16 queries), non-causal, long key ranges (cross-attention)
+constexpr int kSplitMinK = 129;   // key ranges from here use the split-key forward (A/B: at the Amazon
+                                  // contexts, <= 81 keys in 32-key blocks, it ties the chunked form)
 // The kernel policy of one call, from its `flags` argument (RQ_ATTN_* in include/rqvae_hip.h; 0 = the
 // measured-best forms): LDS-DMA short forms, one-pass backwards, split-key / key-split forwards, and the
 // fused backward's query splits (0 = automatic).
@@ -3100,22 +3078,20 @@ static AttnPolicy attn_policy(int flags) {
                     !(flags & RQ_ATTN_FEWQ_WG)};
 }
 // LPT order of the short / few-query forms (by key length: their work per workgroup grows with it)
-static bool short_lpt_plan(int64_t B, const AttnPolicy& pol) { return RQ_ATTN_LPT && pol.lpt_short && B >= 2 && B <= kOrderMax; }
+static bool short_lpt_plan(int64_t B, const AttnPolicy& pol) { return pol.lpt_short && B >= 2 && B <= kOrderMax; }
 
 static bool split_plan(int64_t hd, int64_t max_q, int64_t max_k, int causal, const AttnPolicy& pol) {
-  return RQ_ATTN_SPLIT && pol.split && hd == 64 && !causal && max_q <= 16 && max_k >= RQ_ATTN_SPLIT_MIN_K;
+  return pol.split && hd == 64 && !causal && max_q <= 16 && max_k >= kSplitMinK;
 }
-static int split_kb(int64_t max_k) { return max_k <= 128 ? 32 : 128; }   // 32: RQ_ATTN_SPLIT_MIN_K <= 128 builds
+static int split_kb(int64_t max_k) { return max_k <= 128 ? 32 : 128; }   // 32: for a kSplitMinK <= 128
 // key-split forward for many queries over long keys at low occupancy (attn_fwd_kvsplit_kernel): the C4
 // per-rank config (8 sequences x 6 heads x <= 13 query blocks); RQ_ATTN_NO_SPLIT disables it (A/B)
-#ifndef RQ_ATTN_KVSPLIT_MAX_WG
-#define RQ_ATTN_KVSPLIT_MAX_WG 1024   // unsplit workgroups (B x H x 64-query blocks) up to which it applies
-#endif
+constexpr int kKvSplitMaxWg = 1024;   // unsplit workgroups (B x H x 64-query blocks) up to which it applies
 constexpr int kKvSplitKB = 128;
 static bool kvsplit_plan(int64_t B, int64_t H, int64_t hd, int64_t max_q, int64_t max_k, int causal,
                          const AttnPolicy& pol) {
-  return pol.split && RQ_ATTN_SPLIT && hd == 64 && !causal && max_q > 16 && max_k > 2 * kKvSplitKB &&
-         B * H * ((max_q + 63) / 64) <= RQ_ATTN_KVSPLIT_MAX_WG;
+  return pol.split && hd == 64 && !causal && max_q > 16 && max_k > 2 * kKvSplitKB &&
+         B * H * ((max_q + 63) / 64) <= kKvSplitMaxWg;
 }
 static int64_t split_ws_elems(int64_t B, int64_t H, int64_t hd, int64_t max_q, int64_t max_k, int64_t Tq, int causal,
                               const AttnPolicy& pol) {
@@ -3140,9 +3116,6 @@ static bool fewq_plan(int64_t hd, int64_t max_q, int64_t max_k, const AttnPolicy
   return pol.dma && hd == 64 && max_q <= 16 && max_k <= 128;
 }
 static int fewq_waves(int64_t max_k) { return max_k <= 16 ? 1 : (max_k <= 32 ? 2 : 4); }
-#ifndef RQ_ATTN_FEWQ_STREAM
-#define RQ_ATTN_FEWQ_STREAM 1   // 0: the workgroup-per-unit few-query backward for 4-wave launches too (A/B)
-#endif
 static int attn_cus() {
   static int cus = 0;
   if (cus == 0) {
@@ -3340,7 +3313,7 @@ static void launch_bwd(int64_t B, int64_t H, int64_t max_q, int64_t max_k, hipSt
 #undef RQ_SHF
       return;
     }
-    if (fewq_plan(HD, max_q, max_k, pol) && pol.fused && fewq_waves(max_k) == 4 && RQ_ATTN_FEWQ_STREAM && pol.fewq_stream && Tq > 0 &&
+    if (fewq_plan(HD, max_q, max_k, pol) && pol.fused && fewq_waves(max_k) == 4 && pol.fewq_stream && Tq > 0 &&
         Tk > 0) {   // persistent workgroups, the next unit staged by LDS-DMA
       const int64_t slots = (int64_t)attn_cus() * (max_k <= 96 ? 2 : 1);
       const dim3 gs((unsigned)std::max<int64_t>(1, std::min<int64_t>(B * H, slots)));
@@ -3438,27 +3411,17 @@ static void launch_bwd(int64_t B, int64_t H, int64_t max_q, int64_t max_k, hipSt
 
 // Fused backward (one launch for dQ, dK, dV: attn_bwd_fused_kernel) where the two-pass form would use the
 // chunked dK/dV kernel; the short forms keep the decoder's 5-token self- and cross-attention.
-#ifndef RQ_ATTN_FUSED
-#define RQ_ATTN_FUSED 1
-#endif
-#ifndef RQ_ATTN_FUSED_NW
-#define RQ_ATTN_FUSED_NW 4   // waves per workgroup = key block / 16
-#endif
-#ifndef RQ_ATTN_FUSED_CH
-#define RQ_ATTN_FUSED_CH 32  // staged query rows per LDS round trip (A/B on MI355X: 32 beats 64 by 4-5 %)
-#endif
-#ifndef RQ_ATTN_FUSED_MIN_K
-#define RQ_ATTN_FUSED_MIN_K 129   // shorter key ranges keep the two-pass form (Amazon n <= 81: 0.25 vs 0.30 ms)
-#endif
-#ifndef RQ_ATTN_FUSED_MIN_K_FEWQ
-#define RQ_ATTN_FUSED_MIN_K_FEWQ 129   // the same threshold for <= 16 queries per sequence (cross-attention;
-#endif                                 // A/B from 33 keys: Amazon decoder step 6.53 -> 6.60 ms, fewq_ab.txt)
-constexpr int kFusedKB = 16 * RQ_ATTN_FUSED_NW;
+constexpr int kFusedNW = 4;           // waves per workgroup = key block / 16
+constexpr int kFusedCH = 32;          // staged query rows per LDS round trip (A/B on MI355X: 32 beats 64 by 4-5 %)
+constexpr int kFusedMinK = 129;       // shorter key ranges keep the two-pass form (Amazon n <= 81: 0.25 vs 0.30 ms)
+constexpr int kFusedMinKFewq = 129;   // the same threshold for <= 16 queries per sequence (cross-attention;
+                                      // A/B from 33 keys: Amazon decoder step 6.53 -> 6.60 ms, fewq_ab.txt)
+constexpr int kFusedKB = 16 * kFusedNW;
 
 static bool fused_plan(int64_t hd, int64_t max_q, int64_t max_k, const AttnPolicy& pol) {
-  if (!RQ_ATTN_FUSED || !pol.fused || hd != 64) return false;
-  if (max_q <= 16) return max_k >= RQ_ATTN_FUSED_MIN_K_FEWQ;   // few queries (cross-attention): own threshold
-  if (max_k < RQ_ATTN_FUSED_MIN_K) return false;
+  if (!pol.fused || hd != 64) return false;
+  if (max_q <= 16) return max_k >= kFusedMinKFewq;   // few queries (cross-attention): own threshold
+  if (max_k < kFusedMinK) return false;
   int nw = 0, ch = 0;
   return !short_plan(max_k, max_q, &nw, &ch);
 }
@@ -3470,7 +3433,7 @@ static bool fused_plan(int64_t hd, int64_t max_q, int64_t max_k, const AttnPolic
 static int fused_qsplit(int64_t B, int64_t H, int64_t max_q, int64_t max_k, const AttnPolicy& pol) {
   const int forced = pol.qsplit;
   if (max_q <= 16) return 1;
-  const int64_t max_by_len = std::max<int64_t>(1, max_q / (2 * RQ_ATTN_FUSED_CH));
+  const int64_t max_by_len = std::max<int64_t>(1, max_q / (2 * kFusedCH));
   if (forced > 0) return (int)std::min<int64_t>(std::min(forced, 8), max_by_len);
   static int cus = 0;
   if (cus == 0) {
@@ -3515,7 +3478,7 @@ static void launch_bwd_fused(int64_t B, int64_t H, int64_t max_q, int64_t max_k,
                              float* dv, int64_t sdv, int64_t Tk, float* delta, float* ws, int64_t ws_elems,
                              const AttnPolicy& pol) {
   if constexpr (HD == 64) {
-    constexpr int NW = RQ_ATTN_FUSED_NW, CH = RQ_ATTN_FUSED_CH, KB = 16 * NW;
+    constexpr int NW = kFusedNW, CH = kFusedCH, KB = 16 * NW;
     const int* ord = nullptr;
     if (lpt_plan(B, max_q)) {   // the order lives after the dQ partials in ws
       int* o = reinterpret_cast<int*>(ws + fused_part_elems(H, HD, max_q, max_k, Tq, pol));

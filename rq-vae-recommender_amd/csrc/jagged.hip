@@ -201,10 +201,7 @@ __global__ void __launch_bounds__(1024) dec_prologue_offsets_kernel(const unsign
   // The O(B^2) ranking reads an int32 copy of the lengths 4 at a time (independent compares, 16-byte LDS
   // reads; B = 256 sequences: the int64 one-at-a-time loop was most of the kernel's 21 us); the copy is padded
   // to a multiple of 4 with -1, which never ranks ahead of or ties a length >= 1.
-#ifndef RQ_PRO_DIAG
-#define RQ_PRO_DIAG 0   // diagnostic builds only: 1 = no LPT ranking (the order is left unwritten)
-#endif
-  if (order != nullptr && in_lds && RQ_PRO_DIAG != 1) {
+  if (order != nullptr && in_lds) {
     const int B4 = (int)((B + 3) >> 2);
     for (int64_t b = t; b < 4 * (int64_t)B4; b += 1024) lens32[b] = b < B ? (int)lens[b] : -1;
     __syncthreads();

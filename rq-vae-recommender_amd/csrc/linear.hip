@@ -237,13 +237,10 @@ static WgradPlan wgrad_plan(int64_t Bn, int64_t O, int64_t I) {
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef short s16x4_t __attribute__((ext_vector_type(4)));
 
-#ifndef RQ_X3_BK16
-#define RQ_X3_BK16 0   // 1: 16-deep k stages (32 KiB LDS, 3 workgroups/CU, 32x32x16 MFMA)
-#endif
 constexpr int kXT = 128;                       // output tile (m and n)
-constexpr int kXK = RQ_X3_BK16 ? 16 : 32;      // k per LDS stage
+constexpr int kXK = 32;                        // k per LDS stage
 constexpr int kXCPR = kXK / 8;                 // 16-byte bf16 chunks per row of the row image
-constexpr int kXWG = RQ_X3_BK16 ? 3 : 2;       // resident workgroups per CU
+constexpr int kXWG = 2;                        // resident workgroups per CU
 constexpr int kXPlane = kXT * kXK * 2;         // bytes of one bf16 plane (8 KiB)
 constexpr int kXOp = 2 * kXPlane;              // hi + lo planes of one operand
 constexpr int kXBuf = 2 * kXOp;                // A + B
@@ -251,33 +248,26 @@ constexpr int kXLds = 2 * kXBuf;               // double buffer: 64 KiB (the 64-
 static_assert(kXLds == 65536, "LDS of the 128-tile form");
 
 __device__ __forceinline__ int col_swz(int k) { return ((k & 3) << 2) | ((k >> 2) & 3); }
-#ifndef RQ_X3S_COMPACT
-#define RQ_X3S_COMPACT 1   // 64-tile form: 128-B column-image rows and 32 KiB of LDS (4 workgroups / CU)
-#endif
-constexpr int kXWG64 = RQ_X3S_COMPACT ? 4 : kXWG;   // resident workgroups per CU of the 64-tile form
+constexpr int kXWG64 = 4;   // resident workgroups per CU of the 64-tile form (128-B column-image rows, 32 KiB of LDS)
 // Byte offset of 16-B chunk `c` of k-row kr in a column image of TR columns: 256-B rows with col_swz
-// for TR = 128 (and the wide kernel); for TR = 64 (compact) 128-B rows with a swizzle over the 8 chunks,
+// for TR = 128 (and the wide kernel); for TR = 64 128-B rows with a swizzle over the 8 chunks,
 // s = 2 ((kr >> 1) & 1) + 4 ((kr >> 3) & 1): a ds_read_b64_tr_b16 half-wave touches k-rows {4u..4u+3,
 // 4u+8..4u+11} (+16), chunk pairs (c0, c0 + 1) with c0 even — the even rows land on banks 0-31 and the
 // odd rows on 32-63, each row's pair at a distinct s: conflict-free; the staging stores write whole
 // 128-B rows per 8- / 16-lane group.
 template <int TR>
 __device__ __forceinline__ int col_off(int kr, int c) {
-  if constexpr (TR == 64 && RQ_X3S_COMPACT) return 128 * kr + ((c ^ ((((kr >> 1) & 1) << 1) | (((kr >> 3) & 1) << 2))) << 4);
+  if constexpr (TR == 64) return 128 * kr + ((c ^ ((((kr >> 1) & 1) << 1) | (((kr >> 3) & 1) << 2))) << 4);
   else return 256 * kr + ((c ^ col_swz(kr)) << 4);
 }
-// Row image: row rr of 2 kXK bytes, 16-B chunk c stored at c ^ row_swz(rr). With the 16x16x32 MFMA
-// (default) a fragment read (xfrag16) is a ds_read_b128 whose lane groups {0-3,12-15,20-27},
+// Row image: row rr of 2 kXK bytes, 16-B chunk c stored at c ^ row_swz(rr). A fragment read of the
+// 16x16x32 MFMA (xfrag16) is a ds_read_b128 whose lane groups {0-3,12-15,20-27},
 // {4-11,16-19,28-31} (+32) touch rows {0-3, 12-15} at chunk c and rows 4-11 at chunk c ^ 1: the
 // swizzle (rr >> 2) & 2 puts the four rows of equal rr % 4 on four distinct 16-B bank slots (the
-// wide kernel's image; (rr >> 2) & 3, designed for the 32x32x16 reads, was 2-way conflicted here:
+// wide kernel's image; (rr >> 2) & 3, designed for the retired 32x32x16 reads, was 2-way conflicted here:
 // SQ_LDS_BANK_CONFLICT 2.6 cycles per LDS instruction). Staging writes (ds_write_b128, 8-lane
 // groups over 2 rows) stay conflict-free.
-#if RQ_X3_BK16 || (defined(RQ_X3_MFMA16) && !RQ_X3_MFMA16)
-__device__ __forceinline__ int row_swz(int rr) { return kXCPR == 4 ? ((rr >> 2) & 3) : ((rr >> 3) & 1); }
-#else
 __device__ __forceinline__ int row_swz(int rr) { return (rr >> 2) & 2; }
-#endif
 __device__ __forceinline__ int row_off(int rr, int c) { return rr * (2 * kXK) + ((c ^ row_swz(rr)) << 4); }
 
 // One operand's staging registers (a TR x 32 tile per stage, 256 threads; TR = 128 or 64 rows of m / n).
@@ -292,7 +282,7 @@ __device__ __forceinline__ int row_off(int rr, int c) { return rr * (2 * kXK) + 
 // the stage depth), so no k mask, masked address or zeroing select is emitted.
 template <bool KC, bool SP, int TR = 128, bool KF = false>
 struct XStage {
-  static_assert(TR == 128 || (TR == 64 && kXK == 32), "tile rows (64-row tiles need 32-deep k stages)");
+  static_assert(TR == 128 || TR == 64, "tile rows");
   // fp32, k-contig: float4 per thread (two per 16-B bf16 chunk of the row image)
   static constexpr int NJ_FK = 2 * TR * kXCPR / 256;
   // fp32, m/n-contig: CT threads across the TR columns (4 each), KR k-rows per pass
@@ -416,31 +406,6 @@ struct XStage {
   }
 };
 
-// MFMA operand fragment (8 bf16: row rb + lane % 32, k = 16 s + 8 (lane / 32) + 0..7) of a plane.
-template <bool KC>
-__device__ __forceinline__ bf16x8_t xfrag(const char* plane, int rb, int s, int lane) {
-  if constexpr (KC) {
-    const int rr = rb + (lane & 31), c = 2 * s + (lane >> 5);
-    return *reinterpret_cast<const bf16x8_t*>(plane + row_off(rr, c));
-  } else {
-    // ds_read_b64_tr_b16: 16-lane group G reads a 4 (k) x 16 (row) block; lane 4q + p supplies
-    // the address of k-row q, rows 4p..4p+3, and receives row (lane % 16) of all 4 k-rows.
-    const int G = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
-    const int m = rb + 16 * (G & 1) + 4 * p;
-    s16x4_t t[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int kr = 16 * s + 8 * (G >> 1) + 4 * u + q;
-      const int off = 256 * kr + (((m >> 3) ^ col_swz(kr)) << 4) + (((m >> 2) & 1) << 3);
-      t[u] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-          (__attribute__((address_space(3))) s16x4_t*)(plane + off));
-    }
-    typedef short s16x8_t __attribute__((ext_vector_type(8)));
-    const s16x8_t r = {t[0].x, t[0].y, t[0].z, t[0].w, t[1].x, t[1].y, t[1].z, t[1].w};
-    return __builtin_bit_cast(bf16x8_t, r);
-  }
-}
-
 // 16x16x32 operand fragment (8 bf16: row rb + lane % 16, k = 8 (lane / 16) + 0..7 of the stage).
 template <bool KC, int TR = 128>
 __device__ __forceinline__ bf16x8_t xfrag16(const char* plane, int rb, int lane) {
@@ -465,46 +430,6 @@ __device__ __forceinline__ bf16x8_t xfrag16(const char* plane, int rb, int lane)
     return __builtin_bit_cast(bf16x8_t, r);
   }
 }
-
-#ifndef RQ_X3_DEPTH
-#define RQ_X3_DEPTH 2    // register stage sets in flight (2 or 3; 3 spills on the transposed-B variants)
-#endif
-
-#ifndef RQ_X3S_DEPTH
-#define RQ_X3S_DEPTH 2   // stage sets in flight of the 64-tile form (A/B on MI355X: 2, 3, 4 within 3 %)
-#endif
-
-#ifndef RQ_X3_SETPRIO
-#define RQ_X3_SETPRIO 0   // 1: s_setprio(1) around each stage's MFMA cluster (guide T5; measured -1 %)
-#endif
-#if RQ_X3_SETPRIO
-#define RQ_X3_PRIO(P) __builtin_amdgcn_s_setprio(P);
-#else
-#define RQ_X3_PRIO(P)
-#endif
-
-#ifndef RQ_X3_MAX_SPLIT
-#define RQ_X3_MAX_SPLIT 64   // split-K: at most this many k chunks
-#endif
-
-#ifndef RQ_X3_MIN_STAGES
-#define RQ_X3_MIN_STAGES 2   // split-K: k-stages per workgroup at least (fewer slabs to reduce)
-#endif
-
-#ifndef RQ_X3_INTERLEAVE
-#define RQ_X3_INTERLEAVE 0   // 1: next-stage LDS writes between the MFMAs (measured 20 % slower); 2: the
-                             // 128-tile stage as 8 groups of (6 MFMA, 1 LDS write, 7 VALU) after its reads
-#endif
-
-#ifndef RQ_X3_PEEL
-#define RQ_X3_PEEL 1   // 0: the second stage slot of each loop iteration multiplies under a runtime test (the
-                       // round-4 loop; the MFMAs then sit in their own basic block, apart from the staging)
-#endif
-
-#ifndef RQ_X3_MFMA16
-#define RQ_X3_MFMA16 (RQ_X3_BK16 ? 0 : 1)   // 16x16x32 bf16 MFMA (4 x 4 tiles per wave); 0: 32x32x16 (2 x 2)
-#endif
-static_assert(!(RQ_X3_MFMA16 && RQ_X3_BK16), "16x16x32 MFMA needs 32-deep k stages");
 
 // Epilogues: what the accumulator tile becomes (all fp32 math; dropout mask = keep1(seed, m N + n),
 // the convention of the standalone dropout kernels, dropout.hip).
@@ -535,7 +460,7 @@ __device__ __forceinline__ float sigmoid_fast(float z) {
   return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * z));
 }
 
-// Epilogue stores; NT: non-temporal (the wide kernel's all-CU write bursts, A/B RQ_X3W_NT)
+// Epilogue stores; NT: non-temporal (the wide kernel's all-CU write bursts)
 typedef unsigned ux4_t __attribute__((ext_vector_type(4)));
 typedef unsigned ux2_t __attribute__((ext_vector_type(2)));
 template <bool NT>
@@ -626,7 +551,6 @@ __device__ __forceinline__ void split_store1(float v, uint16_t* hi, uint16_t* lo
 
 // One LDS stage of MFMA work per wave. Transposed product D = B A^T (tile rows = n, columns = m):
 // each lane then holds consecutive n of one row m, so the epilogue stores vectors.
-#if RQ_X3_MFMA16
 #define RQ_X3_MMA                                                                                             \
   {                                                                                                           \
     bf16x8_t fa_h[kP], fa_l[kP], fb_h[kP], fb_l[kP];                                                          \
@@ -642,45 +566,6 @@ __device__ __forceinline__ void split_store1(float v, uint16_t* hi, uint16_t* lo
       acc[p][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb_h[q], fa_h[p], acc[p][q], 0, 0, 0);              \
     }                                                                                                         \
   }
-// The same products in two halves (A fragment rows [0, kP/2) then [kP/2, kP)) with MID between them.
-#define RQ_X3_MMA2(MID)                                                                                       \
-  {                                                                                                           \
-    bf16x8_t fa_h[kP], fa_l[kP], fb_h[kP], fb_l[kP];                                                          \
-    _Pragma("unroll") for (int p = 0; p < kP; ++p) {                                                          \
-      fb_h[p] = xfrag16<BKC, TS>(bh, wn * kWTile + 16 * p, lane);                                             \
-      fb_l[p] = xfrag16<BKC, TS>(bl, wn * kWTile + 16 * p, lane);                                             \
-    }                                                                                                         \
-    _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_) {                                                        \
-      _Pragma("unroll") for (int p = h_ * kP / 2; p < (h_ + 1) * kP / 2; ++p) {                               \
-        fa_h[p] = xfrag16<AKC, TS>(ah, wm * kWTile + 16 * p, lane);                                           \
-        fa_l[p] = xfrag16<AKC, TS>(al, wm * kWTile + 16 * p, lane);                                           \
-      }                                                                                                       \
-      _Pragma("unroll") for (int p = h_ * kP / 2; p < (h_ + 1) * kP / 2; ++p)                                 \
-      _Pragma("unroll") for (int q = 0; q < kP; ++q) {                                                        \
-        acc[p][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb_h[q], fa_l[p], acc[p][q], 0, 0, 0);            \
-        acc[p][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb_l[q], fa_h[p], acc[p][q], 0, 0, 0);            \
-        acc[p][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb_h[q], fa_h[p], acc[p][q], 0, 0, 0);            \
-      }                                                                                                       \
-      if (h_ == 0) { MID }                                                                                    \
-    }                                                                                                         \
-  }
-#else
-#define RQ_X3_MMA                                                                                             \
-  _Pragma("unroll") for (int ks = 0; ks < kXK / 16; ++ks) {                                                   \
-    bf16x8_t fa_h[2], fa_l[2], fb_h[2], fb_l[2];                                                              \
-    _Pragma("unroll") for (int p = 0; p < 2; ++p) {                                                           \
-      fa_h[p] = xfrag<AKC>(ah, wm * 64 + 32 * p, ks, lane);                                                   \
-      fa_l[p] = xfrag<AKC>(al, wm * 64 + 32 * p, ks, lane);                                                   \
-      fb_h[p] = xfrag<BKC>(bh, wn * 64 + 32 * p, ks, lane);                                                   \
-      fb_l[p] = xfrag<BKC>(bl, wn * 64 + 32 * p, ks, lane);                                                   \
-    }                                                                                                         \
-    _Pragma("unroll") for (int p = 0; p < 2; ++p) _Pragma("unroll") for (int q = 0; q < 2; ++q) {            \
-      acc[p][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb_h[q], fa_l[p], acc[p][q], 0, 0, 0);              \
-      acc[p][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb_l[q], fa_h[p], acc[p][q], 0, 0, 0);              \
-      acc[p][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb_h[q], fa_h[p], acc[p][q], 0, 0, 0);              \
-    }                                                                                                         \
-  }
-#endif
 
 // One launch's problem (operands, shape, plan, output, epilogue): the kernel argument of the 128-/64-tile
 // kernel and of the paired launch (gemm_x3_pair_kernel) that runs two problems' workgroups in one grid.
@@ -704,7 +589,7 @@ struct X3Args {
 
 // LDS bytes of one plane of the TS-tile form (the 64-tile form's compact images: half of every plane)
 template <int TS>
-constexpr int x3_plane_bytes() { return (TS == 64 && RQ_X3S_COMPACT) ? kXPlane / 2 : kXPlane; }
+constexpr int x3_plane_bytes() { return TS == 64 ? kXPlane / 2 : kXPlane; }
 
 // TS = output tile (128, or 64 for launches whose 128-tiles cannot fill the chip: the decoder's 1,280
 // future-token rows): 4 waves of (TS / 2)^2 outputs, the same k order (so the same result) either way.
@@ -725,59 +610,39 @@ __device__ __forceinline__ void x3_body_k(const X3Args& a, int bid, char* __rest
   if (lw >= tiles * S) return;
   const int s = lw / tiles, t = lw % tiles;
   const int m0 = (t / tiles_n) * TS, n0 = (t % tiles_n) * TS;
-  static_assert(TS == 128 || (TS == 64 && RQ_X3_MFMA16), "64-row tiles run on the 16x16x32 MFMA");
+  static_assert(TS == 128 || TS == 64, "output tile");
   constexpr int kWTile = TS / 2, kP = TS / 32;   // per-wave tile, 16-row MFMA tiles per wave side
   const int64_t k_lo = (int64_t)s * chunk;
   const int64_t k_hi = k_lo + chunk < K ? k_lo + chunk : K;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int wm = wave >> 1, wn = wave & 1;
 
-#if RQ_X3_MFMA16
   floatx4v acc[kP][kP];
 #pragma unroll
   for (int p = 0; p < kP; ++p)
 #pragma unroll
     for (int q = 0; q < kP; ++q) acc[p][q] = floatx4v{0.f, 0.f, 0.f, 0.f};
-#else
-  floatx16 acc[2][2];
-#pragma unroll
-  for (int p = 0; p < 2; ++p)
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[p][q][r] = 0.f;
-#endif
 
   auto plane = [&](int buf, int op, int hl) { return lds + buf * 4 * kPl + op * 2 * kPl + hl * kPl; };
   const int nst = (int)((k_hi - k_lo + kXK - 1) / kXK);
-  // kDepth register stage sets: stage st + kDepth is loaded while stage st is multiplied and
-  // stage st + 1 (loaded earlier) is written to the other LDS buffer, so each load has kDepth stages
-  // of MFMA work to land in (HBM latency under load is ~2-4k cycles, one 128-tile stage ~1.5k; a
-  // 64-tile stage is 4x less MFMA work, so that form keeps 4 stages in flight).
-  constexpr int kDepth = TS == 64 ? RQ_X3S_DEPTH : RQ_X3_DEPTH;
-  static_assert(kDepth >= 2 && kDepth <= 4, "stage sets");
-  XStage<AKC, ASP, TS, KF> sa0, sa1, sa2, sa3;
-  XStage<BKC, BSP, TS, KF> sb0, sb1, sb2, sb3;
+  // Two register stage sets: stage st + 2 is loaded while stage st is multiplied and stage st + 1
+  // (loaded earlier) is written to the other LDS buffer, so each load has two stages of MFMA work to
+  // land in (HBM latency under load is ~2-4k cycles, one 128-tile stage ~1.5k; a 64-tile stage is 4x
+  // less MFMA work, and measured within 3 % at 2, 3 and 4 sets, so both forms keep 2).
+  constexpr int kDepth = 2;
+  XStage<AKC, ASP, TS, KF> sa0, sa1;
+  XStage<BKC, BSP, TS, KF> sb0, sb1;
   sa0.load(A, Al, lda, m0, M, k_lo, k_lo, k_hi, tid);
   sb0.load(B, Bl, ldb, n0, N, k_lo, k_lo, k_hi, tid);
   sa1.load(A, Al, lda, m0, M, k_lo + (int64_t)min(1, nst - 1) * kXK, k_lo, k_hi, tid);
   sb1.load(B, Bl, ldb, n0, N, k_lo + (int64_t)min(1, nst - 1) * kXK, k_lo, k_hi, tid);
-  if constexpr (kDepth >= 3) {
-    sa2.load(A, Al, lda, m0, M, k_lo + (int64_t)min(2, nst - 1) * kXK, k_lo, k_hi, tid);
-    sb2.load(B, Bl, ldb, n0, N, k_lo + (int64_t)min(2, nst - 1) * kXK, k_lo, k_hi, tid);
-  }
-  if constexpr (kDepth >= 4) {
-    sa3.load(A, Al, lda, m0, M, k_lo + (int64_t)min(3, nst - 1) * kXK, k_lo, k_hi, tid);
-    sb3.load(B, Bl, ldb, n0, N, k_lo + (int64_t)min(3, nst - 1) * kXK, k_lo, k_hi, tid);
-  }
   sa0.store(plane(0, 0, 0), plane(0, 0, 1), tid);
   sb0.store(plane(0, 1, 0), plane(0, 1, 1), tid);
   __syncthreads();
 
-#define RQ_X3_STAGE(ST, LA, LB, SA, SB, ON)                                                                   \
+#define RQ_X3_STAGE(ST, LA, LB, SA, SB)                                                                       \
   {                                                                                                           \
     const int st_ = (ST), buf = st_ & 1;                                                                      \
-    const bool on_ = (ON);                                                                                    \
     {  /* unconditional (past the end: the last stage again, an L2 hit) so vmcnt counts stay static */       \
       const int64_t kb = k_lo + (int64_t)min(st_ + kDepth, nst - 1) * kXK;                                    \
       LA.load(A, Al, lda, m0, M, kb, k_lo, k_hi, tid);                                                        \
@@ -787,163 +652,57 @@ __device__ __forceinline__ void x3_body_k(const X3Args& a, int bid, char* __rest
     const char* al = plane(buf, 0, 1);                                                                        \
     const char* bh = plane(buf, 1, 0);                                                                        \
     const char* bl = plane(buf, 1, 1);                                                                        \
-    RQ_X3_BODY(SA, SB)                                                                                        \
+    RQ_X3_MMA                                                                                                 \
+    SA.store(plane(buf ^ 1, 0, 0), plane(buf ^ 1, 0, 1), tid);                                                \
+    SB.store(plane(buf ^ 1, 1, 0), plane(buf ^ 1, 1, 1), tid);                                                \
     __syncthreads();                                                                                          \
   }
-  // Stage body: the MFMAs on buffer buf and the write of the next stage's registers into buf ^ 1
+  // Stage body: the MFMAs on buffer buf, then the write of the next stage's registers into buf ^ 1
   // (free since the previous barrier; unconditional: past the last stage it writes a buffer nobody
   // reads, and a conditional store would leave the set's loads possibly pending, so the compiler
-  // would wait vmcnt(0) before reloading it). RQ_X3_INTERLEAVE issues the write (its VALU and
-  // ds_writes) between the MFMAs instead of after them.
-#if RQ_X3_INTERLEAVE == 1
-#define RQ_X3_BODY(SA, SB)                                                                                    \
-  SA.store(plane(buf ^ 1, 0, 0), plane(buf ^ 1, 0, 1), tid);                                                  \
-  SB.store(plane(buf ^ 1, 1, 0), plane(buf ^ 1, 1, 1), tid);                                                  \
-  if (on_) RQ_X3_MMA                                                                                          \
-  _Pragma("unroll") for (int i_ = 0; i_ < 8; ++i_) {                                                          \
-    __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);                                                        \
-    __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);                                                        \
-    __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);                                                        \
+  // would wait vmcnt(0) before reloading it).
+  // Set j % 2 holds stage j: after multiplying stage st its set is reloaded with st + 2. The loop is
+  // peeled so that every stage slot multiplies (no runtime test around the MFMAs).
+  int st = 0;
+  for (; st + 1 < nst; st += 2) {
+    RQ_X3_STAGE(st, sa0, sb0, sa1, sb1)
+    RQ_X3_STAGE(st + 1, sa1, sb1, sa0, sb0)
   }
-#elif RQ_X3_INTERLEAVE == 2
-#define RQ_X3_BODY(SA, SB)                                                                                    \
-  if constexpr (TS == 128) {                                                                                  \
-    SA.store(plane(buf ^ 1, 0, 0), plane(buf ^ 1, 0, 1), tid);                                                \
-    SB.store(plane(buf ^ 1, 1, 0), plane(buf ^ 1, 1, 1), tid);                                                \
-    if (on_) RQ_X3_MMA                                                                                        \
-    __builtin_amdgcn_sched_group_barrier(0x020, 8, 0);                                                        \
-    __builtin_amdgcn_sched_group_barrier(0x100, 16, 0);                                                       \
-    _Pragma("unroll") for (int i_ = 0; i_ < 8; ++i_) {                                                        \
-      __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);                                                      \
-      __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);                                                      \
-      __builtin_amdgcn_sched_group_barrier(0x002, 7, 0);                                                      \
-    }                                                                                                         \
-  } else {                                                                                                    \
-    if (on_) RQ_X3_MMA                                                                                        \
-    SA.store(plane(buf ^ 1, 0, 0), plane(buf ^ 1, 0, 1), tid);                                                \
-    SB.store(plane(buf ^ 1, 1, 0), plane(buf ^ 1, 1, 1), tid);                                                \
-  }
-#elif RQ_X3_INTERLEAVE == 3   // A's staging store before the MFMAs, B's after
-#define RQ_X3_BODY(SA, SB)                                                                                    \
-  SA.store(plane(buf ^ 1, 0, 0), plane(buf ^ 1, 0, 1), tid);                                                  \
-  if (on_) RQ_X3_MMA                                                                                          \
-  SB.store(plane(buf ^ 1, 1, 0), plane(buf ^ 1, 1, 1), tid);
-#elif RQ_X3_INTERLEAVE == 4   // the MFMAs in two halves, A's staging store between them, B's after
-#define RQ_X3_BODY(SA, SB)                                                                                    \
-  static_assert(RQ_X3_PEEL, "every slot multiplies");                                                         \
-  RQ_X3_MMA2(SA.store(plane(buf ^ 1, 0, 0), plane(buf ^ 1, 0, 1), tid);)                                      \
-  SB.store(plane(buf ^ 1, 1, 0), plane(buf ^ 1, 1, 1), tid);
-#else
-#define RQ_X3_BODY(SA, SB)                                                                                    \
-  if (on_) {                                                                                                  \
-    RQ_X3_PRIO(1)                                                                                             \
-    RQ_X3_MMA                                                                                                 \
-    RQ_X3_PRIO(0)                                                                                             \
-  }                                                                                                           \
-  SA.store(plane(buf ^ 1, 0, 0), plane(buf ^ 1, 0, 1), tid);                                                  \
-  SB.store(plane(buf ^ 1, 1, 0), plane(buf ^ 1, 1, 1), tid);
-#endif
-  // set j % kDepth holds stage j: after multiplying stage st its set is reloaded with st + kDepth.
-  // Every stage slot of an iteration issues its loads, stores and barrier; only the MFMAs of slots
-  // past the last stage are skipped (a skipped slot's loads would leave the counts path-dependent).
-  if constexpr (kDepth == 4) {
-    for (int st = 0; st < nst; st += 4) {
-      RQ_X3_STAGE(st, sa0, sb0, sa1, sb1, true)
-      RQ_X3_STAGE(st + 1, sa1, sb1, sa2, sb2, st + 1 < nst)
-      RQ_X3_STAGE(st + 2, sa2, sb2, sa3, sb3, st + 2 < nst)
-      RQ_X3_STAGE(st + 3, sa3, sb3, sa0, sb0, st + 3 < nst)
-    }
-  } else if constexpr (kDepth == 3) {
-#if RQ_X3_PEEL
-    int st = 0;
-    for (; st + 2 < nst; st += 3) {
-      RQ_X3_STAGE(st, sa0, sb0, sa1, sb1, true)
-      RQ_X3_STAGE(st + 1, sa1, sb1, sa2, sb2, true)
-      RQ_X3_STAGE(st + 2, sa2, sb2, sa0, sb0, true)
-    }
-    if (st < nst) RQ_X3_STAGE(st, sa0, sb0, sa1, sb1, true)
-    if (st + 1 < nst) RQ_X3_STAGE(st + 1, sa1, sb1, sa2, sb2, true)
-#else
-    for (int st = 0; st < nst; st += 3) {
-      RQ_X3_STAGE(st, sa0, sb0, sa1, sb1, true)
-      RQ_X3_STAGE(st + 1, sa1, sb1, sa2, sb2, st + 1 < nst)
-      RQ_X3_STAGE(st + 2, sa2, sb2, sa0, sb0, st + 2 < nst)
-    }
-#endif
-  } else {
-#if RQ_X3_PEEL
-    int st = 0;
-    for (; st + 1 < nst; st += 2) {
-      RQ_X3_STAGE(st, sa0, sb0, sa1, sb1, true)
-      RQ_X3_STAGE(st + 1, sa1, sb1, sa0, sb0, true)
-    }
-    if (st < nst) RQ_X3_STAGE(st, sa0, sb0, sa1, sb1, true)
-#else
-    for (int st = 0; st < nst; st += 2) {
-      RQ_X3_STAGE(st, sa0, sb0, sa1, sb1, true)
-      RQ_X3_STAGE(st + 1, sa1, sb1, sa0, sb0, st + 1 < nst)
-    }
-#endif
-  }
+  if (st < nst) RQ_X3_STAGE(st, sa0, sb0, sa1, sb1)
 #undef RQ_X3_STAGE
-#undef RQ_X3_BODY
 #undef RQ_X3_MMA
-#undef RQ_X3_MMA2
 
   // Each lane stores C[m][n .. n + 3] quads: 16-B fp32 / 8-B bf16 stores (N % 4 == 0).
   float* Cs = C + (int64_t)s * M * N;   // split-K partial slab (S > 1: ldc == N)
-#if RQ_X3_MFMA16
   // 16x16 C/D map of D = B A^T: column (lane & 15) = m, row 4 (lane >> 4) + j = n (j = register).
-  constexpr int kPM = kP, kPN = kP, kG = 1;
-#else
-  // 32x32 C/D map: column (lane & 31) = m, row (r & 3) + 8 (r >> 2) + 4 (lane >> 5) = n: register
-  // quad g holds n = 8 g + 4 (lane >> 5) + 0..3.
-  constexpr int kPM = 2, kPN = 2, kG = 4;
-#endif
-  auto quad_m = [&](int p) {
-#if RQ_X3_MFMA16
-    return m0 + wm * kWTile + 16 * p + (lane & 15);
-#else
-    return m0 + wm * 64 + 32 * p + (lane & 31);
-#endif
-  };
-  auto quad_n = [&](int q, int g) {
-#if RQ_X3_MFMA16
-    return n0 + wn * kWTile + 16 * q + 4 * (lane >> 4);
-#else
-    return n0 + wn * 64 + 32 * q + 8 * g + 4 * (lane >> 5);
-#endif
-  };
+  auto quad_m = [&](int p) { return m0 + wm * kWTile + 16 * p + (lane & 15); };
+  auto quad_n = [&](int q) { return n0 + wn * kWTile + 16 * q + 4 * (lane >> 4); };
   // the SiLU' epilogue's Z quads for every quad first: one round trip, not one per quad (the residual add
   // keeps its per-quad reads: preloaded it measured 2 us slower per decoder launch, profiles/r06/epi_z)
   constexpr bool kZ = EPI == kEpiSiluBwd;
-  float4 zin[kPM][kPN][kG];
+  float4 zin[kP][kP];
 #pragma unroll
-  for (int p = 0; p < kPM; ++p)
+  for (int p = 0; p < kP; ++p)
 #pragma unroll
-    for (int q = 0; q < kPN; ++q)
+    for (int q = 0; q < kP; ++q) {
+      const int m = quad_m(p), n = quad_n(q);
+      zin[p][q] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (kZ && m < M && n < N) zin[p][q] = x3_epi_in<EPI>(m, n, Cs, ldc, ep);
+    }
 #pragma unroll
-      for (int g = 0; g < kG; ++g) {
-        const int m = quad_m(p), n = quad_n(q, g);
-        zin[p][q][g] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (kZ && m < M && n < N) zin[p][q][g] = x3_epi_in<EPI>(m, n, Cs, ldc, ep);
-      }
-#pragma unroll
-  for (int p = 0; p < kPM; ++p) {
+  for (int p = 0; p < kP; ++p) {
     const int m = quad_m(p);
     if (m < M) {
 #pragma unroll
-      for (int q = 0; q < kPN; ++q)
+      for (int q = 0; q < kP; ++q)
+        // A one-trip loop (a leftover of the 32x32 accumulator map's four register quads per tile): without
+        // it hipcc schedules these kernels differently, and the generated code is pinned by measurement.
 #pragma unroll
-        for (int g = 0; g < kG; ++g) {
-          const int n = quad_n(q, g);
-#if RQ_X3_MFMA16
+        for (int g = 0; g < 1; ++g) {
+          const int n = quad_n(q);
           const float4 v = make_float4(acc[p][q][0], acc[p][q][1], acc[p][q][2], acc[p][q][3]);
-#else
-          const float4 v = make_float4(acc[p][q][4 * g], acc[p][q][4 * g + 1], acc[p][q][4 * g + 2], acc[p][q][4 * g + 3]);
-#endif
           if (n >= N) continue;
-          if constexpr (kZ) x3_epi4z<EPI, DROP>(v, zin[p][q][g], m, n, N, C, Cs, ldc, ep);
+          if constexpr (kZ) x3_epi4z<EPI, DROP>(v, zin[p][q], m, n, N, C, Cs, ldc, ep);
           else x3_epi4<EPI, DROP>(v, m, n, N, C, Cs, ldc, ep);
         }
     }
@@ -999,7 +758,7 @@ __global__ void __launch_bounds__(256, P1::kTS == 64 ? kXWG64 : kXWG) gemm_x3_pa
 // streamed activation: HBM / Infinity-Cache misses) has THREE k-step slots, B (the weights, L2
 // hits) two: 3 x 32 + 2 x 32 KiB = 160 KiB, the whole LDS, one workgroup per CU.
 //
-// Staging is LDS-DMA (global_load_lds_dwordx4: no VGPR round trip; the images' XOR swizzles go on
+// Staging is LDS-DMA (buffer_load_dwordx4 ... lds: no VGPR round trip; the images' XOR swizzles go on
 // the per-lane SOURCE address, the LDS side stays lane-linear: wave w fills bytes [1 KiB w,
 // 1 KiB (w + 1)) of every half-plane). A k step is four phases, one per C quadrant of the wave
 // (A half h x B half g), in the order (0,0) (0,1) (1,1) (1,0); reads: A0 + B0 (phase 0), B1 (1),
@@ -1020,40 +779,11 @@ __global__ void __launch_bounds__(256, P1::kTS == 64 ? kXWG64 : kXWG) gemm_x3_pa
 // The accumulation order over k equals gemm_bf16x3_kernel's (same 32-deep steps, same product
 // order), so for the same split the two kernels agree bitwise.
 // ---------------------------------------------------------------------------------------------
-#ifndef RQ_X3W_STAGGER
-#define RQ_X3W_STAGGER 1   // 0: both wave groups in lock-step (A/B switch)
-#endif
-#ifndef RQ_X3W_EPI_LDS
-#define RQ_X3W_EPI_LDS 1   // epilogue through LDS in whole rows (0: straight from the accumulators)
-#endif
-#ifndef RQ_X3W_DIAG
-#define RQ_X3W_DIAG 0      // diagnostic builds only: 1 = no operand loads, 2 = no MFMAs, 3 = no epilogue, 4 = B re-read
-                           // from its first k step (cache-resident), 5 = A likewise, 6 = k-contiguous operands DMA whole
-                           // 128-B lines (8 rows per KiB, each line once per k-step pair), 7 = phases 1 / 2 skip
-                           // their fragment reads after the first k step (half the LDS reads) (wrong results)
-#endif
-#ifndef RQ_X3W_BUFLDS
-#define RQ_X3W_BUFLDS 1    // operand DMA as buffer_load ... lds (SGPR descriptor rebased at the workgroup's first
-                           // row / k chunk + 32-bit byte offset): 1-2.5 % faster than global_load_lds with 64-bit
-                           // per-lane addresses (profiles/r06/gemm_diag); 0 = global_load_lds (A/B switch)
-#endif
-#ifndef RQ_X3W_NT
-#define RQ_X3W_NT 1        // the wide kernel's epilogue stores non-temporal (0: default policy; A/B)
-#endif
-#ifndef RQ_X3W_PRIO
-#define RQ_X3W_PRIO 1      // s_setprio(1) around each MFMA cluster (keeps hipcc from moving it)
-#endif
-
 constexpr int kWT2 = 256;          // output tile (m and n)
 constexpr int kWH = 8192;          // one half-plane: 128 rows x 32 k bf16
 constexpr int kWStep = 4 * kWH;    // one operand's k step: 2 halves x 2 planes
 constexpr int kWB0 = 3 * kWStep;   // B's slots follow A's three
 constexpr int kWLds = 5 * kWStep;  // 160 KiB
-
-__device__ __forceinline__ void glds16(const uint16_t* src, char* lds_dst) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
-}
 
 __device__ __forceinline__ int wrow_swz(int r) { return (r >> 2) & 2; }
 
@@ -1062,10 +792,6 @@ __device__ __forceinline__ int wrow_swz(int r) { return (r >> 2) & 2; }
 template <bool KC>
 __device__ __forceinline__ int64_t x3w_src(int64_t ld, int r0, int R, int wave, int lane) {
   if constexpr (KC) {   // row image: 16 rows x 4 chunks per 1 KiB; position c holds k-chunk c ^ swz
-    if (RQ_X3W_DIAG == 6) {   // diagnostic: 8 rows x one whole 128-B line per 1 KiB (wrong results)
-      const int row = 8 * wave + (lane >> 3);
-      return (int64_t)min(r0 + row, R - 1) * ld + 8 * (lane & 7);
-    }
     const int row = 16 * wave + (lane >> 2);
     const int kc = (lane & 3) ^ wrow_swz(row);
     return (int64_t)min(r0 + row, R - 1) * ld + 8 * kc;
@@ -1089,7 +815,6 @@ __device__ __forceinline__ bf16x8_t wfrag16(const char* plane, int rb, int lane)
 
 #define RQ_W_BAR() __builtin_amdgcn_s_barrier()
 #define RQ_W_VM6() asm volatile("s_waitcnt vmcnt(6)" ::: "memory")
-
 #define RQ_W_LGKM0() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 
 template <bool AKC, bool BKC, int EPI, bool DROP>
@@ -1111,7 +836,7 @@ gemm_x3w_kernel(const uint16_t* __restrict__ Ah, const uint16_t* __restrict__ Al
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 2, wc = wave & 3;
-  const bool g1 = RQ_X3W_STAGGER && wr != 0;
+  const bool g1 = wr != 0;   // the second wave group, staggered one barrier behind the first
 
   const int64_t da = AKC ? 32 : 32 * lda, db = BKC ? 32 : 32 * ldb;
   const int64_t ka = AKC ? k_lo : k_lo * lda, kb = BKC ? k_lo : k_lo * ldb;
@@ -1121,9 +846,10 @@ gemm_x3w_kernel(const uint16_t* __restrict__ Ah, const uint16_t* __restrict__ Al
   // A half h of k step `step` into A slot `slot`; B half g of step `step` into B parity step & 1.
   // Steps past the end are clamped (the last step again, into a slot nobody reads), so every wave
   // issues the same DMA count in every phase and the vmcnt counts stay static.
-#if RQ_X3W_BUFLDS
-  // descriptors based at the workgroup's first A / B row (k-contiguous) or first k row (m/n-contiguous): every
-  // offset below is then < x3w_span() elements, which x3w_choose keeps under 2^30 (32-bit byte offsets)
+  // The DMA is buffer_load ... lds (an SGPR descriptor + a 32-bit byte offset: 1-2.5 % faster than
+  // global_load_lds with 64-bit per-lane addresses, profiles/r06/gemm_diag). The descriptors are based at
+  // the workgroup's first A / B row (k-contiguous) or first k row (m/n-contiguous): every offset below is
+  // then < x3w_span() elements, which x3_prepare keeps under 2^30 (32-bit byte offsets)
   const int64_t abase = AKC ? (int64_t)m0 * lda : k_lo * lda, bbase = BKC ? (int64_t)n0 * ldb : k_lo * ldb;
   const __amdgpu_buffer_rsrc_t rah = __builtin_amdgcn_make_buffer_rsrc((void*)(Ah + abase), (short)0, 0x7fffffff, 0x00020000);
   const __amdgpu_buffer_rsrc_t ral = __builtin_amdgcn_make_buffer_rsrc((void*)(Al + abase), (short)0, 0x7fffffff, 0x00020000);
@@ -1132,32 +858,19 @@ gemm_x3w_kernel(const uint16_t* __restrict__ Ah, const uint16_t* __restrict__ Al
   auto bdma = [](__amdgpu_buffer_rsrc_t r, int64_t rel, char* dst) {
     __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)dst, 16, (int)(rel * 2), 0, 0, 0);
   };
-#endif
   auto issue_a = [&](int h, int step, int slot) {
-    if (RQ_X3W_DIAG == 1) return;   // diagnostic build: no operand loads (wrong results)
     const int sa = step < nk ? step : nk - 1;
-    const int64_t o = (h == 0 ? oa0 : oa1) + (RQ_X3W_DIAG == 5 ? 0 : (RQ_X3W_DIAG == 6 && AKC ? (int64_t)(sa & ~1) * da + (int64_t)(sa & 1) * 64 * lda : (int64_t)sa * da));
+    const int64_t o = (h == 0 ? oa0 : oa1) + (int64_t)sa * da;
     char* dst = wl + slot * kWStep + h * 2 * kWH;
-#if RQ_X3W_BUFLDS
     bdma(rah, o - abase, dst);
     bdma(ral, o - abase, dst + kWH);
-#else
-    glds16(Ah + o, dst);
-    glds16(Al + o, dst + kWH);
-#endif
   };
   auto issue_b = [&](int g, int step) {
-    if (RQ_X3W_DIAG == 1) return;
     const int sb = step < nk ? step : nk - 1;
-    const int64_t o = (g == 0 ? ob0 : ob1) + (RQ_X3W_DIAG == 4 ? 0 : (RQ_X3W_DIAG == 6 && BKC ? (int64_t)(sb & ~1) * db + (int64_t)(sb & 1) * 64 * ldb : (int64_t)sb * db));
+    const int64_t o = (g == 0 ? ob0 : ob1) + (int64_t)sb * db;
     char* dst = wl + kWB0 + (step & 1) * kWStep + g * 2 * kWH;
-#if RQ_X3W_BUFLDS
     bdma(rbh, o - bbase, dst);
     bdma(rbl, o - bbase, dst + kWH);
-#else
-    glds16(Bh + o, dst);
-    glds16(Bl + o, dst + kWH);
-#endif
   };
   auto aplane = [&](int slot, int h, int pl) -> const char* { return lds + slot * kWStep + (h * 2 + pl) * kWH; };
   auto bplane = [&](int par, int g, int pl) -> const char* {
@@ -1185,17 +898,15 @@ gemm_x3w_kernel(const uint16_t* __restrict__ Ah, const uint16_t* __restrict__ Al
     BH[j] = wfrag16<BKC>(bplane(PAR, G, 0), wc * 32 + 16 * j, lane);                           \
     BL[j] = wfrag16<BKC>(bplane(PAR, G, 1), wc * 32 + 16 * j, lane);                           \
   }
-#define RQ_W_MMA(H, G, BH, BL)                                                                 \
-  if (RQ_X3W_DIAG != 2) {                                                                      \
-  if (RQ_X3W_PRIO) __builtin_amdgcn_s_setprio(1);                                              \
+#define RQ_W_MMA(H, G, BH, BL) /* s_setprio(1) around the cluster keeps hipcc from moving it */ \
+  __builtin_amdgcn_s_setprio(1);                                                               \
   _Pragma("unroll") for (int i = 0; i < 4; ++i) _Pragma("unroll") for (int j = 0; j < 2; ++j) { \
     floatx4v& c_ = acc[H][G][i][j];                                                            \
     c_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(BH[j], fal[i], c_, 0, 0, 0);                  \
     c_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(BL[j], fah[i], c_, 0, 0, 0);                  \
     c_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(BH[j], fah[i], c_, 0, 0, 0);                  \
   }                                                                                            \
-  if (RQ_X3W_PRIO) __builtin_amdgcn_s_setprio(0);                                              \
-  }
+  __builtin_amdgcn_s_setprio(0);
 
   // prologue, in the steady state's issue order (A of steps 0 and 1, B of step 0); phase 0 of
   // step 0 needs A0 (0) and B0 (0): B1 (0), A0 (1), A1 (1) may stay in flight
@@ -1222,14 +933,14 @@ gemm_x3w_kernel(const uint16_t* __restrict__ Ah, const uint16_t* __restrict__ Al
     if (!g1) RQ_W_VM6();
     RQ_W_BAR();
     // phase 1: (A0, B1)
-    if (RQ_X3W_DIAG != 7 || st == 0) RQ_W_READ_B(par, 1, fb1h, fb1l)
+    RQ_W_READ_B(par, 1, fb1h, fb1l)
     issue_b(1, st + 1);
     RQ_W_BAR();
     RQ_W_LGKM0();
     RQ_W_MMA(0, 1, fb1h, fb1l)
     RQ_W_BAR();
     // phase 2: (A1, B1)
-    if (RQ_X3W_DIAG != 7 || st == 0) RQ_W_READ_A(slot, 1)
+    RQ_W_READ_A(slot, 1)
     issue_a(0, st + 2, slot2);
     RQ_W_BAR();
     RQ_W_LGKM0();
@@ -1251,20 +962,6 @@ gemm_x3w_kernel(const uint16_t* __restrict__ Ah, const uint16_t* __restrict__ Al
   if (!g1) RQ_W_BAR();   // balance group 1's extra barrier
 
   float* Cs = C + (int64_t)s * M * N;   // split-K partial slab (S > 1: ldc == N)
-  if (RQ_X3W_DIAG == 3) {   // diagnostic build: no epilogue (the accumulators must look used)
-    float keep = 0.f;
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-      for (int g = 0; g < 2; ++g)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) keep += acc[h][g][i][j][0] + acc[h][g][i][j][3];
-    if (keep == 12345.678f && tid == 0) C[0] = keep;
-    return;
-  }
-#if RQ_X3W_EPI_LDS
   // Epilogue through LDS, one 128-row half of the tile at a time (128 KiB): the waves scatter their
   // accumulator quads into a [128][256] fp32 image (16-B chunk c of row r at c ^ (r & 15): the
   // 16 rows of a quad store and the 16 chunks of a row read hit distinct bank groups), then each
@@ -1301,7 +998,7 @@ gemm_x3w_kernel(const uint16_t* __restrict__ Ah, const uint16_t* __restrict__ Al
         const int r = wave * 16 + q, m = m0 + 128 * h + r;
         const floatx4v a = *reinterpret_cast<const floatx4v*>(img + r * 256 + 4 * (lane ^ (r & 15)));
         if (m < M && n < N)
-          x3_epi4z<EPI, DROP, RQ_X3W_NT>(make_float4(a[0], a[1], a[2], a[3]), zin[q], m, n, N, C, Cs, ldc, ep);
+          x3_epi4z<EPI, DROP, true>(make_float4(a[0], a[1], a[2], a[3]), zin[q], m, n, N, C, Cs, ldc, ep);
       }
     } else {   // store-only epilogues (the accumulating store's C read stays per row: unsplit wide calls only)
       __syncthreads();
@@ -1309,83 +1006,36 @@ gemm_x3w_kernel(const uint16_t* __restrict__ Ah, const uint16_t* __restrict__ Al
       for (int q = 0; q < 16; ++q) {
         const int r = wave * 16 + q, m = m0 + 128 * h + r;
         const floatx4v a = *reinterpret_cast<const floatx4v*>(img + r * 256 + 4 * (lane ^ (r & 15)));
-        if (m < M && n < N) x3_epi4<EPI, DROP, RQ_X3W_NT>(make_float4(a[0], a[1], a[2], a[3]), m, n, N, C, Cs, ldc, ep);
+        if (m < M && n < N) x3_epi4<EPI, DROP, true>(make_float4(a[0], a[1], a[2], a[3]), m, n, N, C, Cs, ldc, ep);
       }
     }
     __syncthreads();
   }
-#else
-#pragma unroll
-  for (int h = 0; h < 2; ++h)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int m = m0 + 128 * h + wr * 64 + 16 * i + (lane & 15);
-      if (m >= M) continue;
-#pragma unroll
-      for (int g = 0; g < 2; ++g)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const int n = n0 + 128 * g + wc * 32 + 16 * j + 4 * (lane >> 4);
-          if (n >= N) continue;
-          const floatx4v a = acc[h][g][i][j];
-          x3_epi4<EPI, DROP>(make_float4(a[0], a[1], a[2], a[3]), m, n, N, C, Cs, ldc, ep);
-        }
-    }
-#endif
 }
 #undef RQ_W_BAR
 #undef RQ_W_VM6
 #undef RQ_W_LGKM0
 
 // Split-K slab reduction with the GEMM's epilogue: element j of the (M, N) output (ldc == N) is the
-// fixed-order sum over s of P[s][j] (wave w sums s = w, w + 4, ...; the four wave partials are added
-// in wave order: deterministic, no atomics), then (ACC) plus the current C[j], then the epilogue of
-// x3_epi4 at (m, n) = (j / N, j % N). Lets every epilogue — SiLU fwd / bwd with dropout, residual
+// fixed-order sum over s of P[s][j] (slab_sum_w4: the partial sums of s = w, w + 4, ... for w = 0..3,
+// added in that order by one thread per float4 column: deterministic, no atomics), then (ACC) plus the
+// current C[j], then the epilogue of x3_epi4 at (m, n) = (j / N, j % N). Lets every epilogue — SiLU fwd / bwd with dropout, residual
 // add, accumulation into an existing gradient — use split-K when the output tiles cannot fill the
 // chip (the decoder's 1,280 future-token rows: 40 tiles of 128 x 128).
-#ifndef RQ_SLAB_THREAD
-#define RQ_SLAB_THREAD 1   // 0: four waves over s per float4 column combined through LDS (the round-4 form)
-#endif
-constexpr int kRedColsPerWg = RQ_SLAB_THREAD ? 256 : 64;   // float4 columns per workgroup (layout 0)
+constexpr int kRedColsPerWg = 256;   // float4 columns per workgroup (layout 0)
 
 template <int EPI, bool DROP, bool ACC>
 __global__ void __launch_bounds__(256) x3_reduce_kernel(const float* __restrict__ P, int S, int64_t n, int N,
                                                         float* __restrict__ C, X3Epilogue ep) {
   ep.seed = epoch_seed(ep.seed);
-#if RQ_SLAB_THREAD   // one thread per float4 column, the same order (slab_sum_w4)
-  {
-    const int64_t j = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    if (j >= n) return;
-    float4 r = slab_sum_w4(P, S, n, j);
-    if constexpr (ACC) {
-      const float4 c = *reinterpret_cast<const float4*>(C + j);
-      r = make_float4(c.x + r.x, c.y + r.y, c.z + r.z, c.w + r.w);
-    }
-    x3_epi4<EPI, DROP>(r, (int)(j / N), (int)(j % N), N, C, C, N, ep);
-    return;
+  const int64_t j = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (j >= n) return;
+  float4 r = slab_sum_w4(P, S, n, j);
+  if constexpr (ACC) {
+    const float4 c = *reinterpret_cast<const float4*>(C + j);
+    r = make_float4(c.x + r.x, c.y + r.y, c.z + r.z, c.w + r.w);
   }
-#endif
-  __shared__ float4 part[4][64];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int64_t j = ((int64_t)blockIdx.x * 64 + lane) * 4;
-  const bool ok = j < n;
-  float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (ok) a = strided_slab_sum(P, S, n, j, wave, 4);
-  part[wave][lane] = a;
-  __syncthreads();
-  if (wave == 0 && ok) {
-    float4 r = part[0][lane];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) {
-      const float4 v = part[w][lane];
-      r.x += v.x; r.y += v.y; r.z += v.z; r.w += v.w;
-    }
-    if constexpr (ACC) {
-      const float4 c = *reinterpret_cast<const float4*>(C + j);
-      r = make_float4(c.x + r.x, c.y + r.y, c.z + r.z, c.w + r.w);
-    }
-    x3_epi4<EPI, DROP>(r, (int)(j / N), (int)(j % N), N, C, C, N, ep);
-  }
+  x3_epi4<EPI, DROP>(r, (int)(j / N), (int)(j % N), N, C, C, N, ep);
 }
 
 // Elementwise split (weights once per step, a large chain input once per step). HBM-bound: 4 B
@@ -1466,15 +1116,32 @@ struct X3Plan {
 
 static int x3_slots() { return resident_slots() / 2 * kXWG; }
 
-#ifndef RQ_X3_SLAB_MB
-#define RQ_X3_SLAB_MB 64   // split-K: slab bytes (S x M x N fp32) allowed beyond RQ_X3_MAX_SPLIT slabs
-#endif
-// Split-K count cap: RQ_X3_MAX_SPLIT slabs, or more while the slabs stay within RQ_X3_SLAB_MB — the
+// ---------------------------------------------------------------------------------------------
+// The planner's constants: split-K limits and the time model's measured rates.
+// ---------------------------------------------------------------------------------------------
+constexpr int kX3MaxSplit = 64;      // split-K: at most this many k chunks
+constexpr int kX3MinStages = 2;      // split-K: k-stages per workgroup at least (fewer slabs to reduce)
+constexpr int kX3SlabMB = 64;        // split-K: slab bytes (S x M x N fp32) allowed beyond kX3MaxSplit slabs
+constexpr int kX3WMinSteps = 8;      // split-K of the wide kernel: k steps per workgroup at least
+// Per-CU rates of the time model (x3_plan_time), M fp32-MAC / us:
+constexpr double kX3Rate2 = 0.53;    // 128-tile kernel, its two workgroups per CU
+constexpr double kX3Rate1 = 0.4;     // 128-tile kernel, a lone workgroup
+constexpr double kX3WSpeed = 1.3;    // wide kernel: this multiple of kX3Rate2
+constexpr double kX3SRate1 = 0.3;    // 64-tile kernel, one workgroup per CU
+constexpr double kX3SRate2 = 0.35;   // 64-tile kernel, kXWG64 workgroups per CU
+// Modelled cost (us) of the separate slab-reduction launch of a split-K call: the reduction kernel plus the
+// gap it adds between launches in a replayed step (4 us measured best of 4 / 8 / 16 at both decoder
+// configs in round 3 with whole rounds, profiles/r03/reduce_us_ab.txt; 3 with the fractional rounds, fitted
+// on the round-5 plan sweeps: a back-to-back tiny launch costs ~2.7 us in a replayed graph).
+constexpr double kX3ReduceUs = 3.0;
+constexpr double kX3SlabBpus = 3.0e6;   // slab bytes per us (written + read back)
+
+// Split-K count cap: kX3MaxSplit slabs, or more while the slabs stay within kX3SlabMB MiB — the
 // small weight grads (e.g. 128 x 64 over 65,536 rows: one output tile) need hundreds of k chunks to
 // cover the chip, and their slabs are tiny.
 static int64_t x3_split_cap(int64_t M, int64_t N) {
-  const int64_t by_bytes = ((int64_t)RQ_X3_SLAB_MB << 20) / (4 * M * N);
-  return by_bytes > RQ_X3_MAX_SPLIT ? by_bytes : RQ_X3_MAX_SPLIT;
+  const int64_t by_bytes = ((int64_t)kX3SlabMB << 20) / (4 * M * N);
+  return by_bytes > kX3MaxSplit ? by_bytes : kX3MaxSplit;
 }
 
 // The 64-tile form's compact LDS (32 KiB) lets 4 workgroups share a CU. A launch that fits in 2 per CU
@@ -1482,11 +1149,11 @@ static int64_t x3_split_cap(int64_t M, int64_t N) {
 // than packing them 4 per CU onto fewer CUs (measured: 1280 x 1536 x 512, 480 workgroups: 14.5 us spread,
 // 24.8 us packed; 26,880 x 384 x 1152, 2,520 workgroups: 122.6 -> 109.1 us at 4 per CU).
 static int x3s_resident(int64_t wgs) {
-  return RQ_X3S_COMPACT && wgs > (int64_t)resident_slots() ? kXWG64 : kXWG;
+  return wgs > (int64_t)resident_slots() ? kXWG64 : kXWG;
 }
 template <typename P>
 static unsigned x3s_pad_lds(const P& pl) {
-  return RQ_X3S_COMPACT && x3s_resident((int64_t)pl.tiles * pl.S) == kXWG ? 32768u : 0u;
+  return x3s_resident((int64_t)pl.tiles * pl.S) == kXWG ? 32768u : 0u;
 }
 
 // Modelled time (us) of a plan, to choose the split-K factor and between the two kernels:
@@ -1498,49 +1165,28 @@ static unsigned x3s_pad_lds(const P& pl) {
 //    256 x 256 tiles quantise into 4x coarser rounds (decoder context rows: a 1,536-wide projection is
 //    270 wide tiles, two rounds, the second nearly empty);
 //  * split-K: the slabs written by the GEMM and read back by the reduction, 2 S M N fp32 at ~3 TB/s (the
-//    rate the batched deferred reductions reach), plus a ~4 us reduce launch. Round 4 priced (S + 1) M N at
+//    rate the batched deferred reductions reach), plus the reduce launch (kX3ReduceUs). Round 4 priced (S + 1) M N at
 //    5 TB/s, which chose 256 x 256-tile plans with S = 21..30 for the decoder's 11k-row weight gradients:
 //    ~64 MB of slabs per weight, 444 MB (C4) / 800 MB (Amazon) a step. Same-process A/B on MI355X: C4
 //    2.766 -> 2.678 ms, Amazon 5.415 -> 5.355, RQ-VAE 1.957 -> 1.924 (half the rate, 1.5 TB/s, loses).
 // Checked against tools/gemm_ab.py on MI355X (RQ-VAE and decoder shapes, both kernels forced).
-#ifndef RQ_X3W_SPEED
-#define RQ_X3W_SPEED 1.3
-#endif
-#ifndef RQ_X3S_RATE1
-#define RQ_X3S_RATE1 0.3    // 64-tile kernel, one workgroup per CU: M fp32-MAC / us
-#endif
-#ifndef RQ_X3S_RATE2
-#define RQ_X3S_RATE2 0.35   // 64-tile kernel, kXWG64 workgroups per CU
-#endif
-// Modelled cost (us) of the separate slab-reduction launch of a split-K call: the reduction kernel plus the
-// gap it adds between launches in a replayed step (4 us measured best of 4 / 8 / 16 at both decoder
-// configs in round 3, profiles/r03/reduce_us_ab.txt; 3 with the fractional rounds, fitted on the round-5
-// plan sweeps: a back-to-back tiny launch costs ~2.7 us in a replayed graph).
-#ifndef RQ_X3_FRAC_ROUNDS
-#define RQ_X3_FRAC_ROUNDS 1   // 0: whole rounds and a 4 us reduction (the model before the round-5 sweeps; A/B)
-#endif
-constexpr double kX3ReduceUs = RQ_X3_FRAC_ROUNDS ? 3.0 : 4.0;
-#ifndef RQ_X3_SLAB_BPUS
-#define RQ_X3_SLAB_BPUS 3.0e6   // slab bytes per us (written + read back)
-#endif
 static double x3_plan_time(const X3Plan& p, int64_t M, int64_t N, bool wide) {
   const int64_t cus = resident_slots() / 2;
   const int64_t wgs = (int64_t)p.tiles * p.S;
   const bool small = p.ts == 64;
   const double tile = wide ? (double)kWT2 * kWT2 : (double)p.ts * p.ts;
-  const double rate = small ? RQ_X3S_RATE2 : 0.53 * (wide ? RQ_X3W_SPEED : 1.0);   // M MAC / us per CU
+  const double rate = small ? kX3SRate2 : kX3Rate2 * (wide ? kX3WSpeed : 1.0);   // M MAC / us per CU
   double t;
   if (wgs <= cus) {   // at most one workgroup per CU
-    t = tile * (double)p.chunk / ((wide ? rate : (small ? RQ_X3S_RATE1 : 0.4)) * 1e6);
+    t = tile * (double)p.chunk / ((wide ? rate : (small ? kX3SRate1 : kX3Rate1)) * 1e6);
   } else {
     const int per_cu = wide ? 1 : (small ? x3s_resident(wgs) : kXWG);
     const int64_t slots = cus * per_cu;
     // a partly filled last round costs its share; one round at least
-    const double rounds = !RQ_X3_FRAC_ROUNDS ? (double)((wgs + slots - 1) / slots)
-                                             : (wgs > slots ? (double)wgs / (double)slots : 1.0);
+    const double rounds = wgs > slots ? (double)wgs / (double)slots : 1.0;
     t = rounds * per_cu * tile * (double)p.chunk / (rate * 1e6);
   }
-  if (p.S > 1) t += (double)(2 * p.S) * (double)(M * N) * 4.0 / RQ_X3_SLAB_BPUS + kX3ReduceUs;
+  if (p.S > 1) t += (double)(2 * p.S) * (double)(M * N) * 4.0 / kX3SlabBpus + kX3ReduceUs;
   return t;
 }
 
@@ -1566,7 +1212,7 @@ static X3Plan x3_plan_t(int64_t M, int64_t N, int64_t K, bool allow_split, int t
   const int64_t slots_t = (int64_t)(resident_slots() / 2) * kXWG;   // split-K fills the 2-per-CU slots
   if (allow_split && p.tiles < slots_t / 2 && (M * N) % 4 == 0) {   // slab reduction reads float4
     int64_t S = slots_t / p.tiles;
-    const int64_t max_s = (K + RQ_X3_MIN_STAGES * kXK - 1) / (RQ_X3_MIN_STAGES * kXK);   // min stages per workgroup
+    const int64_t max_s = (K + kX3MinStages * kXK - 1) / (kX3MinStages * kXK);   // min stages per workgroup
     if (S > max_s) S = max_s;
     if (S > x3_split_cap(M, N)) S = x3_split_cap(M, N);   // slab traffic of the reduction grows with S
     if (ts == 64) {   // small tiles: the best of S = 2, 4, ... up to the one-round heuristic
@@ -1586,19 +1232,13 @@ static X3Plan x3_plan_t(int64_t M, int64_t N, int64_t K, bool allow_split, int t
 // 128-tile kernel, or its 64-tile form where the time model prefers it (the 128-tiles of a
 // 1,280-row operand are 40 workgroups: split-K slabs and their reduction cost more than the GEMM).
 // flags (the call's rq_gemm_desc.flags): RQ_GEMM_ONLY_128 / RQ_GEMM_ONLY_64 pin one tile size.
-#ifndef RQ_X3_SHORTK_64
-#define RQ_X3_SHORTK_64 1   // 0: the time model picks the tile size for K <= 128 too
-#endif
-#ifndef RQ_X3_SKINNY_UNSPLIT
-#define RQ_X3_SKINNY_UNSPLIT 1   // 0: the time model decides split-K for one-row-of-tiles, short-K calls too
-#endif
 
 static X3Plan x3_plan(int64_t M, int64_t N, int64_t K, int flags, bool allow_split = true, int epilogue = 0) {
   // One row of 64-tiles (the C4 decoder's 40 future-token rows) over K <= 384 with a plain or residual
   // epilogue: unsplit. Measured per call (profiles/r05/plan_sweep2/sweep_c4.jsonl, hipGraph of 10 calls with
   // their reductions): 6.7-7.2 us unsplit vs 7.1-7.3 at the model's S = 6 plus a reduction launch per call
   // — the model underprices the short-K workgroups' fixed latency; the SiLU epilogues keep the model's split.
-  if (RQ_X3_SKINNY_UNSPLIT && !(flags & (RQ_GEMM_ONLY_128 | RQ_GEMM_ONLY_64)) && M <= 64 && K <= 384 &&
+  if (!(flags & (RQ_GEMM_ONLY_128 | RQ_GEMM_ONLY_64)) && M <= 64 && K <= 384 &&
       (epilogue == kEpiStore || epilogue == kEpiAdd))
     allow_split = false;
   const X3Plan p = x3_plan_t(M, N, K, allow_split, kXT);
@@ -1609,13 +1249,9 @@ static X3Plan x3_plan(int64_t M, int64_t N, int64_t K, int flags, bool allow_spl
   // per-workgroup prologue / epilogue latency that such short k loops cannot — measured faster than the
   // 128-tile kernel for every short-K call of the three bench steps (plan_sweep2: RQ-VAE 65,536 x 128 x 64
   // SiLU' epilogue 27.6 -> 20.6 us, SiLU 23.4 -> 22.0; Amazon 11,520 x 512 x 128 14.6 -> 13.8)
-  if (RQ_X3_SHORTK_64 && K <= 128) return q;
+  if (K <= 128) return q;
   return x3_plan_time(q, M, N, false) < x3_plan_time(p, M, N, false) ? q : p;
 }
-
-#ifndef RQ_X3W_MIN_STEPS
-#define RQ_X3W_MIN_STEPS 8   // split-K of the wide kernel: k steps per workgroup at least
-#endif
 
 // Plan of the wide kernel, or false when the 128-tile kernel serves the shape better: k steps
 // must be whole (K % 32), padding of a partial 256-row tile must stay small (R % 256 == 0 or
@@ -1628,7 +1264,7 @@ static bool x3w_plan(int64_t M, int64_t N, int64_t K, bool allow_split, X3Plan* 
   *p = x3_plan_s(M, N, K, 1, true);
   if (allow_split && p->tiles < cus / 2 && (M * N) % 4 == 0) {
     int64_t S = cus / p->tiles;
-    const int64_t max_s = K / (32 * RQ_X3W_MIN_STEPS);
+    const int64_t max_s = K / (32 * kX3WMinSteps);
     if (S > max_s) S = max_s;
     if (S > x3_split_cap(M, N)) S = x3_split_cap(M, N);
     if (S > 1) {
@@ -1639,7 +1275,7 @@ static bool x3w_plan(int64_t M, int64_t N, int64_t K, bool allow_split, X3Plan* 
   return (int64_t)p->tiles * p->S >= cus / 4;
 }
 
-// Elements one wide workgroup's operand DMA spans from its descriptor base (RQ_X3W_BUFLDS: 32-bit byte offsets):
+// Elements one wide workgroup's operand DMA spans from its descriptor base (32-bit byte offsets):
 // 256 rows of a k-contiguous operand (+ K), or one k chunk of rows of an m/n-contiguous one (+ its rows).
 static int64_t x3w_span(int64_t R, int64_t K, int64_t ld, bool kc, int64_t chunk) {
   return kc ? (int64_t)kWT2 * ld + K : (chunk + 32) * ld + R;
@@ -2018,7 +1654,7 @@ static bool x3_pair_launch(const X3Call& c1, const X3Call& c2, hipStream_t s) {
   const dim3 grid((unsigned)(n1 + n2));
   const bool t64 = c1.pl.ts == 64;
   unsigned pad = 0;
-  if (t64 && RQ_X3S_COMPACT && x3s_resident(w1 + w2) == kXWG) pad = 32768u;   // few workgroups: 2 per CU (x3s_pad_lds)
+  if (t64 && x3s_resident(w1 + w2) == kXWG) pad = 32768u;   // few workgroups: 2 per CU (x3s_pad_lds)
   if (x3_fwd_form(c1) && x3_fwd_form(c2))
     return t64 ? x3_pair_fwd_ts<64>(c1, c2, grid, pad, s, n1) : x3_pair_fwd_ts<128>(c1, c2, grid, 0u, s, n1);
   const int k1 = x3_pair_k1(c1);
@@ -2100,8 +1736,8 @@ int rq_gemm_bf16x3_pair_plan(const rq_gemm_desc* d) {
 }
 
 // Deferred partial reductions, many in one launch: out_i[j] (+)= sum_s P_i[s n_i + j] for every entry i,
-// each in the SAME order as the reduction it replaces — layout 0 = x3_reduce_kernel's (4 wave lanes over
-// s, combined in wave order; a workgroup owns 64 float4 columns), layout 1 = rms_reduce_kernel's (64 lanes
+// each in the SAME order as the reduction it replaces — layout 0 = x3_reduce_kernel's (slab_sum_w4, one
+// thread per float4 column; a workgroup owns 256 of them), layout 1 = rms_reduce_kernel's (64 lanes
 // over s, fixed LDS tree; 4 float4 columns) — so a deferred result is bitwise the immediate one.
 constexpr int kRedSegMax = 48;
 struct RedSegTable {
@@ -2126,7 +1762,7 @@ __global__ void __launch_bounds__(256) reduce_partials_kernel(RedSegTable t) {
   const int64_t n = t.n[e];
   const int S = t.S[e];
   const int tid = threadIdx.x;
-  if (t.layout[e] == 0 && RQ_SLAB_THREAD) {   // one thread per float4 column (slab_sum_w4: the same order)
+  if (t.layout[e] == 0) {   // one thread per float4 column (slab_sum_w4: the same order)
     const int64_t j = ((int64_t)lb * 256 + tid) * 4;
     if (j >= n) return;
     float4 r = slab_sum_w4(P, S, n, j);
@@ -2135,27 +1771,6 @@ __global__ void __launch_bounds__(256) reduce_partials_kernel(RedSegTable t) {
       r = make_float4(c.x + r.x, c.y + r.y, c.z + r.z, c.w + r.w);
     }
     *reinterpret_cast<float4*>(out + j) = r;
-  } else if (t.layout[e] == 0) {
-    const int wave = tid >> 6, lane = tid & 63;
-    const int64_t j = ((int64_t)lb * 64 + lane) * 4;
-    const bool ok = j < n;
-    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (ok) a = strided_slab_sum(P, S, n, j, wave, 4);
-    red[wave * 64 + lane] = a;
-    __syncthreads();
-    if (wave == 0 && ok) {
-      float4 r = red[lane];
-#pragma unroll
-      for (int w = 1; w < 4; ++w) {
-        const float4 v = red[w * 64 + lane];
-        r.x += v.x; r.y += v.y; r.z += v.z; r.w += v.w;
-      }
-      if (t.acc[e]) {
-        const float4 c = *reinterpret_cast<const float4*>(out + j);
-        r = make_float4(c.x + r.x, c.y + r.y, c.z + r.z, c.w + r.w);
-      }
-      *reinterpret_cast<float4*>(out + j) = r;
-    }
   } else {
     constexpr int kC = 4, kQ = 256 / kC;
     const int c = tid % kC, q = tid / kC;

@@ -611,9 +611,6 @@ __global__ void __launch_bounds__(256) rq_segsum_finalize_kernel(const int* __re
 // deterministic with no atomics. The
 // image goes to partial[l][c] (zeros where the chunk has no row of k); rq_cb_chunk_reduce sums the chunks in
 // c order (four interleaved partial sums, slab_sum_w4). Lane = VPL consecutive dims (D = 64 VPL).
-#ifndef RQ_CB_CHUNK
-#define RQ_CB_CHUNK 1   // 0: the sort + segmented-sum codebook gradient for every mode (A/B)
-#endif
 constexpr int kCbRows = 1024;   // rows per workgroup
 constexpr int kCbWaves = 16, kCbBatch = 16;
 constexpr int kCbList = 256;   // match-list entries per wave (a skewed chunk drains it more often)
@@ -1720,7 +1717,7 @@ int rq_quantize_bwd(const float* residuals, const int64_t* ids, const float* cod
     default: RQ_CHECK_ARG(false, "rq_quantize_bwd: unsupported D");
   }
   RQ_LAUNCH_CHECK("rq_bwd_rows");
-  if (RQ_CB_CHUNK && cb_chunk_path(B, D, K, mode, g_qloss)) {
+  if (cb_chunk_path(B, D, K, mode, g_qloss)) {
     float* partial = (float*)(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
     const int nchunk = (int)cb_chunks(B);
     const size_t lds = (size_t)K * D * sizeof(float) + kCbRows * sizeof(int) + kCbWaves * kCbList * sizeof(unsigned short);
