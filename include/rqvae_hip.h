@@ -440,6 +440,41 @@ int varlen_attn_bwd(const float* q, int64_t sq, const float* k, int64_t sk, cons
                     float scale, float* dq, int64_t sdq, float* dk, int64_t sdk, float* dv, int64_t sdv, int64_t Tk,
                     float* delta, float* ws, int64_t ws_elems, int flags, void* stream);
 
+/* Decoder evaluation (csrc/beam.hip): one beam step of EncoderDecoderRetrievalModel.generate_next_sem_id
+ * (modules/model.py:176-201) in two launches, and the Hit@k counters of TopKAccumulator.accumulate
+ * (evaluate/metrics.py:15-28). No call allocates or synchronises; all are graph-capturable.
+ *
+ * rq_beam_candidates: per row of logits (R, V) fp32, p = softmax(logits / temperature) (model.py:177) and the
+ *   score s_v = p_v / noise[r][v] (noise (R, V) fp32, or NULL: s_v = p_v). cand_ids (R, n_cand) int64 = the n_cand
+ *   classes of largest score, descending, ties to the lower class; cand_lp (R, n_cand) fp32 = log p of each (-inf
+ *   where p underflows to 0; otherwise formed as (z - max) - log1p(sum of the other exponentials), which is
+ *   log p to fp32 relative precision also where one class takes nearly all the mass). With Exponential(1)
+ *   noise the ids are distributed as torch.multinomial(p, n_cand, replacement=False) (model.py:178, the
+ *   exponential-race form torch itself uses); without noise they are the n_cand most probable classes.
+ *   1 <= n_cand <= V <= 4096, temperature > 0.
+ * rq_beam_select: per batch element b the k best of its N = kprev * n_cand candidates (cand_ids / cand_lp viewed as
+ *   (B, N); candidate e continues parent beam e / n_cand). parents (B, kprev, P) int64 and parent_lp (B, kprev) fp32
+ *   are the beams so far (both NULL when P == 0, the first step). Validity of a candidate comes from exactly one of
+ *   valid ((B, N) bool, the result of any inference_verifier_fn) and keys (n_keys sorted unique int64: the packed
+ *   corpus prefixes of length P + 1, SemanticIdTokenizer.prefix_table; the kernel packs (parent prefix, candidate) in
+ *   base `base`, every element required in [0, base), and binary-searches it; a global flat candidate index b N + e
+ *   >= checked is invalid — the reference's exists_prefix skips its last partial batch of 16, semids.py:105-120;
+ *   checked = B N switches that off). score = ((valid ? 0 : -10000) + cand_lp) + parent_lp (model.py:190-194, that
+ *   fp32 order); out_lp (B, k) = the k largest scores, descending, ties to the lower e (a stable sort); out_ids
+ *   (B, k, P + 1) = the parent's prefix followed by the candidate id. 1 <= k <= N <= 8192, P < 64.
+ * rq_topk_hits: actual (B, D) int64 targets, topk (B, k, D) int64 beams, ks: HOST array of n_ks ints (copied into the
+ *   kernel arguments). counts (2, D, n_ks) int64 is ACCUMULATED into (the caller zeroes it once):
+ *   counts[0][i][j] += #rows whose first beam equal to the target in columns 0..i has rank < ks[j] (h@k_slice_:i+1),
+ *   counts[1][i][j] the same for column i alone (h@k_pos_i). D <= 64, n_ks <= 8. */
+int rq_beam_candidates(const float* logits, const float* noise, int64_t R, int64_t V, int64_t n_cand,
+                       float temperature, int64_t* cand_ids, float* cand_lp, void* stream);
+int rq_beam_select(const int64_t* cand_ids, const float* cand_lp, const bool* valid, const int64_t* keys,
+                   int64_t n_keys, int64_t base, int64_t checked, const int64_t* parents, const float* parent_lp,
+                   int64_t B, int64_t kprev, int64_t n_cand, int64_t P, int64_t k, int64_t* out_ids, float* out_lp,
+                   void* stream);
+int rq_topk_hits(const int64_t* actual, const int64_t* topk, int64_t B, int64_t k, int64_t D, const int* ks,
+                 int64_t n_ks, int64_t* counts, void* stream);
+
 /* AdamW step (torch.optim.AdamW as stepped by train_rqvae.py:168-172 / train_decoder.py:203) over
  * every fp32 parameter of a group, one launch per 64 tensors. segs: HOST array of nseg records of 5
  * int64 {p, g, exp_avg, exp_avg_sq (device pointers), n}; it is copied into the kernel arguments, so

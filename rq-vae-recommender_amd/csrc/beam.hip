@@ -1,0 +1,352 @@
+// Decoder evaluation on the device: the per-step beam logic of generate_next_sem_id (reference
+// modules/model.py:176-201) in two launches, and the Hit@k counters of evaluate/metrics.py:15-28.
+//
+//   beam_candidates_kernel  one wave per logits row: softmax(logits / T), optional Exponential(1) noise
+//                           (score p / noise: the n_cand largest are a draw of multinomial without
+//                           replacement), the n_cand best classes by rank counting out of LDS.
+//   beam_select_kernel      one workgroup per batch element: prefix verification (a caller-provided mask or
+//                           a binary search of the tokenizer's packed-prefix table), the cumulative score,
+//                           the k best of the kprev * n_cand candidates in stable order, the parent gather.
+//   topk_hits_kernel        one wave per batch row: first matching beam rank per sem-ID slice / position,
+//                           counters accumulated on the device with one atomic per (wave, counter).
+#include "common.h"
+
+namespace rqhip {
+
+constexpr int kBeamMaxV = 4096;
+constexpr int kBeamMaxN = 8192;
+constexpr int kHitsMaxD = 64;
+constexpr int kHitsMaxKs = 8;
+constexpr int kNoRank = 0x7fffffff;   // no beam matched
+
+// ------------------------------------------------------------------------------------- candidates
+// (max, lowest index of the max) over the wave; NaN never wins a comparison, so a row with a NaN keeps the
+// max of its other entries (its NaN entries then score lowest, below).
+__device__ __forceinline__ void wave_argmax(float& m, int& idx) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const float om = __shfl_xor(m, o, 64);
+    const int oi = __shfl_xor(idx, o, 64);
+    if (om > m || (om == m && oi < idx)) { m = om; idx = oi; }
+  }
+}
+
+// LDS per wave: d[Vp] (z - max, the log of the unnormalised probability) then s[Vp] (the scores), Vp = V
+// rounded up to 4. Every lane owns the classes v = lane + 64 j.
+__global__ void __launch_bounds__(256) beam_candidates_kernel(const float* __restrict__ logits,
+                                                              const float* __restrict__ noise, int64_t R, int V,
+                                                              int Vp, int n_cand, float temperature,
+                                                              int64_t* __restrict__ cand_ids,
+                                                              float* __restrict__ cand_lp) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
+  float* d = reinterpret_cast<float*>(smem) + (size_t)wave * 2 * Vp;
+  float* s = d + Vp;
+  const int64_t row_raw = (int64_t)blockIdx.x * waves + wave;
+  const bool live = row_raw < R;
+  const int64_t row = live ? row_raw : R - 1;   // idle waves repeat the last row (uniform barriers), write nothing
+  const float* x = logits + row * V;
+
+  float m = -INFINITY;
+  int am = 0x7fffffff;
+  for (int v = lane; v < V; v += 64) {
+    const float z = x[v] / temperature;
+    d[v] = z;
+    if (z > m) { m = z; am = v; }
+  }
+  wave_argmax(m, am);
+  // sum of the other classes' exp(z - max): the max class contributes exactly 1, so log p = (z - max) -
+  // log1p(rest) keeps full relative precision where one class dominates (log p -> -rest, not log(1.0f) = 0)
+  float rest = 0.f;
+  for (int v = lane; v < V; v += 64) {
+    const float dv = d[v] - m;
+    d[v] = dv;
+    if (v != am) rest += expf(dv);
+  }
+  rest = group_sum<64>(rest);
+  const float sum = rest + 1.0f;
+  for (int v = lane; v < Vp; v += 64) {
+    float sc = -2.0f;   // padding: below every real score
+    if (v < V) {
+      const float p = expf(d[v]) / sum;
+      sc = noise ? p / noise[row * V + v] : p;
+      if (!(sc == sc)) sc = -1.0f;   // NaN (a NaN logit, 0 / 0): ranked last, ties by index — ranks stay a permutation
+    }
+    s[v] = sc;
+  }
+  __syncthreads();
+  const float log_norm = log1pf(rest);
+  const float4* s4 = reinterpret_cast<const float4*>(s);
+  for (int v0 = lane; v0 < V; v0 += 256) {
+    float sv[4];
+    int vi[4], cnt[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      vi[j] = v0 + 64 * j;
+      sv[j] = vi[j] < V ? s[vi[j]] : INFINITY;
+      cnt[j] = 0;
+    }
+    for (int u4 = 0; u4 < Vp / 4; ++u4) {
+      const float4 q = s4[u4];
+      const float su[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const int u = 4 * u4 + t;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) cnt[j] += (su[t] > sv[j]) || (su[t] == sv[j] && u < vi[j]);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (live && vi[j] < V && cnt[j] < n_cand) {
+        const float dv = d[vi[j]];
+        const float p = expf(dv) / sum;
+        cand_ids[row * n_cand + cnt[j]] = vi[j];
+        cand_lp[row * n_cand + cnt[j]] = p == 0.f ? -INFINITY : dv - log_norm;
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------- select
+// float -> uint32 whose unsigned order is the float order (NaN on top, as torch.sort(descending) places
+// it); 0 is below every float's key and marks a taken candidate.
+__device__ __forceinline__ uint32_t score_key(float f) {
+  if (f != f) return 0xFFFFFFFFu;
+  const uint32_t b = __builtin_bit_cast(uint32_t, f);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float key_score(uint32_t k) {
+  if (k == 0xFFFFFFFFu) return NAN;
+  return __builtin_bit_cast(float, (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
+}
+// best = larger key, then lower candidate index
+__device__ __forceinline__ bool better(uint32_t ka, int ia, uint32_t kb, int ib) {
+  return ka > kb || (ka == kb && ia < ib);
+}
+
+constexpr int kSelThreads = 256;
+
+// Selection: k rounds of a workgroup argmax. A thread owns the candidates e = tid + 256 j (at most 32) and
+// keeps the best of them cached; a round is one wave reduction, one 4-entry exchange through LDS, and a
+// rescan by the single thread that owned the winner — about k (12 shuffles + 2 barriers + 32 LDS reads)
+// for k = 32, N = 6400, against N log^2 N / 256 ~ 2000 compare-exchange steps with a barrier each for an
+// LDS bitonic sort of 8192 keys.
+__global__ void __launch_bounds__(kSelThreads) beam_select_kernel(
+    const int64_t* __restrict__ cand_ids, const float* __restrict__ cand_lp, const bool* __restrict__ valid,
+    const int64_t* __restrict__ keys, int64_t n_keys, int64_t base, int64_t checked,
+    const int64_t* __restrict__ parents, const float* __restrict__ parent_lp, int kprev, int n_cand, int P, int k,
+    int64_t* __restrict__ out_ids, float* __restrict__ out_lp) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int N = kprev * n_cand;
+  uint32_t* key = reinterpret_cast<uint32_t*>(smem);   // [N rounded up to 4], then the per-wave exchange
+  uint32_t* w_key = key + (N + 3) / 4 * 4;
+  int* w_idx = reinterpret_cast<int*>(w_key + kSelThreads / 64);
+  const int64_t b = blockIdx.x;
+  const int64_t* cid = cand_ids + b * N;
+  const float* clp = cand_lp + b * N;
+
+  uint32_t best_k = 0;
+  int best_i = 0x7fffffff;
+  for (int e = tid; e < N; e += kSelThreads) {
+    const int par = e / n_cand;
+    const int64_t c = cid[e];
+    bool ok;
+    if (valid) {
+      ok = valid[b * N + e];
+    } else {
+      // (parent prefix, candidate) packed in base `base` as semids._pack; every element must be a digit
+      const int64_t* pp = parents + (b * kprev + par) * P;
+      int64_t q = 0;
+      ok = c >= 0 && c < base && b * N + e < checked && n_keys > 0;
+      for (int j = 0; j < P; ++j) {
+        const int64_t t = pp[j];
+        ok = ok && t >= 0 && t < base;
+        q = q * base + t;
+      }
+      q = q * base + c;
+      if (ok) {
+        int64_t lo = 0, hi = n_keys;   // first key >= q
+        while (lo < hi) {
+          const int64_t mid = (lo + hi) >> 1;
+          if (keys[mid] < q) lo = mid + 1; else hi = mid;
+        }
+        ok = lo < n_keys && keys[lo] == q;
+      }
+    }
+    const float sc = ((ok ? 0.0f : -10000.0f) + clp[e]) + (parent_lp ? parent_lp[b * kprev + par] : 0.0f);
+    const uint32_t kk = score_key(sc);
+    key[e] = kk;
+    if (better(kk, e, best_k, best_i)) { best_k = kk; best_i = e; }
+  }
+  // every thread rescans only its own entries of key[]: no barrier is needed for them
+
+  for (int r = 0; r < k; ++r) {
+    uint32_t wk = best_k;
+    int wi = best_i;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+      const uint32_t ok_ = __shfl_xor(wk, o, 64);
+      const int oi = __shfl_xor(wi, o, 64);
+      if (better(ok_, oi, wk, wi)) { wk = ok_; wi = oi; }
+    }
+    if (lane == 0) { w_key[wave] = wk; w_idx[wave] = wi; }
+    __syncthreads();
+    wk = w_key[0];
+    wi = w_idx[0];
+#pragma unroll
+    for (int w = 1; w < kSelThreads / 64; ++w)
+      if (better(w_key[w], w_idx[w], wk, wi)) { wk = w_key[w]; wi = w_idx[w]; }
+    __syncthreads();   // w_key / w_idx are rewritten next round
+    // k <= N: a round always finds an untaken candidate (wk != 0, wi < N)
+    if (tid == (wi % kSelThreads)) {
+      key[wi] = 0;
+      best_k = 0;
+      best_i = 0x7fffffff;
+      for (int e = tid; e < N; e += kSelThreads) {
+        const uint32_t kk = key[e];
+        if (better(kk, e, best_k, best_i)) { best_k = kk; best_i = e; }
+      }
+    }
+    if (tid == 0) out_lp[b * k + r] = key_score(wk);
+    // the winner's row: parent prefix then the candidate id
+    int64_t* o = out_ids + (b * k + r) * (P + 1);
+    if (tid < P) o[tid] = parents[(b * kprev + wi / n_cand) * P + tid];   // P < 64
+    if (tid == 0) o[P] = cid[wi];
+  }
+}
+
+// ------------------------------------------------------------------------------------- hits
+struct HitKs {
+  int v[kHitsMaxKs];
+};
+
+// Lane i < D carries column i's two first-match ranks of the current row and its counters; beams are
+// visited 64 at a time, one per lane: bit i of a lane's `pos` says its beam equals the target in column i,
+// `slice` has bit i where columns 0..i all match (the trailing ones of pos).
+__global__ void __launch_bounds__(256) topk_hits_kernel(const int64_t* __restrict__ actual,
+                                                        const int64_t* __restrict__ topk, int64_t B, int k, int D,
+                                                        HitKs ks, int n_ks,
+                                                        unsigned long long* __restrict__ counts) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  int c_slice[kHitsMaxKs], c_pos[kHitsMaxKs];
+#pragma unroll
+  for (int j = 0; j < kHitsMaxKs; ++j) c_slice[j] = c_pos[j] = 0;
+  for (int64_t row = wave; row < B; row += n_waves) {
+    const int64_t* a = actual + row * D;
+    int r_slice = kNoRank, r_pos = kNoRank;
+    for (int r0 = 0; r0 < k; r0 += 64) {
+      const int r = r0 + lane;
+      uint64_t pos = 0;
+      if (r < k) {
+        const int64_t* t = topk + (row * k + r) * D;
+        for (int i = 0; i < D; ++i) pos |= (uint64_t)(t[i] == a[i]) << i;
+      }
+      const uint64_t slice = ~pos & (pos + 1) ? (~pos & (pos + 1)) - 1 : ~0ull;
+      int missing = 0;
+      for (int i = 0; i < D; ++i) {
+        const uint64_t bp = __ballot((pos >> i) & 1);
+        const uint64_t bs = __ballot((slice >> i) & 1);
+        if (lane == i) {
+          if (r_pos == kNoRank && bp) r_pos = r0 + __ffsll((unsigned long long)bp) - 1;
+          if (r_slice == kNoRank && bs) r_slice = r0 + __ffsll((unsigned long long)bs) - 1;
+          missing = r_pos == kNoRank || r_slice == kNoRank;
+        }
+      }
+      if (!__any(missing)) break;
+    }
+#pragma unroll
+    for (int j = 0; j < kHitsMaxKs; ++j) {
+      if (j < n_ks) {
+        c_slice[j] += r_slice < ks.v[j];
+        c_pos[j] += r_pos < ks.v[j];
+      }
+    }
+  }
+  if (lane < D) {
+#pragma unroll
+    for (int j = 0; j < kHitsMaxKs; ++j) {
+      if (j < n_ks) {
+        if (c_slice[j]) atomicAdd(&counts[(size_t)lane * n_ks + j], (unsigned long long)c_slice[j]);
+        if (c_pos[j]) atomicAdd(&counts[((size_t)D + lane) * n_ks + j], (unsigned long long)c_pos[j]);
+      }
+    }
+  }
+}
+
+}  // namespace rqhip
+
+extern "C" {
+
+int rq_beam_candidates(const float* logits, const float* noise, int64_t R, int64_t V, int64_t n_cand,
+                       float temperature, int64_t* cand_ids, float* cand_lp, void* stream) {
+  RQ_CHECK_ARG(R >= 0 && n_cand >= 1 && n_cand <= V && V <= rqhip::kBeamMaxV,
+               "rq_beam_candidates: need R >= 0, 1 <= n_cand <= V <= %d (V=%lld, n_cand=%lld)", rqhip::kBeamMaxV,
+               (long long)V, (long long)n_cand);
+  RQ_CHECK_ARG(temperature > 0.f && temperature <= 3.0e38f, "rq_beam_candidates: temperature must be positive");
+  if (R == 0) return 0;
+  RQ_CHECK_ARG(logits && cand_ids && cand_lp, "rq_beam_candidates: null pointer");
+  const int Vp = (int)((V + 3) / 4 * 4);
+  const int waves = V <= 2048 ? 4 : 1;   // 2 Vp floats of LDS per wave, at most 64 KiB per workgroup
+  const size_t lds = (size_t)waves * 2 * Vp * sizeof(float);
+  const int64_t blocks = (R + waves - 1) / waves;
+  RQ_CHECK_ARG(blocks <= 0x7fffffff, "rq_beam_candidates: too many rows");
+  hipLaunchKernelGGL(rqhip::beam_candidates_kernel, dim3((unsigned)blocks), dim3(64 * waves), lds,
+                     (hipStream_t)stream, logits, noise, R, (int)V, Vp, (int)n_cand, temperature, cand_ids, cand_lp);
+  RQ_LAUNCH_CHECK("rq_beam_candidates");
+  return 0;
+}
+
+int rq_beam_select(const int64_t* cand_ids, const float* cand_lp, const bool* valid, const int64_t* keys,
+                   int64_t n_keys, int64_t base, int64_t checked, const int64_t* parents, const float* parent_lp,
+                   int64_t B, int64_t kprev, int64_t n_cand, int64_t P, int64_t k, int64_t* out_ids, float* out_lp,
+                   void* stream) {
+  RQ_CHECK_ARG(B >= 0 && kprev >= 1 && n_cand >= 1 && P >= 0 && P < 64, "rq_beam_select: bad shape");
+  RQ_CHECK_ARG(kprev <= rqhip::kBeamMaxN && n_cand <= rqhip::kBeamMaxN && kprev * n_cand <= rqhip::kBeamMaxN &&
+                   k >= 1 && k <= kprev * n_cand,
+               "rq_beam_select: need 1 <= k <= kprev * n_cand <= %d (k=%lld, kprev=%lld, n_cand=%lld)",
+               rqhip::kBeamMaxN, (long long)k, (long long)kprev, (long long)n_cand);
+  RQ_CHECK_ARG((valid != nullptr) != (keys != nullptr), "rq_beam_select: give exactly one of valid and keys");
+  RQ_CHECK_ARG((P == 0) ? (!parents && !parent_lp) : (parents && parent_lp),
+               "rq_beam_select: parents and parent_lp are both NULL when P == 0, both given otherwise");
+  if (keys) {
+    RQ_CHECK_ARG(n_keys >= 0 && base >= 1 && checked >= 0, "rq_beam_select: bad key table");
+    int64_t span = 1;   // base^(P+1) must fit an int64 (the packed key)
+    for (int64_t j = 0; j <= P; ++j) {
+      RQ_CHECK_ARG(span <= INT64_MAX / base, "rq_beam_select: base^(P+1) overflows int64 (base=%lld, P=%lld)",
+                   (long long)base, (long long)P);
+      span *= base;
+    }
+  }
+  if (B == 0) return 0;
+  RQ_CHECK_ARG(B <= 0x7fffffff, "rq_beam_select: too many batch elements");
+  RQ_CHECK_ARG(cand_ids && cand_lp && out_ids && out_lp, "rq_beam_select: null pointer");
+  const size_t lds = (size_t)((kprev * n_cand + 3) / 4 * 4 + 2 * (rqhip::kSelThreads / 64)) * sizeof(uint32_t);
+  hipLaunchKernelGGL(rqhip::beam_select_kernel, dim3((unsigned)B), dim3(rqhip::kSelThreads), lds, (hipStream_t)stream,
+                     cand_ids, cand_lp, valid, keys, n_keys, base, checked, parents, parent_lp, (int)kprev, (int)n_cand,
+                     (int)P, (int)k, out_ids, out_lp);
+  RQ_LAUNCH_CHECK("rq_beam_select");
+  return 0;
+}
+
+int rq_topk_hits(const int64_t* actual, const int64_t* topk, int64_t B, int64_t k, int64_t D, const int* ks,
+                 int64_t n_ks, int64_t* counts, void* stream) {
+  RQ_CHECK_ARG(B >= 0 && k >= 1 && k <= 0x3fffffff && D >= 1 && D <= rqhip::kHitsMaxD && n_ks >= 1 &&
+                   n_ks <= rqhip::kHitsMaxKs,
+               "rq_topk_hits: need k >= 1, 1 <= D <= %d, 1 <= n_ks <= %d", rqhip::kHitsMaxD, rqhip::kHitsMaxKs);
+  RQ_CHECK_ARG(ks, "rq_topk_hits: null pointer");
+  if (B == 0) return 0;
+  RQ_CHECK_ARG(actual && topk && counts, "rq_topk_hits: null pointer");
+  rqhip::HitKs h;
+  for (int j = 0; j < rqhip::kHitsMaxKs; ++j) h.v[j] = j < n_ks ? ks[j] : 0;
+  const int64_t blocks = std::min<int64_t>((B + 3) / 4, 1024);
+  hipLaunchKernelGGL(rqhip::topk_hits_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, actual, topk,
+                     B, (int)k, (int)D, h, (int)n_ks, reinterpret_cast<unsigned long long*>(counts));
+  RQ_LAUNCH_CHECK("rq_topk_hits");
+  return 0;
+}
+
+}  // extern "C"

@@ -227,7 +227,10 @@ static bool use_bit_map(int64_t B, double keys) { return use_byte_map(B, keys); 
 size_t rq_unique_fraction_workspace(int64_t B, int64_t L, int64_t K) {
   double keys = 1;
   for (int64_t l = 0; l < L; ++l) keys *= (double)K;
-  return use_bit_map(B, keys) ? (size_t)(((int64_t)keys + 127) / 128 * 16 + 16) : table_bytes(B) + 16;
+  // The two routes never ask for the same size (bit map: a multiple of 16; table: 8 mod 16), so a caller that keeps
+  // one workspace per size (rqvae_hip.ops.unique_fraction) never hands the bit-map route, which needs zeros on
+  // entry, a buffer the table route left full of keys (K = 32, L = 3 and a 256-row table both came to 4,112 bytes).
+  return use_bit_map(B, keys) ? (size_t)(((int64_t)keys + 127) / 128 * 16 + 16) : table_bytes(B) + 24;
 }
 
 int rq_unique_fraction(const int64_t* ids, int64_t B, int64_t L, int64_t K, int64_t* out_count, float* out_frac,

@@ -61,6 +61,9 @@ class EncoderDecoderRetrievalModel(nn.Module):
         self.sem_id_dim = sem_id_dim
         self.attn_dim = attn_dim
         self.inference_verifier_fn = inference_verifier_fn
+        # optional: an object with prefix_table(P) and reference_batching (the SemanticIdTokenizer); fused
+        # generation then verifies prefixes inside its select kernel instead of calling inference_verifier_fn
+        self.inference_prefix_index = None
         self.enable_generation = False
 
         self.bos_emb = nn.Parameter(torch.rand(embedding_dim))
@@ -79,6 +82,12 @@ class EncoderDecoderRetrievalModel(nn.Module):
         self.in_proj = Linear(embedding_dim, attn_dim, bias=False)
         self.in_proj_context = Linear(embedding_dim, attn_dim, bias=False)
         self.out_proj = Linear(attn_dim, num_embeddings, bias=False)
+
+    def __setattr__(self, name, value):
+        if name == "inference_prefix_index":   # held by reference: the tokenizer must not become a submodule
+            object.__setattr__(self, name, value)
+        else:
+            super().__setattr__(name, value)
 
     @staticmethod
     def context_rows(batch: TokenizedSeqBatch, bucket=None) -> int:
@@ -185,13 +194,18 @@ class EncoderDecoderRetrievalModel(nn.Module):
     @eval_mode
     @reset_encoder_cache
     @torch.no_grad()
-    def generate_next_sem_id(self, batch: TokenizedSeqBatch, temperature: int = 1, top_k: bool = True) -> GenerationOutput:
+    def generate_next_sem_id(self, batch: TokenizedSeqBatch, temperature: int = 1, top_k: bool = True, *,
+                             fused: bool = False, sample: bool = True) -> GenerationOutput:
         """Beam-style decoding of the next item's L+1 sem-ID tokens (reference :149-245): per step
         sample 200 candidates per beam from softmax(logits / T), drop prefixes the verifier
         rejects (-10000), keep the top 32 cumulative log-probabilities. The encoder output is
         computed once and repeated per beam with the HIP jagged kernels (jagged -> padded,
-        repeat_interleave, padded -> jagged), as the reference does with torch ops."""
+        repeat_interleave, padded -> jagged), as the reference does with torch ops.
+        fused=True: each step's softmax, sampling, verification, top-k and parent gather on two HIP
+        launches (_generate_fused); sample=False then takes the most probable candidates instead of a draw."""
         assert self.enable_generation, "Model generation is not enabled"
+        if fused:
+            return self._generate_fused(batch, temperature, top_k, sample)
         B = batch.sem_ids.shape[0]
         generated, log_probas = None, 0
         k = 32 if top_k else 1
@@ -237,4 +251,61 @@ class EncoderDecoderRetrievalModel(nn.Module):
                                         token_type_ids=cur.token_type_ids.repeat_interleave(k, dim=0))
                 generated = top_samples.unsqueeze(-1)
                 log_probas = top_lp.detach().clone()
+        return GenerationOutput(sem_ids=generated.squeeze(), log_probas=log_probas.squeeze())
+
+    def _generate_fused(self, batch: TokenizedSeqBatch, temperature, top_k: bool, sample: bool) -> GenerationOutput:
+        """generate_next_sem_id with the per-step beam logic on hip_ops.beam_candidates (softmax, the draw, the
+        candidates' log-probabilities) and hip_ops.beam_select (verification, cumulative score, stable top-k,
+        parent gather). The draw: the n_cand largest p / e with e ~ Exponential(1) from torch's generator — the
+        distribution of torch.multinomial without replacement; sample=False: the n_cand largest p. Prefixes are
+        verified in the select kernel against `inference_prefix_index.prefix_table` (the tokenizer's sorted
+        packed-prefix keys, incl. its reference_batching quirk) when that attribute is set, else by
+        `inference_verifier_fn` on the materialised prefixes. Runs under generate_next_sem_id's decorators."""
+        B = batch.sem_ids.shape[0]
+        k = 32 if top_k else 1
+        n_cand = 200 if top_k else 1
+        index = getattr(self, "inference_prefix_index", None)
+        generated, log_probas = None, None
+        cur = TokenizedSeqBatch(user_ids=batch.user_ids, sem_ids=batch.sem_ids, sem_ids_fut=None,
+                                seq_mask=batch.seq_mask, token_type_ids=batch.token_type_ids, token_type_ids_fut=None)
+        for i in range(self.sem_id_dim):
+            logits = self.forward(cur).logits.contiguous()
+            noise = torch.empty_like(logits).exponential_() if sample else None
+            cand_ids, cand_lp = hip_ops.beam_candidates(logits, n_cand, temperature, noise)
+            if index is not None:
+                from modules.tokenizer.semids import BATCH_SIZE
+                keys, base = index.prefix_table(i + 1)
+                # exists_prefix's batching quirk acts on the prefix tensor's leading axis: here the B * kprev logits
+                # rows (n_cand candidates each), of which the last partial batch of 16 goes unchecked
+                rows = cand_ids.shape[0]
+                verify = dict(keys=keys, base=base,
+                              checked=(rows // BATCH_SIZE * BATCH_SIZE if index.reference_batching else rows) * n_cand)
+            elif generated is None:
+                verify = dict(valid=self.inference_verifier_fn(cand_ids.unsqueeze(-1)))
+            else:
+                prefix = torch.cat([generated.flatten(0, 1).unsqueeze(1).repeat_interleave(n_cand, axis=1),
+                                    cand_ids.unsqueeze(-1)], axis=-1)
+                verify = dict(valid=self.inference_verifier_fn(prefix))
+            if "valid" in verify:
+                verify["valid"] = verify["valid"].to(torch.bool).reshape(-1).contiguous()
+            first = generated is None
+            generated, log_probas = hip_ops.beam_select(cand_ids, cand_lp, k, batch=B, parents=generated,
+                                                        parent_lp=log_probas, **verify)
+            if not first:
+                nxt = generated.flatten(end_dim=1)
+                cur = TokenizedSeqBatch(user_ids=cur.user_ids, sem_ids=cur.sem_ids, sem_ids_fut=nxt,
+                                        token_type_ids_fut=torch.arange(nxt.shape[1], device=nxt.device).repeat(nxt.shape[0], 1),
+                                        seq_mask=cur.seq_mask, token_type_ids=cur.token_type_ids)
+            else:
+                nxt = generated.reshape(-1, 1)
+                enc = self.transformer.cached_enc_output
+                n_ctx = cur.sem_ids.shape[1] + 1
+                padded = jagged_to_padded_tensor(enc, n_ctx).repeat_interleave(k, dim=0)
+                lengths = enc.offsets().diff().repeat_interleave(k)
+                self.transformer.cached_enc_output = padded_to_jagged(padded.contiguous(), lengths, n_ctx)
+                cur = TokenizedSeqBatch(user_ids=cur.user_ids.repeat_interleave(k, dim=0),
+                                        sem_ids=cur.sem_ids.repeat_interleave(k, dim=0), sem_ids_fut=nxt,
+                                        token_type_ids_fut=torch.zeros_like(nxt),
+                                        seq_mask=cur.seq_mask.repeat_interleave(k, dim=0),
+                                        token_type_ids=cur.token_type_ids.repeat_interleave(k, dim=0))
         return GenerationOutput(sem_ids=generated.squeeze(), log_probas=log_probas.squeeze())

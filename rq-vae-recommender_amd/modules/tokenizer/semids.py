@@ -113,6 +113,14 @@ class SemanticIdTokenizer(nn.Module):
             self._prefix_index[P] = (torch.unique(_pack(cols, base)), base)
         return self._prefix_index[P]
 
+    def prefix_table(self, P: int):
+        """(keys, base): the sorted unique packed keys (`_pack` in base `base`) of the corpus ids' length-P
+        prefixes — the table exists_prefix searches, for callers that search it on the device themselves
+        (rqvae_hip.ops.beam_select). Cached per P until the corpus changes."""
+        if self.cached_ids is None:
+            raise Exception("No match can be found in empty cache.")
+        return self._prefix_keys(P)
+
     @torch.no_grad()
     @eval_mode
     def exists_prefix(self, sem_id_prefix: Tensor) -> Tensor:

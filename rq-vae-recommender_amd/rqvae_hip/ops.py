@@ -6,6 +6,7 @@
   padded_to_jagged_values(x, lengths, N)     jagged gather (+1-1 rounding) + offsets (fwd + VJP)
   varlen_attention(q, k, v, cu_q, cu_k, ...) jagged SDPA (fwd + deterministic VJP)
   gemm_bf16x3 / gemm_x3 / mlp_chain          fp32 matmuls at 'high' precision (split-bf16 MFMA)
+  beam_candidates / beam_select / topk_hits  decoder evaluation: one beam step in two launches, Hit@k counters
 
 All kernels run on torch's current HIP stream; tensors must be on the GPU (no CPU path).
 """
@@ -2265,3 +2266,101 @@ def varlen_attention(q, k, v, cu_q, cu_k, num_heads, causal, max_q, max_k, scale
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[1] // num_heads)
     return VarlenAttentionFunction.apply(q, k, v, cu_q, cu_k, num_heads, causal, max_q, max_k, scale)
+
+
+# ---------------------------------------------------------------------------- decoder evaluation (csrc/beam.hip)
+def _beam_arg(t, dtype, what, name, shape=None):
+    if t.dtype != dtype or not t.is_contiguous():
+        raise RqHipError(f"{what}: {name} must be a contiguous {dtype} tensor (got {t.dtype}, "
+                         f"contiguous={t.is_contiguous()})")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise RqHipError(f"{what}: {name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+    return t
+
+
+def beam_candidates(logits: torch.Tensor, n_cand: int, temperature: float = 1.0, noise: torch.Tensor = None):
+    """(cand_ids (R, n_cand) int64, cand_lp (R, n_cand) fp32): per row of logits (R, V) the n_cand classes of
+    largest softmax(logits / temperature) / noise, best first (ties to the lower class), and their log-probabilities
+    (rq_beam_candidates). noise: Exponential(1) draws (R, V) for a multinomial-without-replacement sample, None
+    for the n_cand most probable classes. One launch, no host read."""
+    what = "beam_candidates"
+    require_gpu(logits, noise, what=what)
+    if logits.dim() != 2:
+        raise RqHipError(f"{what}: logits must be (R, V)")
+    _beam_arg(logits, torch.float32, what, "logits")
+    R, V = logits.shape
+    if noise is not None:
+        _beam_arg(noise, torch.float32, what, "noise", (R, V))
+    ids = torch.empty((R, int(n_cand)), device=logits.device, dtype=torch.int64)
+    lp = torch.empty((R, int(n_cand)), device=logits.device, dtype=torch.float32)
+    call("rq_beam_candidates", ptr(logits), ptr(noise), R, V, int(n_cand), float(temperature), ptr(ids), ptr(lp),
+         stream_handle(logits.device))
+    return ids, lp
+
+
+def beam_select(cand_ids: torch.Tensor, cand_lp: torch.Tensor, k: int, *, batch: int, valid: torch.Tensor = None,
+                keys: torch.Tensor = None, base: int = 0, checked: int = None, parents: torch.Tensor = None,
+                parent_lp: torch.Tensor = None):
+    """(out_ids (B, k, P + 1) int64, out_lp (B, k) fp32): the k best continuations per batch element of the
+    candidates beam_candidates returned for its B * kprev rows (rq_beam_select). parents (B, kprev, P) /
+    parent_lp (B, kprev): the beams so far (None on the first step). Validity: `valid` (a bool tensor of B * kprev
+    * n_cand elements) or `keys` / `base` (SemanticIdTokenizer.prefix_table(P + 1)) with `checked` = the number of
+    leading flat candidates the verifier looks at (default: all). One launch, no host read."""
+    what = "beam_select"
+    require_gpu(cand_ids, cand_lp, valid, keys, parents, parent_lp, what=what)
+    B = int(batch)
+    if cand_ids.dim() != 2 or B < 0 or (B and cand_ids.shape[0] % B):
+        raise RqHipError(f"{what}: cand_ids must be (B * kprev, n_cand)")
+    R, n_cand = cand_ids.shape
+    kprev = R // B if B else 1
+    _beam_arg(cand_ids, torch.int64, what, "cand_ids")
+    _beam_arg(cand_lp, torch.float32, what, "cand_lp", (R, n_cand))
+    if (parents is None) != (parent_lp is None):
+        raise RqHipError(f"{what}: parents and parent_lp go together")
+    P = 0
+    if parents is not None:
+        if parents.dim() != 3 or tuple(parents.shape[:2]) != (B, kprev):
+            raise RqHipError(f"{what}: parents must be (B, kprev, P), got {tuple(parents.shape)}")
+        P = parents.shape[2]
+        _beam_arg(parents, torch.int64, what, "parents")
+        _beam_arg(parent_lp, torch.float32, what, "parent_lp", (B, kprev))
+        if P == 0:
+            parents = parent_lp = None
+    if (valid is None) == (keys is None):
+        raise RqHipError(f"{what}: give exactly one of valid and keys")
+    N = kprev * n_cand
+    if valid is not None:
+        _beam_arg(valid, torch.bool, what, "valid")
+        if valid.numel() != B * N:
+            raise RqHipError(f"{what}: valid must have {B * N} elements, got {valid.numel()}")
+    else:
+        if keys.dim() != 1:
+            raise RqHipError(f"{what}: keys must be 1-D")
+        _beam_arg(keys, torch.int64, what, "keys")
+    out_ids = torch.empty((B, int(k), P + 1), device=cand_ids.device, dtype=torch.int64)
+    out_lp = torch.empty((B, int(k)), device=cand_ids.device, dtype=torch.float32)
+    call("rq_beam_select", ptr(cand_ids), ptr(cand_lp), ptr(valid), ptr(keys), 0 if keys is None else keys.numel(),
+         int(base), B * N if checked is None else int(checked), ptr(parents), ptr(parent_lp), B, kprev, n_cand, P,
+         int(k), ptr(out_ids), ptr(out_lp), stream_handle(cand_ids.device))
+    return out_ids, out_lp
+
+
+def topk_hits(actual: torch.Tensor, topk: torch.Tensor, ks, counts: torch.Tensor) -> torch.Tensor:
+    """counts (2, D, len(ks)) int64 += the Hit@k counts of one batch (rq_topk_hits): [0][i][j] rows whose first beam
+    matching the target's columns 0..i ranks below ks[j], [1][i][j] the same for column i alone. actual (B, D),
+    topk (B, k, D) int64. One launch, no host read; the caller zeroes counts once."""
+    what = "topk_hits"
+    require_gpu(actual, topk, counts, what=what)
+    if actual.dim() != 2 or topk.dim() != 3 or topk.shape[0] != actual.shape[0] or topk.shape[2] != actual.shape[1]:
+        raise RqHipError(f"{what}: need actual (B, D) and topk (B, k, D), got {tuple(actual.shape)}, {tuple(topk.shape)}")
+    B, D = actual.shape
+    ks = [int(v) for v in ks]
+    _beam_arg(actual, torch.int64, what, "actual")
+    _beam_arg(topk, torch.int64, what, "topk")
+    _beam_arg(counts, torch.int64, what, "counts")
+    if counts.numel() != 2 * D * len(ks):
+        raise RqHipError(f"{what}: counts must have 2 * D * len(ks) = {2 * D * len(ks)} elements")
+    import ctypes
+    call("rq_topk_hits", ptr(actual), ptr(topk), B, topk.shape[1], D, (ctypes.c_int * len(ks))(*ks), len(ks),
+         ptr(counts), stream_handle(actual.device))
+    return counts

@@ -18,6 +18,10 @@ buckets launch in index order on every rank, so the collective sequence still ma
 The reference rejects non-AMAZON datasets and its ML-32M gin binds a non-existent parameter
 (SURVEY A-8); this entry accepts every RecDataset (the ML-32M config still fails on
 `train.attn_dropout`, exactly like gin). Checkpoints: plain state dicts with "scheduler".
+Evaluation (reference train_decoder.py:208-245) runs eagerly between train steps, outside the captured graphs:
+every `partial_eval_every` iterations the eval split's loss, every `full_eval_every` iterations beam generation
+over the eval split into the device-side Hit@k accumulator (evaluate.metrics), each rank taking every world-th
+batch; see _Evaluator.
 """
 import contextlib
 import json
@@ -33,8 +37,10 @@ from modules.ginlite import gin
 from modules.model import EncoderDecoderRetrievalModel
 from modules.scheduler.inv_sqrt import InverseSquareRootScheduler
 from modules.tokenizer.semids import SemanticIdTokenizer
-from modules.utils import parse_config
+from modules.utils import compute_debug_metrics, parse_config
+from evaluate.metrics import TopKAccumulator
 from rqvae_hip import dp, gemm_tuning
+from rqvae_hip import ops as hip_ops
 from rqvae_hip import optim as hip_optim
 from rqvae_hip.graph import GraphedSteps
 from ops.jagged import copy_row_counts, register_row_counts, row_counts
@@ -102,6 +108,91 @@ class _Prefetch:
             except queue.Empty:
                 pass
             self.thread.join(timeout=0.01)
+
+
+# Generation path of the full eval: the fused HIP beam step (modules/model.py _generate_fused) or the reference's
+# torch composition — whichever measured faster at the Amazon eval shape (tools/generation_time.py).
+EVAL_FUSED_GENERATION = True
+
+
+class _Evaluator:
+    """The two eval passes of the reference loop over the eval split (SeqData(is_train=False), built on first use),
+    in eval mode under no_grad, eagerly. Rank r takes batches r, r + world, ... of `batch_size` users in index
+    order. An eval leaves the training run as it found it: train mode and enable_generation restored, torch's
+    generators and the dropout key counter put back (the sampled generation draws from torch's generator), no
+    captured graph touched. Results go to LAST_RUN["eval"] and, on rank 0, to stdout."""
+
+    def __init__(self, model, tokenizer, make_dataset, batch_size, device, rank, world, partial_every, full_every):
+        self.model, self.tokenizer, self.make_dataset = model, tokenizer, make_dataset
+        self.batch_size, self.device, self.rank, self.world = batch_size, device, rank, world
+        self.partial_every, self.full_every = partial_every, full_every
+        self.dataset = None
+        self.metrics = TopKAccumulator(ks=[1, 5, 10])
+
+    def _batches(self):
+        if self.dataset is None:
+            self.dataset = self.make_dataset()
+        n, bs, D = len(self.dataset), self.batch_size, self.tokenizer.sem_ids_dim
+        for j, a in enumerate(range(0, n, bs)):
+            if j % self.world != self.rank:
+                continue
+            data = self.dataset[list(range(a, min(n, a + bs)))]
+            counts = (data.seq_mask.sum(1) * D).tolist()
+            ids_max = int(max(int(data.ids.max()), int(data.ids_fut.max())))
+            tok = self.tokenizer(batch_to(data, self.device), ids_max=ids_max)
+            register_row_counts(tok.seq_mask, counts)
+            yield tok
+
+    def __call__(self, it: int):
+        partial = self.partial_every and (it + 1) % self.partial_every == 0
+        full = self.full_every and (it + 1) % self.full_every == 0
+        if not (partial or full):
+            return
+        model = self.model
+        gen_flag, seed_state = model.enable_generation, dict(hip_ops._SEED)
+        out = LAST_RUN.setdefault("eval", {})
+        try:
+            with torch.random.fork_rng(devices=[self.device]), torch.no_grad():
+                model.eval()
+                if partial:
+                    out.update(self._partial(it))
+                if full:
+                    out.update(self._full(it))
+        finally:
+            model.enable_generation = gen_flag
+            hip_ops._SEED.update(seed_state)
+            model.train()
+
+    def _partial(self, it):
+        self.model.enable_generation = False
+        acc = torch.zeros(2, device=self.device, dtype=torch.float64)   # (sum of batch loss * rows, rows)
+        debug = {}
+        for tok in self._batches():
+            o = self.model(tok)
+            B = tok.seq_mask.shape[0]
+            acc[0] += o.loss.detach().double() * B
+            acc[1] += B
+            if self.rank == 0:
+                debug = compute_debug_metrics(tok, o, "eval")
+        if self.world > 1:
+            torch.distributed.all_reduce(acc)
+        loss_sum, rows = acc.tolist()
+        res = {"eval_iter": it, "eval_loss": loss_sum / max(rows, 1.0), **debug}
+        if self.rank == 0:
+            print(json.dumps({"iter": it, **res}), flush=True)
+        return res
+
+    def _full(self, it):
+        self.model.enable_generation = True
+        self.metrics.reset()
+        for tok in self._batches():
+            gen = self.model.generate_next_sem_id(tok, top_k=True, temperature=1, fused=EVAL_FUSED_GENERATION)
+            self.metrics.accumulate(actual=tok.sem_ids_fut, top_k=gen.sem_ids)
+        res = self.metrics.reduce()
+        self.metrics.reset()
+        if self.rank == 0:
+            print(res, flush=True)   # the reference prints the Hit@k dictionary as is (train_decoder.py:241)
+        return {"full_eval_iter": it, **res}
 
 
 # Last train() call: steady-state time per iteration (CUDA-synchronised once at the start and once at
@@ -198,9 +289,14 @@ def train(iterations=500000, batch_size=64, learning_rate=0.001, weight_decay=0.
                            prepare=lambda static, inp: copy_row_counts(static[0].seq_mask, inp[0].seq_mask)
                            ) if use_graphs else None
     feed = _Prefetch(loader, rank, world, tokenizer.sem_ids_dim)
+    model.inference_prefix_index = tokenizer   # fused generation verifies prefixes against its key table in-kernel
+    evaluator = _Evaluator(model, tokenizer,
+                           lambda: SeqData(root=dataset_folder, dataset=dataset, is_train=False, subsample=False,
+                                           data_path=data_path, seed=seed, with_features=False),
+                           batch_size, device, rank, world, partial_eval_every, full_eval_every)
     try:
         _train_loop(feed, model, tokenizer, graphed, buckets, opt, sched, device, rank, world, start_iter, iterations,
-                    gradient_accumulate_every, log_every, save_model_every, save_dir_root)
+                    gradient_accumulate_every, log_every, save_model_every, save_dir_root, evaluator)
     finally:
         feed.close()
     return model
@@ -210,7 +306,7 @@ _PHASES = ("feed_wait", "tokenize", "step", "exchange", "optimizer", "log_save")
 
 
 def _train_loop(feed, model, tokenizer, graphed, buckets, opt, sched, device, rank, world, start_iter, iterations,
-                gradient_accumulate_every, log_every, save_model_every, save_dir_root):
+                gradient_accumulate_every, log_every, save_model_every, save_dir_root, evaluator=None):
     """The reference's loop (train_decoder.py:180-204) over the prefetched batches. Host time per phase
     is accumulated over the steady span (LAST_RUN["host_ms_per_iter"]): the loop must stay ahead of the
     GPU, so these are the numbers to read when the trainer is slower than its bench step."""
@@ -306,6 +402,8 @@ def _train_loop(feed, model, tokenizer, graphed, buckets, opt, sched, device, ra
                             graphs=len(graphed.graphs) if graphed is not None else 0,
                             eager_steps=graphed.eager_steps if graphed is not None else iterations - start_iter,
                             exchange="in-graph" if graphed is not None and graphed.in_graph else "hooks + synchronize")
+        if evaluator is not None:
+            evaluator(it)   # a no-op except every partial_eval_every / full_eval_every iterations
         c6 = clock()
         if it % log_every == 0 or it + 1 == iterations:
             mean = torch.stack(hist).mean()

@@ -1,0 +1,140 @@
+#!/usr/bin/env python3
+"""Time of one eval batch of the decoder trainer at the Amazon shape (B = 256 sequences, 32 beams, 200 candidates
+per beam, 256 classes, 4 sem-ID tokens; model dims of configs/decoder_amazon.gin):
+
+  generation   generate_next_sem_id(top_k=True) with fused=False (the reference's torch composition of the beam
+               step) and fused=True (rq_beam_candidates + rq_beam_select), verifier = a tokenizer over a
+               12,101-item corpus; and with the beam step stubbed out (`model`: the four forwards and the encoder
+               cache repeat alone), which gives the beam logic's share of each form;
+  accumulate   TopKAccumulator.accumulate on the device (one rq_topk_hits launch) and the reference's logic
+               (evaluate/metrics.py:15-28, restated below: 24 host reads per batch).
+
+Each form is warmed up, then timed `--reps` times with the forms alternating; a span is a host clock around work
+that ends in a device synchronise. Prints one JSON line (medians, ms). `--only FORM --reps N --warmup 0` runs a
+single form N times for a kernel trace (rocprofv3 --kernel-trace --stats -- python tools/generation_time.py ...):
+launches per beam step = (calls of the form - calls of `model`) / (4 N).
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(ROOT, "rq-vae-recommender_amd")]
+
+import torch  # noqa: E402
+
+
+def reference_accumulate(metrics, ks, actual, top_k):
+    """The reference accumulator's arithmetic on whatever device the tensors live on (a len() per counter)."""
+    B, D = actual.shape
+    pos_match = actual.unsqueeze(1) == top_k
+    for i in range(D):
+        match_found, rank = pos_match[..., :i + 1].all(axis=-1).max(axis=-1)
+        matched_rank = rank[match_found]
+        for k in ks:
+            metrics[f"h@{k}_slice_:{i + 1}"] = metrics.get(f"h@{k}_slice_:{i + 1}", 0) + len(matched_rank[matched_rank < k])
+        match_found, rank = pos_match[..., i:i + 1].all(axis=-1).max(axis=-1)
+        matched_rank = rank[match_found]
+        for k in ks:
+            metrics[f"h@{k}_pos_{i}"] = metrics.get(f"h@{k}_pos_{i}", 0) + len(matched_rank[matched_rank < k])
+
+
+def build(device, B, seed=0):
+    from data.processed import synthetic_tokenized_batch
+    from modules.model import EncoderDecoderRetrievalModel
+    from modules.tokenizer.semids import SemanticIdTokenizer, dedup_rank
+    K, L1, n_items = 256, 4, 12101
+    tok = SemanticIdTokenizer(input_dim=8, output_dim=4, hidden_dims=[8], codebook_size=K, n_layers=L1 - 1, n_cat_feats=0)
+    g = torch.Generator().manual_seed(seed)
+    ids = torch.randint(0, K, (n_items, L1 - 1), generator=g).to(device)
+    tok.cached_ids = torch.cat([ids, dedup_rank(ids).unsqueeze(1)], 1)
+    torch.manual_seed(seed)
+    model = EncoderDecoderRetrievalModel(embedding_dim=128, attn_dim=512, dropout=0.3, num_heads=8, n_layers=8,
+                                         num_embeddings=K, sem_id_dim=L1,
+                                         inference_verifier_fn=lambda x: tok.exists_prefix(x), max_pos=20 * L1).to(device)
+    model.enable_generation = True
+    model.inference_prefix_index = tok
+    model.eval()
+    return model, tok, synthetic_tokenized_batch(B, 20, L1, K, seed + 1, device)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--only", choices=["unfused", "fused", "model", "acc_device", "acc_reference"])
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("generation_time: needs the GPU (a CPU run measures nothing)")
+    from evaluate.metrics import TopKAccumulator
+    from rqvae_hip import ops as hip_ops
+    device = torch.device("cuda", 0)
+    model, tok, batch = build(device, args.batch)
+    B, k, n_cand, L1 = args.batch, 32, 200, 4
+    real = (hip_ops.beam_candidates, hip_ops.beam_select)
+    fixed = {}   # the stubbed beam step's outputs, allocated once
+
+    def stub_candidates(logits, n, temperature=1.0, noise=None):
+        key = ("c", logits.shape[0])
+        if key not in fixed:
+            fixed[key] = (torch.zeros((logits.shape[0], n), dtype=torch.int64, device=device),
+                          torch.zeros((logits.shape[0], n), device=device))
+        return fixed[key]
+
+    def stub_select(cand_ids, cand_lp, kk, *, batch, parents=None, **_):
+        P = 0 if parents is None else parents.shape[2]
+        if P not in fixed:
+            fixed[P] = (torch.zeros((batch, kk, P + 1), dtype=torch.int64, device=device),
+                        torch.zeros((batch, kk), device=device))
+        return fixed[P]
+
+    def gen(fused):
+        return model.generate_next_sem_id(batch, temperature=1, top_k=True, fused=fused)
+
+    def gen_model_only():
+        hip_ops.beam_candidates, hip_ops.beam_select = stub_candidates, stub_select
+        try:
+            return model.generate_next_sem_id(batch, temperature=1, top_k=True, fused=True, sample=False)
+        finally:
+            hip_ops.beam_candidates, hip_ops.beam_select = real
+
+    top = gen(True).sem_ids.contiguous()
+    actual = batch.sem_ids_fut.contiguous()
+    top[::3, 4] = actual[::3]          # some hits, as a trained model has
+    acc = TopKAccumulator(ks=[1, 5, 10])
+
+    def acc_device():
+        acc.accumulate(actual=actual, top_k=top)
+
+    def acc_reference():
+        reference_accumulate({}, [1, 5, 10], actual, top)
+
+    forms = {"unfused": lambda: gen(False), "fused": lambda: gen(True), "model": gen_model_only,
+             "acc_device": acc_device, "acc_reference": acc_reference}
+    if args.only:
+        forms = {args.only: forms[args.only]}
+    times = {n: [] for n in forms}
+    for rep in range(-args.warmup, args.reps):
+        for name, fn in forms.items():   # alternating: every form sees the same drift of the shared host
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            if rep >= 0:
+                times[name].append((time.perf_counter() - t0) * 1e3)
+    med = {n: statistics.median(v) for n, v in times.items() if v}
+    out = {"shape": dict(B=B, k=k, n_cand=n_cand, V=256, L1=L1), "reps": args.reps,
+           "median_ms": {n: round(v, 4) for n, v in med.items()},
+           "min_max_ms": {n: [round(min(v), 4), round(max(v), 4)] for n, v in times.items() if v}}
+    if {"unfused", "fused", "model"} <= set(med):
+        out["beam_logic_share"] = {n: round(1 - med["model"] / med[n], 4) for n in ("unfused", "fused")}
+        out["beam_logic_ms"] = {n: round(med[n] - med["model"], 4) for n in ("unfused", "fused")}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
