@@ -465,13 +465,35 @@ int varlen_attn_bwd(const float* q, int64_t sq, const float* k, int64_t sk, cons
  * rq_topk_hits: actual (B, D) int64 targets, topk (B, k, D) int64 beams, ks: HOST array of n_ks ints (copied into the
  *   kernel arguments). counts (2, D, n_ks) int64 is ACCUMULATED into (the caller zeroes it once):
  *   counts[0][i][j] += #rows whose first beam equal to the target in columns 0..i has rank < ks[j] (h@k_slice_:i+1),
- *   counts[1][i][j] the same for column i alone (h@k_pos_i). D <= 64, n_ks <= 8. */
+ *   counts[1][i][j] the same for column i alone (h@k_pos_i). D <= 64, n_ks <= 8.
+ * rq_beam_select_parent: rq_beam_select that also writes out_parent (B, k) int32 = each winner's parent beam index
+ *   e / n_cand in [0, kprev) (NULL: not written; rq_beam_select is this call with NULL). out_ids / out_lp are the same.
+ * rq_beam_self_attn: incremental decoding — the newest token's causal self-attention of R beams over their own
+ *   ancestors. Step s = 0..t wrote a packed qkv buffer of R_s = rows[s] rows that stays where it is; k_steps[s] /
+ *   v_steps[s] are its K / V column views (device pointers, row stride strides[s] floats, 16-byte aligned). The
+ *   four step arrays are HOST arrays of t + 1 entries, copied into the kernel arguments (no device table, no
+ *   copy). Entry t is the current step: beam r is its own key / value row and rows[t] == R. anc: DEVICE (R, t)
+ *   int32, anc[r][s] = the row of step s's buffer that holds beam r's token s (NULL iff t == 0); beams that share
+ *   an ancestor share its row, so re-ordering beams after a selection moves no K / V. The kernel does NOT check
+ *   anc: entries in [0, rows[s]) are the caller's contract (out-of-range ones are clamped into the buffer and give
+ *   an unspecified result). out[r, h] = sum_s softmax_s(scale q[r,h] . k_s[anc[r][s], h]) v_s[anc[r][s], h]: fp32
+ *   scores, max subtracted, sums over s = 0..t in ascending order; at t == 0 out == v bitwise. q (R, H hd) with
+ *   row stride sq, out row stride so; every stride >= H hd and a multiple of 4; hd in {16, 32, 64, 128};
+ *   0 <= t < RQ_BEAM_MAX_T; R == 0 returns 0 without a launch. */
+#define RQ_BEAM_MAX_T 8 /* tokens per beam incl. BOS; sem_id_dim <= 8 as evaluate.metrics already assumes */
 int rq_beam_candidates(const float* logits, const float* noise, int64_t R, int64_t V, int64_t n_cand,
                        float temperature, int64_t* cand_ids, float* cand_lp, void* stream);
 int rq_beam_select(const int64_t* cand_ids, const float* cand_lp, const bool* valid, const int64_t* keys,
                    int64_t n_keys, int64_t base, int64_t checked, const int64_t* parents, const float* parent_lp,
                    int64_t B, int64_t kprev, int64_t n_cand, int64_t P, int64_t k, int64_t* out_ids, float* out_lp,
                    void* stream);
+int rq_beam_select_parent(const int64_t* cand_ids, const float* cand_lp, const bool* valid, const int64_t* keys,
+                          int64_t n_keys, int64_t base, int64_t checked, const int64_t* parents,
+                          const float* parent_lp, int64_t B, int64_t kprev, int64_t n_cand, int64_t P, int64_t k,
+                          int64_t* out_ids, float* out_lp, int32_t* out_parent, void* stream);
+int rq_beam_self_attn(const float* q, int64_t sq, const float* const* k_steps, const float* const* v_steps,
+                      const int64_t* strides, const int64_t* rows, const int32_t* anc, int64_t R, int64_t t,
+                      int64_t H, int64_t hd, float scale, float* out, int64_t so, void* stream);
 int rq_topk_hits(const int64_t* actual, const int64_t* topk, int64_t B, int64_t k, int64_t D, const int* ks,
                  int64_t n_ks, int64_t* counts, void* stream);
 

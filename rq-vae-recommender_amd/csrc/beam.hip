@@ -7,6 +7,9 @@
 //   beam_select_kernel      one workgroup per batch element: prefix verification (a caller-provided mask or
 //                           a binary search of the tokenizer's packed-prefix table), the cumulative score,
 //                           the k best of the kprev * n_cand candidates in stable order, the parent gather.
+//   beam_self_attn_kernel   incremental decoding: the newest token's causal self-attention over its beam's
+//                           ancestors, read in place from every step's packed qkv output through an
+//                           ancestor row table (no per-beam cache is gathered or appended).
 //   topk_hits_kernel        one wave per batch row: first matching beam rank per sem-ID slice / position,
 //                           counters accumulated on the device with one atomic per (wave, counter).
 #include "common.h"
@@ -136,7 +139,7 @@ __global__ void __launch_bounds__(kSelThreads) beam_select_kernel(
     const int64_t* __restrict__ cand_ids, const float* __restrict__ cand_lp, const bool* __restrict__ valid,
     const int64_t* __restrict__ keys, int64_t n_keys, int64_t base, int64_t checked,
     const int64_t* __restrict__ parents, const float* __restrict__ parent_lp, int kprev, int n_cand, int P, int k,
-    int64_t* __restrict__ out_ids, float* __restrict__ out_lp) {
+    int64_t* __restrict__ out_ids, float* __restrict__ out_lp, int32_t* __restrict__ out_parent) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int N = kprev * n_cand;
@@ -209,12 +212,83 @@ __global__ void __launch_bounds__(kSelThreads) beam_select_kernel(
         if (better(kk, e, best_k, best_i)) { best_k = kk; best_i = e; }
       }
     }
-    if (tid == 0) out_lp[b * k + r] = key_score(wk);
+    if (tid == 0) {
+      out_lp[b * k + r] = key_score(wk);
+      if (out_parent) out_parent[b * k + r] = wi / n_cand;
+    }
     // the winner's row: parent prefix then the candidate id
     int64_t* o = out_ids + (b * k + r) * (P + 1);
     if (tid < P) o[tid] = parents[(b * kprev + wi / n_cand) * P + tid];   // P < 64
     if (tid == 0) o[P] = cid[wi];
   }
+}
+
+// ------------------------------------------------------------------------------------- self-attention
+// The step buffers by value in the kernel arguments (no device-side pointer table): K / V column views of step
+// s's packed qkv output, its row stride and row count.
+struct BeamSteps {
+  const float* k[RQ_BEAM_MAX_T];
+  const float* v[RQ_BEAM_MAX_T];
+  int64_t stride[RQ_BEAM_MAX_T];
+  int64_t rows[RQ_BEAM_MAX_T];
+};
+
+// LPU = hd / 4 lanes per (row, head) unit, 256 / LPU units per workgroup. A lane holds 4 consecutive head
+// columns: one float4 of q, and per step one float4 of the ancestor's key and value row; the dot product is a
+// butterfly sum inside the unit. Bandwidth-bound: 4 R H hd (2 (t + 1) + 2) bytes, no LDS. Scores, max and the
+// sum over s = 0..t (ascending) in fp32; at t == 0 the weight is exp(0) / 1, so out == v bitwise.
+// anc entries are not validated (the caller's contract: in [0, rows[s])); they are clamped to the step's
+// buffer, so a bad entry gives an unspecified result but never a read outside it.
+template <int LPU>
+__global__ void __launch_bounds__(256) beam_self_attn_kernel(const float* __restrict__ q, int64_t sq, BeamSteps st,
+                                                             const int32_t* __restrict__ anc, int64_t units, int H,
+                                                             int t, float scale, float* __restrict__ out,
+                                                             int64_t so) {
+  const int64_t u_raw = ((int64_t)blockIdx.x * 256 + threadIdx.x) / LPU;
+  const bool live = u_raw < units;
+  const int64_t u = live ? u_raw : units - 1;   // idle units repeat the last one (whole-wave shuffles), write nothing
+  const int64_t r = u / H;
+  const int col = (int)(u % H) * (LPU * 4) + (int)(threadIdx.x % LPU) * 4;
+  const float4 qv = *reinterpret_cast<const float4*>(q + r * sq + col);
+  float sc[RQ_BEAM_MAX_T];
+  float4 vv[RQ_BEAM_MAX_T];
+  float m = -INFINITY;
+#pragma unroll
+  for (int s = 0; s < RQ_BEAM_MAX_T; ++s) {
+    if (s <= t) {
+      int64_t row = r;
+      if (s < t) row = min(max((int64_t)anc[r * t + s], (int64_t)0), st.rows[s] - 1);
+      const int64_t off = row * st.stride[s] + col;
+      const float4 kv = *reinterpret_cast<const float4*>(st.k[s] + off);
+      vv[s] = *reinterpret_cast<const float4*>(st.v[s] + off);
+      const float d = group_sum<LPU>(qv.x * kv.x + qv.y * kv.y + qv.z * kv.z + qv.w * kv.w);
+      sc[s] = d * scale;
+      m = fmaxf(m, sc[s]);
+    }
+  }
+  // s = 0 always exists; later terms are added in step order
+  float l = expf(sc[0] - m);
+  float4 acc = make_float4(l * vv[0].x, l * vv[0].y, l * vv[0].z, l * vv[0].w);
+#pragma unroll
+  for (int s = 1; s < RQ_BEAM_MAX_T; ++s) {
+    if (s <= t) {
+      const float p = expf(sc[s] - m);
+      l += p;
+      acc.x += p * vv[s].x;
+      acc.y += p * vv[s].y;
+      acc.z += p * vv[s].z;
+      acc.w += p * vv[s].w;
+    }
+  }
+  if (live) *reinterpret_cast<float4*>(out + r * so + col) = make_float4(acc.x / l, acc.y / l, acc.z / l, acc.w / l);
+}
+
+template <int LPU>
+static void launch_beam_self_attn(const float* q, int64_t sq, const BeamSteps& st, const int32_t* anc, int64_t units,
+                                  int H, int t, float scale, float* out, int64_t so, hipStream_t stream) {
+  const int64_t blocks = (units * LPU + 255) / 256;
+  hipLaunchKernelGGL(beam_self_attn_kernel<LPU>, dim3((unsigned)blocks), dim3(256), 0, stream, q, sq, st, anc, units,
+                     H, t, scale, out, so);
 }
 
 // ------------------------------------------------------------------------------------- hits
@@ -300,10 +374,10 @@ int rq_beam_candidates(const float* logits, const float* noise, int64_t R, int64
   return 0;
 }
 
-int rq_beam_select(const int64_t* cand_ids, const float* cand_lp, const bool* valid, const int64_t* keys,
-                   int64_t n_keys, int64_t base, int64_t checked, const int64_t* parents, const float* parent_lp,
-                   int64_t B, int64_t kprev, int64_t n_cand, int64_t P, int64_t k, int64_t* out_ids, float* out_lp,
-                   void* stream) {
+int rq_beam_select_parent(const int64_t* cand_ids, const float* cand_lp, const bool* valid, const int64_t* keys,
+                          int64_t n_keys, int64_t base, int64_t checked, const int64_t* parents,
+                          const float* parent_lp, int64_t B, int64_t kprev, int64_t n_cand, int64_t P, int64_t k,
+                          int64_t* out_ids, float* out_lp, int32_t* out_parent, void* stream) {
   RQ_CHECK_ARG(B >= 0 && kprev >= 1 && n_cand >= 1 && P >= 0 && P < 64, "rq_beam_select: bad shape");
   RQ_CHECK_ARG(kprev <= rqhip::kBeamMaxN && n_cand <= rqhip::kBeamMaxN && kprev * n_cand <= rqhip::kBeamMaxN &&
                    k >= 1 && k <= kprev * n_cand,
@@ -327,8 +401,62 @@ int rq_beam_select(const int64_t* cand_ids, const float* cand_lp, const bool* va
   const size_t lds = (size_t)((kprev * n_cand + 3) / 4 * 4 + 2 * (rqhip::kSelThreads / 64)) * sizeof(uint32_t);
   hipLaunchKernelGGL(rqhip::beam_select_kernel, dim3((unsigned)B), dim3(rqhip::kSelThreads), lds, (hipStream_t)stream,
                      cand_ids, cand_lp, valid, keys, n_keys, base, checked, parents, parent_lp, (int)kprev, (int)n_cand,
-                     (int)P, (int)k, out_ids, out_lp);
+                     (int)P, (int)k, out_ids, out_lp, out_parent);
   RQ_LAUNCH_CHECK("rq_beam_select");
+  return 0;
+}
+
+int rq_beam_select(const int64_t* cand_ids, const float* cand_lp, const bool* valid, const int64_t* keys,
+                   int64_t n_keys, int64_t base, int64_t checked, const int64_t* parents, const float* parent_lp,
+                   int64_t B, int64_t kprev, int64_t n_cand, int64_t P, int64_t k, int64_t* out_ids, float* out_lp,
+                   void* stream) {
+  return rq_beam_select_parent(cand_ids, cand_lp, valid, keys, n_keys, base, checked, parents, parent_lp, B, kprev,
+                               n_cand, P, k, out_ids, out_lp, nullptr, stream);
+}
+
+int rq_beam_self_attn(const float* q, int64_t sq, const float* const* k_steps, const float* const* v_steps,
+                      const int64_t* strides, const int64_t* rows, const int32_t* anc, int64_t R, int64_t t,
+                      int64_t H, int64_t hd, float scale, float* out, int64_t so, void* stream) {
+  RQ_CHECK_ARG(R >= 0 && t >= 0 && t < RQ_BEAM_MAX_T && H >= 1 && H <= 4096,
+               "rq_beam_self_attn: need R >= 0, 0 <= t < %d, 1 <= H <= 4096 (R=%lld, t=%lld, H=%lld)", RQ_BEAM_MAX_T,
+               (long long)R, (long long)t, (long long)H);
+  RQ_CHECK_ARG(hd == 16 || hd == 32 || hd == 64 || hd == 128, "rq_beam_self_attn: head_dim must be 16, 32, 64 or 128 (got %lld)",
+               (long long)hd);
+  const int64_t A = H * hd;
+  RQ_CHECK_ARG(sq >= A && sq % 4 == 0 && so >= A && so % 4 == 0,
+               "rq_beam_self_attn: q / out row strides must be >= H * hd and multiples of 4");
+  RQ_CHECK_ARG(k_steps && v_steps && strides && rows, "rq_beam_self_attn: null step array");
+  RQ_CHECK_ARG((anc == nullptr) == (t == 0), "rq_beam_self_attn: anc is NULL exactly when t == 0");
+  rqhip::BeamSteps st = {};
+  for (int64_t s = 0; s <= t; ++s) {
+    RQ_CHECK_ARG(rows[s] >= (R > 0 ? 1 : 0) && rows[s] <= 0x7fffffff, "rq_beam_self_attn: step %lld has %lld rows",
+                 (long long)s, (long long)rows[s]);
+    RQ_CHECK_ARG(strides[s] >= A && strides[s] % 4 == 0,
+                 "rq_beam_self_attn: step %lld row stride %lld must be >= H * hd and a multiple of 4", (long long)s,
+                 (long long)strides[s]);
+    RQ_CHECK_ARG(R == 0 || (k_steps[s] && v_steps[s]), "rq_beam_self_attn: null K / V pointer at step %lld", (long long)s);
+    RQ_CHECK_ARG(((uintptr_t)k_steps[s] | (uintptr_t)v_steps[s]) % 16 == 0,
+                 "rq_beam_self_attn: K / V of step %lld must be 16-byte aligned", (long long)s);
+    st.k[s] = k_steps[s];
+    st.v[s] = v_steps[s];
+    st.stride[s] = strides[s];
+    st.rows[s] = rows[s];
+  }
+  RQ_CHECK_ARG(rows[t] == R, "rq_beam_self_attn: the current step holds one row per beam (rows[t]=%lld, R=%lld)",
+               (long long)rows[t], (long long)R);
+  if (R == 0) return 0;
+  RQ_CHECK_ARG(q && out, "rq_beam_self_attn: null pointer");
+  RQ_CHECK_ARG(((uintptr_t)q | (uintptr_t)out) % 16 == 0, "rq_beam_self_attn: q / out must be 16-byte aligned");
+  const int64_t units = R * H;
+  RQ_CHECK_ARG(units <= ((int64_t)1 << 33), "rq_beam_self_attn: too many (row, head) units");
+  hipStream_t hs = (hipStream_t)stream;
+  switch (hd) {
+    case 16: rqhip::launch_beam_self_attn<4>(q, sq, st, anc, units, (int)H, (int)t, scale, out, so, hs); break;
+    case 32: rqhip::launch_beam_self_attn<8>(q, sq, st, anc, units, (int)H, (int)t, scale, out, so, hs); break;
+    case 64: rqhip::launch_beam_self_attn<16>(q, sq, st, anc, units, (int)H, (int)t, scale, out, so, hs); break;
+    default: rqhip::launch_beam_self_attn<32>(q, sq, st, anc, units, (int)H, (int)t, scale, out, so, hs); break;
+  }
+  RQ_LAUNCH_CHECK("rq_beam_self_attn");
   return 0;
 }
 

@@ -156,6 +156,21 @@ class EncoderDecoderRetrievalModel(nn.Module):
         return self.transformer(x=transformer_input, context=transformer_context, padding_mask=batch.seq_mask,
                                 jagged=True)
 
+    def _context_inputs(self, batch: TokenizedSeqBatch) -> Jagged:
+        """The encoder's jagged input alone (_predict's context half, the torch composition; eval: no dropout)."""
+        user_emb = self.user_id_embedder(batch.user_ids)                  # (B, 1, E)
+        seq_emb = self.sem_id_embedder(batch._replace(sem_ids_fut=None, token_type_ids_fut=None)).seq
+        N = seq_emb.shape[1]
+        pos = self.wpe(torch.arange(N, device=seq_emb.device)).unsqueeze(0)
+        if _BATCH_SUM:
+            ctx = torch.cat([user_emb, hip_ops.batch_add(seq_emb, pos)], dim=1)
+        else:
+            ctx = torch.cat([user_emb, pos + seq_emb], dim=1)
+        bucket = gemm_tuning.ROW_BUCKET if gemm_tuning.is_enabled() else None
+        ctx_j = padded_to_jagged(ctx.contiguous(), batch.seq_mask.sum(axis=1) + 1, N + 1,
+                                 alloc_rows=self.context_rows(batch, bucket), known_max=N + 1)
+        return ctx_j.with_values(self.in_proj_context(self.norm.forward_dropout(ctx_j.values(), self.do)))
+
     def _gemm_weights(self):
         return [m.weight for m in self.modules() if isinstance(m, nn.Linear)]
 
@@ -195,15 +210,23 @@ class EncoderDecoderRetrievalModel(nn.Module):
     @reset_encoder_cache
     @torch.no_grad()
     def generate_next_sem_id(self, batch: TokenizedSeqBatch, temperature: int = 1, top_k: bool = True, *,
-                             fused: bool = False, sample: bool = True) -> GenerationOutput:
+                             fused: bool = False, sample: bool = True,
+                             incremental: bool = False) -> GenerationOutput:
         """Beam-style decoding of the next item's L+1 sem-ID tokens (reference :149-245): per step
         sample 200 candidates per beam from softmax(logits / T), drop prefixes the verifier
         rejects (-10000), keep the top 32 cumulative log-probabilities. The encoder output is
         computed once and repeated per beam with the HIP jagged kernels (jagged -> padded,
         repeat_interleave, padded -> jagged), as the reference does with torch ops.
         fused=True: each step's softmax, sampling, verification, top-k and parent gather on two HIP
-        launches (_generate_fused); sample=False then takes the most probable candidates instead of a draw."""
+        launches (_generate_fused); sample=False then takes the most probable candidates instead of a draw.
+        incremental=True (needs fused=True): the same loop over a BeamDecodeState — the context's cross-attention
+        K / V projected once for the B users and only each beam's newest token run through the decoder
+        (_generate_incremental)."""
+        if incremental and not fused:
+            raise ValueError("generate_next_sem_id: incremental=True requires fused=True")
         assert self.enable_generation, "Model generation is not enabled"
+        if incremental:
+            return self._generate_incremental(batch, temperature, top_k, sample)
         if fused:
             return self._generate_fused(batch, temperature, top_k, sample)
         B = batch.sem_ids.shape[0]
@@ -253,6 +276,46 @@ class EncoderDecoderRetrievalModel(nn.Module):
                 log_probas = top_lp.detach().clone()
         return GenerationOutput(sem_ids=generated.squeeze(), log_probas=log_probas.squeeze())
 
+    def _beam_verify(self, index, i: int, cand_ids: Tensor, generated, n_cand: int) -> dict:
+        """hip_ops.beam_select's validity arguments for step i's candidates: the tokenizer's packed-prefix table
+        when `inference_prefix_index` is set, else `inference_verifier_fn` on the materialised prefixes."""
+        if index is not None:
+            from modules.tokenizer.semids import BATCH_SIZE
+            keys, base = index.prefix_table(i + 1)
+            # exists_prefix's batching quirk acts on the prefix tensor's leading axis: here the B * kprev logits
+            # rows (n_cand candidates each), of which the last partial batch of 16 goes unchecked
+            rows = cand_ids.shape[0]
+            return dict(keys=keys, base=base,
+                        checked=(rows // BATCH_SIZE * BATCH_SIZE if index.reference_batching else rows) * n_cand)
+        if generated is None:
+            valid = self.inference_verifier_fn(cand_ids.unsqueeze(-1))
+        else:
+            prefix = torch.cat([generated.flatten(0, 1).unsqueeze(1).repeat_interleave(n_cand, axis=1),
+                                cand_ids.unsqueeze(-1)], axis=-1)
+            valid = self.inference_verifier_fn(prefix)
+        return dict(valid=valid.to(torch.bool).reshape(-1).contiguous())
+
+    def _generate_incremental(self, batch: TokenizedSeqBatch, temperature, top_k: bool, sample: bool) -> GenerationOutput:
+        """_generate_fused's loop with the model's forwards replaced by BeamDecodeState steps: the same
+        hip_ops.beam_candidates / beam_select calls, verification and noise draws on logits of the same shapes.
+        The select launch also returns each winner's parent beam, which is all the state needs to follow the
+        beams. One weight split for the whole call. Runs under generate_next_sem_id's decorators."""
+        B = batch.sem_ids.shape[0]
+        k = 32 if top_k else 1
+        n_cand = 200 if top_k else 1
+        index = getattr(self, "inference_prefix_index", None)
+        generated, log_probas, parent = None, None, None
+        with hip_ops.weight_split_scope(self._gemm_weights(), self._gemm_weight_stacks()):
+            state = BeamDecodeState(self, batch)
+            for i in range(self.sem_id_dim):
+                logits = (state.step() if generated is None else state.step(generated[:, :, -1], parent)).contiguous()
+                noise = torch.empty_like(logits).exponential_() if sample else None
+                cand_ids, cand_lp = hip_ops.beam_candidates(logits, n_cand, temperature, noise)
+                verify = self._beam_verify(index, i, cand_ids, generated, n_cand)
+                generated, log_probas, parent = hip_ops.beam_select(cand_ids, cand_lp, k, batch=B, parents=generated,
+                                                                    parent_lp=log_probas, return_parent=True, **verify)
+        return GenerationOutput(sem_ids=generated.squeeze(), log_probas=log_probas.squeeze())
+
     def _generate_fused(self, batch: TokenizedSeqBatch, temperature, top_k: bool, sample: bool) -> GenerationOutput:
         """generate_next_sem_id with the per-step beam logic on hip_ops.beam_candidates (softmax, the draw, the
         candidates' log-probabilities) and hip_ops.beam_select (verification, cumulative score, stable top-k,
@@ -272,22 +335,7 @@ class EncoderDecoderRetrievalModel(nn.Module):
             logits = self.forward(cur).logits.contiguous()
             noise = torch.empty_like(logits).exponential_() if sample else None
             cand_ids, cand_lp = hip_ops.beam_candidates(logits, n_cand, temperature, noise)
-            if index is not None:
-                from modules.tokenizer.semids import BATCH_SIZE
-                keys, base = index.prefix_table(i + 1)
-                # exists_prefix's batching quirk acts on the prefix tensor's leading axis: here the B * kprev logits
-                # rows (n_cand candidates each), of which the last partial batch of 16 goes unchecked
-                rows = cand_ids.shape[0]
-                verify = dict(keys=keys, base=base,
-                              checked=(rows // BATCH_SIZE * BATCH_SIZE if index.reference_batching else rows) * n_cand)
-            elif generated is None:
-                verify = dict(valid=self.inference_verifier_fn(cand_ids.unsqueeze(-1)))
-            else:
-                prefix = torch.cat([generated.flatten(0, 1).unsqueeze(1).repeat_interleave(n_cand, axis=1),
-                                    cand_ids.unsqueeze(-1)], axis=-1)
-                verify = dict(valid=self.inference_verifier_fn(prefix))
-            if "valid" in verify:
-                verify["valid"] = verify["valid"].to(torch.bool).reshape(-1).contiguous()
+            verify = self._beam_verify(index, i, cand_ids, generated, n_cand)
             first = generated is None
             generated, log_probas = hip_ops.beam_select(cand_ids, cand_lp, k, batch=B, parents=generated,
                                                         parent_lp=log_probas, **verify)
@@ -309,3 +357,55 @@ class EncoderDecoderRetrievalModel(nn.Module):
                                         seq_mask=cur.seq_mask.repeat_interleave(k, dim=0),
                                         token_type_ids=cur.token_type_ids.repeat_interleave(k, dim=0))
         return GenerationOutput(sem_ids=generated.squeeze(), log_probas=log_probas.squeeze())
+
+
+class BeamDecodeState:
+    """Incremental beam decoding of an eval-mode EncoderDecoderRetrievalModel for one batch of B users.
+
+    Construction runs the encoder once and projects every decoder layer's cross-attention K / V once, from the B
+    un-repeated contexts (cross-attention is not causal and a user's beams attend the same keys). `step()` pushes
+    the B BOS rows through the decoder and returns logits (B, K); `step(tokens, parent)` then takes each kept
+    beam's newest token (B, k) int64 and its parent beam index (B, k) in [0, kprev) — hip_ops.beam_select(
+    return_parent=True) — and returns logits (B * k, K), b-major. Only the newest token of every beam runs through
+    the decoder: self-attention is causal and the block's other ops are row-wise, so earlier tokens enter only
+    through their self-attention K / V. Those stay in each step's packed qkv output where they were written; an
+    ancestor row table (hip_ops.beam_advance_ancestors) follows the beams through every re-ordering, so no cache
+    is gathered or appended. The state holds its tensors for one generation call; drop it afterwards."""
+
+    @torch.no_grad()
+    def __init__(self, model: EncoderDecoderRetrievalModel, batch: TokenizedSeqBatch) -> None:
+        assert not model.training, "BeamDecodeState: eval mode only"
+        assert model.sem_id_dim <= hip_ops.BEAM_MAX_T, "BeamDecodeState: sem_id_dim exceeds RQ_BEAM_MAX_T"
+        self.model = model
+        self.B = batch.sem_ids.shape[0]
+        tr = model.transformer
+        enc = tr.encoder(model._context_inputs(batch), padding_mask=batch.seq_mask, is_causal=False, context=None,
+                         jagged=True)
+        self.cross_kvs = tr.decoder.cross_kv(enc)
+        self.cu_k, self.max_k = enc.offsets(), enc.max_len
+        self.self_kv = [[] for _ in tr.decoder.layers]   # per layer: one (k, v) view pair per step so far
+        self.anc = None      # (rows, t) int32: each current beam's row in every earlier step
+        self.rows = self.B   # rows of the previous step
+        self.t = 0           # tokens pushed so far (BOS included)
+
+    @torch.no_grad()
+    def step(self, tokens: Tensor = None, parent: Tensor = None) -> Tensor:
+        m, B = self.model, self.B
+        assert self.t < m.sem_id_dim, "BeamDecodeState: every token of the sem-ID has been decoded"
+        if self.t == 0:
+            assert tokens is None and parent is None, "BeamDecodeState: the first step takes no tokens"
+            group = 1
+            x = m.bos_emb.unsqueeze(0).expand(B, -1).contiguous()
+        else:
+            assert tokens.shape == parent.shape and tokens.shape[0] == B
+            group, j = tokens.shape[1], self.t - 1
+            # the j-th generated token: sem-ID table row j K + token plus token-type row j (token_type_ids_fut)
+            x = m.sem_id_embedder.emb((j * m.num_embeddings + tokens).reshape(-1)) + m.tte.weight[j]
+            self.anc = hip_ops.beam_advance_ancestors(self.anc, parent, self.rows // B)
+        x = m.in_proj(m.norm_cxt(x))
+        cu_q = torch.arange(B + 1, device=x.device, dtype=self.cu_k.dtype) * group
+        h = m.transformer.decoder.decode_step(x, self.self_kv, self.anc, self.cross_kvs, cu_q, self.cu_k, group,
+                                              self.max_k)
+        self.t += 1
+        self.rows = B * group
+        return m.out_proj(h)

@@ -141,6 +141,41 @@ class TransformerBlock(nn.Module):
             return jx.with_values(hip_ops.dropout_add(hr, y, drop.p))
         return jx.with_values(hr + drop(y))
 
+    def decode_step(self, x: Tensor, self_kv: list, anc: Optional[Tensor], cross_kv: Tensor, cu_q: Tensor,
+                    cu_k: Tensor, group: int, max_k: int) -> Tensor:
+        """The block on the NEWEST token of every beam alone (incremental beam decoding, eval only): x (R, d) holds
+        one row per beam, b-major with `group` beams per user. Self-attention is causal and every other op is
+        row-wise, so earlier tokens enter only through their self-attention K / V: `self_kv` is this layer's list
+        of (k, v) column views of the earlier steps' packed qkv outputs — this step's pair is appended — and
+        `anc` (R, t) names each beam's row in every earlier step (hip_ops.beam_self_attention; nothing is copied
+        when beams are re-ordered). Cross-attention is not causal and a user's beams share their keys: `cross_kv`
+        is this layer's K / V projection of the B un-repeated contexts (offsets `cu_k`), attended by each user's
+        `group` contiguous query rows as one segment (`cu_q`). Same op order as forward:
+        h = x + SA(n1(x)); h += CA(n2(x)); out = h + MLP(norm(h))."""
+        assert self.do_cross_attn and not self.training, "decode_step: eval-mode decoder blocks only"
+        a, c, A = self.attention, self.cross_attention, self.d_out
+        norm, mlp, _ = self.ff
+        fork = self._fork_ok(x)
+        if fork:
+            n1, n2, xr = hip_ops.rmsnorm_fork(x, self.attn_norm.eps, self.attn_norm.weight, 0.0,
+                                              self.cross_attn_norm.weight, 0.0)
+        else:
+            n1, n2, xr = self.attn_norm(x), self.cross_attn_norm(x), x
+        if _PAIR_PROJ and self._pair_ok(n1, n2):
+            qkv, q2 = hip_ops.linear_pair(n1, a.qkv.weight, n2, c.q.weight)
+        else:
+            qkv, q2 = a.qkv(n1), c.q(n2)
+        self_kv.append((qkv[:, A:2 * A], qkv[:, 2 * A:]))
+        sa = hip_ops.beam_self_attention(qkv[:, :A], self_kv, anc, self.num_heads)
+        h = hip_ops.linear_add(sa, a.proj.weight, xr)
+        ca = hip_ops.varlen_attention_packed(q2, cross_kv, cu_q, cu_k, self.num_heads, False, group, max_k)
+        h = hip_ops.linear_add(ca, c.proj.weight, h)
+        if fork:
+            n3, h = hip_ops.rmsnorm_fork(h, norm.eps, norm.weight)
+        else:
+            n3 = norm(h)
+        return h + mlp(n3)
+
     def _pair_ok(self, n1, n2) -> bool:
         a, c = self.attention, self.cross_attention
         return (a.qkv.bias is None and c.q.bias is None and
@@ -174,6 +209,19 @@ class TransformerDecoder(nn.Module, KVCacheOpsMixin):
         for i, layer in enumerate(self.layers):
             h = layer._forward_jagged(h, ctx, is_causal, kvs[i] if kvs is not None else None)
         return h if isinstance(x, Jagged) else _wrap_like(h.values(), x)
+
+    def cross_kv(self, ctx: Jagged) -> list:
+        """Every layer's cross-attention K / V projection (T, 2 d_out) of the context: the hoisted projection
+        where it applies, the per-layer `kv` Linears otherwise."""
+        kvs = self._hoisted_kv(ctx)
+        return kvs if kvs is not None else [layer.cross_attention.kv(ctx.values()) for layer in self.layers]
+
+    def decode_step(self, x: Tensor, self_kv: list, anc: Optional[Tensor], cross_kvs: list, cu_q: Tensor,
+                    cu_k: Tensor, group: int, max_k: int) -> Tensor:
+        """TransformerBlock.decode_step through every layer; self_kv / cross_kvs hold one entry per layer."""
+        for layer, skv, ckv in zip(self.layers, self_kv, cross_kvs):
+            x = layer.decode_step(x, skv, anc, ckv, cu_q, cu_k, group, max_k)
+        return x
 
     def hoisted_kv_weights(self):
         """The cross-attention K/V weights _hoisted_kv concatenates (for the forward's weight split), or None."""

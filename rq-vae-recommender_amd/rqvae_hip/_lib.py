@@ -90,6 +90,9 @@ _SIGS = {
     "rq_seed_epoch_set": ([_U64, _P], _I),
     "rq_beam_candidates": ([_P, _P, _I64, _I64, _I64, _F, _P, _P, _P], _I),
     "rq_beam_select": ([_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P], _I),
+    "rq_beam_select_parent": ([_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P],
+                              _I),
+    "rq_beam_self_attn": ([_P, _I64, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _F, _P, _I64, _P], _I),
     "rq_topk_hits": ([_P, _P, _I64, _I64, _I64, _P, _I64, _P, _P], _I),
     "rq_adamw_step": ([_P, _I64, _F, _F, _F, _F, _F, _F, _F, _P], _I),
     "rq_adamw_chunk_elems": ([], _SZ),

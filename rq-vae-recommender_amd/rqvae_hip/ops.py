@@ -2300,12 +2300,14 @@ def beam_candidates(logits: torch.Tensor, n_cand: int, temperature: float = 1.0,
 
 def beam_select(cand_ids: torch.Tensor, cand_lp: torch.Tensor, k: int, *, batch: int, valid: torch.Tensor = None,
                 keys: torch.Tensor = None, base: int = 0, checked: int = None, parents: torch.Tensor = None,
-                parent_lp: torch.Tensor = None):
+                parent_lp: torch.Tensor = None, return_parent: bool = False):
     """(out_ids (B, k, P + 1) int64, out_lp (B, k) fp32): the k best continuations per batch element of the
     candidates beam_candidates returned for its B * kprev rows (rq_beam_select). parents (B, kprev, P) /
     parent_lp (B, kprev): the beams so far (None on the first step). Validity: `valid` (a bool tensor of B * kprev
     * n_cand elements) or `keys` / `base` (SemanticIdTokenizer.prefix_table(P + 1)) with `checked` = the number of
-    leading flat candidates the verifier looks at (default: all). One launch, no host read."""
+    leading flat candidates the verifier looks at (default: all). One launch, no host read.
+    return_parent=True: a third result, (B, k) int32, each winner's parent beam index in [0, kprev)
+    (rq_beam_select_parent; the first two results are unchanged)."""
     what = "beam_select"
     require_gpu(cand_ids, cand_lp, valid, keys, parents, parent_lp, what=what)
     B = int(batch)
@@ -2339,10 +2341,85 @@ def beam_select(cand_ids: torch.Tensor, cand_lp: torch.Tensor, k: int, *, batch:
         _beam_arg(keys, torch.int64, what, "keys")
     out_ids = torch.empty((B, int(k), P + 1), device=cand_ids.device, dtype=torch.int64)
     out_lp = torch.empty((B, int(k)), device=cand_ids.device, dtype=torch.float32)
+    if return_parent:
+        out_parent = torch.empty((B, int(k)), device=cand_ids.device, dtype=torch.int32)
+        call("rq_beam_select_parent", ptr(cand_ids), ptr(cand_lp), ptr(valid), ptr(keys),
+             0 if keys is None else keys.numel(), int(base), B * N if checked is None else int(checked), ptr(parents),
+             ptr(parent_lp), B, kprev, n_cand, P, int(k), ptr(out_ids), ptr(out_lp), ptr(out_parent),
+             stream_handle(cand_ids.device))
+        return out_ids, out_lp, out_parent
     call("rq_beam_select", ptr(cand_ids), ptr(cand_lp), ptr(valid), ptr(keys), 0 if keys is None else keys.numel(),
          int(base), B * N if checked is None else int(checked), ptr(parents), ptr(parent_lp), B, kprev, n_cand, P,
          int(k), ptr(out_ids), ptr(out_lp), stream_handle(cand_ids.device))
     return out_ids, out_lp
+
+
+BEAM_MAX_T = 8   # RQ_BEAM_MAX_T
+
+
+def beam_self_attention(q: torch.Tensor, kv_steps, anc: torch.Tensor, num_heads: int, scale: float = None):
+    """out (R, A) fp32: the newest token's causal self-attention of R beams over their ancestors
+    (rq_beam_self_attn). q (R, A): the newest token's queries; kv_steps: t + 1 pairs (k, v) of (R_s, A) column
+    views of each decoding step's packed qkv tensor, the last pair the current step's own (R rows); anc (R, t)
+    int32, anc[r][s] = the row of step s holding beam r's token s (beam_advance_ancestors), None when t == 0. The
+    step tensors are read where they were written: no per-beam cache is gathered. The entries of anc are the
+    caller's contract (in [0, R_s)); they are not checked. One launch, no host read."""
+    import ctypes
+    what = "beam_self_attention"
+    kv_steps = list(kv_steps)
+    require_gpu(q, anc, *(x for kv in kv_steps for x in kv), what=what)
+    t = len(kv_steps) - 1
+    if not 0 <= t < BEAM_MAX_T:
+        raise RqHipError(f"{what}: need 1..{BEAM_MAX_T} steps, got {t + 1}")
+    if q.dim() != 2 or q.dtype != torch.float32 or (q.shape[1] > 1 and q.stride(1) != 1):
+        raise RqHipError(f"{what}: q must be (R, A) fp32 with a contiguous last dimension")
+    R, A = q.shape
+    H = int(num_heads)
+    if H < 1 or A % H:
+        raise RqHipError(f"{what}: A = {A} is not a multiple of num_heads = {H}")
+    for s, kv in enumerate(kv_steps):
+        if len(kv) != 2:
+            raise RqHipError(f"{what}: kv_steps[{s}] must be a (k, v) pair")
+        k, v = kv
+        for name, x in (("k", k), ("v", v)):
+            if x.dim() != 2 or x.dtype != torch.float32 or x.shape[1] != A or x.stride(1) != 1 or x.device != q.device:
+                raise RqHipError(f"{what}: {name} of step {s} must be (R_s, {A}) fp32 on {q.device} with a contiguous "
+                                 f"last dimension, got {tuple(x.shape)} {x.dtype} strides {x.stride()}")
+        if k.shape[0] != v.shape[0] or k.stride(0) != v.stride(0):
+            raise RqHipError(f"{what}: k and v of step {s} must be views of one tensor (rows / row stride differ)")
+    if kv_steps[t][0].shape[0] != R:
+        raise RqHipError(f"{what}: the last step must hold one row per beam ({kv_steps[t][0].shape[0]} != {R})")
+    if t == 0:
+        if anc is not None and anc.numel():
+            raise RqHipError(f"{what}: anc must be None for a single step")
+        anc = None
+    else:
+        if anc is None:
+            raise RqHipError(f"{what}: anc (R, t) is required for t = {t}")
+        _beam_arg(anc, torch.int32, what, "anc", (R, t))
+    out = torch.empty((R, A), device=q.device, dtype=torch.float32)
+    n = t + 1
+    P = ctypes.c_void_p * n
+    I = ctypes.c_int64 * n
+    call("rq_beam_self_attn", ptr(q), q.stride(0), P(*[k.data_ptr() for k, _ in kv_steps]),
+         P(*[v.data_ptr() for _, v in kv_steps]), I(*[k.stride(0) for k, _ in kv_steps]),
+         I(*[k.shape[0] for k, _ in kv_steps]), ptr(anc), R, t, H, A // H,
+         float(scale) if scale is not None else 1.0 / math.sqrt(A // H), ptr(out), out.stride(0),
+         stream_handle(q.device))
+    return out
+
+
+def beam_advance_ancestors(anc: torch.Tensor, parent: torch.Tensor, kprev: int) -> torch.Tensor:
+    """The ancestor table of the beams a selection kept (plain torch; CPU or device tensors). parent (B, k): each
+    new beam's parent beam index in [0, kprev) (beam_select(return_parent=True)); anc (B * kprev, t - 1) int32: the
+    parents' table (None on the first advance, when the parents are the BOS rows). Returns (B * k, t) int32:
+    cat([anc[prow], prow[:, None]], 1) with prow = b * kprev + parent[b, j] the parent's row in the previous step."""
+    B = parent.shape[0]
+    prow = (torch.arange(B, device=parent.device).unsqueeze(1) * int(kprev) + parent.long()).reshape(-1)
+    last = prow.unsqueeze(1).to(torch.int32)
+    if anc is None:
+        return last
+    return torch.cat([anc[prow].to(torch.int32), last], 1)
 
 
 def topk_hits(actual: torch.Tensor, topk: torch.Tensor, ks, counts: torch.Tensor) -> torch.Tensor:

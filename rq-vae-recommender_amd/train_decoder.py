@@ -113,6 +113,8 @@ class _Prefetch:
 # Generation path of the full eval: the fused HIP beam step (modules/model.py _generate_fused) or the reference's
 # torch composition — whichever measured faster at the Amazon eval shape (tools/generation_time.py).
 EVAL_FUSED_GENERATION = True
+# Incremental beam decoding under the fused beam step (modules/model.py BeamDecodeState): opt-in.
+EVAL_INCREMENTAL_GENERATION = False
 
 
 class _Evaluator:
@@ -186,7 +188,8 @@ class _Evaluator:
         self.model.enable_generation = True
         self.metrics.reset()
         for tok in self._batches():
-            gen = self.model.generate_next_sem_id(tok, top_k=True, temperature=1, fused=EVAL_FUSED_GENERATION)
+            gen = self.model.generate_next_sem_id(tok, top_k=True, temperature=1, fused=EVAL_FUSED_GENERATION,
+                                                  incremental=EVAL_INCREMENTAL_GENERATION)
             self.metrics.accumulate(actual=tok.sem_ids_fut, top_k=gen.sem_ids)
         res = self.metrics.reduce()
         self.metrics.reset()

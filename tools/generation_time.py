@@ -3,16 +3,19 @@
 per beam, 256 classes, 4 sem-ID tokens; model dims of configs/decoder_amazon.gin):
 
   generation   generate_next_sem_id(top_k=True) with fused=False (the reference's torch composition of the beam
-               step) and fused=True (rq_beam_candidates + rq_beam_select), verifier = a tokenizer over a
-               12,101-item corpus; and with the beam step stubbed out (`model`: the four forwards and the encoder
-               cache repeat alone), which gives the beam logic's share of each form;
+               step), fused=True (rq_beam_candidates + rq_beam_select) and fused=True, incremental=True (the same
+               beam step over a BeamDecodeState: cross K/V projected once per user, only each beam's newest token
+               through the decoder), verifier = a tokenizer over a 12,101-item corpus; and with the beam step
+               stubbed out (`model`: the four forwards and the encoder cache repeat alone), which gives the
+               beam logic's share of the first two forms;
   accumulate   TopKAccumulator.accumulate on the device (one rq_topk_hits launch) and the reference's logic
                (evaluate/metrics.py:15-28, restated below: 24 host reads per batch).
 
 Each form is warmed up, then timed `--reps` times with the forms alternating; a span is a host clock around work
-that ends in a device synchronise. Prints one JSON line (medians, ms). `--only FORM --reps N --warmup 0` runs a
-single form N times for a kernel trace (rocprofv3 --kernel-trace --stats -- python tools/generation_time.py ...):
-launches per beam step = (calls of the form - calls of `model`) / (4 N).
+that ends in a device synchronise. Prints one JSON line (medians, ms; `peak_mem_mib`: torch.cuda.max_memory_allocated
+over one further call of each generation form). `--only FORM --reps N --warmup 0` runs a single form N times for a
+kernel trace (rocprofv3 --kernel-trace --stats -- python tools/generation_time.py ...), after the set-up's one
+fused call: launches per beam step = (calls of the form - calls of `model`) / (4 N).
 """
 import argparse
 import json
@@ -66,7 +69,7 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--only", choices=["unfused", "fused", "model", "acc_device", "acc_reference"])
+    ap.add_argument("--only", choices=["unfused", "fused", "incremental", "model", "acc_device", "acc_reference"])
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("generation_time: needs the GPU (a CPU run measures nothing)")
@@ -92,8 +95,8 @@ def main():
                         torch.zeros((batch, kk), device=device))
         return fixed[P]
 
-    def gen(fused):
-        return model.generate_next_sem_id(batch, temperature=1, top_k=True, fused=fused)
+    def gen(fused, incremental=False):
+        return model.generate_next_sem_id(batch, temperature=1, top_k=True, fused=fused, incremental=incremental)
 
     def gen_model_only():
         hip_ops.beam_candidates, hip_ops.beam_select = stub_candidates, stub_select
@@ -113,7 +116,8 @@ def main():
     def acc_reference():
         reference_accumulate({}, [1, 5, 10], actual, top)
 
-    forms = {"unfused": lambda: gen(False), "fused": lambda: gen(True), "model": gen_model_only,
+    forms = {"unfused": lambda: gen(False), "fused": lambda: gen(True),
+             "incremental": lambda: gen(True, True), "model": gen_model_only,
              "acc_device": acc_device, "acc_reference": acc_reference}
     if args.only:
         forms = {args.only: forms[args.only]}
@@ -130,6 +134,18 @@ def main():
     out = {"shape": dict(B=B, k=k, n_cand=n_cand, V=256, L1=L1), "reps": args.reps,
            "median_ms": {n: round(v, 4) for n, v in med.items()},
            "min_max_ms": {n: [round(min(v), 4), round(max(v), 4)] for n, v in times.items() if v}}
+    peak = {}
+    for name in ("unfused", "fused", "incremental"):
+        if name in forms and not args.only:   # one more call of each generation form, alone after a peak reset
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats(device)
+            forms[name]()
+            torch.cuda.synchronize()
+            peak[name] = round(torch.cuda.max_memory_allocated(device) / 2 ** 20, 1)
+    if peak:
+        out["peak_mem_mib"] = peak
+    if {"fused", "incremental"} <= set(med):
+        out["incremental_speedup"] = round(med["fused"] / med["incremental"], 4)
     if {"unfused", "fused", "model"} <= set(med):
         out["beam_logic_share"] = {n: round(1 - med["model"] / med[n], 4) for n in ("unfused", "fused")}
         out["beam_logic_ms"] = {n: round(med[n] - med["model"], 4) for n in ("unfused", "fused")}
