@@ -479,7 +479,22 @@ int varlen_attn_bwd(const float* q, int64_t sq, const float* k, int64_t sk, cons
  *   an unspecified result). out[r, h] = sum_s softmax_s(scale q[r,h] . k_s[anc[r][s], h]) v_s[anc[r][s], h]: fp32
  *   scores, max subtracted, sums over s = 0..t in ascending order; at t == 0 out == v bitwise. q (R, H hd) with
  *   row stride sq, out row stride so; every stride >= H hd and a multiple of 4; hd in {16, 32, 64, 128};
- *   0 <= t < RQ_BEAM_MAX_T; R == 0 returns 0 without a launch. */
+ *   0 <= t < RQ_BEAM_MAX_T; R == 0 returns 0 without a launch.
+ * rq_beam_expand: constrained decoding — one beam step against the corpus' prefix trie in ONE launch (no noise, no
+ *   candidate lists, no table search). The trie is level-by-level CSR (SemanticIdTokenizer.prefix_trie): child_off
+ *   (n_nodes + 1 int32) of level P and tok (n_children int32) of level P + 1; node i's children are
+ *   [child_off[i], child_off[i + 1]), ascending by token. node (B, kprev) int32 is each beam's level-P node (NULL iff
+ *   P == 0: every beam sits on the root, node 0); parents (B, kprev, P) int64 / parent_lp (B, kprev) fp32 as
+ *   rq_beam_select (NULL iff P == 0). Candidates of batch element b: for every live beam j (node in [0, n_nodes)),
+ *   every child c of its node with v = tok[c] in [0, V); score = lp(j, v) + parent_lp[b][j], lp the log-softmax of
+ *   logits[b kprev + j] / temperature formed exactly as rq_beam_candidates forms cand_lp (bitwise equal). Outputs, k
+ *   best in descending score order, ties to the lower beam then the lower token, NaN on top: out_ids (B, k, P + 1)
+ *   int64 = parent prefix then token, out_lp (B, k) fp32, out_parent (B, k) int32 in [0, kprev), out_node (B, k)
+ *   int32 = the winner's level-(P + 1) node c. With fewer than k candidates the remaining rows are DEAD: out_ids all
+ *   -1, out_lp -inf, out_parent 0, out_node -1; a dead or out-of-range node entry contributes no candidates. The
+ *   tables are the caller's contract, but a bad one never reads outside a buffer: child_off is clamped into
+ *   [0, n_children], tokens outside [0, V) are skipped (an unsorted range gives an unspecified out_node or -1).
+ *   V <= 4096, kprev V <= 8192, 1 <= k <= 8192, P < 64, temperature > 0; outside that -22, never a truncated result. */
 #define RQ_BEAM_MAX_T 8 /* tokens per beam incl. BOS; sem_id_dim <= 8 as evaluate.metrics already assumes */
 int rq_beam_candidates(const float* logits, const float* noise, int64_t R, int64_t V, int64_t n_cand,
                        float temperature, int64_t* cand_ids, float* cand_lp, void* stream);
@@ -494,6 +509,10 @@ int rq_beam_select_parent(const int64_t* cand_ids, const float* cand_lp, const b
 int rq_beam_self_attn(const float* q, int64_t sq, const float* const* k_steps, const float* const* v_steps,
                       const int64_t* strides, const int64_t* rows, const int32_t* anc, int64_t R, int64_t t,
                       int64_t H, int64_t hd, float scale, float* out, int64_t so, void* stream);
+int rq_beam_expand(const float* logits, float temperature, const int32_t* node, const int32_t* child_off,
+                   int64_t n_nodes, const int32_t* tok, int64_t n_children, const int64_t* parents,
+                   const float* parent_lp, int64_t B, int64_t kprev, int64_t V, int64_t P, int64_t k, int64_t* out_ids,
+                   float* out_lp, int32_t* out_parent, int32_t* out_node, void* stream);
 int rq_topk_hits(const int64_t* actual, const int64_t* topk, int64_t B, int64_t k, int64_t D, const int* ks,
                  int64_t n_ks, int64_t* counts, void* stream);
 

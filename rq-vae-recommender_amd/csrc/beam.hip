@@ -7,6 +7,9 @@
 //   beam_select_kernel      one workgroup per batch element: prefix verification (a caller-provided mask or
 //                           a binary search of the tokenizer's packed-prefix table), the cumulative score,
 //                           the k best of the kprev * n_cand candidates in stable order, the parent gather.
+//   beam_expand_kernel      constrained decoding, the whole beam step in one launch: one workgroup per batch
+//                           element walks the corpus' prefix trie (only valid continuations are scored), the k
+//                           best in stable order, the parent gather and each winner's trie node.
 //   beam_self_attn_kernel   incremental decoding: the newest token's causal self-attention over its beam's
 //                           ancestors, read in place from every step's packed qkv output through an
 //                           ancestor row table (no per-beam cache is gathered or appended).
@@ -223,6 +226,149 @@ __global__ void __launch_bounds__(kSelThreads) beam_select_kernel(
   }
 }
 
+// ------------------------------------------------------------------------------------- expand (trie walk)
+// Constrained beam step: one workgroup per batch element walks the corpus' prefix trie instead of drawing,
+// searching and masking candidates. The candidates of beam j are the children of its level-P node — a contiguous
+// range of level P + 1 that ascends by token — so only real continuations are ever scored.
+//   1. a wave per beam (round robin; 16 waves when kprev > 4, else 4: a beam is a chain of dependent global loads
+//      — node, child range, logits row, tokens — so this phase is latency-bound and more waves are what hides it):
+//      the row's max / lowest argmax and the sum of the other classes' exp(z - max),
+//      with beam_candidates_kernel's lane order (v = lane + 64 j) and wave reductions, so log p is bitwise what
+//      that kernel returns; the same wave then walks the node's children and writes score_key(log p + parent_lp)
+//      to key[j V + token] in LDS (0 = absent: the (beam, token) tie rule is the index order).
+//   2. beam_select_kernel's k rounds of a workgroup argmax over key[]; a round that finds only absent entries
+//      writes a dead row (ids -1, -inf, parent 0, node -1), as do all rounds after it.
+//   3. each winner's node index: a binary search of its parent's child range (<= 12 dependent probes), one
+//      thread per output row after the rounds, so the probes of the k rows overlap instead of stalling a round each.
+// Tables are the caller's contract but never trusted for addressing: node outside [0, n_nodes) is a dead beam,
+// child_off is clamped into [0, n_children], tokens outside [0, V) are skipped.
+constexpr int kExpMaxWaves = 16;
+
+__global__ void __launch_bounds__(64 * kExpMaxWaves) beam_expand_kernel(
+    const float* __restrict__ logits, float temperature, const int32_t* __restrict__ node,
+    const int32_t* __restrict__ child_off, int n_nodes, const int32_t* __restrict__ tok, int n_children,
+    const int64_t* __restrict__ parents, const float* __restrict__ parent_lp, int kprev, int V, int P, int k,
+    int64_t* __restrict__ out_ids, float* __restrict__ out_lp, int32_t* __restrict__ out_parent,
+    int32_t* __restrict__ out_node) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nthr = blockDim.x, nwave = nthr >> 6;   // 4 or kExpMaxWaves waves (the host picks by kprev)
+  const int N = kprev * V;
+  uint32_t* key = reinterpret_cast<uint32_t*>(smem);   // [N rounded up to 4], then the per-wave exchange
+  uint32_t* w_key = key + (N + 3) / 4 * 4;
+  int* w_idx = reinterpret_cast<int*>(w_key + kExpMaxWaves);
+  const int64_t b = blockIdx.x;
+
+  for (int e = tid; e < N; e += nthr) key[e] = 0;
+  __syncthreads();
+
+  for (int j = wave; j < kprev; j += nwave) {
+    const int nd = node ? node[b * kprev + j] : 0;
+    if (nd < 0 || nd >= n_nodes) continue;   // dead beam (wave-uniform)
+    const int lo = min(max(child_off[nd], 0), n_children);
+    const int hi = min(max(child_off[nd + 1], 0), n_children);
+    if (lo >= hi) continue;
+    const float* x = logits + (b * kprev + j) * V;
+    float m = -INFINITY;
+    int am = 0x7fffffff;
+    for (int v = lane; v < V; v += 64) {
+      const float z = x[v] / temperature;
+      if (z > m) { m = z; am = v; }
+    }
+    wave_argmax(m, am);
+    float rest = 0.f;
+    for (int v = lane; v < V; v += 64) {
+      const float dv = x[v] / temperature - m;
+      if (v != am) rest += expf(dv);
+    }
+    rest = group_sum<64>(rest);
+    const float sum = rest + 1.0f;
+    const float log_norm = log1pf(rest);
+    const float plp = parent_lp ? parent_lp[b * kprev + j] : 0.0f;
+    for (int c = lo + lane; c < hi; c += 64) {
+      const int v = tok[c];
+      if (v < 0 || v >= V) continue;   // a class the model cannot generate (e.g. a dedup count >= V)
+      const float dv = x[v] / temperature - m;
+      const float p = expf(dv) / sum;
+      const float lp = p == 0.f ? -INFINITY : dv - log_norm;
+      key[j * V + v] = score_key(lp + plp);
+    }
+  }
+  __syncthreads();
+
+  uint32_t best_k = 0;
+  int best_i = 0x7fffffff;
+  for (int e = tid; e < N; e += nthr) {
+    const uint32_t kk = key[e];
+    if (better(kk, e, best_k, best_i)) { best_k = kk; best_i = e; }
+  }
+  for (int r = 0; r < k; ++r) {
+    uint32_t wk = best_k;
+    int wi = best_i;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+      const uint32_t ok_ = __shfl_xor(wk, o, 64);
+      const int oi = __shfl_xor(wi, o, 64);
+      if (better(ok_, oi, wk, wi)) { wk = ok_; wi = oi; }
+    }
+    if (lane == 0) { w_key[wave] = wk; w_idx[wave] = wi; }
+    __syncthreads();
+    // lanes 0..nwave-1 hold the waves' winners: a butterfly inside the first 16 lanes, lane 0 broadcasts
+    wk = lane < nwave ? w_key[lane] : 0;
+    wi = lane < nwave ? w_idx[lane] : 0x7fffffff;
+#pragma unroll
+    for (int o = kExpMaxWaves / 2; o >= 1; o >>= 1) {
+      const uint32_t ok_ = __shfl_xor(wk, o, 64);
+      const int oi = __shfl_xor(wi, o, 64);
+      if (better(ok_, oi, wk, wi)) { wk = ok_; wi = oi; }
+    }
+    wk = __shfl(wk, 0, 64);
+    wi = __shfl(wi, 0, 64);
+    __syncthreads();   // w_key / w_idx are rewritten next round
+    int64_t* o = out_ids + (b * k + r) * (P + 1);
+    if (wk == 0) {   // no candidate left (block-uniform): a dead row
+      if (tid <= P) o[tid] = -1;   // P < 64
+      if (tid == 0) {
+        out_lp[b * k + r] = -INFINITY;
+        out_parent[b * k + r] = 0;
+        out_node[b * k + r] = -1;
+      }
+      continue;
+    }
+    if (tid == (wi % nthr)) {
+      key[wi] = 0;
+      best_k = 0;
+      best_i = 0x7fffffff;
+      for (int e = tid; e < N; e += nthr) {
+        const uint32_t kk = key[e];
+        if (better(kk, e, best_k, best_i)) { best_k = kk; best_i = e; }
+      }
+    }
+    const int par = wi / V, v = wi - par * V;
+    if (tid < P) o[tid] = parents[(b * kprev + par) * P + tid];
+    if (tid == 0) {
+      o[P] = v;
+      out_lp[b * k + r] = key_score(wk);
+      out_parent[b * k + r] = par;
+    }
+  }
+  __syncthreads();   // thread 0's rows (global) are visible to the workgroup
+  for (int r = tid; r < k; r += nthr) {
+    const int v = (int)out_ids[(b * k + r) * (P + 1) + P];
+    if (v < 0) continue;   // a dead row: its node is already -1
+    // the child of the parent's node that carries token v: the first entry >= v of its ascending range
+    const int nd = node ? node[b * kprev + out_parent[b * k + r]] : 0;
+    int lo = min(max(child_off[nd], 0), n_children);
+    const int end = min(max(child_off[nd + 1], 0), n_children);
+    int hi = end;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (tok[mid] < v) lo = mid + 1; else hi = mid;
+    }
+    out_node[b * k + r] = (lo < end && tok[lo] == v) ? lo : -1;   // -1: an unsorted (bad) table
+  }
+}
+
 // ------------------------------------------------------------------------------------- self-attention
 // The step buffers by value in the kernel arguments (no device-side pointer table): K / V column views of step
 // s's packed qkv output, its row stride and row count.
@@ -412,6 +558,35 @@ int rq_beam_select(const int64_t* cand_ids, const float* cand_lp, const bool* va
                    void* stream) {
   return rq_beam_select_parent(cand_ids, cand_lp, valid, keys, n_keys, base, checked, parents, parent_lp, B, kprev,
                                n_cand, P, k, out_ids, out_lp, nullptr, stream);
+}
+
+int rq_beam_expand(const float* logits, float temperature, const int32_t* node, const int32_t* child_off,
+                   int64_t n_nodes, const int32_t* tok, int64_t n_children, const int64_t* parents,
+                   const float* parent_lp, int64_t B, int64_t kprev, int64_t V, int64_t P, int64_t k, int64_t* out_ids,
+                   float* out_lp, int32_t* out_parent, int32_t* out_node, void* stream) {
+  RQ_CHECK_ARG(B >= 0 && kprev >= 1 && V >= 1 && P >= 0 && P < 64, "rq_beam_expand: bad shape");
+  RQ_CHECK_ARG(V <= rqhip::kBeamMaxV && kprev <= rqhip::kBeamMaxN && kprev * V <= rqhip::kBeamMaxN,
+               "rq_beam_expand: need V <= %d and kprev * V <= %d (kprev=%lld, V=%lld)", rqhip::kBeamMaxV,
+               rqhip::kBeamMaxN, (long long)kprev, (long long)V);
+  RQ_CHECK_ARG(k >= 1 && k <= rqhip::kBeamMaxN, "rq_beam_expand: need 1 <= k <= %d (k=%lld)", rqhip::kBeamMaxN,
+               (long long)k);
+  RQ_CHECK_ARG(temperature > 0.f && temperature <= 3.0e38f, "rq_beam_expand: temperature must be positive");
+  RQ_CHECK_ARG(n_nodes >= 0 && n_nodes < 0x7fffffff && n_children >= 0 && n_children <= 0x7fffffff,
+               "rq_beam_expand: bad trie level (n_nodes=%lld, n_children=%lld)", (long long)n_nodes,
+               (long long)n_children);
+  RQ_CHECK_ARG((P == 0) ? (!node && !parents && !parent_lp) : (node && parents && parent_lp),
+               "rq_beam_expand: node, parents and parent_lp are all NULL when P == 0, all given otherwise");
+  if (B == 0) return 0;
+  RQ_CHECK_ARG(B <= 0x7fffffff, "rq_beam_expand: too many batch elements");
+  RQ_CHECK_ARG(logits && child_off && (tok || n_children == 0) && out_ids && out_lp && out_parent && out_node,
+               "rq_beam_expand: null pointer");
+  const int waves = kprev > 4 ? rqhip::kExpMaxWaves : 4;
+  const size_t lds = (size_t)((kprev * V + 3) / 4 * 4 + 2 * rqhip::kExpMaxWaves) * sizeof(uint32_t);
+  hipLaunchKernelGGL(rqhip::beam_expand_kernel, dim3((unsigned)B), dim3(64 * waves), lds, (hipStream_t)stream,
+                     logits, temperature, node, child_off, (int)n_nodes, tok, (int)n_children, parents, parent_lp,
+                     (int)kprev, (int)V, (int)P, (int)k, out_ids, out_lp, out_parent, out_node);
+  RQ_LAUNCH_CHECK("rq_beam_expand");
+  return 0;
 }
 
 int rq_beam_self_attn(const float* q, int64_t sq, const float* const* k_steps, const float* const* v_steps,

@@ -10,6 +10,7 @@ Forward (training) path, jagged mode (the only working mode in the reference, SU
   over the L+1 positions and averaged over B; loss_d = per-position mean.
 The module-level Dropout(p=0.5) is hard-coded as in the reference (:67).
 """
+import contextlib
 from typing import NamedTuple
 
 import torch
@@ -49,6 +50,12 @@ class GenerationOutput(NamedTuple):
     log_probas: Tensor
 
 
+class Recommendation(NamedTuple):
+    item_ids: Tensor     # (B, k) int64 corpus indices, -1 for dead beams
+    sem_ids: Tensor      # (B, k, D)
+    log_probas: Tensor   # (B, k)
+
+
 class EncoderDecoderRetrievalModel(nn.Module):
     def __init__(self, embedding_dim, attn_dim, dropout, num_heads, n_layers, num_embeddings, sem_id_dim,
                  inference_verifier_fn, max_pos=2048, jagged_mode: bool = True) -> None:
@@ -62,7 +69,8 @@ class EncoderDecoderRetrievalModel(nn.Module):
         self.attn_dim = attn_dim
         self.inference_verifier_fn = inference_verifier_fn
         # optional: an object with prefix_table(P) and reference_batching (the SemanticIdTokenizer); fused
-        # generation then verifies prefixes inside its select kernel instead of calling inference_verifier_fn
+        # generation then verifies prefixes inside its select kernel instead of calling inference_verifier_fn, and
+        # constrained generation / recommend walk its prefix_trie()
         self.inference_prefix_index = None
         self.enable_generation = False
 
@@ -211,7 +219,7 @@ class EncoderDecoderRetrievalModel(nn.Module):
     @torch.no_grad()
     def generate_next_sem_id(self, batch: TokenizedSeqBatch, temperature: int = 1, top_k: bool = True, *,
                              fused: bool = False, sample: bool = True,
-                             incremental: bool = False) -> GenerationOutput:
+                             incremental: bool = False, constrained: bool = False) -> GenerationOutput:
         """Beam-style decoding of the next item's L+1 sem-ID tokens (reference :149-245): per step
         sample 200 candidates per beam from softmax(logits / T), drop prefixes the verifier
         rejects (-10000), keep the top 32 cumulative log-probabilities. The encoder output is
@@ -221,10 +229,24 @@ class EncoderDecoderRetrievalModel(nn.Module):
         launches (_generate_fused); sample=False then takes the most probable candidates instead of a draw.
         incremental=True (needs fused=True): the same loop over a BeamDecodeState — the context's cross-attention
         K / V projected once for the B users and only each beam's newest token run through the decoder
-        (_generate_incremental)."""
+        (_generate_incremental).
+        constrained=True (needs fused=True, an explicit sample=False and `inference_prefix_index`): the beams walk
+        the corpus' prefix trie (_generate_constrained), one hip_ops.beam_expand launch per step; with or without
+        incremental. Deterministic (no generator draw), every valid continuation is scored (not 200 of them), every
+        returned beam is a corpus item or dead (ids -1, log-probability -inf) when a user has fewer valid beams than
+        k. `reference_batching` does not apply and is not consulted."""
         if incremental and not fused:
             raise ValueError("generate_next_sem_id: incremental=True requires fused=True")
+        if constrained:
+            if not fused:
+                raise ValueError("generate_next_sem_id: constrained=True requires fused=True")
+            if sample:
+                raise ValueError("generate_next_sem_id: constrained=True is deterministic; pass sample=False")
+            self._constrained_trie("generate_next_sem_id")
         assert self.enable_generation, "Model generation is not enabled"
+        if constrained:
+            generated, log_probas, _ = self._generate_constrained(batch, temperature, 32 if top_k else 1, incremental)
+            return GenerationOutput(sem_ids=generated.squeeze(), log_probas=log_probas.squeeze())
         if incremental:
             return self._generate_incremental(batch, temperature, top_k, sample)
         if fused:
@@ -275,6 +297,86 @@ class EncoderDecoderRetrievalModel(nn.Module):
                 generated = top_samples.unsqueeze(-1)
                 log_probas = top_lp.detach().clone()
         return GenerationOutput(sem_ids=generated.squeeze(), log_probas=log_probas.squeeze())
+
+    def _constrained_trie(self, what: str):
+        index = getattr(self, "inference_prefix_index", None)
+        if index is None:
+            raise ValueError(f"{what}: constrained decoding requires inference_prefix_index (the tokenizer)")
+        trie = index.prefix_trie()
+        if trie.depth < self.sem_id_dim:
+            raise ValueError(f"{what}: the corpus trie has depth {trie.depth} < sem_id_dim = {self.sem_id_dim}")
+        return trie
+
+    @eval_mode
+    @reset_encoder_cache
+    @torch.no_grad()
+    def recommend(self, batch: TokenizedSeqBatch, k: int = 10, temperature: int = 1,
+                  incremental: bool = True) -> Recommendation:
+        """The k <= 32 most probable corpus items for every user: the constrained beam search (32 beams,
+        sample=False; generate_next_sem_id(constrained=True)) with each kept beam mapped back to its corpus index
+        through the trie's leaves. A user with fewer than k valid beams gets item id -1 (sem ids -1,
+        log-probability -inf) in the remaining places."""
+        if not 1 <= k <= 32:
+            raise ValueError(f"recommend: need 1 <= k <= 32, got {k}")
+        trie = self._constrained_trie("recommend")
+        if trie.depth != self.sem_id_dim:
+            raise ValueError(f"recommend: the corpus trie has depth {trie.depth}, the model generates {self.sem_id_dim} "
+                             "tokens; items are the leaves of the full depth")
+        assert self.enable_generation, "Model generation is not enabled"
+        generated, log_probas, node = self._generate_constrained(batch, temperature, 32, incremental)
+        node = node[:, :k].long()
+        items = torch.where(node >= 0, trie.leaf_item[node.clamp_min(0)], -1)
+        return Recommendation(item_ids=items, sem_ids=generated[:, :k], log_probas=log_probas[:, :k])
+
+    def _generate_constrained(self, batch: TokenizedSeqBatch, temperature, k: int, incremental: bool):
+        """_generate_fused's / _generate_incremental's loop with beam_candidates + _beam_verify + beam_select
+        replaced by one hip_ops.beam_expand per step: a beam carries its trie node, the node's children are the
+        only candidates. Returns (sem_ids (B, k, L+1), log_probas (B, k), the beams' leaf nodes (B, k) int32), dead
+        beams as beam_expand marks them. Tokens handed back to the model for dead beams are clamped to 0 (row
+        counts stay B * k: static shapes, no negative index reaches an embedding kernel); whatever they compute is
+        never read, a dead beam has no children. Runs under the caller's decorators."""
+        trie = self._constrained_trie("generate_next_sem_id")
+        B = batch.sem_ids.shape[0]
+        generated, log_probas, parent, node = None, None, None, None
+        cur = TokenizedSeqBatch(user_ids=batch.user_ids, sem_ids=batch.sem_ids, sem_ids_fut=None,
+                                seq_mask=batch.seq_mask, token_type_ids=batch.token_type_ids, token_type_ids_fut=None)
+        with (hip_ops.weight_split_scope(self._gemm_weights(), self._gemm_weight_stacks()) if incremental
+              else contextlib.nullcontext()):
+            state = BeamDecodeState(self, batch) if incremental else None
+            for i in range(self.sem_id_dim):
+                if not incremental:
+                    logits = self.forward(cur).logits
+                elif generated is None:
+                    logits = state.step()
+                else:
+                    logits = state.step(generated[:, :, -1].clamp_min(0), parent)
+                first = generated is None
+                generated, log_probas, parent, node = hip_ops.beam_expand(
+                    logits.contiguous(), k, batch=B, child_off=trie.child_off[i], tok=trie.tok[i + 1], node=node,
+                    parents=generated, parent_lp=log_probas, temperature=temperature)
+                if not incremental and i + 1 < self.sem_id_dim:
+                    cur = self._beams_batch(cur, generated.clamp_min(0), first, k)
+        return generated, log_probas, node
+
+    def _beams_batch(self, cur: TokenizedSeqBatch, generated: Tensor, first: bool, k: int) -> TokenizedSeqBatch:
+        """The next full forward's batch for the beams `generated` (B, k, i + 1) of _generate_fused and
+        _generate_constrained: after the first step the users (and the cached encoder output) are repeated per beam."""
+        if not first:
+            nxt = generated.flatten(end_dim=1)
+            return TokenizedSeqBatch(user_ids=cur.user_ids, sem_ids=cur.sem_ids, sem_ids_fut=nxt,
+                                     token_type_ids_fut=torch.arange(nxt.shape[1], device=nxt.device).repeat(nxt.shape[0], 1),
+                                     seq_mask=cur.seq_mask, token_type_ids=cur.token_type_ids)
+        nxt = generated.reshape(-1, 1)
+        enc = self.transformer.cached_enc_output
+        n_ctx = cur.sem_ids.shape[1] + 1
+        padded = jagged_to_padded_tensor(enc, n_ctx).repeat_interleave(k, dim=0)
+        lengths = enc.offsets().diff().repeat_interleave(k)
+        self.transformer.cached_enc_output = padded_to_jagged(padded.contiguous(), lengths, n_ctx)
+        return TokenizedSeqBatch(user_ids=cur.user_ids.repeat_interleave(k, dim=0),
+                                 sem_ids=cur.sem_ids.repeat_interleave(k, dim=0), sem_ids_fut=nxt,
+                                 token_type_ids_fut=torch.zeros_like(nxt),
+                                 seq_mask=cur.seq_mask.repeat_interleave(k, dim=0),
+                                 token_type_ids=cur.token_type_ids.repeat_interleave(k, dim=0))
 
     def _beam_verify(self, index, i: int, cand_ids: Tensor, generated, n_cand: int) -> dict:
         """hip_ops.beam_select's validity arguments for step i's candidates: the tokenizer's packed-prefix table
@@ -339,23 +441,7 @@ class EncoderDecoderRetrievalModel(nn.Module):
             first = generated is None
             generated, log_probas = hip_ops.beam_select(cand_ids, cand_lp, k, batch=B, parents=generated,
                                                         parent_lp=log_probas, **verify)
-            if not first:
-                nxt = generated.flatten(end_dim=1)
-                cur = TokenizedSeqBatch(user_ids=cur.user_ids, sem_ids=cur.sem_ids, sem_ids_fut=nxt,
-                                        token_type_ids_fut=torch.arange(nxt.shape[1], device=nxt.device).repeat(nxt.shape[0], 1),
-                                        seq_mask=cur.seq_mask, token_type_ids=cur.token_type_ids)
-            else:
-                nxt = generated.reshape(-1, 1)
-                enc = self.transformer.cached_enc_output
-                n_ctx = cur.sem_ids.shape[1] + 1
-                padded = jagged_to_padded_tensor(enc, n_ctx).repeat_interleave(k, dim=0)
-                lengths = enc.offsets().diff().repeat_interleave(k)
-                self.transformer.cached_enc_output = padded_to_jagged(padded.contiguous(), lengths, n_ctx)
-                cur = TokenizedSeqBatch(user_ids=cur.user_ids.repeat_interleave(k, dim=0),
-                                        sem_ids=cur.sem_ids.repeat_interleave(k, dim=0), sem_ids_fut=nxt,
-                                        token_type_ids_fut=torch.zeros_like(nxt),
-                                        seq_mask=cur.seq_mask.repeat_interleave(k, dim=0),
-                                        token_type_ids=cur.token_type_ids.repeat_interleave(k, dim=0))
+            cur = self._beams_batch(cur, generated, first, k)
         return GenerationOutput(sem_ids=generated.squeeze(), log_probas=log_probas.squeeze())
 
 

@@ -16,7 +16,7 @@ MI355X path:
     behaviour.
 """
 import math
-from typing import List, Optional
+from typing import List, NamedTuple, Optional
 
 import torch
 from torch import nn
@@ -56,6 +56,17 @@ def dedup_rank(ids: Tensor) -> Tensor:
     return rank
 
 
+class PrefixTrie(NamedTuple):
+    """Level-by-level CSR trie of the corpus ids (SemanticIdTokenizer.prefix_trie). Level p holds the sorted unique
+    length-p prefixes (prefix_table(p)'s keys, in that order); level 0 is the single root."""
+    tok: tuple          # tok[p], p = 1..depth: int32 (n_p), the last token of each level-p node (tok[0] is None)
+    child_off: tuple    # child_off[p], p = 0..depth-1: int32 (n_p + 1), node i's children in level p + 1 are
+                        # [child_off[p][i], child_off[p][i + 1]): contiguous, ascending by token
+    leaf_item: Tensor   # int64 (n_depth): the lowest corpus index whose row is that level-depth path
+    depth: int
+    base: int
+
+
 class SemanticIdTokenizer(nn.Module):
     """Tokenizes sequences of item features into sequences of semantic ids (L codewords + dedup)."""
 
@@ -81,6 +92,7 @@ class SemanticIdTokenizer(nn.Module):
     def reset(self):
         self.cached_ids = None
         self._prefix_index = {}
+        self._trie = None
 
     @property
     def sem_ids_dim(self):
@@ -104,6 +116,7 @@ class SemanticIdTokenizer(nn.Module):
             ids = dp.all_gather_rows(ids, n)
         self.cached_ids = torch.cat([ids, dedup_rank(ids).unsqueeze(1)], 1)
         self._prefix_index = {}
+        self._trie = None
         return self.cached_ids
 
     def _prefix_keys(self, P: int):
@@ -120,6 +133,36 @@ class SemanticIdTokenizer(nn.Module):
         if self.cached_ids is None:
             raise Exception("No match can be found in empty cache.")
         return self._prefix_keys(P)
+
+    @torch.no_grad()
+    def prefix_trie(self) -> PrefixTrie:
+        """The corpus ids (N, D) as a PrefixTrie, for callers that decode against it on the device
+        (rqvae_hip.ops.beam_expand): only valid continuations of a prefix are ever scored. Built with torch ops on
+        the device of `cached_ids` (CPU tensors work too); cached until the corpus changes."""
+        if self.cached_ids is None:
+            raise Exception("No match can be found in empty cache.")
+        if self._trie is None:
+            ids = self.cached_ids
+            dev, D = ids.device, ids.shape[1]
+            keys = [torch.zeros(1, dtype=torch.int64, device=dev)]
+            base = 1
+            for p in range(1, D + 1):
+                k, base = self._prefix_keys(p)
+                keys.append(k)
+            tok, child_off = [None], []
+            for p in range(1, D + 1):
+                tok.append((keys[p] % base).to(torch.int32))
+                parent = torch.searchsorted(keys[p - 1], torch.div(keys[p], base, rounding_mode="floor"))
+                off = torch.zeros(keys[p - 1].numel() + 1, dtype=torch.int64, device=dev)
+                off[1:] = torch.cumsum(torch.bincount(parent, minlength=keys[p - 1].numel()), 0)
+                child_off.append(off.to(torch.int32))
+            # a stable sort of the full rows' keys: the first row of every run is the lowest corpus index
+            sk, order = torch.sort(_pack(ids, base), stable=True)
+            first = torch.ones(sk.numel(), dtype=torch.bool, device=dev)
+            first[1:] = sk[1:] != sk[:-1]
+            self._trie = PrefixTrie(tok=tuple(tok), child_off=tuple(child_off), leaf_item=order[first], depth=D,
+                                    base=base)
+        return self._trie
 
     @torch.no_grad()
     @eval_mode

@@ -93,6 +93,7 @@ _SIGS = {
     "rq_beam_select_parent": ([_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P],
                               _I),
     "rq_beam_self_attn": ([_P, _I64, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _F, _P, _I64, _P], _I),
+    "rq_beam_expand": ([_P, _F, _P, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P], _I),
     "rq_topk_hits": ([_P, _P, _I64, _I64, _I64, _P, _I64, _P, _P], _I),
     "rq_adamw_step": ([_P, _I64, _F, _F, _F, _F, _F, _F, _F, _P], _I),
     "rq_adamw_chunk_elems": ([], _SZ),

@@ -7,6 +7,7 @@
   varlen_attention(q, k, v, cu_q, cu_k, ...) jagged SDPA (fwd + deterministic VJP)
   gemm_bf16x3 / gemm_x3 / mlp_chain          fp32 matmuls at 'high' precision (split-bf16 MFMA)
   beam_candidates / beam_select / topk_hits  decoder evaluation: one beam step in two launches, Hit@k counters
+  beam_expand                                constrained decoding: one beam step against the corpus' prefix trie, one launch
 
 All kernels run on torch's current HIP stream; tensors must be on the GPU (no CPU path).
 """
@@ -2352,6 +2353,58 @@ def beam_select(cand_ids: torch.Tensor, cand_lp: torch.Tensor, k: int, *, batch:
          int(base), B * N if checked is None else int(checked), ptr(parents), ptr(parent_lp), B, kprev, n_cand, P,
          int(k), ptr(out_ids), ptr(out_lp), stream_handle(cand_ids.device))
     return out_ids, out_lp
+
+
+BEAM_MAX_V, BEAM_MAX_N = 4096, 8192   # kBeamMaxV, kBeamMaxN (csrc/beam.hip)
+
+
+def beam_expand(logits: torch.Tensor, k: int, *, batch: int, child_off: torch.Tensor, tok: torch.Tensor,
+                node: torch.Tensor = None, parents: torch.Tensor = None, parent_lp: torch.Tensor = None,
+                temperature: float = 1.0):
+    """(out_ids (B, k, P + 1) int64, out_lp (B, k) fp32, out_parent (B, k) int32, out_node (B, k) int32): one
+    constrained beam step against the corpus' prefix trie (rq_beam_expand) — the k best of the valid continuations of
+    the B * kprev beams whose logits (B * kprev, V) these are, with beam_candidates' log-probabilities. child_off
+    (n_nodes + 1) / tok (n_children) int32: SemanticIdTokenizer.prefix_trie()'s child_off[P] and tok[P + 1]. node
+    (B, kprev) int32, parents (B, kprev, P) int64 and parent_lp (B, kprev) fp32: the beams so far — the previous call's
+    out_node, out_ids and out_lp — all None on the first step (every beam on the root). With fewer than k valid
+    continuations the remaining rows are dead: ids -1, -inf, parent 0, node -1. One launch, no host read."""
+    what = "beam_expand"
+    require_gpu(logits, child_off, tok, node, parents, parent_lp, what=what)
+    B = int(batch)
+    if logits.dim() != 2 or B < 0 or (B and logits.shape[0] % B):
+        raise RqHipError(f"{what}: logits must be (B * kprev, V)")
+    _beam_arg(logits, torch.float32, what, "logits")
+    R, V = logits.shape
+    kprev = R // B if B else 1
+    given = [t is not None for t in (node, parents, parent_lp)]
+    if any(given) != all(given):
+        raise RqHipError(f"{what}: node, parents and parent_lp go together")
+    P = 0
+    if parents is not None:
+        if parents.dim() != 3 or tuple(parents.shape[:2]) != (B, kprev):
+            raise RqHipError(f"{what}: parents must be (B, kprev, P), got {tuple(parents.shape)}")
+        P = parents.shape[2]
+        _beam_arg(parents, torch.int64, what, "parents")
+        _beam_arg(parent_lp, torch.float32, what, "parent_lp", (B, kprev))
+        _beam_arg(node, torch.int32, what, "node", (B, kprev))
+        if P == 0:
+            raise RqHipError(f"{what}: parents with P == 0; pass node, parents and parent_lp as None on the first step")
+    if child_off.dim() != 1 or tok.dim() != 1 or child_off.numel() < 1:
+        raise RqHipError(f"{what}: child_off (n_nodes + 1) and tok (n_children) must be 1-D")
+    _beam_arg(child_off, torch.int32, what, "child_off")
+    _beam_arg(tok, torch.int32, what, "tok")
+    if V < 1 or V > BEAM_MAX_V or kprev * V > BEAM_MAX_N or not 1 <= int(k) <= BEAM_MAX_N:
+        raise RqHipError(f"{what}: outside the supported envelope V <= {BEAM_MAX_V}, kprev * V <= {BEAM_MAX_N}, "
+                         f"1 <= k <= {BEAM_MAX_N} (kprev={kprev}, V={V}, k={k})")
+    dev = logits.device
+    out_ids = torch.empty((B, int(k), P + 1), device=dev, dtype=torch.int64)
+    out_lp = torch.empty((B, int(k)), device=dev, dtype=torch.float32)
+    out_parent = torch.empty((B, int(k)), device=dev, dtype=torch.int32)
+    out_node = torch.empty((B, int(k)), device=dev, dtype=torch.int32)
+    call("rq_beam_expand", ptr(logits), float(temperature), ptr(node), ptr(child_off), child_off.numel() - 1, ptr(tok),
+         tok.numel(), ptr(parents), ptr(parent_lp), B, kprev, V, P, int(k), ptr(out_ids), ptr(out_lp),
+         ptr(out_parent), ptr(out_node), stream_handle(dev))
+    return out_ids, out_lp, out_parent, out_node
 
 
 BEAM_MAX_T = 8   # RQ_BEAM_MAX_T

@@ -115,6 +115,9 @@ class _Prefetch:
 EVAL_FUSED_GENERATION = True
 # Incremental beam decoding under the fused beam step (modules/model.py BeamDecodeState): opt-in.
 EVAL_INCREMENTAL_GENERATION = False
+# Prefix-trie constrained beam search (modules/model.py _generate_constrained): opt-in. Deterministic and
+# exact, so Hit@k differs from the sampled path's; needs EVAL_FUSED_GENERATION and the tokenizer as prefix index.
+EVAL_CONSTRAINED_GENERATION = False
 
 
 class _Evaluator:
@@ -188,8 +191,9 @@ class _Evaluator:
         self.model.enable_generation = True
         self.metrics.reset()
         for tok in self._batches():
+            constrained = dict(constrained=True, sample=False) if EVAL_CONSTRAINED_GENERATION else {}
             gen = self.model.generate_next_sem_id(tok, top_k=True, temperature=1, fused=EVAL_FUSED_GENERATION,
-                                                  incremental=EVAL_INCREMENTAL_GENERATION)
+                                                  incremental=EVAL_INCREMENTAL_GENERATION, **constrained)
             self.metrics.accumulate(actual=tok.sem_ids_fut, top_k=gen.sem_ids)
         res = self.metrics.reduce()
         self.metrics.reset()

@@ -5,7 +5,9 @@ per beam, 256 classes, 4 sem-ID tokens; model dims of configs/decoder_amazon.gin
   generation   generate_next_sem_id(top_k=True) with fused=False (the reference's torch composition of the beam
                step), fused=True (rq_beam_candidates + rq_beam_select) and fused=True, incremental=True (the same
                beam step over a BeamDecodeState: cross K/V projected once per user, only each beam's newest token
-               through the decoder), verifier = a tokenizer over a 12,101-item corpus; and with the beam step
+               through the decoder), and fused=True, incremental=True, constrained=True, sample=False (the
+               incremental loop with the beam step replaced by one rq_beam_expand launch that walks the corpus'
+               prefix trie), verifier = a tokenizer over a 12,101-item corpus; and with the beam step
                stubbed out (`model`: the four forwards and the encoder cache repeat alone), which gives the
                beam logic's share of the first two forms;
   accumulate   TopKAccumulator.accumulate on the device (one rq_topk_hits launch) and the reference's logic
@@ -69,7 +71,7 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--only", choices=["unfused", "fused", "incremental", "model", "acc_device", "acc_reference"])
+    ap.add_argument("--only", choices=["unfused", "fused", "incremental", "constrained", "model", "acc_device", "acc_reference"])
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("generation_time: needs the GPU (a CPU run measures nothing)")
@@ -98,6 +100,10 @@ def main():
     def gen(fused, incremental=False):
         return model.generate_next_sem_id(batch, temperature=1, top_k=True, fused=fused, incremental=incremental)
 
+    def gen_constrained():
+        return model.generate_next_sem_id(batch, temperature=1, top_k=True, fused=True, sample=False, incremental=True,
+                                          constrained=True)
+
     def gen_model_only():
         hip_ops.beam_candidates, hip_ops.beam_select = stub_candidates, stub_select
         try:
@@ -117,7 +123,7 @@ def main():
         reference_accumulate({}, [1, 5, 10], actual, top)
 
     forms = {"unfused": lambda: gen(False), "fused": lambda: gen(True),
-             "incremental": lambda: gen(True, True), "model": gen_model_only,
+             "incremental": lambda: gen(True, True), "constrained": gen_constrained, "model": gen_model_only,
              "acc_device": acc_device, "acc_reference": acc_reference}
     if args.only:
         forms = {args.only: forms[args.only]}
@@ -135,7 +141,7 @@ def main():
            "median_ms": {n: round(v, 4) for n, v in med.items()},
            "min_max_ms": {n: [round(min(v), 4), round(max(v), 4)] for n, v in times.items() if v}}
     peak = {}
-    for name in ("unfused", "fused", "incremental"):
+    for name in ("unfused", "fused", "incremental", "constrained"):
         if name in forms and not args.only:   # one more call of each generation form, alone after a peak reset
             torch.cuda.synchronize()
             torch.cuda.reset_peak_memory_stats(device)
@@ -146,6 +152,12 @@ def main():
         out["peak_mem_mib"] = peak
     if {"fused", "incremental"} <= set(med):
         out["incremental_speedup"] = round(med["fused"] / med["incremental"], 4)
+    if {"incremental", "constrained"} <= set(med):
+        # the acceptance condition: the constrained form's median within the incremental form's own spread
+        spread = max(times["incremental"]) - min(times["incremental"])
+        out["constrained_vs_incremental"] = dict(delta_ms=round(med["constrained"] - med["incremental"], 4),
+                                                 incremental_spread_ms=round(spread, 4),
+                                                 within_spread=med["constrained"] - med["incremental"] <= spread)
     if {"unfused", "fused", "model"} <= set(med):
         out["beam_logic_share"] = {n: round(1 - med["model"] / med[n], 4) for n in ("unfused", "fused")}
         out["beam_logic_ms"] = {n: round(med[n] - med["model"], 4) for n in ("unfused", "fused")}
