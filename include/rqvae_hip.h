@@ -494,7 +494,25 @@ int varlen_attn_bwd(const float* q, int64_t sq, const float* k, int64_t sk, cons
  *   -1, out_lp -inf, out_parent 0, out_node -1; a dead or out-of-range node entry contributes no candidates. The
  *   tables are the caller's contract, but a bad one never reads outside a buffer: child_off is clamped into
  *   [0, n_children], tokens outside [0, V) are skipped (an unsorted range gives an unspecified out_node or -1).
- *   V <= 4096, kprev V <= 8192, 1 <= k <= 8192, P < 64, temperature > 0; outside that -22, never a truncated result. */
+ *   V <= 4096, kprev V <= 8192, 1 <= k <= 8192, P < 64, temperature > 0; outside that -22, never a truncated result.
+ * rq_beam_expand_blocked: rq_beam_expand with a per-user filter (seen-item exclusion). blocked (B, n_blocked) int32:
+ *   row b holds the level-(P + 1) nodes that are not candidates for batch element b, ascending and padded with
+ *   INT32_MAX (a slice of rq_trie_blocked_nodes' output); a child c found in row b is skipped, everything else is
+ *   rq_beam_expand (the same kernel body: scores, tie rule, dead rows, out_node, table clamping, limits). An unsorted
+ *   row may filter the wrong children but is never read outside [0, n_blocked). 0 <= n_blocked <= 1024; n_blocked == 0
+ *   (blocked may be NULL) is rq_beam_expand.
+ * rq_trie_blocked_nodes: per user the trie nodes of every level 1..D whose leaves are ALL on the user's exclusion
+ *   list, in ONE launch (one workgroup per user). items (B, H) int64 corpus indices, entries outside [0, n_items) are
+ *   padding; item_leaf (n_items) int32 = each item's leaf (level-D node; items with equal rows share it, so
+ *   exclusion is by row); leaf_anc[q - 1] (n_leaves) int32 = each leaf's level-q ancestor, leaf_count[q - 1]
+ *   (n_nodes[q - 1]) int32 = each level-q node's number of leaves, q = 1..D (SemanticIdTokenizer.trie_index). The
+ *   three level arrays are HOST arrays of D entries copied into the kernel arguments (no device table). out
+ *   (D, B, H) int32: out[q - 1][b] = user b's blocked level-q nodes, ascending and distinct, then INT32_MAX. The
+ *   ancestors of ascending leaves must be non-decreasing (a level's nodes are in key order). H <= 1024,
+ *   D <= RQ_BEAM_MAX_T, else -22; B == 0 or H == 0 returns 0 without a launch.
+ * rq_rank_hist: actual (B, D) int64 targets, topk (B, k, D) int64 beams; hist (k + 1) int64 is ACCUMULATED into:
+ *   hist[r] += #rows whose first beam equal to the target in all D columns has rank r, hist[k] += #rows without one.
+ *   Rows with actual[b][0] < 0 are skipped entirely. D <= 64, k <= 1024. D == 1 serves item ids. */
 #define RQ_BEAM_MAX_T 8 /* tokens per beam incl. BOS; sem_id_dim <= 8 as evaluate.metrics already assumes */
 int rq_beam_candidates(const float* logits, const float* noise, int64_t R, int64_t V, int64_t n_cand,
                        float temperature, int64_t* cand_ids, float* cand_lp, void* stream);
@@ -515,6 +533,16 @@ int rq_beam_expand(const float* logits, float temperature, const int32_t* node, 
                    float* out_lp, int32_t* out_parent, int32_t* out_node, void* stream);
 int rq_topk_hits(const int64_t* actual, const int64_t* topk, int64_t B, int64_t k, int64_t D, const int* ks,
                  int64_t n_ks, int64_t* counts, void* stream);
+int rq_beam_expand_blocked(const float* logits, float temperature, const int32_t* node, const int32_t* child_off,
+                           int64_t n_nodes, const int32_t* tok, int64_t n_children, const int64_t* parents,
+                           const float* parent_lp, int64_t B, int64_t kprev, int64_t V, int64_t P, int64_t k,
+                           int64_t* out_ids, float* out_lp, int32_t* out_parent, int32_t* out_node,
+                           const int32_t* blocked, int64_t n_blocked, void* stream);
+int rq_trie_blocked_nodes(const int64_t* items, int64_t B, int64_t H, const int32_t* item_leaf, int64_t n_items,
+                          int64_t n_leaves, const int32_t* const* leaf_anc, const int32_t* const* leaf_count,
+                          const int64_t* n_nodes, int64_t D, int32_t* out, void* stream);
+int rq_rank_hist(const int64_t* actual, const int64_t* topk, int64_t B, int64_t k, int64_t D, int64_t* hist,
+                 void* stream);
 
 /* AdamW step (torch.optim.AdamW as stepped by train_rqvae.py:168-172 / train_decoder.py:203) over
  * every fp32 parameter of a group, one launch per 64 tensors. segs: HOST array of nseg records of 5

@@ -9,12 +9,18 @@
 //                           the k best of the kprev * n_cand candidates in stable order, the parent gather.
 //   beam_expand_kernel      constrained decoding, the whole beam step in one launch: one workgroup per batch
 //                           element walks the corpus' prefix trie (only valid continuations are scored), the k
-//                           best in stable order, the parent gather and each winner's trie node.
+//                           best in stable order, the parent gather and each winner's trie node. A second
+//                           instantiation (BLOCKED) skips the children found in a per-user sorted row of blocked
+//                           nodes (seen-item exclusion).
+//   trie_blocked_kernel     one workgroup per user: the trie nodes of every level whose leaves are all on the
+//                           user's exclusion list, sorted / deduplicated / counted in LDS.
 //   beam_self_attn_kernel   incremental decoding: the newest token's causal self-attention over its beam's
 //                           ancestors, read in place from every step's packed qkv output through an
 //                           ancestor row table (no per-beam cache is gathered or appended).
 //   topk_hits_kernel        one wave per batch row: first matching beam rank per sem-ID slice / position,
 //                           counters accumulated on the device with one atomic per (wave, counter).
+//   rank_hist_kernel        one wave per batch row: the rank of the first beam equal to the target in every column,
+//                           a workgroup-local histogram, one atomic per non-empty bin.
 #include "common.h"
 
 namespace rqhip {
@@ -24,6 +30,8 @@ constexpr int kBeamMaxN = 8192;
 constexpr int kHitsMaxD = 64;
 constexpr int kHitsMaxKs = 8;
 constexpr int kNoRank = 0x7fffffff;   // no beam matched
+constexpr int kBlockedMax = 1024;     // widest blocked row / exclusion list
+constexpr int kRankMaxK = 1024;
 
 // ------------------------------------------------------------------------------------- candidates
 // (max, lowest index of the max) over the wave; NaN never wins a comparison, so a row with a NaN keeps the
@@ -242,14 +250,18 @@ __global__ void __launch_bounds__(kSelThreads) beam_select_kernel(
 //      thread per output row after the rounds, so the probes of the k rows overlap instead of stalling a round each.
 // Tables are the caller's contract but never trusted for addressing: node outside [0, n_nodes) is a dead beam,
 // child_off is clamped into [0, n_children], tokens outside [0, V) are skipped.
+// BLOCKED: `blocked` (B, n_blocked) int32 holds per user the level-(P + 1) nodes that are not candidates, ascending
+// and INT32_MAX-padded; the row is staged once into LDS after the exchange area and phase 1 looks every child index
+// up in it (a binary search over [0, n_blocked): an unsorted row filters the wrong children, never reads outside).
 constexpr int kExpMaxWaves = 16;
 
+template <bool BLOCKED>
 __global__ void __launch_bounds__(64 * kExpMaxWaves) beam_expand_kernel(
     const float* __restrict__ logits, float temperature, const int32_t* __restrict__ node,
     const int32_t* __restrict__ child_off, int n_nodes, const int32_t* __restrict__ tok, int n_children,
     const int64_t* __restrict__ parents, const float* __restrict__ parent_lp, int kprev, int V, int P, int k,
     int64_t* __restrict__ out_ids, float* __restrict__ out_lp, int32_t* __restrict__ out_parent,
-    int32_t* __restrict__ out_node) {
+    int32_t* __restrict__ out_node, const int32_t* __restrict__ blocked, int n_blocked) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nthr = blockDim.x, nwave = nthr >> 6;   // 4 or kExpMaxWaves waves (the host picks by kprev)
@@ -260,6 +272,10 @@ __global__ void __launch_bounds__(64 * kExpMaxWaves) beam_expand_kernel(
   const int64_t b = blockIdx.x;
 
   for (int e = tid; e < N; e += nthr) key[e] = 0;
+  if constexpr (BLOCKED) {
+    int* blk = w_idx + kExpMaxWaves;   // [n_blocked <= kBlockedMax]
+    for (int e = tid; e < n_blocked; e += nthr) blk[e] = blocked[b * n_blocked + e];
+  }
   __syncthreads();
 
   for (int j = wave; j < kprev; j += nwave) {
@@ -288,6 +304,15 @@ __global__ void __launch_bounds__(64 * kExpMaxWaves) beam_expand_kernel(
     for (int c = lo + lane; c < hi; c += 64) {
       const int v = tok[c];
       if (v < 0 || v >= V) continue;   // a class the model cannot generate (e.g. a dedup count >= V)
+      if constexpr (BLOCKED) {
+        const int* blk = w_idx + kExpMaxWaves;
+        int l = 0, h = n_blocked;   // first entry >= c
+        while (l < h) {
+          const int mid = (l + h) >> 1;
+          if (blk[mid] < c) l = mid + 1; else h = mid;
+        }
+        if (l < n_blocked && blk[l] == c) continue;   // every leaf below this child is excluded for the user
+      }
       const float dv = x[v] / temperature - m;
       const float p = expf(dv) / sum;
       const float lp = p == 0.f ? -INFINITY : dv - log_norm;
@@ -497,6 +522,139 @@ __global__ void __launch_bounds__(256) topk_hits_kernel(const int64_t* __restric
   }
 }
 
+// ------------------------------------------------------------------------------------- rank histogram
+// One wave per row (grid-stride): beams are visited 64 at a time, one per lane; the first 64-block with a beam equal
+// to the target in all D columns gives the rank. Lane 0 counts into the workgroup's LDS histogram, which is flushed
+// with one global atomic per non-empty bin: integer counts, so the result does not depend on the order.
+__global__ void __launch_bounds__(256) rank_hist_kernel(const int64_t* __restrict__ actual,
+                                                        const int64_t* __restrict__ topk, int64_t B, int k, int D,
+                                                        unsigned long long* __restrict__ hist) {
+  __shared__ int h[kRankMaxK + 1];
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  for (int i = threadIdx.x; i <= k; i += blockDim.x) h[i] = 0;
+  __syncthreads();
+  for (int64_t row = wave; row < B; row += n_waves) {
+    const int64_t* a = actual + row * D;
+    if (a[0] < 0) continue;   // no target (wave-uniform)
+    int rank = k;
+    for (int r0 = 0; r0 < k; r0 += 64) {
+      const int r = r0 + lane;
+      bool eq = r < k;
+      if (eq) {
+        const int64_t* t = topk + (row * k + r) * D;
+        for (int i = 0; i < D; ++i) eq = eq && t[i] == a[i];
+      }
+      const uint64_t hit = __ballot(eq);
+      if (hit) {
+        rank = r0 + __ffsll((unsigned long long)hit) - 1;
+        break;
+      }
+    }
+    if (lane == 0) atomicAdd(&h[rank], 1);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i <= k; i += blockDim.x)
+    if (h[i]) atomicAdd(&hist[i], (unsigned long long)h[i]);
+}
+
+// ------------------------------------------------------------------------------------- blocked trie nodes
+// The per-level tables by value in the kernel arguments (no device-side pointer table): level q = 1..D at [q - 1].
+struct TrieLevels {
+  const int32_t* anc[RQ_BEAM_MAX_T];   // (n_leaves): each leaf's level-q ancestor
+  const int32_t* cnt[RQ_BEAM_MAX_T];   // (n_nodes[q - 1]): each level-q node's number of leaves
+  int n_nodes[RQ_BEAM_MAX_T];
+};
+
+constexpr int kBlkThreads = 256;
+constexpr int kBlkNone = 0x7fffffff;
+
+// ascending bitonic sort of s[0, n), n a power of two <= kBlockedMax; starts and ends with a barrier
+__device__ __forceinline__ void lds_sort(int* s, int n) {
+  __syncthreads();
+  for (int k = 2; k <= n; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int i = threadIdx.x; i < n; i += kBlkThreads) {
+        const int o = i ^ j;
+        if (o > i) {
+          const int a = s[i], c = s[o];
+          if ((a > c) == ((i & k) == 0)) { s[i] = c; s[o] = a; }
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// One workgroup per user. The user's listed items become leaves (an entry outside [0, n_items) is padding), sorted
+// and made distinct in LDS: leaf[0, n) ascending. A level's nodes are in key order, so the leaves' level-q ancestors
+// are non-decreasing: a node is blocked iff its run in that sequence is as long as its leaf count (all of its leaves
+// are listed). The run heads that qualify are sorted once more, which moves them to the front of the output row in
+// ascending order with the INT32_MAX padding behind. Table values are never trusted for addressing: a leaf outside
+// [0, n_leaves) is padding, an ancestor outside [0, n_nodes) is never blocked.
+__global__ void __launch_bounds__(kBlkThreads) trie_blocked_kernel(const int64_t* __restrict__ items, int H, int Hp,
+                                                                  const int32_t* __restrict__ item_leaf,
+                                                                  int64_t n_items, int n_leaves, TrieLevels lv, int D,
+                                                                  int64_t B, int32_t* __restrict__ out) {
+  __shared__ int leaf[kBlockedMax];
+  __shared__ int anc[kBlockedMax];
+  __shared__ int res[kBlockedMax];
+  const int tid = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  for (int i = tid; i < Hp; i += kBlkThreads) {
+    int lf = kBlkNone;
+    if (i < H) {
+      const int64_t it = items[b * H + i];
+      if (it >= 0 && it < n_items) {
+        lf = item_leaf[it];
+        if (lf < 0 || lf >= n_leaves) lf = kBlkNone;
+      }
+    }
+    leaf[i] = lf;
+  }
+  lds_sort(leaf, Hp);
+  for (int i = tid; i < Hp; i += kBlkThreads) res[i] = (i > 0 && leaf[i] == leaf[i - 1]) ? kBlkNone : leaf[i];
+  __syncthreads();
+  for (int i = tid; i < Hp; i += kBlkThreads) leaf[i] = res[i];
+  lds_sort(leaf, Hp);
+  // n = the number of distinct leaves: the first padding entry of the ascending row
+  int n = 0;
+  {
+    int lo = 0, hi = Hp;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (leaf[mid] < kBlkNone) lo = mid + 1; else hi = mid;
+    }
+    n = lo;
+  }
+#pragma unroll 1
+  for (int q = 0; q < D; ++q) {
+    const int32_t* aq = lv.anc[q];
+    const int32_t* cq = lv.cnt[q];
+    const int nq = lv.n_nodes[q];
+    for (int i = tid; i < Hp; i += kBlkThreads) anc[i] = i < n ? aq[leaf[i]] : kBlkNone;
+    __syncthreads();
+    for (int i = tid; i < Hp; i += kBlkThreads) {
+      int r = kBlkNone;
+      const int a = anc[i];
+      if (i < n && a >= 0 && a < nq && (i == 0 || anc[i - 1] != a)) {
+        int lo = i + 1, hi = n;   // first entry > a: the end of a's run
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (anc[mid] <= a) lo = mid + 1; else hi = mid;
+        }
+        if (lo - i == cq[a]) r = a;
+      }
+      res[i] = r;
+    }
+    lds_sort(res, Hp);
+    int32_t* o = out + ((int64_t)q * B + b) * H;
+    for (int i = tid; i < H; i += kBlkThreads) o[i] = res[i];
+    __syncthreads();   // anc / res are rewritten by the next level
+  }
+}
+
 }  // namespace rqhip
 
 extern "C" {
@@ -560,32 +718,95 @@ int rq_beam_select(const int64_t* cand_ids, const float* cand_lp, const bool* va
                                n_cand, P, k, out_ids, out_lp, nullptr, stream);
 }
 
+static int beam_expand_launch(const char* fn, const float* logits, float temperature, const int32_t* node,
+                              const int32_t* child_off, int64_t n_nodes, const int32_t* tok, int64_t n_children,
+                              const int64_t* parents, const float* parent_lp, int64_t B, int64_t kprev, int64_t V,
+                              int64_t P, int64_t k, int64_t* out_ids, float* out_lp, int32_t* out_parent,
+                              int32_t* out_node, const int32_t* blocked, int64_t n_blocked, void* stream) {
+  RQ_CHECK_ARG(B >= 0 && kprev >= 1 && V >= 1 && P >= 0 && P < 64, "%s: bad shape", fn);
+  RQ_CHECK_ARG(V <= rqhip::kBeamMaxV && kprev <= rqhip::kBeamMaxN && kprev * V <= rqhip::kBeamMaxN,
+               "%s: need V <= %d and kprev * V <= %d (kprev=%lld, V=%lld)", fn, rqhip::kBeamMaxV, rqhip::kBeamMaxN,
+               (long long)kprev, (long long)V);
+  RQ_CHECK_ARG(k >= 1 && k <= rqhip::kBeamMaxN, "%s: need 1 <= k <= %d (k=%lld)", fn, rqhip::kBeamMaxN, (long long)k);
+  RQ_CHECK_ARG(temperature > 0.f && temperature <= 3.0e38f, "%s: temperature must be positive", fn);
+  RQ_CHECK_ARG(n_nodes >= 0 && n_nodes < 0x7fffffff && n_children >= 0 && n_children <= 0x7fffffff,
+               "%s: bad trie level (n_nodes=%lld, n_children=%lld)", fn, (long long)n_nodes, (long long)n_children);
+  RQ_CHECK_ARG((P == 0) ? (!node && !parents && !parent_lp) : (node && parents && parent_lp),
+               "%s: node, parents and parent_lp are all NULL when P == 0, all given otherwise", fn);
+  RQ_CHECK_ARG(n_blocked >= 0 && n_blocked <= rqhip::kBlockedMax, "%s: need 0 <= n_blocked <= %d (n_blocked=%lld)", fn,
+               rqhip::kBlockedMax, (long long)n_blocked);
+  if (B == 0) return 0;
+  RQ_CHECK_ARG(B <= 0x7fffffff, "%s: too many batch elements", fn);
+  RQ_CHECK_ARG(logits && child_off && (tok || n_children == 0) && out_ids && out_lp && out_parent && out_node &&
+                   (blocked || n_blocked == 0),
+               "%s: null pointer", fn);
+  const int waves = kprev > 4 ? rqhip::kExpMaxWaves : 4;
+  const size_t lds = (size_t)((kprev * V + 3) / 4 * 4 + 2 * rqhip::kExpMaxWaves) * sizeof(uint32_t);
+  if (n_blocked > 0) {
+    hipLaunchKernelGGL(rqhip::beam_expand_kernel<true>, dim3((unsigned)B), dim3(64 * waves),
+                       lds + (size_t)n_blocked * sizeof(int32_t), (hipStream_t)stream, logits, temperature, node,
+                       child_off, (int)n_nodes, tok, (int)n_children, parents, parent_lp, (int)kprev, (int)V, (int)P,
+                       (int)k, out_ids, out_lp, out_parent, out_node, blocked, (int)n_blocked);
+  } else {
+    hipLaunchKernelGGL(rqhip::beam_expand_kernel<false>, dim3((unsigned)B), dim3(64 * waves), lds, (hipStream_t)stream,
+                       logits, temperature, node, child_off, (int)n_nodes, tok, (int)n_children, parents, parent_lp,
+                       (int)kprev, (int)V, (int)P, (int)k, out_ids, out_lp, out_parent, out_node,
+                       (const int32_t*)nullptr, 0);
+  }
+  return 0;
+}
+
 int rq_beam_expand(const float* logits, float temperature, const int32_t* node, const int32_t* child_off,
                    int64_t n_nodes, const int32_t* tok, int64_t n_children, const int64_t* parents,
                    const float* parent_lp, int64_t B, int64_t kprev, int64_t V, int64_t P, int64_t k, int64_t* out_ids,
                    float* out_lp, int32_t* out_parent, int32_t* out_node, void* stream) {
-  RQ_CHECK_ARG(B >= 0 && kprev >= 1 && V >= 1 && P >= 0 && P < 64, "rq_beam_expand: bad shape");
-  RQ_CHECK_ARG(V <= rqhip::kBeamMaxV && kprev <= rqhip::kBeamMaxN && kprev * V <= rqhip::kBeamMaxN,
-               "rq_beam_expand: need V <= %d and kprev * V <= %d (kprev=%lld, V=%lld)", rqhip::kBeamMaxV,
-               rqhip::kBeamMaxN, (long long)kprev, (long long)V);
-  RQ_CHECK_ARG(k >= 1 && k <= rqhip::kBeamMaxN, "rq_beam_expand: need 1 <= k <= %d (k=%lld)", rqhip::kBeamMaxN,
-               (long long)k);
-  RQ_CHECK_ARG(temperature > 0.f && temperature <= 3.0e38f, "rq_beam_expand: temperature must be positive");
-  RQ_CHECK_ARG(n_nodes >= 0 && n_nodes < 0x7fffffff && n_children >= 0 && n_children <= 0x7fffffff,
-               "rq_beam_expand: bad trie level (n_nodes=%lld, n_children=%lld)", (long long)n_nodes,
-               (long long)n_children);
-  RQ_CHECK_ARG((P == 0) ? (!node && !parents && !parent_lp) : (node && parents && parent_lp),
-               "rq_beam_expand: node, parents and parent_lp are all NULL when P == 0, all given otherwise");
-  if (B == 0) return 0;
-  RQ_CHECK_ARG(B <= 0x7fffffff, "rq_beam_expand: too many batch elements");
-  RQ_CHECK_ARG(logits && child_off && (tok || n_children == 0) && out_ids && out_lp && out_parent && out_node,
-               "rq_beam_expand: null pointer");
-  const int waves = kprev > 4 ? rqhip::kExpMaxWaves : 4;
-  const size_t lds = (size_t)((kprev * V + 3) / 4 * 4 + 2 * rqhip::kExpMaxWaves) * sizeof(uint32_t);
-  hipLaunchKernelGGL(rqhip::beam_expand_kernel, dim3((unsigned)B), dim3(64 * waves), lds, (hipStream_t)stream,
-                     logits, temperature, node, child_off, (int)n_nodes, tok, (int)n_children, parents, parent_lp,
-                     (int)kprev, (int)V, (int)P, (int)k, out_ids, out_lp, out_parent, out_node);
+  const int rc = beam_expand_launch("rq_beam_expand", logits, temperature, node, child_off, n_nodes, tok, n_children,
+                                    parents, parent_lp, B, kprev, V, P, k, out_ids, out_lp, out_parent, out_node,
+                                    nullptr, 0, stream);
+  if (rc != 0 || B == 0) return rc;
   RQ_LAUNCH_CHECK("rq_beam_expand");
+  return 0;
+}
+
+int rq_beam_expand_blocked(const float* logits, float temperature, const int32_t* node, const int32_t* child_off,
+                           int64_t n_nodes, const int32_t* tok, int64_t n_children, const int64_t* parents,
+                           const float* parent_lp, int64_t B, int64_t kprev, int64_t V, int64_t P, int64_t k,
+                           int64_t* out_ids, float* out_lp, int32_t* out_parent, int32_t* out_node,
+                           const int32_t* blocked, int64_t n_blocked, void* stream) {
+  const int rc = beam_expand_launch("rq_beam_expand_blocked", logits, temperature, node, child_off, n_nodes, tok,
+                                    n_children, parents, parent_lp, B, kprev, V, P, k, out_ids, out_lp, out_parent,
+                                    out_node, blocked, n_blocked, stream);
+  if (rc != 0 || B == 0) return rc;
+  RQ_LAUNCH_CHECK("rq_beam_expand_blocked");
+  return 0;
+}
+
+int rq_trie_blocked_nodes(const int64_t* items, int64_t B, int64_t H, const int32_t* item_leaf, int64_t n_items,
+                          int64_t n_leaves, const int32_t* const* leaf_anc, const int32_t* const* leaf_count,
+                          const int64_t* n_nodes, int64_t D, int32_t* out, void* stream) {
+  RQ_CHECK_ARG(B >= 0 && H >= 0 && H <= rqhip::kBlockedMax && D >= 1 && D <= RQ_BEAM_MAX_T,
+               "rq_trie_blocked_nodes: need B >= 0, 0 <= H <= %d, 1 <= D <= %d (H=%lld, D=%lld)", rqhip::kBlockedMax,
+               RQ_BEAM_MAX_T, (long long)H, (long long)D);
+  RQ_CHECK_ARG(n_items >= 0 && n_leaves >= 0 && n_leaves < 0x7fffffff, "rq_trie_blocked_nodes: bad corpus size");
+  RQ_CHECK_ARG(leaf_anc && leaf_count && n_nodes, "rq_trie_blocked_nodes: null level array");
+  rqhip::TrieLevels lv = {};
+  for (int64_t q = 0; q < D; ++q) {
+    RQ_CHECK_ARG(n_nodes[q] >= 0 && n_nodes[q] < 0x7fffffff, "rq_trie_blocked_nodes: level %lld has %lld nodes",
+                 (long long)(q + 1), (long long)n_nodes[q]);
+    RQ_CHECK_ARG((leaf_anc[q] || n_leaves == 0) && (leaf_count[q] || n_nodes[q] == 0),
+                 "rq_trie_blocked_nodes: null table at level %lld", (long long)(q + 1));
+    lv.anc[q] = leaf_anc[q];
+    lv.cnt[q] = leaf_count[q];
+    lv.n_nodes[q] = (int)n_nodes[q];
+  }
+  if (B == 0 || H == 0) return 0;
+  RQ_CHECK_ARG(B <= 0x7fffffff, "rq_trie_blocked_nodes: too many batch elements");
+  RQ_CHECK_ARG(items && out && (item_leaf || n_items == 0), "rq_trie_blocked_nodes: null pointer");
+  int Hp = 1;
+  while (Hp < H) Hp <<= 1;
+  hipLaunchKernelGGL(rqhip::trie_blocked_kernel, dim3((unsigned)B), dim3(rqhip::kBlkThreads), 0, (hipStream_t)stream,
+                     items, (int)H, Hp, item_leaf, n_items, (int)n_leaves, lv, (int)D, B, out);
+  RQ_LAUNCH_CHECK("rq_trie_blocked_nodes");
   return 0;
 }
 
@@ -649,6 +870,20 @@ int rq_topk_hits(const int64_t* actual, const int64_t* topk, int64_t B, int64_t 
   hipLaunchKernelGGL(rqhip::topk_hits_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, actual, topk,
                      B, (int)k, (int)D, h, (int)n_ks, reinterpret_cast<unsigned long long*>(counts));
   RQ_LAUNCH_CHECK("rq_topk_hits");
+  return 0;
+}
+
+int rq_rank_hist(const int64_t* actual, const int64_t* topk, int64_t B, int64_t k, int64_t D, int64_t* hist,
+                 void* stream) {
+  RQ_CHECK_ARG(B >= 0 && k >= 1 && k <= rqhip::kRankMaxK && D >= 1 && D <= rqhip::kHitsMaxD,
+               "rq_rank_hist: need 1 <= k <= %d, 1 <= D <= %d (k=%lld, D=%lld)", rqhip::kRankMaxK, rqhip::kHitsMaxD,
+               (long long)k, (long long)D);
+  if (B == 0) return 0;
+  RQ_CHECK_ARG(actual && topk && hist, "rq_rank_hist: null pointer");
+  const int64_t blocks = std::min<int64_t>((B + 3) / 4, 1024);
+  hipLaunchKernelGGL(rqhip::rank_hist_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, actual, topk, B,
+                     (int)k, (int)D, reinterpret_cast<unsigned long long*>(hist));
+  RQ_LAUNCH_CHECK("rq_rank_hist");
   return 0;
 }
 

@@ -10,7 +10,14 @@ of a masked tensor). Here the counters are one int64 tensor (2, D, len(ks)):
   * CPU tensors: the same counts with plain torch (module drop-in contract).
 Under data parallelism reduce() sums the counters and the row total over the ranks with ONE all-reduce; ranks
 may have accumulated different numbers of batches (also none).
+
+RankAccumulator (this build's addition; the reference has only Hit@k): Recall@k, NDCG@k and MRR@k of a ranked list
+against ONE relevant target per row, all derived from the histogram of the target's first-match rank — item ids
+(model.recommend) or whole sem-ID tuples. Same split: one HIP launch per batch on the device
+(rqvae_hip.ops.rank_hist), plain torch on the CPU, one host read and one all-reduce in reduce().
 """
+import math
+
 import torch
 from torch import Tensor
 
@@ -81,4 +88,77 @@ class TopKAccumulator:
             for t, name in ((0, f"slice_:{i + 1}"), (1, f"pos_{i}")):
                 for j, k in enumerate(self.ks):
                     out[f"h@{k}_{name}"] = c[t][i][j] / total
+        return out
+
+
+class RankAccumulator:
+    """First-match rank histogram -> recall@k / ndcg@k / mrr@k for k in `ks`.
+
+    accumulate(actual, top_k): actual (B,) with top_k (B, k) item ids, or (B, D) with (B, k, D) tuples, k <= width.
+    A row's rank is the index of its first beam equal to the target in every column; rows whose target starts with a
+    negative id (no target) are skipped, a dead beam (-1) never equals a target. With one relevant item the ideal
+    DCG is 1, so per row recall@k = [rank < k], ndcg@k = [rank < k] / log2(rank + 2), mrr@k = [rank < k] / (rank + 1).
+    One int64 histogram (k + 1: ranks, then the misses) per distinct k seen, allocated on its first batch; reduce()
+    folds them into the fixed (width + 1) vector (ranks 0..width-1, misses) that is all-reduced and read once."""
+
+    def __init__(self, ks=[1, 5, 10], width: int = 32):
+        self.ks = ks
+        self.width = int(width)
+        self.reset()
+
+    def reset(self):
+        self.hists = {}   # k -> (k + 1) int64
+
+    @staticmethod
+    def _cpu_hist(actual: Tensor, top_k: Tensor) -> Tensor:
+        k = top_k.shape[1]
+        match = (actual.unsqueeze(1) == top_k).all(-1)                                  # (B, k)
+        ranks = torch.arange(k).view(1, k)
+        rank = torch.where(match, ranks, torch.full_like(ranks, k)).min(dim=1).values    # k: no beam matched
+        return torch.bincount(rank[actual[:, 0] >= 0], minlength=k + 1)
+
+    def accumulate(self, actual: Tensor, top_k: Tensor) -> None:
+        if actual.dim() == 1 and top_k.dim() == 2:
+            actual, top_k = actual.unsqueeze(-1), top_k.unsqueeze(-1)
+        if actual.dim() != 2 or top_k.dim() != 3 or top_k.shape[0] != actual.shape[0] or top_k.shape[2] != actual.shape[1]:
+            raise ValueError(f"need actual (B,) / (B, D) and top_k (B, k) / (B, k, D), got {tuple(actual.shape)}, "
+                             f"{tuple(top_k.shape)}")
+        k = top_k.shape[1]
+        if not 1 <= k <= self.width:
+            raise ValueError(f"top_k holds {k} beams, the accumulator was built for 1..{self.width}")
+        if actual.shape[1] > _MAX_D:
+            raise ValueError(f"sem-ID tuples wider than {_MAX_D} are not supported")
+        if k not in self.hists:
+            self.hists[k] = torch.zeros(k + 1, dtype=torch.int64, device=actual.device)
+        if actual.is_cuda:
+            from rqvae_hip import ops as hip_ops
+            hip_ops.rank_hist(actual.to(torch.int64).contiguous(), top_k.to(torch.int64).contiguous(), self.hists[k])
+        else:
+            self.hists[k] += self._cpu_hist(actual, top_k)
+
+    def reduce(self) -> dict:
+        import torch.distributed as dist
+        multi = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+        if not self.hists and not multi:
+            return {}
+        if self.hists:
+            dev = next(iter(self.hists.values())).device
+        else:
+            dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else "cpu"
+        hist = torch.zeros(self.width + 1, dtype=torch.int64, device=dev)
+        for k, h in self.hists.items():
+            hist[:k] += h[:k]
+            hist[self.width] += h[k]
+        if multi:
+            dist.all_reduce(hist)
+        c = hist.tolist()   # the one host read
+        total = sum(c)
+        if total == 0:
+            return {}
+        out = {}
+        for k in self.ks:
+            top = c[:min(int(k), self.width)]
+            out[f"recall@{k}"] = math.fsum(top) / total
+            out[f"ndcg@{k}"] = math.fsum(n / math.log2(r + 2) for r, n in enumerate(top)) / total
+            out[f"mrr@{k}"] = math.fsum(n / (r + 1) for r, n in enumerate(top)) / total
         return out

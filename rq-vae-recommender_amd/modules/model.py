@@ -219,7 +219,8 @@ class EncoderDecoderRetrievalModel(nn.Module):
     @torch.no_grad()
     def generate_next_sem_id(self, batch: TokenizedSeqBatch, temperature: int = 1, top_k: bool = True, *,
                              fused: bool = False, sample: bool = True,
-                             incremental: bool = False, constrained: bool = False) -> GenerationOutput:
+                             incremental: bool = False, constrained: bool = False,
+                             exclude_items: Tensor = None) -> GenerationOutput:
         """Beam-style decoding of the next item's L+1 sem-ID tokens (reference :149-245): per step
         sample 200 candidates per beam from softmax(logits / T), drop prefixes the verifier
         rejects (-10000), keep the top 32 cumulative log-probabilities. The encoder output is
@@ -234,9 +235,15 @@ class EncoderDecoderRetrievalModel(nn.Module):
         the corpus' prefix trie (_generate_constrained), one hip_ops.beam_expand launch per step; with or without
         incremental. Deterministic (no generator draw), every valid continuation is scored (not 200 of them), every
         returned beam is a corpus item or dead (ids -1, log-probability -inf) when a user has fewer valid beams than
-        k. `reference_batching` does not apply and is not consulted."""
+        k. `reference_batching` does not apply and is not consulted.
+        exclude_items (needs constrained=True): (B, H <= 1024) int64 corpus indices, -1 as padding (the layout of
+        SeqBatch.ids) — the search runs over the corpus without each user's listed rows (an item whose sem-ID row
+        duplicates a listed one goes with it): the tokenizer's blocked_nodes mask, built by one launch per call, is
+        applied by beam_expand at every level, so no beam is spent on a prefix that only leads to listed items."""
         if incremental and not fused:
             raise ValueError("generate_next_sem_id: incremental=True requires fused=True")
+        if exclude_items is not None and not constrained:
+            raise ValueError("generate_next_sem_id: exclude_items requires constrained=True")
         if constrained:
             if not fused:
                 raise ValueError("generate_next_sem_id: constrained=True requires fused=True")
@@ -245,7 +252,8 @@ class EncoderDecoderRetrievalModel(nn.Module):
             self._constrained_trie("generate_next_sem_id")
         assert self.enable_generation, "Model generation is not enabled"
         if constrained:
-            generated, log_probas, _ = self._generate_constrained(batch, temperature, 32 if top_k else 1, incremental)
+            generated, log_probas, _ = self._generate_constrained(batch, temperature, 32 if top_k else 1, incremental,
+                                                                  exclude_items)
             return GenerationOutput(sem_ids=generated.squeeze(), log_probas=log_probas.squeeze())
         if incremental:
             return self._generate_incremental(batch, temperature, top_k, sample)
@@ -311,11 +319,13 @@ class EncoderDecoderRetrievalModel(nn.Module):
     @reset_encoder_cache
     @torch.no_grad()
     def recommend(self, batch: TokenizedSeqBatch, k: int = 10, temperature: int = 1,
-                  incremental: bool = True) -> Recommendation:
+                  incremental: bool = True, exclude_items: Tensor = None) -> Recommendation:
         """The k <= 32 most probable corpus items for every user: the constrained beam search (32 beams,
         sample=False; generate_next_sem_id(constrained=True)) with each kept beam mapped back to its corpus index
         through the trie's leaves. A user with fewer than k valid beams gets item id -1 (sem ids -1,
-        log-probability -inf) in the remaining places."""
+        log-probability -inf) in the remaining places. exclude_items (B, H) int64, -1 as padding: corpus items (and
+        the items sharing their sem-ID rows) that are never returned — the k best of the REMAINING corpus, see
+        generate_next_sem_id."""
         if not 1 <= k <= 32:
             raise ValueError(f"recommend: need 1 <= k <= 32, got {k}")
         trie = self._constrained_trie("recommend")
@@ -323,20 +333,29 @@ class EncoderDecoderRetrievalModel(nn.Module):
             raise ValueError(f"recommend: the corpus trie has depth {trie.depth}, the model generates {self.sem_id_dim} "
                              "tokens; items are the leaves of the full depth")
         assert self.enable_generation, "Model generation is not enabled"
-        generated, log_probas, node = self._generate_constrained(batch, temperature, 32, incremental)
+        generated, log_probas, node = self._generate_constrained(batch, temperature, 32, incremental, exclude_items)
         node = node[:, :k].long()
         items = torch.where(node >= 0, trie.leaf_item[node.clamp_min(0)], -1)
         return Recommendation(item_ids=items, sem_ids=generated[:, :k], log_probas=log_probas[:, :k])
 
-    def _generate_constrained(self, batch: TokenizedSeqBatch, temperature, k: int, incremental: bool):
+    def _generate_constrained(self, batch: TokenizedSeqBatch, temperature, k: int, incremental: bool,
+                              exclude_items: Tensor = None):
         """_generate_fused's / _generate_incremental's loop with beam_candidates + _beam_verify + beam_select
         replaced by one hip_ops.beam_expand per step: a beam carries its trie node, the node's children are the
         only candidates. Returns (sem_ids (B, k, L+1), log_probas (B, k), the beams' leaf nodes (B, k) int32), dead
         beams as beam_expand marks them. Tokens handed back to the model for dead beams are clamped to 0 (row
         counts stay B * k: static shapes, no negative index reaches an embedding kernel); whatever they compute is
-        never read, a dead beam has no children. Runs under the caller's decorators."""
+        never read, a dead beam has no children. exclude_items (B, H): step i's beam_expand skips the user's blocked
+        level-(i + 1) nodes (the tokenizer's blocked_nodes, one launch for the whole call). Runs under the caller's
+        decorators."""
         trie = self._constrained_trie("generate_next_sem_id")
         B = batch.sem_ids.shape[0]
+        blocked = None
+        if exclude_items is not None:
+            if exclude_items.dim() != 2 or exclude_items.shape[0] != B:
+                raise ValueError(f"generate_next_sem_id: exclude_items must be (B, H) with B = {B} rows, got "
+                                 f"{tuple(exclude_items.shape)}")
+            blocked = self.inference_prefix_index.blocked_nodes(exclude_items)
         generated, log_probas, parent, node = None, None, None, None
         cur = TokenizedSeqBatch(user_ids=batch.user_ids, sem_ids=batch.sem_ids, sem_ids_fut=None,
                                 seq_mask=batch.seq_mask, token_type_ids=batch.token_type_ids, token_type_ids_fut=None)
@@ -353,7 +372,8 @@ class EncoderDecoderRetrievalModel(nn.Module):
                 first = generated is None
                 generated, log_probas, parent, node = hip_ops.beam_expand(
                     logits.contiguous(), k, batch=B, child_off=trie.child_off[i], tok=trie.tok[i + 1], node=node,
-                    parents=generated, parent_lp=log_probas, temperature=temperature)
+                    parents=generated, parent_lp=log_probas, temperature=temperature,
+                    blocked=None if blocked is None else blocked[i])
                 if not incremental and i + 1 < self.sem_id_dim:
                     cur = self._beams_batch(cur, generated.clamp_min(0), first, k)
         return generated, log_probas, node

@@ -13,7 +13,10 @@ MI355X path:
     the O(P x N) broadcast compare. `reference_batching=True` (default) reproduces the reference's
     batching quirk (`math.ceil(n // 16)` skips the last partial batch of 16 prefixes, which then
     report False; SURVEY A-12) so generation matches the reference; pass False for the fixed
-    behaviour.
+    behaviour;
+  * `prefix_trie` / `trie_index` / `blocked_nodes` (this build's additions): the corpus ids as a level-by-level CSR
+    trie for constrained decoding, and per batch of item-id histories the trie nodes whose leaves are all listed
+    (seen-item exclusion) — one HIP launch on the device, plain torch on the CPU.
 """
 import math
 from typing import List, NamedTuple, Optional
@@ -67,6 +70,17 @@ class PrefixTrie(NamedTuple):
     base: int
 
 
+class TrieIndex(NamedTuple):
+    """Per-item and per-leaf views of the PrefixTrie (SemanticIdTokenizer.trie_index), for seen-item exclusion."""
+    item_leaf: Tensor   # int32 (N): each corpus item's leaf (level-depth node); items with equal rows share it
+    leaf_anc: tuple     # leaf_anc[q - 1], q = 1..depth: int32 (n_depth), each leaf's level-q ancestor (non-decreasing;
+                        # the last one is the leaf itself)
+    leaf_count: tuple   # leaf_count[q - 1], q = 1..depth: int32 (n_q), each level-q node's number of leaves
+
+
+_NO_NODE = torch.iinfo(torch.int32).max   # padding of blocked_nodes' rows
+
+
 class SemanticIdTokenizer(nn.Module):
     """Tokenizes sequences of item features into sequences of semantic ids (L codewords + dedup)."""
 
@@ -93,6 +107,7 @@ class SemanticIdTokenizer(nn.Module):
         self.cached_ids = None
         self._prefix_index = {}
         self._trie = None
+        self._trie_index = None
 
     @property
     def sem_ids_dim(self):
@@ -117,6 +132,7 @@ class SemanticIdTokenizer(nn.Module):
         self.cached_ids = torch.cat([ids, dedup_rank(ids).unsqueeze(1)], 1)
         self._prefix_index = {}
         self._trie = None
+        self._trie_index = None
         return self.cached_ids
 
     def _prefix_keys(self, P: int):
@@ -163,6 +179,66 @@ class SemanticIdTokenizer(nn.Module):
             self._trie = PrefixTrie(tok=tuple(tok), child_off=tuple(child_off), leaf_item=order[first], depth=D,
                                     base=base)
         return self._trie
+
+    @torch.no_grad()
+    def trie_index(self) -> TrieIndex:
+        """prefix_trie()'s companion: every item's leaf, every leaf's ancestors and every node's leaf count. Built
+        with torch ops on the device of `cached_ids` (CPU tensors work too); cached until the corpus changes."""
+        trie = self.prefix_trie()
+        if self._trie_index is None:
+            ids, D, base = self.cached_ids, trie.depth, trie.base
+            leaf_keys = self._prefix_keys(D)[0]
+            item_leaf = torch.searchsorted(leaf_keys, _pack(ids, base)).to(torch.int32)
+            anc, count = [], []
+            for q in range(1, D + 1):
+                keys = self._prefix_keys(q)[0]
+                a = torch.searchsorted(keys, torch.div(leaf_keys, base ** (D - q), rounding_mode="floor"))
+                anc.append(a.to(torch.int32))
+                count.append(torch.bincount(a, minlength=keys.numel()).to(torch.int32))
+            self._trie_index = TrieIndex(item_leaf=item_leaf, leaf_anc=tuple(anc), leaf_count=tuple(count))
+        return self._trie_index
+
+    @torch.no_grad()
+    def blocked_nodes(self, items: Tensor) -> Tensor:
+        """(D, B, H) int32 for `items` (B, H) int64 corpus indices, -1 (any entry outside [0, N)) as padding — the
+        layout of SeqBatch.ids: slice q - 1 holds per user the BLOCKED level-q trie nodes, ascending and distinct,
+        then INT32_MAX. A node is blocked iff every leaf below it is the row of a listed item (exclusion is by sem-ID
+        row: an item whose row duplicates a listed one goes with it), so a constrained search that skips the blocked
+        nodes of every level is exactly the search over the corpus without that user's rows
+        (rqvae_hip.ops.beam_expand(blocked=...)). Device tensors: one HIP launch for all levels
+        (rqvae_hip.ops.trie_blocked_nodes), no host read; CPU tensors: the same result with plain torch."""
+        idx = self.trie_index()
+        if items.dim() != 2:
+            raise ValueError(f"blocked_nodes: items must be (B, H), got {tuple(items.shape)}")
+        if items.is_cuda:
+            from rqvae_hip import ops as hip_ops
+            return hip_ops.trie_blocked_nodes(items.to(torch.int64).contiguous(), idx.item_leaf, idx.leaf_anc,
+                                              idx.leaf_count)
+        B, H = items.shape
+        D, n = len(idx.leaf_anc), idx.item_leaf.numel()
+        out = torch.full((D, B, H), _NO_NODE, dtype=torch.int32)
+        if B == 0 or H == 0:
+            return out
+        ok = (items >= 0) & (items < n)
+        leaf = torch.where(ok, idx.item_leaf[items.clamp(0, max(n - 1, 0))].long(), _NO_NODE).sort(dim=1).values
+        dup = torch.zeros_like(ok)
+        dup[:, 1:] = leaf[:, 1:] == leaf[:, :-1]
+        leaf = torch.where(dup, _NO_NODE, leaf).sort(dim=1).values        # distinct leaves first, ascending
+        live = leaf < _NO_NODE
+        row = torch.arange(B).unsqueeze(1).expand(B, H)
+        if not bool(live.any()):
+            return out
+        leaf = leaf.clamp_max(idx.leaf_anc[0].numel() - 1)                # padding reads the last leaf, masked by `live`
+        for q in range(D):
+            n_q = idx.leaf_count[q].numel()
+            a = idx.leaf_anc[q].long()[leaf]                              # (B, H), non-decreasing over the live part
+            # the user's listed leaves under every node, against the node's leaf count
+            listed = torch.bincount((row * n_q + a)[live], minlength=B * n_q).view(B, n_q)
+            head = live.clone()
+            head[:, 1:] &= a[:, 1:] != a[:, :-1]                          # the first listed leaf of a node
+            full = head & (listed[row, a] == idx.leaf_count[q].long()[a])
+            out[q] = torch.where(full, a, _NO_NODE).sort(dim=1).values.to(torch.int32)
+        return out
 
     @torch.no_grad()
     @eval_mode

@@ -95,6 +95,10 @@ _SIGS = {
     "rq_beam_self_attn": ([_P, _I64, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _F, _P, _I64, _P], _I),
     "rq_beam_expand": ([_P, _F, _P, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P], _I),
     "rq_topk_hits": ([_P, _P, _I64, _I64, _I64, _P, _I64, _P, _P], _I),
+    "rq_beam_expand_blocked": ([_P, _F, _P, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P,
+                                _P, _I64, _P], _I),
+    "rq_trie_blocked_nodes": ([_P, _I64, _I64, _P, _I64, _I64, _P, _P, _P, _I64, _P, _P], _I),
+    "rq_rank_hist": ([_P, _P, _I64, _I64, _I64, _P, _P], _I),
     "rq_adamw_step": ([_P, _I64, _F, _F, _F, _F, _F, _F, _F, _P], _I),
     "rq_adamw_chunk_elems": ([], _SZ),
 }

@@ -8,6 +8,8 @@
   gemm_bf16x3 / gemm_x3 / mlp_chain          fp32 matmuls at 'high' precision (split-bf16 MFMA)
   beam_candidates / beam_select / topk_hits  decoder evaluation: one beam step in two launches, Hit@k counters
   beam_expand                                constrained decoding: one beam step against the corpus' prefix trie, one launch
+  trie_blocked_nodes / rank_hist             seen-item exclusion: a batch's blocked trie nodes of every level, one launch;
+                                             first-match rank histogram (Recall / NDCG / MRR), one launch
 
 All kernels run on torch's current HIP stream; tensors must be on the GPU (no CPU path).
 """
@@ -2360,16 +2362,18 @@ BEAM_MAX_V, BEAM_MAX_N = 4096, 8192   # kBeamMaxV, kBeamMaxN (csrc/beam.hip)
 
 def beam_expand(logits: torch.Tensor, k: int, *, batch: int, child_off: torch.Tensor, tok: torch.Tensor,
                 node: torch.Tensor = None, parents: torch.Tensor = None, parent_lp: torch.Tensor = None,
-                temperature: float = 1.0):
+                temperature: float = 1.0, blocked: torch.Tensor = None):
     """(out_ids (B, k, P + 1) int64, out_lp (B, k) fp32, out_parent (B, k) int32, out_node (B, k) int32): one
     constrained beam step against the corpus' prefix trie (rq_beam_expand) — the k best of the valid continuations of
     the B * kprev beams whose logits (B * kprev, V) these are, with beam_candidates' log-probabilities. child_off
     (n_nodes + 1) / tok (n_children) int32: SemanticIdTokenizer.prefix_trie()'s child_off[P] and tok[P + 1]. node
     (B, kprev) int32, parents (B, kprev, P) int64 and parent_lp (B, kprev) fp32: the beams so far — the previous call's
     out_node, out_ids and out_lp — all None on the first step (every beam on the root). With fewer than k valid
-    continuations the remaining rows are dead: ids -1, -inf, parent 0, node -1. One launch, no host read."""
+    continuations the remaining rows are dead: ids -1, -inf, parent 0, node -1. One launch, no host read.
+    blocked (B, n_blocked <= 1024) int32: per batch element the level-(P + 1) nodes that are not candidates, ascending
+    and INT32_MAX-padded — slice P of trie_blocked_nodes' result (rq_beam_expand_blocked); None: no filter."""
     what = "beam_expand"
-    require_gpu(logits, child_off, tok, node, parents, parent_lp, what=what)
+    require_gpu(logits, child_off, tok, node, parents, parent_lp, blocked, what=what)
     B = int(batch)
     if logits.dim() != 2 or B < 0 or (B and logits.shape[0] % B):
         raise RqHipError(f"{what}: logits must be (B * kprev, V)")
@@ -2396,11 +2400,21 @@ def beam_expand(logits: torch.Tensor, k: int, *, batch: int, child_off: torch.Te
     if V < 1 or V > BEAM_MAX_V or kprev * V > BEAM_MAX_N or not 1 <= int(k) <= BEAM_MAX_N:
         raise RqHipError(f"{what}: outside the supported envelope V <= {BEAM_MAX_V}, kprev * V <= {BEAM_MAX_N}, "
                          f"1 <= k <= {BEAM_MAX_N} (kprev={kprev}, V={V}, k={k})")
+    if blocked is not None:
+        if blocked.dim() != 2 or blocked.shape[0] != B or blocked.shape[1] > BLOCKED_MAX:
+            raise RqHipError(f"{what}: blocked must be (B, n_blocked <= {BLOCKED_MAX}), got {tuple(blocked.shape)}")
+        _beam_arg(blocked, torch.int32, what, "blocked")
     dev = logits.device
     out_ids = torch.empty((B, int(k), P + 1), device=dev, dtype=torch.int64)
     out_lp = torch.empty((B, int(k)), device=dev, dtype=torch.float32)
     out_parent = torch.empty((B, int(k)), device=dev, dtype=torch.int32)
     out_node = torch.empty((B, int(k)), device=dev, dtype=torch.int32)
+    if blocked is not None:
+        call("rq_beam_expand_blocked", ptr(logits), float(temperature), ptr(node), ptr(child_off), child_off.numel() - 1,
+             ptr(tok), tok.numel(), ptr(parents), ptr(parent_lp), B, kprev, V, P, int(k), ptr(out_ids), ptr(out_lp),
+             ptr(out_parent), ptr(out_node), ptr(blocked) if blocked.shape[1] else None, blocked.shape[1],
+             stream_handle(dev))
+        return out_ids, out_lp, out_parent, out_node
     call("rq_beam_expand", ptr(logits), float(temperature), ptr(node), ptr(child_off), child_off.numel() - 1, ptr(tok),
          tok.numel(), ptr(parents), ptr(parent_lp), B, kprev, V, P, int(k), ptr(out_ids), ptr(out_lp),
          ptr(out_parent), ptr(out_node), stream_handle(dev))
@@ -2408,6 +2422,42 @@ def beam_expand(logits: torch.Tensor, k: int, *, batch: int, child_off: torch.Te
 
 
 BEAM_MAX_T = 8   # RQ_BEAM_MAX_T
+BLOCKED_MAX = 1024   # kBlockedMax (csrc/beam.hip): widest exclusion list / blocked row
+
+
+def trie_blocked_nodes(items: torch.Tensor, item_leaf: torch.Tensor, leaf_anc, leaf_count) -> torch.Tensor:
+    """(D, B, H) int32: slice q - 1 holds per user the level-q trie nodes whose leaves are all rows of the user's
+    listed items, ascending and distinct, then INT32_MAX (rq_trie_blocked_nodes) — beam_expand's `blocked` of step
+    q - 1. items (B, H <= 1024) int64 corpus indices (entries outside [0, N) are padding); item_leaf (N) int32,
+    leaf_anc / leaf_count: D int32 tensors each, (n_leaves) and (n_q) — SemanticIdTokenizer.trie_index(). One launch
+    for all D levels, no host read."""
+    import ctypes
+    what = "trie_blocked_nodes"
+    leaf_anc, leaf_count = list(leaf_anc), list(leaf_count)
+    require_gpu(items, item_leaf, *leaf_anc, *leaf_count, what=what)
+    D = len(leaf_anc)
+    if items.dim() != 2:
+        raise RqHipError(f"{what}: items must be (B, H), got {tuple(items.shape)}")
+    B, H = items.shape
+    if not 1 <= D <= BEAM_MAX_T or len(leaf_count) != D or H > BLOCKED_MAX:
+        raise RqHipError(f"{what}: outside the supported envelope H <= {BLOCKED_MAX}, 1 <= D <= {BEAM_MAX_T} with D "
+                         f"tables of each kind (H={H}, D={D}, {len(leaf_count)} count tables)")
+    _beam_arg(items, torch.int64, what, "items")
+    if item_leaf.dim() != 1:
+        raise RqHipError(f"{what}: item_leaf must be 1-D")
+    _beam_arg(item_leaf, torch.int32, what, "item_leaf")
+    n_leaves = leaf_anc[0].numel()
+    for q in range(D):
+        _beam_arg(leaf_anc[q], torch.int32, what, f"leaf_anc[{q}]", (n_leaves,))
+        if leaf_count[q].dim() != 1:
+            raise RqHipError(f"{what}: leaf_count[{q}] must be 1-D")
+        _beam_arg(leaf_count[q], torch.int32, what, f"leaf_count[{q}]")
+    out = torch.empty((D, B, H), device=items.device, dtype=torch.int32)
+    P = ctypes.c_void_p * D
+    call("rq_trie_blocked_nodes", ptr(items), B, H, ptr(item_leaf), item_leaf.numel(), n_leaves,
+         P(*[t.data_ptr() for t in leaf_anc]), P(*[t.data_ptr() for t in leaf_count]),
+         (ctypes.c_int64 * D)(*[t.numel() for t in leaf_count]), D, ptr(out), stream_handle(items.device))
+    return out
 
 
 def beam_self_attention(q: torch.Tensor, kv_steps, anc: torch.Tensor, num_heads: int, scale: float = None):
@@ -2494,3 +2544,24 @@ def topk_hits(actual: torch.Tensor, topk: torch.Tensor, ks, counts: torch.Tensor
     call("rq_topk_hits", ptr(actual), ptr(topk), B, topk.shape[1], D, (ctypes.c_int * len(ks))(*ks), len(ks),
          ptr(counts), stream_handle(actual.device))
     return counts
+
+
+RANK_MAX_K = 1024   # kRankMaxK (csrc/beam.hip)
+
+
+def rank_hist(actual: torch.Tensor, topk: torch.Tensor, hist: torch.Tensor) -> torch.Tensor:
+    """hist (k + 1) int64 += the first-match rank histogram of one batch (rq_rank_hist): hist[r] the rows whose first
+    beam equal to the target in all D columns has rank r, hist[k] the rows without one; rows whose target starts with
+    a negative id are skipped. actual (B, D), topk (B, k, D) int64. One launch, no host read; the caller zeroes hist
+    once."""
+    what = "rank_hist"
+    require_gpu(actual, topk, hist, what=what)
+    if actual.dim() != 2 or topk.dim() != 3 or topk.shape[0] != actual.shape[0] or topk.shape[2] != actual.shape[1]:
+        raise RqHipError(f"{what}: need actual (B, D) and topk (B, k, D), got {tuple(actual.shape)}, {tuple(topk.shape)}")
+    B, D = actual.shape
+    k = topk.shape[1]
+    _beam_arg(actual, torch.int64, what, "actual")
+    _beam_arg(topk, torch.int64, what, "topk")
+    _beam_arg(hist, torch.int64, what, "hist", (k + 1,))
+    call("rq_rank_hist", ptr(actual), ptr(topk), B, k, D, ptr(hist), stream_handle(actual.device))
+    return hist

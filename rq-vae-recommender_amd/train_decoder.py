@@ -21,7 +21,9 @@ The reference rejects non-AMAZON datasets and its ML-32M gin binds a non-existen
 Evaluation (reference train_decoder.py:208-245) runs eagerly between train steps, outside the captured graphs:
 every `partial_eval_every` iterations the eval split's loss, every `full_eval_every` iterations beam generation
 over the eval split into the device-side Hit@k accumulator (evaluate.metrics), each rank taking every world-th
-batch; see _Evaluator.
+batch; see _Evaluator. Opt-in (EVAL_ITEM_METRICS with EVAL_CONSTRAINED_GENERATION): item-level Recall / NDCG / MRR@k
+of model.recommend against the next item (evaluate.metrics.RankAccumulator), with EVAL_EXCLUDE_SEEN over the corpus
+minus each user's history.
 """
 import contextlib
 import json
@@ -38,7 +40,7 @@ from modules.model import EncoderDecoderRetrievalModel
 from modules.scheduler.inv_sqrt import InverseSquareRootScheduler
 from modules.tokenizer.semids import SemanticIdTokenizer
 from modules.utils import compute_debug_metrics, parse_config
-from evaluate.metrics import TopKAccumulator
+from evaluate.metrics import RankAccumulator, TopKAccumulator
 from rqvae_hip import dp, gemm_tuning
 from rqvae_hip import ops as hip_ops
 from rqvae_hip import optim as hip_optim
@@ -118,6 +120,11 @@ EVAL_INCREMENTAL_GENERATION = False
 # Prefix-trie constrained beam search (modules/model.py _generate_constrained): opt-in. Deterministic and
 # exact, so Hit@k differs from the sampled path's; needs EVAL_FUSED_GENERATION and the tokenizer as prefix index.
 EVAL_CONSTRAINED_GENERATION = False
+# Item-level metrics of the full eval (needs EVAL_CONSTRAINED_GENERATION): model.recommend(k=10) against the next
+# item's corpus index -> recall@k / ndcg@k / mrr@k (evaluate.metrics.RankAccumulator) next to the Hit@k keys. Opt-in.
+EVAL_ITEM_METRICS = False
+# recommend() over the corpus minus each user's own history (exclude_items = the batch's item ids). Opt-in.
+EVAL_EXCLUDE_SEEN = False
 
 
 class _Evaluator:
@@ -133,8 +140,10 @@ class _Evaluator:
         self.partial_every, self.full_every = partial_every, full_every
         self.dataset = None
         self.metrics = TopKAccumulator(ks=[1, 5, 10])
+        self.item_metrics = RankAccumulator(ks=[1, 5, 10])
 
-    def _batches(self):
+    def _batches(self, with_ids: bool = False):
+        """The rank's tokenized eval batches; with_ids: (tokenized, item ids (B, N) with -1 padding, next item (B,))."""
         if self.dataset is None:
             self.dataset = self.make_dataset()
         n, bs, D = len(self.dataset), self.batch_size, self.tokenizer.sem_ids_dim
@@ -144,9 +153,10 @@ class _Evaluator:
             data = self.dataset[list(range(a, min(n, a + bs)))]
             counts = (data.seq_mask.sum(1) * D).tolist()
             ids_max = int(max(int(data.ids.max()), int(data.ids_fut.max())))
-            tok = self.tokenizer(batch_to(data, self.device), ids_max=ids_max)
+            data = batch_to(data, self.device)
+            tok = self.tokenizer(data, ids_max=ids_max)
             register_row_counts(tok.seq_mask, counts)
-            yield tok
+            yield (tok, data.ids, data.ids_fut.reshape(-1)) if with_ids else tok
 
     def __call__(self, it: int):
         partial = self.partial_every and (it + 1) % self.partial_every == 0
@@ -190,13 +200,22 @@ class _Evaluator:
     def _full(self, it):
         self.model.enable_generation = True
         self.metrics.reset()
-        for tok in self._batches():
+        self.item_metrics.reset()
+        items = EVAL_ITEM_METRICS and EVAL_CONSTRAINED_GENERATION
+        for tok, ids, ids_fut in self._batches(with_ids=True):
             constrained = dict(constrained=True, sample=False) if EVAL_CONSTRAINED_GENERATION else {}
             gen = self.model.generate_next_sem_id(tok, top_k=True, temperature=1, fused=EVAL_FUSED_GENERATION,
                                                   incremental=EVAL_INCREMENTAL_GENERATION, **constrained)
             self.metrics.accumulate(actual=tok.sem_ids_fut, top_k=gen.sem_ids)
+            if items:
+                rec = self.model.recommend(tok, k=10, incremental=EVAL_INCREMENTAL_GENERATION,
+                                           exclude_items=ids if EVAL_EXCLUDE_SEEN else None)
+                self.item_metrics.accumulate(actual=ids_fut, top_k=rec.item_ids)
         res = self.metrics.reduce()
         self.metrics.reset()
+        if items:
+            res.update(self.item_metrics.reduce())
+            self.item_metrics.reset()
         if self.rank == 0:
             print(res, flush=True)   # the reference prints the Hit@k dictionary as is (train_decoder.py:241)
         return {"full_eval_iter": it, **res}

@@ -7,7 +7,10 @@ per beam, 256 classes, 4 sem-ID tokens; model dims of configs/decoder_amazon.gin
                beam step over a BeamDecodeState: cross K/V projected once per user, only each beam's newest token
                through the decoder), and fused=True, incremental=True, constrained=True, sample=False (the
                incremental loop with the beam step replaced by one rq_beam_expand launch that walks the corpus'
-               prefix trie), verifier = a tokenizer over a 12,101-item corpus; and with the beam step
+               prefix trie) and the same call with exclude_items (`excluded`: H = the batch's history length of 20
+               items per user, drawn from the corpus, padded where the sequence is; one rq_trie_blocked_nodes launch
+               per call and the filtered rq_beam_expand_blocked per step), verifier = a tokenizer over a 12,101-item
+               corpus; and with the beam step
                stubbed out (`model`: the four forwards and the encoder cache repeat alone), which gives the
                beam logic's share of the first two forms;
   accumulate   TopKAccumulator.accumulate on the device (one rq_topk_hits launch) and the reference's logic
@@ -15,7 +18,7 @@ per beam, 256 classes, 4 sem-ID tokens; model dims of configs/decoder_amazon.gin
 
 Each form is warmed up, then timed `--reps` times with the forms alternating; a span is a host clock around work
 that ends in a device synchronise. Prints one JSON line (medians, ms; `peak_mem_mib`: torch.cuda.max_memory_allocated
-over one further call of each generation form). `--only FORM --reps N --warmup 0` runs a single form N times for a
+over one further call of each generation form). `--forms A,B` alternates only those forms. `--only FORM --reps N --warmup 0` runs a single form N times for a
 kernel trace (rocprofv3 --kernel-trace --stats -- python tools/generation_time.py ...), after the set-up's one
 fused call: launches per beam step = (calls of the form - calls of `model`) / (4 N).
 """
@@ -71,7 +74,9 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--only", choices=["unfused", "fused", "incremental", "constrained", "model", "acc_device", "acc_reference"])
+    names = ["unfused", "fused", "incremental", "constrained", "excluded", "model", "acc_device", "acc_reference"]
+    ap.add_argument("--only", choices=names)
+    ap.add_argument("--forms", type=lambda v: v.split(","), help="comma-separated subset of the forms to alternate")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("generation_time: needs the GPU (a CPU run measures nothing)")
@@ -104,6 +109,17 @@ def main():
         return model.generate_next_sem_id(batch, temperature=1, top_k=True, fused=True, sample=False, incremental=True,
                                           constrained=True)
 
+    # one history per user: as many corpus items as the sequence holds (its mask), -1 behind them
+    L1_ = model.sem_id_dim
+    n_hist = batch.seq_mask.shape[1] // L1_
+    seen = torch.randint(0, tok.cached_ids.shape[0], (args.batch, n_hist),
+                         generator=torch.Generator().manual_seed(7)).to(device)
+    seen = seen.masked_fill(~batch.seq_mask[:, ::L1_], -1)
+
+    def gen_excluded():
+        return model.generate_next_sem_id(batch, temperature=1, top_k=True, fused=True, sample=False, incremental=True,
+                                          constrained=True, exclude_items=seen)
+
     def gen_model_only():
         hip_ops.beam_candidates, hip_ops.beam_select = stub_candidates, stub_select
         try:
@@ -123,10 +139,13 @@ def main():
         reference_accumulate({}, [1, 5, 10], actual, top)
 
     forms = {"unfused": lambda: gen(False), "fused": lambda: gen(True),
-             "incremental": lambda: gen(True, True), "constrained": gen_constrained, "model": gen_model_only,
+             "incremental": lambda: gen(True, True), "constrained": gen_constrained, "excluded": gen_excluded,
+             "model": gen_model_only,
              "acc_device": acc_device, "acc_reference": acc_reference}
     if args.only:
         forms = {args.only: forms[args.only]}
+    elif args.forms:
+        forms = {n: forms[n] for n in args.forms}
     times = {n: [] for n in forms}
     for rep in range(-args.warmup, args.reps):
         for name, fn in forms.items():   # alternating: every form sees the same drift of the shared host
@@ -141,7 +160,7 @@ def main():
            "median_ms": {n: round(v, 4) for n, v in med.items()},
            "min_max_ms": {n: [round(min(v), 4), round(max(v), 4)] for n, v in times.items() if v}}
     peak = {}
-    for name in ("unfused", "fused", "incremental", "constrained"):
+    for name in ("unfused", "fused", "incremental", "constrained", "excluded"):
         if name in forms and not args.only:   # one more call of each generation form, alone after a peak reset
             torch.cuda.synchronize()
             torch.cuda.reset_peak_memory_stats(device)
@@ -158,6 +177,12 @@ def main():
         out["constrained_vs_incremental"] = dict(delta_ms=round(med["constrained"] - med["incremental"], 4),
                                                  incremental_spread_ms=round(spread, 4),
                                                  within_spread=med["constrained"] - med["incremental"] <= spread)
+    if {"constrained", "excluded"} <= set(med):
+        # the exclusion's cost against the constrained form of the same run, next to that form's own spread
+        spread = max(times["constrained"]) - min(times["constrained"])
+        out["excluded_vs_constrained"] = dict(delta_ms=round(med["excluded"] - med["constrained"], 4),
+                                              constrained_spread_ms=round(spread, 4), history=n_hist,
+                                              within_spread=med["excluded"] - med["constrained"] <= spread)
     if {"unfused", "fused", "model"} <= set(med):
         out["beam_logic_share"] = {n: round(1 - med["model"] / med[n], 4) for n in ("unfused", "fused")}
         out["beam_logic_ms"] = {n: round(med[n] - med["model"], 4) for n in ("unfused", "fused")}
