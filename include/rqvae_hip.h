@@ -512,7 +512,20 @@ int varlen_attn_bwd(const float* q, int64_t sq, const float* k, int64_t sk, cons
  *   D <= RQ_BEAM_MAX_T, else -22; B == 0 or H == 0 returns 0 without a launch.
  * rq_rank_hist: actual (B, D) int64 targets, topk (B, k, D) int64 beams; hist (k + 1) int64 is ACCUMULATED into:
  *   hist[r] += #rows whose first beam equal to the target in all D columns has rank r, hist[k] += #rows without one.
- *   Rows with actual[b][0] < 0 are skipped entirely. D <= 64, k <= 1024. D == 1 serves item ids. */
+ *   Rows with actual[b][0] < 0 are skipped entirely. D <= 64, k <= 1024. D == 1 serves item ids.
+ * rq_score_paths: teacher-forced scoring — one decoding step of log p(candidate | user) for C candidates per user that
+ *   the CALLER names, one launch per step, one workgroup per user. logits (B G, V) fp32: G == 1 on step 0 (one BOS row
+ *   per user, shared by its candidates), G == C afterwards (row b C + c belongs to candidate c). tokens: this step's
+ *   token of every candidate, int64, element (b, c) at tokens[b tok_stride_b + c tok_stride_c] (strides in elements:
+ *   a column of a (B, C, D) tensor is passed in place). present (B, C) bool: 0 marks PADDING (NULL: all present).
+ *   prev_lp (B, C) fp32: the score so far (NULL on step 0: 0). out_lp[b][c] = lp + prev_lp[b][c] with lp the
+ *   log-softmax of the candidate's row / temperature at its token, formed exactly as rq_beam_expand forms it (bitwise
+ *   equal for the same row, token and parent score). A present candidate whose token is outside [0, V) — a class the
+ *   model cannot generate — gets -inf (and keeps it on later steps); its row is not read. Padding gets -inf; its row
+ *   is never read and its token never used. out_rank (B, C) int32 or NULL (give it on the last step): the number of
+ *   the user's candidates that come before c in (score descending, index ascending) order, padding last and real
+ *   -inf candidates before padding — every user's ranks are a permutation of 0..C-1. 1 <= V <= 4096, 1 <= C <= 1024,
+ *   G in {1, C}, temperature > 0, strides >= 0, else -22; B == 0 returns 0 without a launch. */
 #define RQ_BEAM_MAX_T 8 /* tokens per beam incl. BOS; sem_id_dim <= 8 as evaluate.metrics already assumes */
 int rq_beam_candidates(const float* logits, const float* noise, int64_t R, int64_t V, int64_t n_cand,
                        float temperature, int64_t* cand_ids, float* cand_lp, void* stream);
@@ -543,6 +556,9 @@ int rq_trie_blocked_nodes(const int64_t* items, int64_t B, int64_t H, const int3
                           const int64_t* n_nodes, int64_t D, int32_t* out, void* stream);
 int rq_rank_hist(const int64_t* actual, const int64_t* topk, int64_t B, int64_t k, int64_t D, int64_t* hist,
                  void* stream);
+int rq_score_paths(const float* logits, float temperature, const int64_t* tokens, int64_t tok_stride_b,
+                   int64_t tok_stride_c, const bool* present, const float* prev_lp, int64_t B, int64_t C, int64_t V,
+                   int64_t G, float* out_lp, int32_t* out_rank, void* stream);
 
 /* AdamW step (torch.optim.AdamW as stepped by train_rqvae.py:168-172 / train_decoder.py:203) over
  * every fp32 parameter of a group, one launch per 64 tensors. segs: HOST array of nseg records of 5

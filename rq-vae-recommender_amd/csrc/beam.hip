@@ -12,6 +12,9 @@
 //                           best in stable order, the parent gather and each winner's trie node. A second
 //                           instantiation (BLOCKED) skips the children found in a per-user sorted row of blocked
 //                           nodes (seen-item exclusion).
+//   score_paths_kernel      teacher-forced scoring of caller-named candidates: one workgroup per user, per step the
+//                           log-probability of every candidate's token in beam_expand_kernel's arithmetic (bitwise),
+//                           accumulated over the steps; on the last step each candidate's rank among the user's.
 //   trie_blocked_kernel     one workgroup per user: the trie nodes of every level whose leaves are all on the
 //                           user's exclusion list, sorted / deduplicated / counted in LDS.
 //   beam_self_attn_kernel   incremental decoding: the newest token's causal self-attention over its beam's
@@ -392,6 +395,123 @@ __global__ void __launch_bounds__(64 * kExpMaxWaves) beam_expand_kernel(
     }
     out_node[b * k + r] = (lo < end && tok[lo] == v) ? lo : -1;   // -1: an unsorted (bad) table
   }
+}
+
+// ------------------------------------------------------------------------------------- score paths
+// Teacher-forced scoring: the log-probability of the token every one of a user's C candidates names at this step, in
+// beam_expand_kernel's arithmetic and lane order (v = lane + 64 j, wave_argmax, group_sum<64>, log1p form), so a
+// candidate's score is bitwise what rq_beam_expand gives the same (row, token, parent score). One workgroup per user.
+//   G == 1 (step 0): the user's candidates share the BOS row. Every wave forms the row's statistics itself (the same
+//          lane order gives the same bits, so no barrier), then the threads stride over the candidates.
+//   G == C (later steps): a wave per candidate row, round robin. The row is read from memory once, into J registers
+//          per lane (J = 4 / 16 / 64 by V, picked on the host); only the named class is fetched again (one dword).
+// A padding candidate (present[b][c] == 0) gets -inf, its row is never read and its token is never used; a present
+// candidate whose token is outside [0, V) gets -inf without touching its row (and stays -inf: -inf + prev_lp).
+// out_rank: the scores' keys stay in LDS (0 for padding: below every float's key) and rank[c] counts the candidates
+// that are better(...) than c — a permutation of 0..C-1, ties to the lower index, real -inf above padding.
+// Waves per workgroup in the G == C form: 16 (as beam_expand_kernel's latency-bound phase) for J <= 16; 8 for J = 64,
+// whose 64 row registers per lane do not fit the 128 VGPRs a 16-wave workgroup leaves a lane.
+template <int J>
+constexpr int kScoreWaves = J <= 16 ? 16 : 8;
+
+// (max, sum of the other classes' exp(z - max)) of one row, every lane holding z[j] = x[lane + 64 j] / T
+template <int J>
+__device__ __forceinline__ void score_row_stats(const float* __restrict__ x, int V, float temperature, int lane,
+                                                float& m, float& rest) {
+  float z[J];
+  m = -INFINITY;
+  int am = 0x7fffffff;
+#pragma unroll
+  for (int j = 0; j < J; ++j) {
+    const int v = lane + 64 * j;
+    z[j] = -INFINITY;
+    if (v < V) {
+      z[j] = x[v] / temperature;
+      if (z[j] > m) { m = z[j]; am = v; }
+    }
+  }
+  wave_argmax(m, am);
+  rest = 0.f;
+#pragma unroll
+  for (int j = 0; j < J; ++j) {
+    const int v = lane + 64 * j;
+    if (v < V && v != am) rest += expf(z[j] - m);
+  }
+  rest = group_sum<64>(rest);
+}
+
+__device__ __forceinline__ float score_token(const float* __restrict__ x, int v, float temperature, float m,
+                                             float rest, float prev) {
+  const float sum = rest + 1.0f;
+  const float log_norm = log1pf(rest);
+  const float dv = x[v] / temperature - m;
+  const float p = expf(dv) / sum;
+  const float lp = p == 0.f ? -INFINITY : dv - log_norm;
+  return lp + prev;
+}
+
+template <int J>
+__global__ void __launch_bounds__(64 * kScoreWaves<J>) score_paths_kernel(
+    const float* __restrict__ logits, float temperature, const int64_t* __restrict__ tokens, int64_t tok_sb,
+    int64_t tok_sc, const bool* __restrict__ present, const float* __restrict__ prev_lp, int C, int V, int G,
+    float* __restrict__ out_lp, int32_t* __restrict__ out_rank) {
+  __shared__ uint32_t key[kRankMaxK];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nthr = blockDim.x, nwave = nthr >> 6;
+  const int64_t b = blockIdx.x;
+  const int64_t* tk = tokens + b * tok_sb;
+  const int64_t bc = b * C;
+
+  if (G == 1) {
+    const float* x = logits + b * V;
+    float m, rest;
+    score_row_stats<J>(x, V, temperature, lane, m, rest);
+    for (int c = tid; c < C; c += nthr) {
+      const bool pr = !present || present[bc + c];
+      float out = -INFINITY;
+      if (pr) {
+        const int64_t t = tk[c * tok_sc];
+        if (t >= 0 && t < V) out = score_token(x, (int)t, temperature, m, rest, prev_lp ? prev_lp[bc + c] : 0.0f);
+      }
+      out_lp[bc + c] = out;
+      key[c] = pr ? score_key(out) : 0;
+    }
+  } else {
+    for (int c = wave; c < C; c += nwave) {   // everything below is wave-uniform
+      const bool pr = !present || present[bc + c];
+      float out = -INFINITY;
+      if (pr) {
+        const int64_t t = tk[c * tok_sc];
+        if (t >= 0 && t < V) {
+          const float* x = logits + (bc + c) * V;
+          float m, rest;
+          score_row_stats<J>(x, V, temperature, lane, m, rest);
+          out = score_token(x, (int)t, temperature, m, rest, prev_lp ? prev_lp[bc + c] : 0.0f);
+        }
+      }
+      if (lane == 0) {
+        out_lp[bc + c] = out;
+        key[c] = pr ? score_key(out) : 0;
+      }
+    }
+  }
+  if (!out_rank) return;   // workgroup-uniform
+  __syncthreads();
+  for (int c = tid; c < C; c += nthr) {
+    const uint32_t kc = key[c];
+    int cnt = 0;
+    for (int u = 0; u < C; ++u) cnt += better(key[u], u, kc, c);   // every lane reads key[u]: an LDS broadcast
+    out_rank[bc + c] = cnt;
+  }
+}
+
+template <int J>
+static void launch_score_paths(const float* logits, float temperature, const int64_t* tokens, int64_t tok_sb,
+                               int64_t tok_sc, const bool* present, const float* prev_lp, int64_t B, int C, int V,
+                               int G, float* out_lp, int32_t* out_rank, hipStream_t stream) {
+  const int waves = (G == 1 || C <= 4) ? 4 : kScoreWaves<J>;
+  hipLaunchKernelGGL(score_paths_kernel<J>, dim3((unsigned)B), dim3(64 * waves), 0, stream, logits, temperature,
+                     tokens, tok_sb, tok_sc, present, prev_lp, C, V, G, out_lp, out_rank);
 }
 
 // ------------------------------------------------------------------------------------- self-attention
@@ -778,6 +898,32 @@ int rq_beam_expand_blocked(const float* logits, float temperature, const int32_t
                                     out_node, blocked, n_blocked, stream);
   if (rc != 0 || B == 0) return rc;
   RQ_LAUNCH_CHECK("rq_beam_expand_blocked");
+  return 0;
+}
+
+int rq_score_paths(const float* logits, float temperature, const int64_t* tokens, int64_t tok_stride_b,
+                   int64_t tok_stride_c, const bool* present, const float* prev_lp, int64_t B, int64_t C, int64_t V,
+                   int64_t G, float* out_lp, int32_t* out_rank, void* stream) {
+  RQ_CHECK_ARG(B >= 0 && V >= 1 && V <= rqhip::kBeamMaxV && C >= 1 && C <= rqhip::kRankMaxK && (G == 1 || G == C),
+               "rq_score_paths: need B >= 0, 1 <= V <= %d, 1 <= C <= %d, G in {1, C} (V=%lld, C=%lld, G=%lld)",
+               rqhip::kBeamMaxV, rqhip::kRankMaxK, (long long)V, (long long)C, (long long)G);
+  RQ_CHECK_ARG(temperature > 0.f && temperature <= 3.0e38f, "rq_score_paths: temperature must be positive");
+  RQ_CHECK_ARG(tok_stride_b >= 0 && tok_stride_c >= 0, "rq_score_paths: negative token stride");
+  if (B == 0) return 0;
+  RQ_CHECK_ARG(B <= 0x7fffffff, "rq_score_paths: too many batch elements");
+  RQ_CHECK_ARG(logits && tokens && out_lp, "rq_score_paths: null pointer");
+  hipStream_t hs = (hipStream_t)stream;
+  if (V <= 256) {
+    rqhip::launch_score_paths<4>(logits, temperature, tokens, tok_stride_b, tok_stride_c, present, prev_lp, B, (int)C,
+                                 (int)V, (int)G, out_lp, out_rank, hs);
+  } else if (V <= 1024) {
+    rqhip::launch_score_paths<16>(logits, temperature, tokens, tok_stride_b, tok_stride_c, present, prev_lp, B, (int)C,
+                                  (int)V, (int)G, out_lp, out_rank, hs);
+  } else {
+    rqhip::launch_score_paths<64>(logits, temperature, tokens, tok_stride_b, tok_stride_c, present, prev_lp, B, (int)C,
+                                  (int)V, (int)G, out_lp, out_rank, hs);
+  }
+  RQ_LAUNCH_CHECK("rq_score_paths");
   return 0;
 }
 

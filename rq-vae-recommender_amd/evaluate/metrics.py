@@ -15,6 +15,9 @@ RankAccumulator (this build's addition; the reference has only Hit@k): Recall@k,
 against ONE relevant target per row, all derived from the histogram of the target's first-match rank — item ids
 (model.recommend) or whole sem-ID tuples. Same split: one HIP launch per batch on the device
 (rqvae_hip.ops.rank_hist), plain torch on the CPU, one host read and one all-reduce in reduce().
+
+ranked_candidates turns the per-candidate ranks of model.score_items into the ranked list RankAccumulator(width=C)
+takes (the sampled-negatives protocol: 1 positive + N negatives, the rank of the positive).
 """
 import math
 
@@ -22,6 +25,14 @@ import torch
 from torch import Tensor
 
 _MAX_D = 64   # widest sem-ID tuple (the kernel's limit); the all-reduce buffer is laid out for it
+
+
+def ranked_candidates(items: Tensor, rank: Tensor) -> Tensor:
+    """(B, C): the candidates `items` (B, C) in rank order — out[b, rank[b, c]] = items[b, c] for `rank` (B, C), a
+    permutation of 0..C-1 per row (model.score_items). One scatter; CPU or device tensors."""
+    if items.dim() != 2 or items.shape != rank.shape:
+        raise ValueError(f"need items (B, C) and rank (B, C), got {tuple(items.shape)}, {tuple(rank.shape)}")
+    return torch.empty_like(items).scatter_(1, rank.to(torch.int64), items)
 
 
 class TopKAccumulator:

@@ -56,6 +56,11 @@ class Recommendation(NamedTuple):
     log_probas: Tensor   # (B, k)
 
 
+class Scores(NamedTuple):
+    log_probas: Tensor   # (B, C) fp32, -inf for padding and for candidates the model cannot generate
+    rank: Tensor         # (B, C) int32: each candidate's place among its user's, a permutation of 0..C-1
+
+
 class EncoderDecoderRetrievalModel(nn.Module):
     def __init__(self, embedding_dim, attn_dim, dropout, num_heads, n_layers, num_embeddings, sem_id_dim,
                  inference_verifier_fn, max_pos=2048, jagged_mode: bool = True) -> None:
@@ -337,6 +342,92 @@ class EncoderDecoderRetrievalModel(nn.Module):
         node = node[:, :k].long()
         items = torch.where(node >= 0, trie.leaf_item[node.clamp_min(0)], -1)
         return Recommendation(item_ids=items, sem_ids=generated[:, :k], log_probas=log_probas[:, :k])
+
+    @eval_mode
+    @reset_encoder_cache
+    @torch.no_grad()
+    def score_sem_ids(self, batch: TokenizedSeqBatch, sem_ids: Tensor, temperature: int = 1,
+                      incremental: bool = True) -> Scores:
+        """log p(sem-ID tuple | user) for C tuples per user that the caller names: sem_ids (B, C, D) int64 with
+        D = sem_id_dim and 1 <= C <= 1024. A tuple whose first token is negative is padding (log-probability -inf,
+        ranked last); any other tuple is scored as it stands — it need not be a corpus row, nothing consults the
+        trie — and one naming a token outside [0, num_embeddings), a class the model cannot generate, gets -inf.
+        The walk is teacher-forced: step i's logits for every candidate's own prefix, one hip_ops.score_paths launch
+        per step that adds the log-softmax at the candidate's token. Scores are the model's full-V softmax, formed as
+        beam_expand forms them, so a tuple that recommend() / generate_next_sem_id(constrained=True) returns scores
+        what it was returned with. `rank` is each tuple's place in its user's (score descending, index ascending)
+        order, a permutation of 0..C-1. No generator draw, no host read, no beam search.
+        incremental=True: one BeamDecodeState — the encoder and the cross-attention K / V once per user, then only the
+        newest token of every candidate (every candidate its own ancestor); incremental=False: full forwards over
+        _beams_batch batches (the independent path, as in _generate_constrained)."""
+        assert self.enable_generation, "Model generation is not enabled"
+        if sem_ids.dim() != 3 or sem_ids.dtype != torch.int64:
+            raise ValueError(f"score_sem_ids: sem_ids must be (B, C, D) int64, got {tuple(sem_ids.shape)} "
+                             f"{sem_ids.dtype}")
+        return self._score_paths(batch, sem_ids, sem_ids[:, :, 0] >= 0, temperature, incremental, "score_sem_ids")
+
+    @eval_mode
+    @reset_encoder_cache
+    @torch.no_grad()
+    def score_items(self, batch: TokenizedSeqBatch, items: Tensor, temperature: int = 1,
+                    incremental: bool = True) -> Scores:
+        """log p(item | user) for C corpus items per user that the caller names: items (B, C) int64 corpus indices,
+        anything outside [0, N) is padding (blocked_nodes' rule, the layout of SeqBatch.ids). The items' sem-ID rows
+        come from `inference_prefix_index.cached_ids` (the trie is not needed) and are scored by score_sem_ids, which
+        see: full-V softmax scores in beam_expand's arithmetic, so score_items(batch, recommend(batch, k).item_ids)
+        .log_probas is recommend's log_probas (-inf in the dead places; equal to rtol 1e-5 — the kernel arithmetic is
+        bitwise the same, the decoder's GEMMs round differently at another row count), and items that share a sem-ID
+        row tie exactly."""
+        index = getattr(self, "inference_prefix_index", None)
+        if index is None or getattr(index, "cached_ids", None) is None:
+            raise ValueError("score_items: requires inference_prefix_index (the tokenizer) with its corpus ids cached")
+        assert self.enable_generation, "Model generation is not enabled"
+        ids = index.cached_ids
+        if ids.shape[1] != self.sem_id_dim:
+            raise ValueError(f"score_items: the corpus rows hold {ids.shape[1]} tokens, the model generates "
+                             f"{self.sem_id_dim}")
+        if items.dim() != 2 or items.dtype != torch.int64:
+            raise ValueError(f"score_items: items must be (B, C) int64, got {tuple(items.shape)} {items.dtype}")
+        N = ids.shape[0]
+        present = (items >= 0) & (items < N)
+        sem_ids = torch.where(present.unsqueeze(-1), ids[items.clamp(0, max(N - 1, 0))].to(torch.int64), -1)
+        return self._score_paths(batch, sem_ids, present, temperature, incremental, "score_items")
+
+    def _score_paths(self, batch: TokenizedSeqBatch, sem_ids: Tensor, present: Tensor, temperature, incremental: bool,
+                     what: str) -> Scores:
+        """score_sem_ids' loop. Tokens handed back to the model are clamped into [0, V) (static shapes, no bad index
+        reaches an embedding kernel); what a padding or unreachable candidate's rows compute is never read. Runs
+        under the caller's decorators."""
+        B, V = batch.sem_ids.shape[0], self.num_embeddings
+        if sem_ids.shape[0] != B or sem_ids.shape[2] != self.sem_id_dim:
+            raise ValueError(f"{what}: need {B} users and {self.sem_id_dim} tokens per candidate, got sem-ID tuples "
+                             f"{tuple(sem_ids.shape)}")
+        if sem_ids.device != batch.sem_ids.device:
+            raise ValueError(f"{what}: the candidates must live on the batch's device {batch.sem_ids.device}, got "
+                             f"{sem_ids.device}")
+        C = sem_ids.shape[1]
+        if not 1 <= C <= hip_ops.RANK_MAX_K:
+            raise ValueError(f"{what}: need 1 <= C <= {hip_ops.RANK_MAX_K} candidates per user, got {C}")
+        sem_ids, present = sem_ids.contiguous(), present.contiguous()
+        lp = rank = None
+        cur = TokenizedSeqBatch(user_ids=batch.user_ids, sem_ids=batch.sem_ids, sem_ids_fut=None,
+                                seq_mask=batch.seq_mask, token_type_ids=batch.token_type_ids, token_type_ids_fut=None)
+        with (hip_ops.weight_split_scope(self._gemm_weights(), self._gemm_weight_stacks()) if incremental
+              else contextlib.nullcontext()):
+            state = BeamDecodeState(self, batch) if incremental else None
+            own = torch.arange(C, device=sem_ids.device).expand(B, C)
+            for i in range(self.sem_id_dim):
+                if not incremental:
+                    logits = self.forward(cur).logits
+                elif i == 0:
+                    logits = state.step()
+                else:   # the BOS rows are every candidate's parent at i == 1; afterwards every candidate is its own
+                    logits = state.step(sem_ids[:, :, i - 1].clamp(0, V - 1), torch.zeros_like(own) if i == 1 else own)
+                lp, rank = hip_ops.score_paths(logits.contiguous(), sem_ids[:, :, i], present=present, prev_lp=lp,
+                                               temperature=temperature, want_rank=i + 1 == self.sem_id_dim)
+                if not incremental and i + 1 < self.sem_id_dim:
+                    cur = self._beams_batch(cur, sem_ids[:, :, :i + 1].clamp(0, V - 1), i == 0, C)
+        return Scores(log_probas=lp, rank=rank)
 
     def _generate_constrained(self, batch: TokenizedSeqBatch, temperature, k: int, incremental: bool,
                               exclude_items: Tensor = None):

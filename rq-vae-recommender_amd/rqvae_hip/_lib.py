@@ -99,6 +99,7 @@ _SIGS = {
                                 _P, _I64, _P], _I),
     "rq_trie_blocked_nodes": ([_P, _I64, _I64, _P, _I64, _I64, _P, _P, _P, _I64, _P, _P], _I),
     "rq_rank_hist": ([_P, _P, _I64, _I64, _I64, _P, _P], _I),
+    "rq_score_paths": ([_P, _F, _P, _I64, _I64, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _P], _I),
     "rq_adamw_step": ([_P, _I64, _F, _F, _F, _F, _F, _F, _F, _P], _I),
     "rq_adamw_chunk_elems": ([], _SZ),
 }

@@ -2565,3 +2565,48 @@ def rank_hist(actual: torch.Tensor, topk: torch.Tensor, hist: torch.Tensor) -> t
     _beam_arg(hist, torch.int64, what, "hist", (k + 1,))
     call("rq_rank_hist", ptr(actual), ptr(topk), B, k, D, ptr(hist), stream_handle(actual.device))
     return hist
+
+
+def score_paths(logits: torch.Tensor, tokens: torch.Tensor, *, present: torch.Tensor = None,
+                prev_lp: torch.Tensor = None, temperature: float = 1.0, want_rank: bool = False):
+    """(lp (B, C) fp32, rank (B, C) int32 or None): one teacher-forced decoding step of C caller-named candidates per
+    user (rq_score_paths). tokens (B, C) int64: this step's token of every candidate — any view with non-negative
+    strides, e.g. a column of a (B, C, D) tensor, is read in place. logits fp32: (B, V) — the step-0 row every
+    candidate of a user shares — or (B * C, V) with row b C + c candidate c's. present (B, C) bool: False marks
+    padding (None: all present); prev_lp (B, C) fp32: the score so far (None on step 0). lp = prev_lp + the
+    log-softmax of logits / temperature at the token, bitwise beam_expand's value for the same row, token and parent
+    score; -inf for padding and for a token outside [0, V). want_rank=True (the last step): each candidate's place in
+    its user's (score descending, index ascending) order, padding last — a permutation of 0..C-1 per user. One launch,
+    no host read."""
+    what = "score_paths"
+    require_gpu(logits, tokens, present, prev_lp, what=what)
+    if tokens.dim() != 2 or tokens.dtype != torch.int64:
+        raise RqHipError(f"{what}: tokens must be (B, C) int64, got {tuple(tokens.shape)} {tokens.dtype}")
+    B, C = tokens.shape
+    if B and C and min(tokens.stride()) < 0:
+        raise RqHipError(f"{what}: tokens must have non-negative strides, got {tokens.stride()}")
+    if logits.dim() != 2 or logits.dtype != torch.float32:
+        raise RqHipError(f"{what}: logits must be (B, V) or (B * C, V) float32, got {tuple(logits.shape)} "
+                         f"{logits.dtype}")
+    if not logits.is_contiguous():
+        raise RqHipError(f"{what}: logits must be contiguous (a non-contiguous last dimension or padded rows are not "
+                         f"supported), got strides {logits.stride()}")
+    R, V = logits.shape
+    if not (1 <= V <= BEAM_MAX_V and 1 <= C <= RANK_MAX_K and R in (B, B * C)):
+        raise RqHipError(f"{what}: outside the supported envelope 1 <= V <= {BEAM_MAX_V}, 1 <= C <= {RANK_MAX_K}, "
+                         f"logits rows B or B * C (B={B}, C={C}, V={V}, rows={R})")
+    G = 1 if R == B else C
+    if present is not None:
+        _beam_arg(present, torch.bool, what, "present", (B, C))
+    if prev_lp is not None:
+        _beam_arg(prev_lp, torch.float32, what, "prev_lp", (B, C))
+    for t in (tokens, present, prev_lp):
+        if t is not None and t.device != logits.device:
+            raise RqHipError(f"{what}: every tensor must be on {logits.device}, got {t.device}")
+    dev = logits.device
+    lp = torch.empty((B, C), device=dev, dtype=torch.float32)
+    rank = torch.empty((B, C), device=dev, dtype=torch.int32) if want_rank else None
+    call("rq_score_paths", ptr(logits), float(temperature), ptr(tokens), tokens.stride(0) if B > 1 else 0,
+         tokens.stride(1) if C > 1 else 0, ptr(present), ptr(prev_lp), B, C, V, G, ptr(lp), ptr(rank),
+         stream_handle(dev))
+    return lp, rank

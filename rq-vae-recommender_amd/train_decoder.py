@@ -40,7 +40,7 @@ from modules.model import EncoderDecoderRetrievalModel
 from modules.scheduler.inv_sqrt import InverseSquareRootScheduler
 from modules.tokenizer.semids import SemanticIdTokenizer
 from modules.utils import compute_debug_metrics, parse_config
-from evaluate.metrics import RankAccumulator, TopKAccumulator
+from evaluate.metrics import RankAccumulator, TopKAccumulator, ranked_candidates
 from rqvae_hip import dp, gemm_tuning
 from rqvae_hip import ops as hip_ops
 from rqvae_hip import optim as hip_optim
@@ -125,6 +125,11 @@ EVAL_CONSTRAINED_GENERATION = False
 EVAL_ITEM_METRICS = False
 # recommend() over the corpus minus each user's own history (exclude_items = the batch's item ids). Opt-in.
 EVAL_EXCLUDE_SEEN = False
+# Sampled-negatives metrics of the full eval (needs EVAL_FUSED_GENERATION and the tokenizer as prefix index): N > 0
+# scores, for every user, N corpus indices drawn uniformly (a generator of its own, re-seeded at every eval pass: the
+# same negatives every pass, torch's global generators untouched) plus the next item with model.score_items and adds
+# neg{N}_recall@k / neg{N}_ndcg@k / neg{N}_mrr@k of the next item's rank among the N + 1. 0: off. Opt-in.
+EVAL_SAMPLED_NEGATIVES = 0
 
 
 class _Evaluator:
@@ -202,6 +207,13 @@ class _Evaluator:
         self.metrics.reset()
         self.item_metrics.reset()
         items = EVAL_ITEM_METRICS and EVAL_CONSTRAINED_GENERATION
+        n_neg = 0
+        if EVAL_FUSED_GENERATION and self.model.inference_prefix_index is not None:
+            n_neg = int(EVAL_SAMPLED_NEGATIVES)
+        if n_neg > 0:
+            neg_metrics = RankAccumulator(ks=[1, 5, 10], width=n_neg + 1)
+            neg_gen = torch.Generator().manual_seed(7919 + self.rank)
+            n_corpus = self.tokenizer.cached_ids.shape[0]
         for tok, ids, ids_fut in self._batches(with_ids=True):
             constrained = dict(constrained=True, sample=False) if EVAL_CONSTRAINED_GENERATION else {}
             gen = self.model.generate_next_sem_id(tok, top_k=True, temperature=1, fused=EVAL_FUSED_GENERATION,
@@ -211,11 +223,21 @@ class _Evaluator:
                 rec = self.model.recommend(tok, k=10, incremental=EVAL_INCREMENTAL_GENERATION,
                                            exclude_items=ids if EVAL_EXCLUDE_SEEN else None)
                 self.item_metrics.accumulate(actual=ids_fut, top_k=rec.item_ids)
+            if n_neg > 0:
+                # the target goes in the LAST column: ties go to the lower candidate index, so a negative that shares
+                # the target's sem-ID row (an equal score) ranks before it — a tie counts against the model, not for
+                # it. Users without a target (ids_fut < 0) are skipped by RankAccumulator.
+                neg = torch.randint(0, n_corpus, (ids_fut.shape[0], n_neg), generator=neg_gen).to(ids_fut.device)
+                cand = torch.cat([neg, ids_fut.to(torch.int64).unsqueeze(1)], dim=1)
+                rank = self.model.score_items(tok, cand, incremental=True).rank
+                neg_metrics.accumulate(actual=ids_fut, top_k=ranked_candidates(cand, rank))
         res = self.metrics.reduce()
         self.metrics.reset()
         if items:
             res.update(self.item_metrics.reduce())
             self.item_metrics.reset()
+        if n_neg > 0:
+            res.update({f"neg{n_neg}_{key}": v for key, v in neg_metrics.reduce().items()})
         if self.rank == 0:
             print(res, flush=True)   # the reference prints the Hit@k dictionary as is (train_decoder.py:241)
         return {"full_eval_iter": it, **res}

@@ -13,6 +13,10 @@ per beam, 256 classes, 4 sem-ID tokens; model dims of configs/decoder_amazon.gin
                corpus; and with the beam step
                stubbed out (`model`: the four forwards and the encoder cache repeat alone), which gives the
                beam logic's share of the first two forms;
+  scoring      `recommend`: model.recommend(k=10) (the constrained incremental search); `score`: model.score_items
+               with --score-candidates (100) corpus items per user drawn from the corpus (one BeamDecodeState, one
+               rq_score_paths launch per step); `score_full`: the same with incremental=False (full forwards over
+               B C rows) at --score-full-candidates per user (default: the same C; the JSON states both);
   accumulate   TopKAccumulator.accumulate on the device (one rq_topk_hits launch) and the reference's logic
                (evaluate/metrics.py:15-28, restated below: 24 host reads per batch).
 
@@ -74,7 +78,10 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=2)
-    names = ["unfused", "fused", "incremental", "constrained", "excluded", "model", "acc_device", "acc_reference"]
+    names = ["unfused", "fused", "incremental", "constrained", "excluded", "model", "acc_device", "acc_reference",
+             "recommend", "score", "score_full"]
+    ap.add_argument("--score-candidates", type=int, default=100)
+    ap.add_argument("--score-full-candidates", type=int, default=None)
     ap.add_argument("--only", choices=names)
     ap.add_argument("--forms", type=lambda v: v.split(","), help="comma-separated subset of the forms to alternate")
     args = ap.parse_args()
@@ -127,6 +134,13 @@ def main():
         finally:
             hip_ops.beam_candidates, hip_ops.beam_select = real
 
+    C, C_full = args.score_candidates, args.score_full_candidates or args.score_candidates
+    cands = torch.randint(0, tok.cached_ids.shape[0], (args.batch, max(C, C_full)),
+                          generator=torch.Generator().manual_seed(11)).to(device)
+
+    def score(incremental, c):
+        return model.score_items(batch, cands[:, :c].contiguous(), incremental=incremental)
+
     top = gen(True).sem_ids.contiguous()
     actual = batch.sem_ids_fut.contiguous()
     top[::3, 4] = actual[::3]          # some hits, as a trained model has
@@ -141,7 +155,9 @@ def main():
     forms = {"unfused": lambda: gen(False), "fused": lambda: gen(True),
              "incremental": lambda: gen(True, True), "constrained": gen_constrained, "excluded": gen_excluded,
              "model": gen_model_only,
-             "acc_device": acc_device, "acc_reference": acc_reference}
+             "acc_device": acc_device, "acc_reference": acc_reference,
+             "recommend": lambda: model.recommend(batch, k=10), "score": lambda: score(True, C),
+             "score_full": lambda: score(False, C_full)}
     if args.only:
         forms = {args.only: forms[args.only]}
     elif args.forms:
@@ -160,7 +176,7 @@ def main():
            "median_ms": {n: round(v, 4) for n, v in med.items()},
            "min_max_ms": {n: [round(min(v), 4), round(max(v), 4)] for n, v in times.items() if v}}
     peak = {}
-    for name in ("unfused", "fused", "incremental", "constrained", "excluded"):
+    for name in ("unfused", "fused", "incremental", "constrained", "excluded", "recommend", "score", "score_full"):
         if name in forms and not args.only:   # one more call of each generation form, alone after a peak reset
             torch.cuda.synchronize()
             torch.cuda.reset_peak_memory_stats(device)
@@ -183,6 +199,8 @@ def main():
         out["excluded_vs_constrained"] = dict(delta_ms=round(med["excluded"] - med["constrained"], 4),
                                               constrained_spread_ms=round(spread, 4), history=n_hist,
                                               within_spread=med["excluded"] - med["constrained"] <= spread)
+    if {"score", "score_full"} & set(med):
+        out["score_candidates"] = {n: c for n, c in (("score", C), ("score_full", C_full)) if n in med}
     if {"unfused", "fused", "model"} <= set(med):
         out["beam_logic_share"] = {n: round(1 - med["model"] / med[n], 4) for n in ("unfused", "fused")}
         out["beam_logic_ms"] = {n: round(med[n] - med["model"], 4) for n in ("unfused", "fused")}
