@@ -48,6 +48,72 @@ __device__ __forceinline__ void wave_argmax(float& m, int& idx) {
   }
 }
 
+// The classes a lane owns, ascending: f(j, v) for v = lane + 64 j < V. J > 0: J unrolled steps (j is a constant in
+// each, so a row can live in J registers per lane); J == 0: as many steps as V needs.
+template <int J, typename F>
+__device__ __forceinline__ void for_owned(int V, int lane, F f) {
+  if constexpr (J > 0) {
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+      const int v = lane + 64 * j;
+      if (v < V) f(j, v);
+    }
+  } else {
+    for (int v = lane, j = 0; v < V; v += 64, ++j) f(j, v);
+  }
+}
+
+// Softmax statistics of one row z = logits / T, formed by one wave: the max, then the sum of the other classes'
+// exp(z - max) — the max class (its lowest index) contributes exactly 1, so log p = (z - max) - log1p(rest) keeps full
+// relative precision where one class dominates (log p -> -rest, not log(1.0f) = 0).
+struct RowStats {
+  float m, sum, log_norm;   // max z; 1 + rest; log1p(rest)
+};
+// Where a kernel keeps its row is its own business: load(j, v) gives z of class v, shifted(j, v, m) gives z - m
+// (for_owned's (j, v); each is called once per owned class, loads first). Every kernel's statistics come from this one
+// sequence of operations, so equal rows give equal bits in all of them.
+template <int J, typename Load, typename Shifted>
+__device__ __forceinline__ RowStats row_stats(int V, int lane, Load load, Shifted shifted) {
+  float m = -INFINITY;
+  int am = 0x7fffffff;
+  for_owned<J>(V, lane, [&](int j, int v) {
+    const float z = load(j, v);
+    if (z > m) { m = z; am = v; }
+  });
+  wave_argmax(m, am);
+  float rest = 0.f;
+  for_owned<J>(V, lane, [&](int j, int v) {
+    const float dv = shifted(j, v, m);
+    if (v != am) rest += expf(dv);
+  });
+  rest = group_sum<64>(rest);
+  return {m, rest + 1.0f, log1pf(rest)};
+}
+// log softmax of the class with dv = z - max; -inf where its probability underflows to 0
+__device__ __forceinline__ float log_prob(float dv, const RowStats& st) {
+  const float p = expf(dv) / st.sum;
+  return p == 0.f ? -INFINITY : dv - st.log_norm;
+}
+
+// First index in [lo, hi) of the ascending a[] (global or LDS) whose entry is >= key (lower_bound) / > key
+// (upper_bound); hi if there is none.
+template <typename T, typename I>
+__device__ __forceinline__ I lower_bound(const T* a, I lo, I hi, T key) {
+  while (lo < hi) {
+    const I mid = (lo + hi) >> 1;
+    if (a[mid] < key) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+template <typename T, typename I>
+__device__ __forceinline__ I upper_bound(const T* a, I lo, I hi, T key) {
+  while (lo < hi) {
+    const I mid = (lo + hi) >> 1;
+    if (a[mid] <= key) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
 // LDS per wave: d[Vp] (z - max, the log of the unnormalised probability) then s[Vp] (the scores), Vp = V
 // rounded up to 4. Every lane owns the classes v = lane + 64 j.
 __global__ void __launch_bounds__(256) beam_candidates_kernel(const float* __restrict__ logits,
@@ -64,35 +130,19 @@ __global__ void __launch_bounds__(256) beam_candidates_kernel(const float* __res
   const int64_t row = live ? row_raw : R - 1;   // idle waves repeat the last row (uniform barriers), write nothing
   const float* x = logits + row * V;
 
-  float m = -INFINITY;
-  int am = 0x7fffffff;
-  for (int v = lane; v < V; v += 64) {
-    const float z = x[v] / temperature;
-    d[v] = z;
-    if (z > m) { m = z; am = v; }
-  }
-  wave_argmax(m, am);
-  // sum of the other classes' exp(z - max): the max class contributes exactly 1, so log p = (z - max) -
-  // log1p(rest) keeps full relative precision where one class dominates (log p -> -rest, not log(1.0f) = 0)
-  float rest = 0.f;
-  for (int v = lane; v < V; v += 64) {
-    const float dv = d[v] - m;
-    d[v] = dv;
-    if (v != am) rest += expf(dv);
-  }
-  rest = group_sum<64>(rest);
-  const float sum = rest + 1.0f;
+  const RowStats st = row_stats<0>(
+      V, lane, [&](int, int v) { return d[v] = x[v] / temperature; },
+      [&](int, int v, float m) { return d[v] = d[v] - m; });
   for (int v = lane; v < Vp; v += 64) {
     float sc = -2.0f;   // padding: below every real score
     if (v < V) {
-      const float p = expf(d[v]) / sum;
+      const float p = expf(d[v]) / st.sum;
       sc = noise ? p / noise[row * V + v] : p;
       if (!(sc == sc)) sc = -1.0f;   // NaN (a NaN logit, 0 / 0): ranked last, ties by index — ranks stay a permutation
     }
     s[v] = sc;
   }
   __syncthreads();
-  const float log_norm = log1pf(rest);
   const float4* s4 = reinterpret_cast<const float4*>(s);
   for (int v0 = lane; v0 < V; v0 += 256) {
     float sv[4];
@@ -116,10 +166,8 @@ __global__ void __launch_bounds__(256) beam_candidates_kernel(const float* __res
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       if (live && vi[j] < V && cnt[j] < n_cand) {
-        const float dv = d[vi[j]];
-        const float p = expf(dv) / sum;
         cand_ids[row * n_cand + cnt[j]] = vi[j];
-        cand_lp[row * n_cand + cnt[j]] = p == 0.f ? -INFINITY : dv - log_norm;
+        cand_lp[row * n_cand + cnt[j]] = log_prob(d[vi[j]], st);
       }
     }
   }
@@ -144,28 +192,75 @@ __device__ __forceinline__ bool better(uint32_t ka, int ia, uint32_t kb, int ib)
 
 constexpr int kSelThreads = 256;
 
-// Selection: k rounds of a workgroup argmax. A thread owns the candidates e = tid + 256 j (at most 32) and
-// keeps the best of them cached; a round is one wave reduction, one 4-entry exchange through LDS, and a
-// rescan by the single thread that owned the winner — about k (12 shuffles + 2 barriers + 32 LDS reads)
-// for k = 32, N = 6400, against N log^2 N / 256 ~ 2000 compare-exchange steps with a barrier each for an
-// LDS bitonic sort of 8192 keys.
+// Selection: k rounds of a workgroup argmax over key[0, N) in LDS (0 = absent or taken). A thread owns the
+// candidates e = tid + nthr j and keeps the best of them cached; a round is one wave reduction, an exchange of the
+// waves' winners through LDS (lanes 0..nwave-1 pick them up: a butterfly inside the first MAXW lanes, lane 0
+// broadcasts), and a rescan by the single thread that owned the winner — about k (12 shuffles + the exchange + 2
+// barriers + 32 LDS reads) for k = 32, N = 6400 on 256 threads, against N log^2 N / 256 ~ 2000 compare-exchange
+// steps with a barrier each for an LDS bitonic sort of 8192 keys. out(r, wk, wi) runs on every thread with round r's
+// winner, best first in better()'s order; wk == 0 (block-uniform): no candidate is left, in this round or later.
+// LDS behind key[]: at N rounded up to 4 the waves' keys [MAXW], then their indices [MAXW]. nthr = blockDim.x, a
+// multiple of 64 up to 64 MAXW. A thread reads only its own entries of key[] here: the caller needs a barrier before
+// the call only where other threads wrote them.
+template <int MAXW, typename Out>
+__device__ __forceinline__ void select_rounds(uint32_t* key, int N, int k, int nthr, Out out) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwave = nthr >> 6;
+  uint32_t* w_key = key + (N + 3) / 4 * 4;
+  int* w_idx = reinterpret_cast<int*>(w_key + MAXW);
+  uint32_t best_k;
+  int best_i;
+  auto scan_own = [&] {
+    best_k = 0;
+    best_i = 0x7fffffff;
+    for (int e = tid; e < N; e += nthr) {
+      const uint32_t kk = key[e];
+      if (better(kk, e, best_k, best_i)) { best_k = kk; best_i = e; }
+    }
+  };
+  scan_own();
+  for (int r = 0; r < k; ++r) {
+    uint32_t wk = best_k;
+    int wi = best_i;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+      const uint32_t ok_ = __shfl_xor(wk, o, 64);
+      const int oi = __shfl_xor(wi, o, 64);
+      if (better(ok_, oi, wk, wi)) { wk = ok_; wi = oi; }
+    }
+    if (lane == 0) { w_key[wave] = wk; w_idx[wave] = wi; }
+    __syncthreads();
+    wk = lane < nwave ? w_key[lane] : 0;
+    wi = lane < nwave ? w_idx[lane] : 0x7fffffff;
+#pragma unroll
+    for (int o = MAXW / 2; o >= 1; o >>= 1) {
+      const uint32_t ok_ = __shfl_xor(wk, o, 64);
+      const int oi = __shfl_xor(wi, o, 64);
+      if (better(ok_, oi, wk, wi)) { wk = ok_; wi = oi; }
+    }
+    wk = __shfl(wk, 0, 64);
+    wi = __shfl(wi, 0, 64);
+    __syncthreads();   // w_key / w_idx are rewritten next round
+    if (wk != 0 && tid == (wi % nthr)) {
+      key[wi] = 0;
+      scan_own();
+    }
+    out(r, wk, wi);
+  }
+}
+
 __global__ void __launch_bounds__(kSelThreads) beam_select_kernel(
     const int64_t* __restrict__ cand_ids, const float* __restrict__ cand_lp, const bool* __restrict__ valid,
     const int64_t* __restrict__ keys, int64_t n_keys, int64_t base, int64_t checked,
     const int64_t* __restrict__ parents, const float* __restrict__ parent_lp, int kprev, int n_cand, int P, int k,
     int64_t* __restrict__ out_ids, float* __restrict__ out_lp, int32_t* __restrict__ out_parent) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int N = kprev * n_cand;
-  uint32_t* key = reinterpret_cast<uint32_t*>(smem);   // [N rounded up to 4], then the per-wave exchange
-  uint32_t* w_key = key + (N + 3) / 4 * 4;
-  int* w_idx = reinterpret_cast<int*>(w_key + kSelThreads / 64);
+  uint32_t* key = reinterpret_cast<uint32_t*>(smem);   // [N rounded up to 4], then select_rounds' exchange
   const int64_t b = blockIdx.x;
   const int64_t* cid = cand_ids + b * N;
   const float* clp = cand_lp + b * N;
 
-  uint32_t best_k = 0;
-  int best_i = 0x7fffffff;
   for (int e = tid; e < N; e += kSelThreads) {
     const int par = e / n_cand;
     const int64_t c = cid[e];
@@ -184,48 +279,15 @@ __global__ void __launch_bounds__(kSelThreads) beam_select_kernel(
       }
       q = q * base + c;
       if (ok) {
-        int64_t lo = 0, hi = n_keys;   // first key >= q
-        while (lo < hi) {
-          const int64_t mid = (lo + hi) >> 1;
-          if (keys[mid] < q) lo = mid + 1; else hi = mid;
-        }
-        ok = lo < n_keys && keys[lo] == q;
+        const int64_t at = lower_bound(keys, (int64_t)0, n_keys, q);
+        ok = at < n_keys && keys[at] == q;
       }
     }
     const float sc = ((ok ? 0.0f : -10000.0f) + clp[e]) + (parent_lp ? parent_lp[b * kprev + par] : 0.0f);
-    const uint32_t kk = score_key(sc);
-    key[e] = kk;
-    if (better(kk, e, best_k, best_i)) { best_k = kk; best_i = e; }
+    key[e] = score_key(sc);   // never 0
   }
-  // every thread rescans only its own entries of key[]: no barrier is needed for them
-
-  for (int r = 0; r < k; ++r) {
-    uint32_t wk = best_k;
-    int wi = best_i;
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-      const uint32_t ok_ = __shfl_xor(wk, o, 64);
-      const int oi = __shfl_xor(wi, o, 64);
-      if (better(ok_, oi, wk, wi)) { wk = ok_; wi = oi; }
-    }
-    if (lane == 0) { w_key[wave] = wk; w_idx[wave] = wi; }
-    __syncthreads();
-    wk = w_key[0];
-    wi = w_idx[0];
-#pragma unroll
-    for (int w = 1; w < kSelThreads / 64; ++w)
-      if (better(w_key[w], w_idx[w], wk, wi)) { wk = w_key[w]; wi = w_idx[w]; }
-    __syncthreads();   // w_key / w_idx are rewritten next round
-    // k <= N: a round always finds an untaken candidate (wk != 0, wi < N)
-    if (tid == (wi % kSelThreads)) {
-      key[wi] = 0;
-      best_k = 0;
-      best_i = 0x7fffffff;
-      for (int e = tid; e < N; e += kSelThreads) {
-        const uint32_t kk = key[e];
-        if (better(kk, e, best_k, best_i)) { best_k = kk; best_i = e; }
-      }
-    }
+  // k <= N: every round finds an untaken candidate (wk != 0, wi < N)
+  select_rounds<kSelThreads / 64>(key, N, k, kSelThreads, [&](int r, uint32_t wk, int wi) {
     if (tid == 0) {
       out_lp[b * k + r] = key_score(wk);
       if (out_parent) out_parent[b * k + r] = wi / n_cand;
@@ -234,7 +296,7 @@ __global__ void __launch_bounds__(kSelThreads) beam_select_kernel(
     int64_t* o = out_ids + (b * k + r) * (P + 1);
     if (tid < P) o[tid] = parents[(b * kprev + wi / n_cand) * P + tid];   // P < 64
     if (tid == 0) o[P] = cid[wi];
-  }
+  });
 }
 
 // ------------------------------------------------------------------------------------- expand (trie walk)
@@ -243,12 +305,12 @@ __global__ void __launch_bounds__(kSelThreads) beam_select_kernel(
 // range of level P + 1 that ascends by token — so only real continuations are ever scored.
 //   1. a wave per beam (round robin; 16 waves when kprev > 4, else 4: a beam is a chain of dependent global loads
 //      — node, child range, logits row, tokens — so this phase is latency-bound and more waves are what hides it):
-//      the row's max / lowest argmax and the sum of the other classes' exp(z - max),
-//      with beam_candidates_kernel's lane order (v = lane + 64 j) and wave reductions, so log p is bitwise what
-//      that kernel returns; the same wave then walks the node's children and writes score_key(log p + parent_lp)
-//      to key[j V + token] in LDS (0 = absent: the (beam, token) tie rule is the index order).
-//   2. beam_select_kernel's k rounds of a workgroup argmax over key[]; a round that finds only absent entries
-//      writes a dead row (ids -1, -inf, parent 0, node -1), as do all rounds after it.
+//      the row's statistics by row_stats and log p by log_prob, the functions beam_candidates_kernel uses, so log p
+//      is bitwise what that kernel returns; the same wave then walks the node's children and writes
+//      score_key(log p + parent_lp) to key[j V + token] in LDS (0 = absent: the (beam, token) tie rule is the index
+//      order).
+//   2. select_rounds over key[], as in beam_select_kernel; a round that finds only absent entries writes a dead row
+//      (ids -1, -inf, parent 0, node -1), as do all rounds after it.
 //   3. each winner's node index: a binary search of its parent's child range (<= 12 dependent probes), one
 //      thread per output row after the rounds, so the probes of the k rows overlap instead of stalling a round each.
 // Tables are the caller's contract but never trusted for addressing: node outside [0, n_nodes) is a dead beam,
@@ -269,14 +331,12 @@ __global__ void __launch_bounds__(64 * kExpMaxWaves) beam_expand_kernel(
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nthr = blockDim.x, nwave = nthr >> 6;   // 4 or kExpMaxWaves waves (the host picks by kprev)
   const int N = kprev * V;
-  uint32_t* key = reinterpret_cast<uint32_t*>(smem);   // [N rounded up to 4], then the per-wave exchange
-  uint32_t* w_key = key + (N + 3) / 4 * 4;
-  int* w_idx = reinterpret_cast<int*>(w_key + kExpMaxWaves);
+  uint32_t* key = reinterpret_cast<uint32_t*>(smem);   // [N rounded up to 4], then select_rounds' exchange
+  int* blk = reinterpret_cast<int*>(key + (N + 3) / 4 * 4 + 2 * kExpMaxWaves);   // BLOCKED: [n_blocked <= kBlockedMax]
   const int64_t b = blockIdx.x;
 
   for (int e = tid; e < N; e += nthr) key[e] = 0;
   if constexpr (BLOCKED) {
-    int* blk = w_idx + kExpMaxWaves;   // [n_blocked <= kBlockedMax]
     for (int e = tid; e < n_blocked; e += nthr) blk[e] = blocked[b * n_blocked + e];
   }
   __syncthreads();
@@ -288,89 +348,32 @@ __global__ void __launch_bounds__(64 * kExpMaxWaves) beam_expand_kernel(
     const int hi = min(max(child_off[nd + 1], 0), n_children);
     if (lo >= hi) continue;
     const float* x = logits + (b * kprev + j) * V;
-    float m = -INFINITY;
-    int am = 0x7fffffff;
-    for (int v = lane; v < V; v += 64) {
-      const float z = x[v] / temperature;
-      if (z > m) { m = z; am = v; }
-    }
-    wave_argmax(m, am);
-    float rest = 0.f;
-    for (int v = lane; v < V; v += 64) {
-      const float dv = x[v] / temperature - m;
-      if (v != am) rest += expf(dv);
-    }
-    rest = group_sum<64>(rest);
-    const float sum = rest + 1.0f;
-    const float log_norm = log1pf(rest);
+    const RowStats st = row_stats<0>(
+        V, lane, [&](int, int v) { return x[v] / temperature; },
+        [&](int, int v, float m) { return x[v] / temperature - m; });
     const float plp = parent_lp ? parent_lp[b * kprev + j] : 0.0f;
     for (int c = lo + lane; c < hi; c += 64) {
       const int v = tok[c];
       if (v < 0 || v >= V) continue;   // a class the model cannot generate (e.g. a dedup count >= V)
       if constexpr (BLOCKED) {
-        const int* blk = w_idx + kExpMaxWaves;
-        int l = 0, h = n_blocked;   // first entry >= c
-        while (l < h) {
-          const int mid = (l + h) >> 1;
-          if (blk[mid] < c) l = mid + 1; else h = mid;
-        }
-        if (l < n_blocked && blk[l] == c) continue;   // every leaf below this child is excluded for the user
+        const int at = lower_bound(blk, 0, n_blocked, c);
+        if (at < n_blocked && blk[at] == c) continue;   // every leaf below this child is excluded for the user
       }
-      const float dv = x[v] / temperature - m;
-      const float p = expf(dv) / sum;
-      const float lp = p == 0.f ? -INFINITY : dv - log_norm;
-      key[j * V + v] = score_key(lp + plp);
+      key[j * V + v] = score_key(log_prob(x[v] / temperature - st.m, st) + plp);
     }
   }
   __syncthreads();
 
-  uint32_t best_k = 0;
-  int best_i = 0x7fffffff;
-  for (int e = tid; e < N; e += nthr) {
-    const uint32_t kk = key[e];
-    if (better(kk, e, best_k, best_i)) { best_k = kk; best_i = e; }
-  }
-  for (int r = 0; r < k; ++r) {
-    uint32_t wk = best_k;
-    int wi = best_i;
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-      const uint32_t ok_ = __shfl_xor(wk, o, 64);
-      const int oi = __shfl_xor(wi, o, 64);
-      if (better(ok_, oi, wk, wi)) { wk = ok_; wi = oi; }
-    }
-    if (lane == 0) { w_key[wave] = wk; w_idx[wave] = wi; }
-    __syncthreads();
-    // lanes 0..nwave-1 hold the waves' winners: a butterfly inside the first 16 lanes, lane 0 broadcasts
-    wk = lane < nwave ? w_key[lane] : 0;
-    wi = lane < nwave ? w_idx[lane] : 0x7fffffff;
-#pragma unroll
-    for (int o = kExpMaxWaves / 2; o >= 1; o >>= 1) {
-      const uint32_t ok_ = __shfl_xor(wk, o, 64);
-      const int oi = __shfl_xor(wi, o, 64);
-      if (better(ok_, oi, wk, wi)) { wk = ok_; wi = oi; }
-    }
-    wk = __shfl(wk, 0, 64);
-    wi = __shfl(wi, 0, 64);
-    __syncthreads();   // w_key / w_idx are rewritten next round
+  select_rounds<kExpMaxWaves>(key, N, k, nthr, [&](int r, uint32_t wk, int wi) {
     int64_t* o = out_ids + (b * k + r) * (P + 1);
-    if (wk == 0) {   // no candidate left (block-uniform): a dead row
+    if (wk == 0) {   // no candidate left: a dead row
       if (tid <= P) o[tid] = -1;   // P < 64
       if (tid == 0) {
         out_lp[b * k + r] = -INFINITY;
         out_parent[b * k + r] = 0;
         out_node[b * k + r] = -1;
       }
-      continue;
-    }
-    if (tid == (wi % nthr)) {
-      key[wi] = 0;
-      best_k = 0;
-      best_i = 0x7fffffff;
-      for (int e = tid; e < N; e += nthr) {
-        const uint32_t kk = key[e];
-        if (better(kk, e, best_k, best_i)) { best_k = kk; best_i = e; }
-      }
+      return;
     }
     const int par = wi / V, v = wi - par * V;
     if (tid < P) o[tid] = parents[(b * kprev + par) * P + tid];
@@ -379,30 +382,25 @@ __global__ void __launch_bounds__(64 * kExpMaxWaves) beam_expand_kernel(
       out_lp[b * k + r] = key_score(wk);
       out_parent[b * k + r] = par;
     }
-  }
+  });
   __syncthreads();   // thread 0's rows (global) are visible to the workgroup
   for (int r = tid; r < k; r += nthr) {
     const int v = (int)out_ids[(b * k + r) * (P + 1) + P];
     if (v < 0) continue;   // a dead row: its node is already -1
     // the child of the parent's node that carries token v: the first entry >= v of its ascending range
     const int nd = node ? node[b * kprev + out_parent[b * k + r]] : 0;
-    int lo = min(max(child_off[nd], 0), n_children);
     const int end = min(max(child_off[nd + 1], 0), n_children);
-    int hi = end;
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (tok[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    out_node[b * k + r] = (lo < end && tok[lo] == v) ? lo : -1;   // -1: an unsorted (bad) table
+    const int at = lower_bound(tok, min(max(child_off[nd], 0), n_children), end, v);
+    out_node[b * k + r] = (at < end && tok[at] == v) ? at : -1;   // -1: an unsorted (bad) table
   }
 }
 
 // ------------------------------------------------------------------------------------- score paths
 // Teacher-forced scoring: the log-probability of the token every one of a user's C candidates names at this step, in
-// beam_expand_kernel's arithmetic and lane order (v = lane + 64 j, wave_argmax, group_sum<64>, log1p form), so a
-// candidate's score is bitwise what rq_beam_expand gives the same (row, token, parent score). One workgroup per user.
+// beam_expand_kernel's arithmetic (the same functions: row_stats, log_prob), so a candidate's score is bitwise what
+// rq_beam_expand gives the same (row, token, parent score). One workgroup per user.
 //   G == 1 (step 0): the user's candidates share the BOS row. Every wave forms the row's statistics itself (the same
-//          lane order gives the same bits, so no barrier), then the threads stride over the candidates.
+//          function gives the same bits, so no barrier), then the threads stride over the candidates.
 //   G == C (later steps): a wave per candidate row, round robin. The row is read from memory once, into J registers
 //          per lane (J = 4 / 16 / 64 by V, picked on the host); only the named class is fetched again (one dword).
 // A padding candidate (present[b][c] == 0) gets -inf, its row is never read and its token is never used; a present
@@ -414,40 +412,12 @@ __global__ void __launch_bounds__(64 * kExpMaxWaves) beam_expand_kernel(
 template <int J>
 constexpr int kScoreWaves = J <= 16 ? 16 : 8;
 
-// (max, sum of the other classes' exp(z - max)) of one row, every lane holding z[j] = x[lane + 64 j] / T
+// row_stats of one row that every lane holds in registers, z[j] = x[lane + 64 j] / T: read from memory once
 template <int J>
-__device__ __forceinline__ void score_row_stats(const float* __restrict__ x, int V, float temperature, int lane,
-                                                float& m, float& rest) {
+__device__ __forceinline__ RowStats score_row_stats(const float* __restrict__ x, int V, float temperature, int lane) {
   float z[J];
-  m = -INFINITY;
-  int am = 0x7fffffff;
-#pragma unroll
-  for (int j = 0; j < J; ++j) {
-    const int v = lane + 64 * j;
-    z[j] = -INFINITY;
-    if (v < V) {
-      z[j] = x[v] / temperature;
-      if (z[j] > m) { m = z[j]; am = v; }
-    }
-  }
-  wave_argmax(m, am);
-  rest = 0.f;
-#pragma unroll
-  for (int j = 0; j < J; ++j) {
-    const int v = lane + 64 * j;
-    if (v < V && v != am) rest += expf(z[j] - m);
-  }
-  rest = group_sum<64>(rest);
-}
-
-__device__ __forceinline__ float score_token(const float* __restrict__ x, int v, float temperature, float m,
-                                             float rest, float prev) {
-  const float sum = rest + 1.0f;
-  const float log_norm = log1pf(rest);
-  const float dv = x[v] / temperature - m;
-  const float p = expf(dv) / sum;
-  const float lp = p == 0.f ? -INFINITY : dv - log_norm;
-  return lp + prev;
+  return row_stats<J>(
+      V, lane, [&](int j, int v) { return z[j] = x[v] / temperature; }, [&](int j, int, float m) { return z[j] - m; });
 }
 
 template <int J>
@@ -464,14 +434,13 @@ __global__ void __launch_bounds__(64 * kScoreWaves<J>) score_paths_kernel(
 
   if (G == 1) {
     const float* x = logits + b * V;
-    float m, rest;
-    score_row_stats<J>(x, V, temperature, lane, m, rest);
+    const RowStats st = score_row_stats<J>(x, V, temperature, lane);
     for (int c = tid; c < C; c += nthr) {
       const bool pr = !present || present[bc + c];
       float out = -INFINITY;
       if (pr) {
         const int64_t t = tk[c * tok_sc];
-        if (t >= 0 && t < V) out = score_token(x, (int)t, temperature, m, rest, prev_lp ? prev_lp[bc + c] : 0.0f);
+        if (t >= 0 && t < V) out = log_prob(x[t] / temperature - st.m, st) + (prev_lp ? prev_lp[bc + c] : 0.0f);
       }
       out_lp[bc + c] = out;
       key[c] = pr ? score_key(out) : 0;
@@ -484,9 +453,8 @@ __global__ void __launch_bounds__(64 * kScoreWaves<J>) score_paths_kernel(
         const int64_t t = tk[c * tok_sc];
         if (t >= 0 && t < V) {
           const float* x = logits + (bc + c) * V;
-          float m, rest;
-          score_row_stats<J>(x, V, temperature, lane, m, rest);
-          out = score_token(x, (int)t, temperature, m, rest, prev_lp ? prev_lp[bc + c] : 0.0f);
+          const RowStats st = score_row_stats<J>(x, V, temperature, lane);
+          out = log_prob(x[t] / temperature - st.m, st) + (prev_lp ? prev_lp[bc + c] : 0.0f);
         }
       }
       if (lane == 0) {
@@ -739,15 +707,7 @@ __global__ void __launch_bounds__(kBlkThreads) trie_blocked_kernel(const int64_t
   for (int i = tid; i < Hp; i += kBlkThreads) leaf[i] = res[i];
   lds_sort(leaf, Hp);
   // n = the number of distinct leaves: the first padding entry of the ascending row
-  int n = 0;
-  {
-    int lo = 0, hi = Hp;
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (leaf[mid] < kBlkNone) lo = mid + 1; else hi = mid;
-    }
-    n = lo;
-  }
+  const int n = lower_bound(leaf, 0, Hp, kBlkNone);
 #pragma unroll 1
   for (int q = 0; q < D; ++q) {
     const int32_t* aq = lv.anc[q];
@@ -759,12 +719,7 @@ __global__ void __launch_bounds__(kBlkThreads) trie_blocked_kernel(const int64_t
       int r = kBlkNone;
       const int a = anc[i];
       if (i < n && a >= 0 && a < nq && (i == 0 || anc[i - 1] != a)) {
-        int lo = i + 1, hi = n;   // first entry > a: the end of a's run
-        while (lo < hi) {
-          const int mid = (lo + hi) >> 1;
-          if (anc[mid] <= a) lo = mid + 1; else hi = mid;
-        }
-        if (lo - i == cq[a]) r = a;
+        if (upper_bound(anc, i + 1, n, a) - i == cq[a]) r = a;   // the end of a's run
       }
       res[i] = r;
     }

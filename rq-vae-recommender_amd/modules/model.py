@@ -232,10 +232,10 @@ class EncoderDecoderRetrievalModel(nn.Module):
         computed once and repeated per beam with the HIP jagged kernels (jagged -> padded,
         repeat_interleave, padded -> jagged), as the reference does with torch ops.
         fused=True: each step's softmax, sampling, verification, top-k and parent gather on two HIP
-        launches (_generate_fused); sample=False then takes the most probable candidates instead of a draw.
+        launches (_generate_sampled); sample=False then takes the most probable candidates instead of a draw.
         incremental=True (needs fused=True): the same loop over a BeamDecodeState — the context's cross-attention
         K / V projected once for the B users and only each beam's newest token run through the decoder
-        (_generate_incremental).
+        (_step_logits).
         constrained=True (needs fused=True, an explicit sample=False and `inference_prefix_index`): the beams walk
         the corpus' prefix trie (_generate_constrained), one hip_ops.beam_expand launch per step; with or without
         incremental. Deterministic (no generator draw), every valid continuation is scored (not 200 of them), every
@@ -260,10 +260,8 @@ class EncoderDecoderRetrievalModel(nn.Module):
             generated, log_probas, _ = self._generate_constrained(batch, temperature, 32 if top_k else 1, incremental,
                                                                   exclude_items)
             return GenerationOutput(sem_ids=generated.squeeze(), log_probas=log_probas.squeeze())
-        if incremental:
-            return self._generate_incremental(batch, temperature, top_k, sample)
         if fused:
-            return self._generate_fused(batch, temperature, top_k, sample)
+            return self._generate_sampled(batch, temperature, top_k, sample, incremental)
         B = batch.sem_ids.shape[0]
         generated, log_probas = None, 0
         k = 32 if top_k else 1
@@ -359,7 +357,7 @@ class EncoderDecoderRetrievalModel(nn.Module):
         order, a permutation of 0..C-1. No generator draw, no host read, no beam search.
         incremental=True: one BeamDecodeState — the encoder and the cross-attention K / V once per user, then only the
         newest token of every candidate (every candidate its own ancestor); incremental=False: full forwards over
-        _beams_batch batches (the independent path, as in _generate_constrained)."""
+        _beams_batch batches (the independent path; _step_logits holds both)."""
         assert self.enable_generation, "Model generation is not enabled"
         if sem_ids.dim() != 3 or sem_ids.dtype != torch.int64:
             raise ValueError(f"score_sem_ids: sem_ids must be (B, C, D) int64, got {tuple(sem_ids.shape)} "
@@ -410,29 +408,21 @@ class EncoderDecoderRetrievalModel(nn.Module):
             raise ValueError(f"{what}: need 1 <= C <= {hip_ops.RANK_MAX_K} candidates per user, got {C}")
         sem_ids, present = sem_ids.contiguous(), present.contiguous()
         lp = rank = None
-        cur = TokenizedSeqBatch(user_ids=batch.user_ids, sem_ids=batch.sem_ids, sem_ids_fut=None,
-                                seq_mask=batch.seq_mask, token_type_ids=batch.token_type_ids, token_type_ids_fut=None)
-        with (hip_ops.weight_split_scope(self._gemm_weights(), self._gemm_weight_stacks()) if incremental
-              else contextlib.nullcontext()):
-            state = BeamDecodeState(self, batch) if incremental else None
+        with self._step_logits(batch, incremental) as step:
             own = torch.arange(C, device=sem_ids.device).expand(B, C)
             for i in range(self.sem_id_dim):
-                if not incremental:
-                    logits = self.forward(cur).logits
-                elif i == 0:
-                    logits = state.step()
+                if i == 0:
+                    logits = step()
                 else:   # the BOS rows are every candidate's parent at i == 1; afterwards every candidate is its own
-                    logits = state.step(sem_ids[:, :, i - 1].clamp(0, V - 1), torch.zeros_like(own) if i == 1 else own)
+                    logits = step(sem_ids[:, :, :i].clamp(0, V - 1), torch.zeros_like(own) if i == 1 else own)
                 lp, rank = hip_ops.score_paths(logits.contiguous(), sem_ids[:, :, i], present=present, prev_lp=lp,
                                                temperature=temperature, want_rank=i + 1 == self.sem_id_dim)
-                if not incremental and i + 1 < self.sem_id_dim:
-                    cur = self._beams_batch(cur, sem_ids[:, :, :i + 1].clamp(0, V - 1), i == 0, C)
         return Scores(log_probas=lp, rank=rank)
 
     def _generate_constrained(self, batch: TokenizedSeqBatch, temperature, k: int, incremental: bool,
                               exclude_items: Tensor = None):
-        """_generate_fused's / _generate_incremental's loop with beam_candidates + _beam_verify + beam_select
-        replaced by one hip_ops.beam_expand per step: a beam carries its trie node, the node's children are the
+        """_generate_sampled's loop with beam_candidates + _beam_verify + beam_select replaced by one
+        hip_ops.beam_expand per step: a beam carries its trie node, the node's children are the
         only candidates. Returns (sem_ids (B, k, L+1), log_probas (B, k), the beams' leaf nodes (B, k) int32), dead
         beams as beam_expand marks them. Tokens handed back to the model for dead beams are clamped to 0 (row
         counts stay B * k: static shapes, no negative index reaches an embedding kernel); whatever they compute is
@@ -448,30 +438,18 @@ class EncoderDecoderRetrievalModel(nn.Module):
                                  f"{tuple(exclude_items.shape)}")
             blocked = self.inference_prefix_index.blocked_nodes(exclude_items)
         generated, log_probas, parent, node = None, None, None, None
-        cur = TokenizedSeqBatch(user_ids=batch.user_ids, sem_ids=batch.sem_ids, sem_ids_fut=None,
-                                seq_mask=batch.seq_mask, token_type_ids=batch.token_type_ids, token_type_ids_fut=None)
-        with (hip_ops.weight_split_scope(self._gemm_weights(), self._gemm_weight_stacks()) if incremental
-              else contextlib.nullcontext()):
-            state = BeamDecodeState(self, batch) if incremental else None
+        with self._step_logits(batch, incremental) as step:
             for i in range(self.sem_id_dim):
-                if not incremental:
-                    logits = self.forward(cur).logits
-                elif generated is None:
-                    logits = state.step()
-                else:
-                    logits = state.step(generated[:, :, -1].clamp_min(0), parent)
-                first = generated is None
+                logits = step() if generated is None else step(generated.clamp_min(0), parent)
                 generated, log_probas, parent, node = hip_ops.beam_expand(
                     logits.contiguous(), k, batch=B, child_off=trie.child_off[i], tok=trie.tok[i + 1], node=node,
                     parents=generated, parent_lp=log_probas, temperature=temperature,
                     blocked=None if blocked is None else blocked[i])
-                if not incremental and i + 1 < self.sem_id_dim:
-                    cur = self._beams_batch(cur, generated.clamp_min(0), first, k)
         return generated, log_probas, node
 
     def _beams_batch(self, cur: TokenizedSeqBatch, generated: Tensor, first: bool, k: int) -> TokenizedSeqBatch:
-        """The next full forward's batch for the beams `generated` (B, k, i + 1) of _generate_fused and
-        _generate_constrained: after the first step the users (and the cached encoder output) are repeated per beam."""
+        """The next full forward's batch for the beams `generated` (B, k, i + 1) of _ForwardSteps: after the first
+        step the users (and the cached encoder output) are repeated per beam."""
         if not first:
             nxt = generated.flatten(end_dim=1)
             return TokenizedSeqBatch(user_ids=cur.user_ids, sem_ids=cur.sem_ids, sem_ids_fut=nxt,
@@ -508,52 +486,72 @@ class EncoderDecoderRetrievalModel(nn.Module):
             valid = self.inference_verifier_fn(prefix)
         return dict(valid=valid.to(torch.bool).reshape(-1).contiguous())
 
-    def _generate_incremental(self, batch: TokenizedSeqBatch, temperature, top_k: bool, sample: bool) -> GenerationOutput:
-        """_generate_fused's loop with the model's forwards replaced by BeamDecodeState steps: the same
-        hip_ops.beam_candidates / beam_select calls, verification and noise draws on logits of the same shapes.
-        The select launch also returns each winner's parent beam, which is all the state needs to follow the
-        beams. One weight split for the whole call. Runs under generate_next_sem_id's decorators."""
-        B = batch.sem_ids.shape[0]
-        k = 32 if top_k else 1
-        n_cand = 200 if top_k else 1
-        index = getattr(self, "inference_prefix_index", None)
-        generated, log_probas, parent = None, None, None
-        with hip_ops.weight_split_scope(self._gemm_weights(), self._gemm_weight_stacks()):
-            state = BeamDecodeState(self, batch)
-            for i in range(self.sem_id_dim):
-                logits = (state.step() if generated is None else state.step(generated[:, :, -1], parent)).contiguous()
-                noise = torch.empty_like(logits).exponential_() if sample else None
-                cand_ids, cand_lp = hip_ops.beam_candidates(logits, n_cand, temperature, noise)
-                verify = self._beam_verify(index, i, cand_ids, generated, n_cand)
-                generated, log_probas, parent = hip_ops.beam_select(cand_ids, cand_lp, k, batch=B, parents=generated,
-                                                                    parent_lp=log_probas, return_parent=True, **verify)
-        return GenerationOutput(sem_ids=generated.squeeze(), log_probas=log_probas.squeeze())
+    @contextlib.contextmanager
+    def _step_logits(self, batch: TokenizedSeqBatch, incremental: bool):
+        """The per-step logits of every decoding loop below, as a callable: step() gives the B BOS rows' logits,
+        step(beams, parent) those of the beams (B, k, i) int64 kept so far (tokens the model can embed: clamping is the
+        caller's), parent (B, k) each beam's index among the previous step's. incremental: one BeamDecodeState under
+        one weight split for the whole call; else full forwards (forward opens a weight split per call)."""
+        if incremental:
+            with hip_ops.weight_split_scope(self._gemm_weights(), self._gemm_weight_stacks()):
+                yield _IncrementalSteps(BeamDecodeState(self, batch))
+        else:
+            yield _ForwardSteps(self, batch)
 
-    def _generate_fused(self, batch: TokenizedSeqBatch, temperature, top_k: bool, sample: bool) -> GenerationOutput:
+    def _generate_sampled(self, batch: TokenizedSeqBatch, temperature, top_k: bool, sample: bool,
+                          incremental: bool) -> GenerationOutput:
         """generate_next_sem_id with the per-step beam logic on hip_ops.beam_candidates (softmax, the draw, the
         candidates' log-probabilities) and hip_ops.beam_select (verification, cumulative score, stable top-k,
         parent gather). The draw: the n_cand largest p / e with e ~ Exponential(1) from torch's generator — the
         distribution of torch.multinomial without replacement; sample=False: the n_cand largest p. Prefixes are
         verified in the select kernel against `inference_prefix_index.prefix_table` (the tokenizer's sorted
         packed-prefix keys, incl. its reference_batching quirk) when that attribute is set, else by
-        `inference_verifier_fn` on the materialised prefixes. Runs under generate_next_sem_id's decorators."""
+        `inference_verifier_fn` on the materialised prefixes. incremental: the logits come from BeamDecodeState
+        steps (_step_logits) — the same calls, verification and noise draws on logits of the same shapes — and the
+        select launch also returns each winner's parent beam, which is all the state needs to follow the beams (the
+        full-forward form does not ask for it: no output it never reads). Runs under generate_next_sem_id's
+        decorators."""
         B = batch.sem_ids.shape[0]
         k = 32 if top_k else 1
         n_cand = 200 if top_k else 1
         index = getattr(self, "inference_prefix_index", None)
-        generated, log_probas = None, None
-        cur = TokenizedSeqBatch(user_ids=batch.user_ids, sem_ids=batch.sem_ids, sem_ids_fut=None,
-                                seq_mask=batch.seq_mask, token_type_ids=batch.token_type_ids, token_type_ids_fut=None)
-        for i in range(self.sem_id_dim):
-            logits = self.forward(cur).logits.contiguous()
-            noise = torch.empty_like(logits).exponential_() if sample else None
-            cand_ids, cand_lp = hip_ops.beam_candidates(logits, n_cand, temperature, noise)
-            verify = self._beam_verify(index, i, cand_ids, generated, n_cand)
-            first = generated is None
-            generated, log_probas = hip_ops.beam_select(cand_ids, cand_lp, k, batch=B, parents=generated,
-                                                        parent_lp=log_probas, **verify)
-            cur = self._beams_batch(cur, generated, first, k)
+        generated, log_probas, parent = None, None, ()
+        with self._step_logits(batch, incremental) as step:
+            for i in range(self.sem_id_dim):
+                logits = (step() if generated is None else step(generated, *parent)).contiguous()
+                noise = torch.empty_like(logits).exponential_() if sample else None
+                cand_ids, cand_lp = hip_ops.beam_candidates(logits, n_cand, temperature, noise)
+                verify = self._beam_verify(index, i, cand_ids, generated, n_cand)
+                generated, log_probas, *parent = hip_ops.beam_select(cand_ids, cand_lp, k, batch=B, parents=generated,
+                                                                     parent_lp=log_probas, return_parent=incremental,
+                                                                     **verify)
         return GenerationOutput(sem_ids=generated.squeeze(), log_probas=log_probas.squeeze())
+
+
+class _ForwardSteps:
+    """_step_logits by full forwards: owns the batch, which grows by the beams' tokens. The next batch
+    (_beams_batch) is built when the next step is asked for, so nothing is built after the last token."""
+
+    def __init__(self, model: EncoderDecoderRetrievalModel, batch: TokenizedSeqBatch) -> None:
+        self.model = model
+        self.cur = TokenizedSeqBatch(user_ids=batch.user_ids, sem_ids=batch.sem_ids, sem_ids_fut=None,
+                                     seq_mask=batch.seq_mask, token_type_ids=batch.token_type_ids,
+                                     token_type_ids_fut=None)
+
+    def __call__(self, beams: Tensor = None, parent: Tensor = None) -> Tensor:
+        if beams is not None:   # parent is not needed: a beam's row holds its whole prefix
+            self.cur = self.model._beams_batch(self.cur, beams, self.cur.sem_ids_fut is None, beams.shape[1])
+        return self.model.forward(self.cur).logits
+
+
+class _IncrementalSteps:
+    """_step_logits by a BeamDecodeState: passes on the beams' newest token column and their parent indices."""
+
+    def __init__(self, state: "BeamDecodeState") -> None:
+        self.state = state
+
+    def __call__(self, beams: Tensor = None, parent: Tensor = None) -> Tensor:
+        return self.state.step() if beams is None else self.state.step(beams[:, :, -1], parent)
 
 
 class BeamDecodeState:

@@ -2281,6 +2281,23 @@ def _beam_arg(t, dtype, what, name, shape=None):
     return t
 
 
+def _beam_parents(what, B, kprev, parents, parent_lp, *node) -> int:
+    """P of the beams so far — parents (B, kprev, P) int64, parent_lp (B, kprev) fp32 and, for beam_expand, node
+    (B, kprev) int32: given together or not at all (P = 0)."""
+    given = [t is not None for t in (*node, parents, parent_lp)]
+    if any(given) != all(given):
+        raise RqHipError(f"{what}: {'node, ' if node else ''}parents and parent_lp go together")
+    if parents is None:
+        return 0
+    if parents.dim() != 3 or tuple(parents.shape[:2]) != (B, kprev):
+        raise RqHipError(f"{what}: parents must be (B, kprev, P), got {tuple(parents.shape)}")
+    _beam_arg(parents, torch.int64, what, "parents")
+    _beam_arg(parent_lp, torch.float32, what, "parent_lp", (B, kprev))
+    if node:
+        _beam_arg(node[0], torch.int32, what, "node", (B, kprev))
+    return parents.shape[2]
+
+
 def beam_candidates(logits: torch.Tensor, n_cand: int, temperature: float = 1.0, noise: torch.Tensor = None):
     """(cand_ids (R, n_cand) int64, cand_lp (R, n_cand) fp32): per row of logits (R, V) the n_cand classes of
     largest softmax(logits / temperature) / noise, best first (ties to the lower class), and their log-probabilities
@@ -2320,17 +2337,9 @@ def beam_select(cand_ids: torch.Tensor, cand_lp: torch.Tensor, k: int, *, batch:
     kprev = R // B if B else 1
     _beam_arg(cand_ids, torch.int64, what, "cand_ids")
     _beam_arg(cand_lp, torch.float32, what, "cand_lp", (R, n_cand))
-    if (parents is None) != (parent_lp is None):
-        raise RqHipError(f"{what}: parents and parent_lp go together")
-    P = 0
-    if parents is not None:
-        if parents.dim() != 3 or tuple(parents.shape[:2]) != (B, kprev):
-            raise RqHipError(f"{what}: parents must be (B, kprev, P), got {tuple(parents.shape)}")
-        P = parents.shape[2]
-        _beam_arg(parents, torch.int64, what, "parents")
-        _beam_arg(parent_lp, torch.float32, what, "parent_lp", (B, kprev))
-        if P == 0:
-            parents = parent_lp = None
+    P = _beam_parents(what, B, kprev, parents, parent_lp)
+    if P == 0:
+        parents = parent_lp = None
     if (valid is None) == (keys is None):
         raise RqHipError(f"{what}: give exactly one of valid and keys")
     N = kprev * n_cand
@@ -2342,19 +2351,14 @@ def beam_select(cand_ids: torch.Tensor, cand_lp: torch.Tensor, k: int, *, batch:
         if keys.dim() != 1:
             raise RqHipError(f"{what}: keys must be 1-D")
         _beam_arg(keys, torch.int64, what, "keys")
-    out_ids = torch.empty((B, int(k), P + 1), device=cand_ids.device, dtype=torch.int64)
-    out_lp = torch.empty((B, int(k)), device=cand_ids.device, dtype=torch.float32)
+    outs = (torch.empty((B, int(k), P + 1), device=cand_ids.device, dtype=torch.int64),
+            torch.empty((B, int(k)), device=cand_ids.device, dtype=torch.float32))
     if return_parent:
-        out_parent = torch.empty((B, int(k)), device=cand_ids.device, dtype=torch.int32)
-        call("rq_beam_select_parent", ptr(cand_ids), ptr(cand_lp), ptr(valid), ptr(keys),
-             0 if keys is None else keys.numel(), int(base), B * N if checked is None else int(checked), ptr(parents),
-             ptr(parent_lp), B, kprev, n_cand, P, int(k), ptr(out_ids), ptr(out_lp), ptr(out_parent),
-             stream_handle(cand_ids.device))
-        return out_ids, out_lp, out_parent
-    call("rq_beam_select", ptr(cand_ids), ptr(cand_lp), ptr(valid), ptr(keys), 0 if keys is None else keys.numel(),
-         int(base), B * N if checked is None else int(checked), ptr(parents), ptr(parent_lp), B, kprev, n_cand, P,
-         int(k), ptr(out_ids), ptr(out_lp), stream_handle(cand_ids.device))
-    return out_ids, out_lp
+        outs += (torch.empty((B, int(k)), device=cand_ids.device, dtype=torch.int32),)
+    call("rq_beam_select_parent" if return_parent else "rq_beam_select", ptr(cand_ids), ptr(cand_lp), ptr(valid),
+         ptr(keys), 0 if keys is None else keys.numel(), int(base), B * N if checked is None else int(checked),
+         ptr(parents), ptr(parent_lp), B, kprev, n_cand, P, int(k), *map(ptr, outs), stream_handle(cand_ids.device))
+    return outs
 
 
 BEAM_MAX_V, BEAM_MAX_N = 4096, 8192   # kBeamMaxV, kBeamMaxN (csrc/beam.hip)
@@ -2380,19 +2384,9 @@ def beam_expand(logits: torch.Tensor, k: int, *, batch: int, child_off: torch.Te
     _beam_arg(logits, torch.float32, what, "logits")
     R, V = logits.shape
     kprev = R // B if B else 1
-    given = [t is not None for t in (node, parents, parent_lp)]
-    if any(given) != all(given):
-        raise RqHipError(f"{what}: node, parents and parent_lp go together")
-    P = 0
-    if parents is not None:
-        if parents.dim() != 3 or tuple(parents.shape[:2]) != (B, kprev):
-            raise RqHipError(f"{what}: parents must be (B, kprev, P), got {tuple(parents.shape)}")
-        P = parents.shape[2]
-        _beam_arg(parents, torch.int64, what, "parents")
-        _beam_arg(parent_lp, torch.float32, what, "parent_lp", (B, kprev))
-        _beam_arg(node, torch.int32, what, "node", (B, kprev))
-        if P == 0:
-            raise RqHipError(f"{what}: parents with P == 0; pass node, parents and parent_lp as None on the first step")
+    P = _beam_parents(what, B, kprev, parents, parent_lp, node)
+    if parents is not None and P == 0:
+        raise RqHipError(f"{what}: parents with P == 0; pass node, parents and parent_lp as None on the first step")
     if child_off.dim() != 1 or tok.dim() != 1 or child_off.numel() < 1:
         raise RqHipError(f"{what}: child_off (n_nodes + 1) and tok (n_children) must be 1-D")
     _beam_arg(child_off, torch.int32, what, "child_off")
@@ -2409,15 +2403,10 @@ def beam_expand(logits: torch.Tensor, k: int, *, batch: int, child_off: torch.Te
     out_lp = torch.empty((B, int(k)), device=dev, dtype=torch.float32)
     out_parent = torch.empty((B, int(k)), device=dev, dtype=torch.int32)
     out_node = torch.empty((B, int(k)), device=dev, dtype=torch.int32)
-    if blocked is not None:
-        call("rq_beam_expand_blocked", ptr(logits), float(temperature), ptr(node), ptr(child_off), child_off.numel() - 1,
-             ptr(tok), tok.numel(), ptr(parents), ptr(parent_lp), B, kprev, V, P, int(k), ptr(out_ids), ptr(out_lp),
-             ptr(out_parent), ptr(out_node), ptr(blocked) if blocked.shape[1] else None, blocked.shape[1],
-             stream_handle(dev))
-        return out_ids, out_lp, out_parent, out_node
-    call("rq_beam_expand", ptr(logits), float(temperature), ptr(node), ptr(child_off), child_off.numel() - 1, ptr(tok),
-         tok.numel(), ptr(parents), ptr(parent_lp), B, kprev, V, P, int(k), ptr(out_ids), ptr(out_lp),
-         ptr(out_parent), ptr(out_node), stream_handle(dev))
+    filt = () if blocked is None else (ptr(blocked) if blocked.shape[1] else None, blocked.shape[1])
+    call("rq_beam_expand" if blocked is None else "rq_beam_expand_blocked", ptr(logits), float(temperature), ptr(node),
+         ptr(child_off), child_off.numel() - 1, ptr(tok), tok.numel(), ptr(parents), ptr(parent_lp), B, kprev, V, P,
+         int(k), ptr(out_ids), ptr(out_lp), ptr(out_parent), ptr(out_node), *filt, stream_handle(dev))
     return out_ids, out_lp, out_parent, out_node
 
 

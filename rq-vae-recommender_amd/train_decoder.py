@@ -112,7 +112,7 @@ class _Prefetch:
             self.thread.join(timeout=0.01)
 
 
-# Generation path of the full eval: the fused HIP beam step (modules/model.py _generate_fused) or the reference's
+# Generation path of the full eval: the fused HIP beam step (modules/model.py _generate_sampled) or the reference's
 # torch composition — whichever measured faster at the Amazon eval shape (tools/generation_time.py).
 EVAL_FUSED_GENERATION = True
 # Incremental beam decoding under the fused beam step (modules/model.py BeamDecodeState): opt-in.

@@ -143,7 +143,7 @@ _PARENTS = {1: [2, 2, 0], 2: [1, 0, 1]}   # per user, rolled by its index: a dup
 
 def _teacher_forced_logits(model, batch, k):
     """[(incremental logits, full-forward logits)] per step, the beams chosen by hand. `cur` and the repeated
-    encoder cache are built exactly as _generate_fused builds them."""
+    encoder cache are built exactly as _ForwardSteps (modules/model.py) builds them."""
     from data.schemas import TokenizedSeqBatch
     from modules.model import BeamDecodeState
     from ops.jagged import jagged_to_padded_tensor, padded_to_jagged

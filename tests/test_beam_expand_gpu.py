@@ -300,8 +300,8 @@ def test_beam_expand_refuses_bad_arguments(device):
 # ------------------------------------------------------------------------------------------ generation
 def _reference_constrained(model, batch, corpus, k, T=1.0):
     """The constrained search with the expansion in fp64 on the CPU: logits from the model's own forwards over batches
-    built as _generate_fused builds them (dead beams' tokens clamped to 0). Asserts the separation precondition at
-    every step. Returns ids (B, k, L1), fp64 log-probabilities (B, k) and the leaf nodes (B, k)."""
+    built as _ForwardSteps (modules/model.py) builds them (dead beams' tokens clamped to 0). Asserts the separation
+    precondition at every step. Returns ids (B, k, L1), fp64 log-probabilities (B, k) and the leaf nodes (B, k)."""
     from data.schemas import TokenizedSeqBatch
     from ops.jagged import jagged_to_padded_tensor, padded_to_jagged
     B, L1, V = batch.sem_ids.shape[0], model.sem_id_dim, model.num_embeddings

@@ -55,7 +55,8 @@ def _assert_scores(lp, want, what=""):
 # C, V, G == C, T, strided tokens, prev_lp given
 _KERNEL_CASES = [(1, 5, False, 1.0, False, False), (3, 12, False, 1.0, True, True), (64, 37, True, 1.0, False, True),
                  (65, 64, True, 1.0, True, True), (200, 65, True, 1.0, True, True), (1024, 256, False, 1.0, False, True),
-                 (1024, 256, True, 1.0, False, True), (7, 300, True, 0.7, True, True)]
+                 (1024, 256, True, 1.0, False, True), (7, 300, True, 0.7, True, True),
+                 (70, 1100, True, 1.0, True, True)]   # V > 1024: the 64-registers-per-lane instantiation
 
 
 @pytest.mark.parametrize("C,V,per_cand,T,strided,with_prev", _KERNEL_CASES)
@@ -102,7 +103,7 @@ def test_score_paths_dominant_and_underflow_rows(device):
 
 # ------------------------------------------------------------------------------------------ bitwise vs beam_expand
 @pytest.mark.parametrize("kprev,V,with_parent", [(1, 256, True), (1, 37, False), (1, 300, True), (4, 12, True),
-                                                 (32, 256, True)])
+                                                 (32, 256, True), (1, 1100, True), (6, 1100, True)])
 def test_score_paths_bitwise_equals_beam_expand(device, kprev, V, with_parent):
     """A complete trie level (every node has the children 0..V-1) and k = kprev V: beam_expand returns lp + parent_lp
     of every (beam, token). score_paths fed the same logits and prev_lp = parent_lp returns the same float bits."""
@@ -126,7 +127,10 @@ def test_score_paths_bitwise_equals_beam_expand(device, kprev, V, with_parent):
     plp = beams.get("parent_lp")
     if kprev == 1:   # G == 1: the tokens are a permutation of 0..V-1, every candidate continues the one parent
         tokens = torch.stack([torch.randperm(V, generator=g) for _ in range(B)]).to(device)
-        got = ops.score_paths(logits, tokens, prev_lp=None if plp is None else plp.expand(B, V).contiguous())[0]
+        # a call takes at most RANK_MAX_K candidates per user: a wider permutation goes in column chunks (views)
+        got = torch.cat([ops.score_paths(logits, t, prev_lp=None if plp is None else
+                                         plp.expand(B, t.shape[1]).contiguous())[0]
+                         for t in tokens.split(ops.RANK_MAX_K, dim=1)], dim=1)
         want = table[:, 0].gather(1, tokens)
     else:            # G == C == kprev: one random token per row
         tokens = torch.randint(0, V, (B, kprev), generator=g).to(device)
