@@ -501,6 +501,14 @@ int varlen_attn_bwd(const float* q, int64_t sq, const float* k, int64_t sk, cons
  *   rq_beam_expand (the same kernel body: scores, tie rule, dead rows, out_node, table clamping, limits). An unsorted
  *   row may filter the wrong children but is never read outside [0, n_blocked). 0 <= n_blocked <= 1024; n_blocked == 0
  *   (blocked may be NULL) is rq_beam_expand.
+ * rq_beam_expand_wide / rq_beam_expand_wide_blocked: rq_beam_expand / rq_beam_expand_blocked (the same arguments, one
+ *   launch, one workgroup per batch element) for 1 <= kprev <= 1024 and 1 <= k <= 1024 with V <= 4096 and NO bound on
+ *   kprev V: the candidates are enumerated from the trie, never stored, and the k best are found by an exact radix
+ *   select over (score, beam, token). Wherever both accept a shape the four outputs are bit for bit the same — ids,
+ *   out_lp, parents, nodes, the dead rows after the last candidate, the tie rule, the table clamping; a child range
+ *   longer than V is searched for its first token >= V (a sorted range loses only skipped children), and duplicate
+ *   (beam, token) pairs of a bad table give an unspecified choice among them, never an access outside a buffer.
+ *   kprev > 1024 or k > 1024: -22.
  * rq_trie_blocked_nodes: per user the trie nodes of every level 1..D whose leaves are ALL on the user's exclusion
  *   list, in ONE launch (one workgroup per user). items (B, H) int64 corpus indices, entries outside [0, n_items) are
  *   padding; item_leaf (n_items) int32 = each item's leaf (level-D node; items with equal rows share it, so
@@ -551,6 +559,15 @@ int rq_beam_expand_blocked(const float* logits, float temperature, const int32_t
                            const float* parent_lp, int64_t B, int64_t kprev, int64_t V, int64_t P, int64_t k,
                            int64_t* out_ids, float* out_lp, int32_t* out_parent, int32_t* out_node,
                            const int32_t* blocked, int64_t n_blocked, void* stream);
+int rq_beam_expand_wide(const float* logits, float temperature, const int32_t* node, const int32_t* child_off,
+                        int64_t n_nodes, const int32_t* tok, int64_t n_children, const int64_t* parents,
+                        const float* parent_lp, int64_t B, int64_t kprev, int64_t V, int64_t P, int64_t k,
+                        int64_t* out_ids, float* out_lp, int32_t* out_parent, int32_t* out_node, void* stream);
+int rq_beam_expand_wide_blocked(const float* logits, float temperature, const int32_t* node, const int32_t* child_off,
+                                int64_t n_nodes, const int32_t* tok, int64_t n_children, const int64_t* parents,
+                                const float* parent_lp, int64_t B, int64_t kprev, int64_t V, int64_t P, int64_t k,
+                                int64_t* out_ids, float* out_lp, int32_t* out_parent, int32_t* out_node,
+                                const int32_t* blocked, int64_t n_blocked, void* stream);
 int rq_trie_blocked_nodes(const int64_t* items, int64_t B, int64_t H, const int32_t* item_leaf, int64_t n_items,
                           int64_t n_leaves, const int32_t* const* leaf_anc, const int32_t* const* leaf_count,
                           const int64_t* n_nodes, int64_t D, int32_t* out, void* stream);

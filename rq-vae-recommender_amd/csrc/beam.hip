@@ -12,7 +12,10 @@
 //                           best in stable order, the parent gather and each winner's trie node. A second
 //                           instantiation (BLOCKED) skips the children found in a per-user sorted row of blocked
 //                           nodes (seen-item exclusion).
-//   score_paths_kernel      teacher-forced scoring of caller-named candidates: one workgroup per user, per step the
+//   beam_expand_wide_kernel the same step for up to 1,024 beams in and out, any kprev * V: the candidates are enumerated
+//                           from the trie instead of kept as a dense key array, the k best come from an exact radix
+//                           select and one LDS sort; bit for bit beam_expand_kernel's outputs where both take the shape.
+//   score_paths_kernel     teacher-forced scoring of caller-named candidates: one workgroup per user, per step the
 //                           log-probability of every candidate's token in beam_expand_kernel's arithmetic (bitwise),
 //                           accumulated over the steps; on the last step each candidate's rank among the user's.
 //   trie_blocked_kernel     one workgroup per user: the trie nodes of every level whose leaves are all on the
@@ -392,6 +395,201 @@ __global__ void __launch_bounds__(64 * kExpMaxWaves) beam_expand_kernel(
     const int end = min(max(child_off[nd + 1], 0), n_children);
     const int at = lower_bound(tok, min(max(child_off[nd], 0), n_children), end, v);
     out_node[b * k + r] = (at < end && tok[at] == v) ? at : -1;   // -1: an unsorted (bad) table
+  }
+}
+
+// ------------------------------------------------------------------------------------- expand, wide
+// beam_expand_kernel's step without its dense key[kprev V] array, for up to kWideMax beams in and out: a user's
+// candidates are enumerated, never stored. One workgroup of 16 waves per user.
+//   1. a thread per beam: node -> child range (clamped as above; a range longer than V is cut at its first token >= V,
+//      which a sorted range only ever loses skipped children to, and at V entries, so M <= kprev V fits an int), the
+//      exclusive scan of the ranges' lengths: candidate e of the user's M is child lo[j] + e - off[j] of the beam j
+//      with off[j] <= e < off[j + 1] (a binary search of off[] in LDS; every thread strides over e, whatever the
+//      ranges' lengths). Then a wave per live beam, round robin: row_stats as beam_expand_kernel calls it, kept in LDS.
+//   2. exact radix select of the k-th largest 64-bit key (score_key << 32 | ~(beam V + token): a strict total order
+//      that is better()'s, so there are no ties to resolve): 8 bits per pass from the top through a 256-bin LDS
+//      histogram; every pass enumerates the candidates again and wide_for_candidates forms each key anew from the
+//      stored statistics — one function, the operations of beam_expand_kernel (log_prob(x / T - m) + plp: no
+//      multiply-add pair to contract), for every pass and for the output. The passes stop at the first bin that holds
+//      exactly the keys still needed (with fewer than k candidates: before the first).
+//   3. one more enumeration collects the keys >= the cut with their child index — the winner's trie node, no search —
+//      an LDS bitonic sort puts the <= kWideMax (key, node) pairs in output order, then the rows are written, the
+//      parent prefixes gathered over k rows.
+// Duplicate (beam, token) pairs (a bad table) make equal keys: more than k may pass the cut, the collection stops at
+// kWideMax slots and k rows are written — which of the duplicates is unspecified, every index stays in bounds.
+constexpr int kWideMax = 1024;
+constexpr int kWideThreads = 1024;
+
+struct WideBeams {   // LDS, per beam
+  float m[kWideMax], sum[kWideMax], log_norm[kWideMax], plp[kWideMax];
+  int lo[kWideMax], off[kWideMax + 1];   // first child; candidates before this beam (off[kprev] = M)
+};
+
+// f(key, c) for every candidate of the user that thread tid owns: c its level-(P + 1) node
+template <bool BLOCKED, typename F>
+__device__ __forceinline__ void wide_for_candidates(const WideBeams& s, const int* blk, int n_blocked,
+                                                    const float* __restrict__ x, float temperature,
+                                                    const int32_t* __restrict__ tok, int kprev, int V, F f) {
+  const int M = s.off[kprev];
+  for (int e = threadIdx.x; e < M; e += kWideThreads) {
+    const int j = upper_bound(s.off, 0, kprev, e) - 1;
+    const int c = s.lo[j] + (e - s.off[j]);
+    const int v = tok[c];
+    if (v < 0 || v >= V) continue;
+    if constexpr (BLOCKED) {
+      const int at = lower_bound(blk, 0, n_blocked, c);
+      if (at < n_blocked && blk[at] == c) continue;
+    }
+    const RowStats st = {s.m[j], s.sum[j], s.log_norm[j]};
+    const uint32_t sk = score_key(log_prob(x[(int64_t)j * V + v] / temperature - st.m, st) + s.plp[j]);
+    f(((uint64_t)sk << 32) | (uint32_t)~(uint32_t)(j * V + v), c);
+  }
+}
+
+template <bool BLOCKED>
+__global__ void __launch_bounds__(kWideThreads) beam_expand_wide_kernel(
+    const float* __restrict__ logits, float temperature, const int32_t* __restrict__ node,
+    const int32_t* __restrict__ child_off, int n_nodes, const int32_t* __restrict__ tok, int n_children,
+    const int64_t* __restrict__ parents, const float* __restrict__ parent_lp, int kprev, int V, int P, int k,
+    int64_t* __restrict__ out_ids, float* __restrict__ out_lp, int32_t* __restrict__ out_parent,
+    int32_t* __restrict__ out_node, const int32_t* __restrict__ blocked, int n_blocked) {
+  __shared__ WideBeams s;
+  __shared__ int hist[256];
+  __shared__ uint64_t wkey[kWideMax];
+  __shared__ int wnode[kWideMax];
+  __shared__ int blk[BLOCKED ? kBlockedMax : 1];
+  __shared__ int wsum[kWideThreads / 64];
+  __shared__ int sel[3];   // the cut's bin (-1: none), the keys above it, the keys in it
+  __shared__ int n_won;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t b = blockIdx.x;
+  const float* x = logits + b * kprev * V;
+
+  // 1. child ranges and their scan
+  int lo = 0, cnt = 0;
+  if (tid < kprev) {
+    const int nd = node ? node[b * kprev + tid] : 0;
+    if (nd >= 0 && nd < n_nodes) {
+      lo = min(max(child_off[nd], 0), n_children);
+      int hi = min(max(child_off[nd + 1], 0), n_children);
+      if (hi - lo > V) hi = min(lower_bound(tok, lo, hi, V), lo + V);
+      cnt = max(hi - lo, 0);
+    }
+    s.lo[tid] = lo;
+    s.plp[tid] = parent_lp ? parent_lp[b * kprev + tid] : 0.0f;
+  }
+  if constexpr (BLOCKED) {
+    for (int e = tid; e < n_blocked; e += kWideThreads) blk[e] = blocked[b * n_blocked + e];
+  }
+  int incl = cnt;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int t = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += t;
+  }
+  if (lane == 63) wsum[wave] = incl;
+  if (tid == 0) n_won = 0;
+  __syncthreads();
+  for (int w = 0; w < wave; ++w) incl += wsum[w];
+  if (tid < kprev) s.off[tid] = incl - cnt;
+  if (tid == kWideThreads - 1) s.off[kprev] = incl;   // threads past kprev add nothing: the total
+  __syncthreads();
+  for (int j = wave; j < kprev; j += kWideThreads / 64) {
+    if (s.off[j + 1] == s.off[j]) continue;   // a dead beam or an empty range (wave-uniform)
+    const float* xr = x + (int64_t)j * V;
+    const RowStats st = row_stats<0>(
+        V, lane, [&](int, int v) { return xr[v] / temperature; },
+        [&](int, int v, float m) { return xr[v] / temperature - m; });
+    if (lane == 0) { s.m[j] = st.m; s.sum[j] = st.sum; s.log_norm[j] = st.log_norm; }
+  }
+
+  // 2. the cut: the k-th largest key, or 0 with fewer than k candidates
+  uint64_t cut = 0;
+  int need = k;
+#pragma unroll 1
+  for (int shift = 56; shift >= 0; shift -= 8) {
+    if (tid < 256) hist[tid] = 0;
+    __syncthreads();   // also: the statistics are written
+    const uint64_t above = shift == 56 ? 0 : ~0ull << (shift + 8);   // the digits already fixed
+    wide_for_candidates<BLOCKED>(s, blk, n_blocked, x, temperature, tok, kprev, V, [&](uint64_t key, int) {
+      if ((key & above) == cut) atomicAdd(&hist[(int)(key >> shift) & 255], 1);
+    });
+    __syncthreads();
+    if (wave == 0) {   // lane l: bins 255 - 4 l down to 252 - 4 l; the first bin, from the top, that reaches `need`
+      int h[4], sum = 0;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) sum += h[t] = hist[255 - 4 * lane - t];
+      int run = sum;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(run, o, 64);
+        if (lane >= o) run += t;
+      }
+      const uint64_t reach = __ballot(run >= need);
+      if (!reach) {
+        if (lane == 0) sel[0] = -1;
+      } else if (lane == __ffsll((unsigned long long)reach) - 1) {
+        int acc = run - sum, d = -1, in_d = 0;   // this lane's bins reach `need`
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          if (d < 0 && acc + h[t] >= need) { d = 255 - 4 * lane - t; in_d = h[t]; }
+          if (d < 0) acc += h[t];
+        }
+        sel[0] = d;
+        sel[1] = acc;
+        sel[2] = in_d;
+      }
+    }
+    __syncthreads();
+    if (sel[0] < 0) break;   // fewer than k candidates (first pass only): all of them
+    cut |= (uint64_t)sel[0] << shift;
+    need -= sel[1];
+    if (sel[2] == need) break;   // the bin holds exactly the keys still needed
+  }
+
+  // 3. collect, sort, write
+  wide_for_candidates<BLOCKED>(s, blk, n_blocked, x, temperature, tok, kprev, V, [&](uint64_t key, int c) {
+    if (key >= cut) {
+      const int at = atomicAdd(&n_won, 1);
+      if (at < kWideMax) { wkey[at] = key; wnode[at] = c; }
+    }
+  });
+  __syncthreads();
+  const int n = min(n_won, kWideMax);
+  int n2 = 1;
+  while (n2 < n) n2 <<= 1;
+  if (tid >= n && tid < n2) wkey[tid] = 0;   // below every key
+  __syncthreads();
+  for (int kk = 2; kk <= n2; kk <<= 1) {
+    for (int jj = kk >> 1; jj > 0; jj >>= 1) {
+      const int o = tid ^ jj;
+      if (tid < n2 && o > tid) {
+        const uint64_t a = wkey[tid], c = wkey[o];
+        if ((a < c) == ((tid & kk) == 0)) {   // descending
+          const int na = wnode[tid];
+          wkey[tid] = c; wkey[o] = a;
+          wnode[tid] = wnode[o]; wnode[o] = na;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  const int live = min(n, k);
+  if (tid < k) {
+    const bool dead = tid >= live;
+    const uint64_t key = dead ? 0 : wkey[tid];
+    out_lp[b * k + tid] = dead ? -INFINITY : key_score((uint32_t)(key >> 32));
+    out_parent[b * k + tid] = dead ? 0 : (int)(~(uint32_t)key) / V;
+    out_node[b * k + tid] = dead ? -1 : wnode[tid];
+  }
+  for (int e = tid; e < k * (P + 1); e += kWideThreads) {
+    const int r = e / (P + 1), t = e - r * (P + 1);
+    int64_t id = -1;
+    if (r < live) {
+      const int at = (int)~(uint32_t)wkey[r], par = at / V;
+      id = t < P ? parents[(b * kprev + par) * P + t] : at - par * V;
+    }
+    out_ids[b * k * (P + 1) + e] = id;
   }
 }
 
@@ -793,16 +991,22 @@ int rq_beam_select(const int64_t* cand_ids, const float* cand_lp, const bool* va
                                n_cand, P, k, out_ids, out_lp, nullptr, stream);
 }
 
-static int beam_expand_launch(const char* fn, const float* logits, float temperature, const int32_t* node,
+static int beam_expand_launch(const char* fn, bool wide, const float* logits, float temperature, const int32_t* node,
                               const int32_t* child_off, int64_t n_nodes, const int32_t* tok, int64_t n_children,
                               const int64_t* parents, const float* parent_lp, int64_t B, int64_t kprev, int64_t V,
                               int64_t P, int64_t k, int64_t* out_ids, float* out_lp, int32_t* out_parent,
                               int32_t* out_node, const int32_t* blocked, int64_t n_blocked, void* stream) {
   RQ_CHECK_ARG(B >= 0 && kprev >= 1 && V >= 1 && P >= 0 && P < 64, "%s: bad shape", fn);
-  RQ_CHECK_ARG(V <= rqhip::kBeamMaxV && kprev <= rqhip::kBeamMaxN && kprev * V <= rqhip::kBeamMaxN,
-               "%s: need V <= %d and kprev * V <= %d (kprev=%lld, V=%lld)", fn, rqhip::kBeamMaxV, rqhip::kBeamMaxN,
-               (long long)kprev, (long long)V);
-  RQ_CHECK_ARG(k >= 1 && k <= rqhip::kBeamMaxN, "%s: need 1 <= k <= %d (k=%lld)", fn, rqhip::kBeamMaxN, (long long)k);
+  if (wide) {
+    RQ_CHECK_ARG(V <= rqhip::kBeamMaxV && kprev <= rqhip::kWideMax && k >= 1 && k <= rqhip::kWideMax,
+                 "%s: need V <= %d, kprev <= %d and 1 <= k <= %d (kprev=%lld, V=%lld, k=%lld)", fn, rqhip::kBeamMaxV,
+                 rqhip::kWideMax, rqhip::kWideMax, (long long)kprev, (long long)V, (long long)k);
+  } else {
+    RQ_CHECK_ARG(V <= rqhip::kBeamMaxV && kprev <= rqhip::kBeamMaxN && kprev * V <= rqhip::kBeamMaxN,
+                 "%s: need V <= %d and kprev * V <= %d (kprev=%lld, V=%lld)", fn, rqhip::kBeamMaxV, rqhip::kBeamMaxN,
+                 (long long)kprev, (long long)V);
+    RQ_CHECK_ARG(k >= 1 && k <= rqhip::kBeamMaxN, "%s: need 1 <= k <= %d (k=%lld)", fn, rqhip::kBeamMaxN, (long long)k);
+  }
   RQ_CHECK_ARG(temperature > 0.f && temperature <= 3.0e38f, "%s: temperature must be positive", fn);
   RQ_CHECK_ARG(n_nodes >= 0 && n_nodes < 0x7fffffff && n_children >= 0 && n_children <= 0x7fffffff,
                "%s: bad trie level (n_nodes=%lld, n_children=%lld)", fn, (long long)n_nodes, (long long)n_children);
@@ -815,6 +1019,20 @@ static int beam_expand_launch(const char* fn, const float* logits, float tempera
   RQ_CHECK_ARG(logits && child_off && (tok || n_children == 0) && out_ids && out_lp && out_parent && out_node &&
                    (blocked || n_blocked == 0),
                "%s: null pointer", fn);
+  if (wide) {   // static LDS, one shape of workgroup
+    if (n_blocked > 0) {
+      hipLaunchKernelGGL(rqhip::beam_expand_wide_kernel<true>, dim3((unsigned)B), dim3(rqhip::kWideThreads), 0,
+                         (hipStream_t)stream, logits, temperature, node, child_off, (int)n_nodes, tok, (int)n_children,
+                         parents, parent_lp, (int)kprev, (int)V, (int)P, (int)k, out_ids, out_lp, out_parent, out_node,
+                         blocked, (int)n_blocked);
+    } else {
+      hipLaunchKernelGGL(rqhip::beam_expand_wide_kernel<false>, dim3((unsigned)B), dim3(rqhip::kWideThreads), 0,
+                         (hipStream_t)stream, logits, temperature, node, child_off, (int)n_nodes, tok, (int)n_children,
+                         parents, parent_lp, (int)kprev, (int)V, (int)P, (int)k, out_ids, out_lp, out_parent, out_node,
+                         (const int32_t*)nullptr, 0);
+    }
+    return 0;
+  }
   const int waves = kprev > 4 ? rqhip::kExpMaxWaves : 4;
   const size_t lds = (size_t)((kprev * V + 3) / 4 * 4 + 2 * rqhip::kExpMaxWaves) * sizeof(uint32_t);
   if (n_blocked > 0) {
@@ -835,7 +1053,7 @@ int rq_beam_expand(const float* logits, float temperature, const int32_t* node, 
                    int64_t n_nodes, const int32_t* tok, int64_t n_children, const int64_t* parents,
                    const float* parent_lp, int64_t B, int64_t kprev, int64_t V, int64_t P, int64_t k, int64_t* out_ids,
                    float* out_lp, int32_t* out_parent, int32_t* out_node, void* stream) {
-  const int rc = beam_expand_launch("rq_beam_expand", logits, temperature, node, child_off, n_nodes, tok, n_children,
+  const int rc = beam_expand_launch("rq_beam_expand", false, logits, temperature, node, child_off, n_nodes, tok, n_children,
                                     parents, parent_lp, B, kprev, V, P, k, out_ids, out_lp, out_parent, out_node,
                                     nullptr, 0, stream);
   if (rc != 0 || B == 0) return rc;
@@ -848,11 +1066,36 @@ int rq_beam_expand_blocked(const float* logits, float temperature, const int32_t
                            const float* parent_lp, int64_t B, int64_t kprev, int64_t V, int64_t P, int64_t k,
                            int64_t* out_ids, float* out_lp, int32_t* out_parent, int32_t* out_node,
                            const int32_t* blocked, int64_t n_blocked, void* stream) {
-  const int rc = beam_expand_launch("rq_beam_expand_blocked", logits, temperature, node, child_off, n_nodes, tok,
+  const int rc = beam_expand_launch("rq_beam_expand_blocked", false, logits, temperature, node, child_off, n_nodes, tok,
                                     n_children, parents, parent_lp, B, kprev, V, P, k, out_ids, out_lp, out_parent,
                                     out_node, blocked, n_blocked, stream);
   if (rc != 0 || B == 0) return rc;
   RQ_LAUNCH_CHECK("rq_beam_expand_blocked");
+  return 0;
+}
+
+int rq_beam_expand_wide(const float* logits, float temperature, const int32_t* node, const int32_t* child_off,
+                        int64_t n_nodes, const int32_t* tok, int64_t n_children, const int64_t* parents,
+                        const float* parent_lp, int64_t B, int64_t kprev, int64_t V, int64_t P, int64_t k,
+                        int64_t* out_ids, float* out_lp, int32_t* out_parent, int32_t* out_node, void* stream) {
+  const int rc = beam_expand_launch("rq_beam_expand_wide", true, logits, temperature, node, child_off, n_nodes, tok,
+                                    n_children, parents, parent_lp, B, kprev, V, P, k, out_ids, out_lp, out_parent,
+                                    out_node, nullptr, 0, stream);
+  if (rc != 0 || B == 0) return rc;
+  RQ_LAUNCH_CHECK("rq_beam_expand_wide");
+  return 0;
+}
+
+int rq_beam_expand_wide_blocked(const float* logits, float temperature, const int32_t* node, const int32_t* child_off,
+                                int64_t n_nodes, const int32_t* tok, int64_t n_children, const int64_t* parents,
+                                const float* parent_lp, int64_t B, int64_t kprev, int64_t V, int64_t P, int64_t k,
+                                int64_t* out_ids, float* out_lp, int32_t* out_parent, int32_t* out_node,
+                                const int32_t* blocked, int64_t n_blocked, void* stream) {
+  const int rc = beam_expand_launch("rq_beam_expand_wide_blocked", true, logits, temperature, node, child_off, n_nodes,
+                                    tok, n_children, parents, parent_lp, B, kprev, V, P, k, out_ids, out_lp, out_parent,
+                                    out_node, blocked, n_blocked, stream);
+  if (rc != 0 || B == 0) return rc;
+  RQ_LAUNCH_CHECK("rq_beam_expand_wide_blocked");
   return 0;
 }
 

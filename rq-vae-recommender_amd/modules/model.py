@@ -225,7 +225,7 @@ class EncoderDecoderRetrievalModel(nn.Module):
     def generate_next_sem_id(self, batch: TokenizedSeqBatch, temperature: int = 1, top_k: bool = True, *,
                              fused: bool = False, sample: bool = True,
                              incremental: bool = False, constrained: bool = False,
-                             exclude_items: Tensor = None) -> GenerationOutput:
+                             exclude_items: Tensor = None, beams: int = 32) -> GenerationOutput:
         """Beam-style decoding of the next item's L+1 sem-ID tokens (reference :149-245): per step
         sample 200 candidates per beam from softmax(logits / T), drop prefixes the verifier
         rejects (-10000), keep the top 32 cumulative log-probabilities. The encoder output is
@@ -244,7 +244,15 @@ class EncoderDecoderRetrievalModel(nn.Module):
         exclude_items (needs constrained=True): (B, H <= 1024) int64 corpus indices, -1 as padding (the layout of
         SeqBatch.ids) — the search runs over the corpus without each user's listed rows (an item whose sem-ID row
         duplicates a listed one goes with it): the tokenizer's blocked_nodes mask, built by one launch per call, is
-        applied by beam_expand at every level, so no beam is spent on a prefix that only leads to listed items."""
+        applied by beam_expand at every level, so no beam is spent on a prefix that only leads to listed items.
+        beams (needs constrained=True and top_k=True): the search's width, 1..1024 beams per user instead of 32 — the
+        returned tensors are (B, beams, L+1) / (B, beams); past 32 beams at V = 256 the steps run the wide expand
+        kernel (hip_ops.beam_expand(wide=None)), at 32 they are the launches they were."""
+        if not 1 <= beams <= hip_ops.BEAM_WIDE_MAX:
+            raise ValueError(f"generate_next_sem_id: need 1 <= beams <= {hip_ops.BEAM_WIDE_MAX}, got {beams}")
+        if beams != 32 and not (constrained and top_k):
+            raise ValueError("generate_next_sem_id: beams is the width of the constrained search; it requires "
+                             "constrained=True and top_k=True")
         if incremental and not fused:
             raise ValueError("generate_next_sem_id: incremental=True requires fused=True")
         if exclude_items is not None and not constrained:
@@ -257,8 +265,8 @@ class EncoderDecoderRetrievalModel(nn.Module):
             self._constrained_trie("generate_next_sem_id")
         assert self.enable_generation, "Model generation is not enabled"
         if constrained:
-            generated, log_probas, _ = self._generate_constrained(batch, temperature, 32 if top_k else 1, incremental,
-                                                                  exclude_items)
+            generated, log_probas, _ = self._generate_constrained(batch, temperature, beams if top_k else 1,
+                                                                  incremental, exclude_items)
             return GenerationOutput(sem_ids=generated.squeeze(), log_probas=log_probas.squeeze())
         if fused:
             return self._generate_sampled(batch, temperature, top_k, sample, incremental)
@@ -322,21 +330,21 @@ class EncoderDecoderRetrievalModel(nn.Module):
     @reset_encoder_cache
     @torch.no_grad()
     def recommend(self, batch: TokenizedSeqBatch, k: int = 10, temperature: int = 1,
-                  incremental: bool = True, exclude_items: Tensor = None) -> Recommendation:
-        """The k <= 32 most probable corpus items for every user: the constrained beam search (32 beams,
-        sample=False; generate_next_sem_id(constrained=True)) with each kept beam mapped back to its corpus index
-        through the trie's leaves. A user with fewer than k valid beams gets item id -1 (sem ids -1,
-        log-probability -inf) in the remaining places. exclude_items (B, H) int64, -1 as padding: corpus items (and
+                  incremental: bool = True, exclude_items: Tensor = None, beams: int = 32) -> Recommendation:
+        """The k <= beams most probable corpus items for every user: the constrained beam search (`beams` wide, 32
+        by default and up to 1024; sample=False; generate_next_sem_id(constrained=True, beams=beams)) with each kept
+        beam mapped back to its corpus index through the trie's leaves. A user with fewer than k valid beams gets
+        item id -1 (sem ids -1, log-probability -inf) in the remaining places. exclude_items (B, H) int64, -1 as padding: corpus items (and
         the items sharing their sem-ID rows) that are never returned — the k best of the REMAINING corpus, see
         generate_next_sem_id."""
-        if not 1 <= k <= 32:
-            raise ValueError(f"recommend: need 1 <= k <= 32, got {k}")
+        if not 1 <= k <= beams <= hip_ops.BEAM_WIDE_MAX:
+            raise ValueError(f"recommend: need 1 <= k <= {beams} beams <= {hip_ops.BEAM_WIDE_MAX}, got k = {k}")
         trie = self._constrained_trie("recommend")
         if trie.depth != self.sem_id_dim:
             raise ValueError(f"recommend: the corpus trie has depth {trie.depth}, the model generates {self.sem_id_dim} "
                              "tokens; items are the leaves of the full depth")
         assert self.enable_generation, "Model generation is not enabled"
-        generated, log_probas, node = self._generate_constrained(batch, temperature, 32, incremental, exclude_items)
+        generated, log_probas, node = self._generate_constrained(batch, temperature, beams, incremental, exclude_items)
         node = node[:, :k].long()
         items = torch.where(node >= 0, trie.leaf_item[node.clamp_min(0)], -1)
         return Recommendation(item_ids=items, sem_ids=generated[:, :k], log_probas=log_probas[:, :k])
@@ -444,7 +452,7 @@ class EncoderDecoderRetrievalModel(nn.Module):
                 generated, log_probas, parent, node = hip_ops.beam_expand(
                     logits.contiguous(), k, batch=B, child_off=trie.child_off[i], tok=trie.tok[i + 1], node=node,
                     parents=generated, parent_lp=log_probas, temperature=temperature,
-                    blocked=None if blocked is None else blocked[i])
+                    blocked=None if blocked is None else blocked[i], wide=None)
         return generated, log_probas, node
 
     def _beams_batch(self, cur: TokenizedSeqBatch, generated: Tensor, first: bool, k: int) -> TokenizedSeqBatch:

@@ -8,6 +8,7 @@
   gemm_bf16x3 / gemm_x3 / mlp_chain          fp32 matmuls at 'high' precision (split-bf16 MFMA)
   beam_candidates / beam_select / topk_hits  decoder evaluation: one beam step in two launches, Hit@k counters
   beam_expand                                constrained decoding: one beam step against the corpus' prefix trie, one launch
+                                             (wide=: up to 1,024 beams per user)
   trie_blocked_nodes / rank_hist             seen-item exclusion: a batch's blocked trie nodes of every level, one launch;
                                              first-match rank histogram (Recall / NDCG / MRR), one launch
 
@@ -2362,11 +2363,12 @@ def beam_select(cand_ids: torch.Tensor, cand_lp: torch.Tensor, k: int, *, batch:
 
 
 BEAM_MAX_V, BEAM_MAX_N = 4096, 8192   # kBeamMaxV, kBeamMaxN (csrc/beam.hip)
+BEAM_WIDE_MAX = 1024   # kWideMax (csrc/beam.hip): most beams in / out of the wide kernel
 
 
 def beam_expand(logits: torch.Tensor, k: int, *, batch: int, child_off: torch.Tensor, tok: torch.Tensor,
                 node: torch.Tensor = None, parents: torch.Tensor = None, parent_lp: torch.Tensor = None,
-                temperature: float = 1.0, blocked: torch.Tensor = None):
+                temperature: float = 1.0, blocked: torch.Tensor = None, wide: bool = False):
     """(out_ids (B, k, P + 1) int64, out_lp (B, k) fp32, out_parent (B, k) int32, out_node (B, k) int32): one
     constrained beam step against the corpus' prefix trie (rq_beam_expand) — the k best of the valid continuations of
     the B * kprev beams whose logits (B * kprev, V) these are, with beam_candidates' log-probabilities. child_off
@@ -2375,7 +2377,11 @@ def beam_expand(logits: torch.Tensor, k: int, *, batch: int, child_off: torch.Te
     out_node, out_ids and out_lp — all None on the first step (every beam on the root). With fewer than k valid
     continuations the remaining rows are dead: ids -1, -inf, parent 0, node -1. One launch, no host read.
     blocked (B, n_blocked <= 1024) int32: per batch element the level-(P + 1) nodes that are not candidates, ascending
-    and INT32_MAX-padded — slice P of trie_blocked_nodes' result (rq_beam_expand_blocked); None: no filter."""
+    and INT32_MAX-padded — slice P of trie_blocked_nodes' result (rq_beam_expand_blocked); None: no filter.
+    wide: False (the default: a plain call refuses what it always refused) — that kernel, whose envelope is
+    kprev * V <= 8192; True — rq_beam_expand_wide(_blocked), the same contract and, where both take the shape, the
+    same bits, for kprev <= 1024 and k <= 1024 at any kprev * V; None (what the model's search passes) — the first
+    wherever its envelope holds, so results and timings there are what they were, else the wide one."""
     what = "beam_expand"
     require_gpu(logits, child_off, tok, node, parents, parent_lp, blocked, what=what)
     B = int(batch)
@@ -2391,7 +2397,13 @@ def beam_expand(logits: torch.Tensor, k: int, *, batch: int, child_off: torch.Te
         raise RqHipError(f"{what}: child_off (n_nodes + 1) and tok (n_children) must be 1-D")
     _beam_arg(child_off, torch.int32, what, "child_off")
     _beam_arg(tok, torch.int32, what, "tok")
-    if V < 1 or V > BEAM_MAX_V or kprev * V > BEAM_MAX_N or not 1 <= int(k) <= BEAM_MAX_N:
+    if wide is None:
+        wide = kprev * V > BEAM_MAX_N
+    if wide:
+        if V < 1 or V > BEAM_MAX_V or kprev > BEAM_WIDE_MAX or not 1 <= int(k) <= BEAM_WIDE_MAX:
+            raise RqHipError(f"{what}: outside the wide kernel's envelope V <= {BEAM_MAX_V}, kprev <= {BEAM_WIDE_MAX}, "
+                             f"1 <= k <= {BEAM_WIDE_MAX} (kprev={kprev}, V={V}, k={k})")
+    elif V < 1 or V > BEAM_MAX_V or kprev * V > BEAM_MAX_N or not 1 <= int(k) <= BEAM_MAX_N:
         raise RqHipError(f"{what}: outside the supported envelope V <= {BEAM_MAX_V}, kprev * V <= {BEAM_MAX_N}, "
                          f"1 <= k <= {BEAM_MAX_N} (kprev={kprev}, V={V}, k={k})")
     if blocked is not None:
@@ -2404,9 +2416,18 @@ def beam_expand(logits: torch.Tensor, k: int, *, batch: int, child_off: torch.Te
     out_parent = torch.empty((B, int(k)), device=dev, dtype=torch.int32)
     out_node = torch.empty((B, int(k)), device=dev, dtype=torch.int32)
     filt = () if blocked is None else (ptr(blocked) if blocked.shape[1] else None, blocked.shape[1])
-    call("rq_beam_expand" if blocked is None else "rq_beam_expand_blocked", ptr(logits), float(temperature), ptr(node),
-         ptr(child_off), child_off.numel() - 1, ptr(tok), tok.numel(), ptr(parents), ptr(parent_lp), B, kprev, V, P,
-         int(k), ptr(out_ids), ptr(out_lp), ptr(out_parent), ptr(out_node), *filt, stream_handle(dev))
+    if not wide:
+        call("rq_beam_expand" if blocked is None else "rq_beam_expand_blocked", ptr(logits), float(temperature),
+             ptr(node), ptr(child_off), child_off.numel() - 1, ptr(tok), tok.numel(), ptr(parents), ptr(parent_lp), B,
+             kprev, V, P, int(k), ptr(out_ids), ptr(out_lp), ptr(out_parent), ptr(out_node), *filt, stream_handle(dev))
+    elif blocked is None:
+        call("rq_beam_expand_wide", ptr(logits), float(temperature), ptr(node), ptr(child_off), child_off.numel() - 1,
+             ptr(tok), tok.numel(), ptr(parents), ptr(parent_lp), B, kprev, V, P, int(k), ptr(out_ids), ptr(out_lp),
+             ptr(out_parent), ptr(out_node), stream_handle(dev))
+    else:
+        call("rq_beam_expand_wide_blocked", ptr(logits), float(temperature), ptr(node), ptr(child_off),
+             child_off.numel() - 1, ptr(tok), tok.numel(), ptr(parents), ptr(parent_lp), B, kprev, V, P, int(k),
+             ptr(out_ids), ptr(out_lp), ptr(out_parent), ptr(out_node), filt[0], filt[1], stream_handle(dev))
     return out_ids, out_lp, out_parent, out_node
 
 

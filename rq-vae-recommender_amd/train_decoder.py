@@ -120,9 +120,14 @@ EVAL_INCREMENTAL_GENERATION = False
 # Prefix-trie constrained beam search (modules/model.py _generate_constrained): opt-in. Deterministic and
 # exact, so Hit@k differs from the sampled path's; needs EVAL_FUSED_GENERATION and the tokenizer as prefix index.
 EVAL_CONSTRAINED_GENERATION = False
-# Item-level metrics of the full eval (needs EVAL_CONSTRAINED_GENERATION): model.recommend(k=10) against the next
+# Item-level metrics of the full eval (needs EVAL_CONSTRAINED_GENERATION): model.recommend against the next
 # item's corpus index -> recall@k / ndcg@k / mrr@k (evaluate.metrics.RankAccumulator) next to the Hit@k keys. Opt-in.
 EVAL_ITEM_METRICS = False
+# The item metrics' cut-offs and the width of the search behind them: recommend(k=max(EVAL_ITEM_KS),
+# beams=EVAL_BEAM_WIDTH), 1 <= max(EVAL_ITEM_KS) <= EVAL_BEAM_WIDTH <= 1024 (checked when train() starts). Past 32
+# beams the steps run the wide expand kernel; the defaults are the 32-beam launches and the keys they were.
+EVAL_BEAM_WIDTH = 32
+EVAL_ITEM_KS = (1, 5, 10)
 # recommend() over the corpus minus each user's own history (exclude_items = the batch's item ids). Opt-in.
 EVAL_EXCLUDE_SEEN = False
 # Sampled-negatives metrics of the full eval (needs EVAL_FUSED_GENERATION and the tokenizer as prefix index): N > 0
@@ -145,7 +150,7 @@ class _Evaluator:
         self.partial_every, self.full_every = partial_every, full_every
         self.dataset = None
         self.metrics = TopKAccumulator(ks=[1, 5, 10])
-        self.item_metrics = RankAccumulator(ks=[1, 5, 10])
+        self.item_metrics = RankAccumulator(ks=list(EVAL_ITEM_KS), width=max(32, max(EVAL_ITEM_KS)))
 
     def _batches(self, with_ids: bool = False):
         """The rank's tokenized eval batches; with_ids: (tokenized, item ids (B, N) with -1 padding, next item (B,))."""
@@ -220,8 +225,8 @@ class _Evaluator:
                                                   incremental=EVAL_INCREMENTAL_GENERATION, **constrained)
             self.metrics.accumulate(actual=tok.sem_ids_fut, top_k=gen.sem_ids)
             if items:
-                rec = self.model.recommend(tok, k=10, incremental=EVAL_INCREMENTAL_GENERATION,
-                                           exclude_items=ids if EVAL_EXCLUDE_SEEN else None)
+                rec = self.model.recommend(tok, k=max(EVAL_ITEM_KS), incremental=EVAL_INCREMENTAL_GENERATION,
+                                           exclude_items=ids if EVAL_EXCLUDE_SEEN else None, beams=EVAL_BEAM_WIDTH)
                 self.item_metrics.accumulate(actual=ids_fut, top_k=rec.item_ids)
             if n_neg > 0:
                 # the target goes in the LAST column: ties go to the lower candidate index, so a negative that shares
@@ -270,6 +275,9 @@ def train(iterations=500000, batch_size=64, learning_rate=0.001, weight_decay=0.
                       "(the decoder hot path is split-bf16 'high' MFMA GEMMs + fp32 kernels)", stacklevel=2)
     if push_vae_to_hf:
         raise NotImplementedError("HF hub upload is out of scope (network)")
+    if not 1 <= max(EVAL_ITEM_KS) <= EVAL_BEAM_WIDTH <= hip_ops.BEAM_WIDE_MAX or min(EVAL_ITEM_KS) < 1:
+        raise ValueError(f"EVAL_ITEM_KS = {tuple(EVAL_ITEM_KS)} with EVAL_BEAM_WIDTH = {EVAL_BEAM_WIDTH}: need 1 <= every "
+                         f"cut-off <= the beam width <= {hip_ops.BEAM_WIDE_MAX}")
     LAST_RUN.clear()
     rank, world, local_rank = dp.init_from_env()
     device = torch.device("cuda", local_rank)

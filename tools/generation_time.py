@@ -17,6 +17,10 @@ per beam, 256 classes, 4 sem-ID tokens; model dims of configs/decoder_amazon.gin
                with --score-candidates (100) corpus items per user drawn from the corpus (one BeamDecodeState, one
                rq_score_paths launch per step); `score_full`: the same with incremental=False (full forwards over
                B C rows) at --score-full-candidates per user (default: the same C; the JSON states both);
+               `wide`: model.recommend(k=min(100, beams), beams=--beams (128)) — past 32 beams at V = 256 the steps
+               after the first run rq_beam_expand_wide; `wide_excluded`: the same call with `excluded`'s histories;
+               `recommend_forced`: `recommend` with every beam_expand call handed to the wide kernel (wide=True), so
+               one trace of the two forms times both kernels at the 32-beam shape;
   accumulate   TopKAccumulator.accumulate on the device (one rq_topk_hits launch) and the reference's logic
                (evaluate/metrics.py:15-28, restated below: 24 host reads per batch).
 
@@ -79,9 +83,10 @@ def main():
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=2)
     names = ["unfused", "fused", "incremental", "constrained", "excluded", "model", "acc_device", "acc_reference",
-             "recommend", "score", "score_full"]
+             "recommend", "score", "score_full", "wide", "wide_excluded", "recommend_forced"]
     ap.add_argument("--score-candidates", type=int, default=100)
     ap.add_argument("--score-full-candidates", type=int, default=None)
+    ap.add_argument("--beams", type=int, default=128, help="width of the `wide` / `wide_excluded` search")
     ap.add_argument("--only", choices=names)
     ap.add_argument("--forms", type=lambda v: v.split(","), help="comma-separated subset of the forms to alternate")
     args = ap.parse_args()
@@ -93,6 +98,15 @@ def main():
     model, tok, batch = build(device, args.batch)
     B, k, n_cand, L1 = args.batch, 32, 200, 4
     real = (hip_ops.beam_candidates, hip_ops.beam_select)
+    expand = hip_ops.beam_expand
+
+    def recommend_forced():
+        hip_ops.beam_expand = lambda *a, **kw: expand(*a, **{**kw, "wide": True})
+        try:
+            return model.recommend(batch, k=10)
+        finally:
+            hip_ops.beam_expand = expand
+
     fixed = {}   # the stubbed beam step's outputs, allocated once
 
     def stub_candidates(logits, n, temperature=1.0, noise=None):
@@ -157,7 +171,11 @@ def main():
              "model": gen_model_only,
              "acc_device": acc_device, "acc_reference": acc_reference,
              "recommend": lambda: model.recommend(batch, k=10), "score": lambda: score(True, C),
-             "score_full": lambda: score(False, C_full)}
+             "score_full": lambda: score(False, C_full),
+             "wide": lambda: model.recommend(batch, k=min(100, args.beams), beams=args.beams),
+             "wide_excluded": lambda: model.recommend(batch, k=min(100, args.beams), beams=args.beams,
+                                                      exclude_items=seen),
+             "recommend_forced": recommend_forced}
     if args.only:
         forms = {args.only: forms[args.only]}
     elif args.forms:
@@ -176,7 +194,8 @@ def main():
            "median_ms": {n: round(v, 4) for n, v in med.items()},
            "min_max_ms": {n: [round(min(v), 4), round(max(v), 4)] for n, v in times.items() if v}}
     peak = {}
-    for name in ("unfused", "fused", "incremental", "constrained", "excluded", "recommend", "score", "score_full"):
+    for name in ("unfused", "fused", "incremental", "constrained", "excluded", "recommend", "score", "score_full",
+                 "wide", "wide_excluded", "recommend_forced"):
         if name in forms and not args.only:   # one more call of each generation form, alone after a peak reset
             torch.cuda.synchronize()
             torch.cuda.reset_peak_memory_stats(device)
@@ -199,6 +218,8 @@ def main():
         out["excluded_vs_constrained"] = dict(delta_ms=round(med["excluded"] - med["constrained"], 4),
                                               constrained_spread_ms=round(spread, 4), history=n_hist,
                                               within_spread=med["excluded"] - med["constrained"] <= spread)
+    if {"wide", "wide_excluded"} & set(med):
+        out["wide"] = dict(beams=args.beams, k=min(100, args.beams))
     if {"score", "score_full"} & set(med):
         out["score_candidates"] = {n: c for n, c in (("score", C), ("score_full", C_full)) if n in med}
     if {"unfused", "fused", "model"} <= set(med):
