@@ -5,8 +5,8 @@ import numpy as np
 import pytest
 import torch
 
+import beam_support as bs
 import gen_inputs as gi
-import test_beam_gpu as fused_tests   # the fused-generation fixtures' model / batch / tokenizer builders
 
 pytestmark = pytest.mark.gpu
 
@@ -95,22 +95,22 @@ def test_beam_self_attention_refuses_bad_arguments(device):
 @pytest.mark.parametrize("B,kprev,n_cand,P,k", [(3, 1, 7, 0, 5), (2, 4, 6, 2, 4)])
 def test_beam_select_return_parent(device, B, kprev, n_cand, P, k):
     from rqvae_hip import ops
-    g, cand_ids, cand_lp, parents, parent_lp = fused_tests._select_inputs(B, kprev, n_cand, P, 7 + kprev)
+    g, cand_ids, cand_lp, parents, parent_lp = bs.select_inputs(B, kprev, n_cand, P, 7 + kprev)
     valid = torch.rand(B, kprev * n_cand, generator=g) < 0.7
     score = torch.where(valid, 0.0, -10000.0).float() + cand_lp.reshape(B, -1)
     if parent_lp is not None:
         score = score + parent_lp.repeat_interleave(n_cand, dim=1)
     want_parent = torch.sort(score, dim=-1, descending=True, stable=True).indices[:, :k] // n_cand
     args = (cand_ids.to(device), cand_lp.to(device), k)
-    kw = dict(batch=B, valid=valid.to(device), parents=fused_tests._dev(parents, device),
-              parent_lp=fused_tests._dev(parent_lp, device))
+    kw = dict(batch=B, valid=valid.to(device), parents=bs.dev(parents, device),
+              parent_lp=bs.dev(parent_lp, device))
     plain = ops.beam_select(*args, **kw)
     assert len(plain) == 2
     ids, lp, parent = ops.beam_select(*args, return_parent=True, **kw)
     assert parent.dtype == torch.int32 and parent.shape == (B, k)
     assert torch.equal(parent.cpu().long(), want_parent)
-    fused_tests._assert_select((ids, lp), (plain[0].cpu(), plain[1].cpu()))
-    fused_tests._assert_select((ids, lp), fused_tests._select_reference(cand_ids, cand_lp, valid, parents, parent_lp, B, k))
+    bs.assert_select((ids, lp), (plain[0].cpu(), plain[1].cpu()))
+    bs.assert_select((ids, lp), bs.select_reference(cand_ids, cand_lp, valid, parents, parent_lp, B, k))
 
 
 # ------------------------------------------------------------------------------------------ teacher-forced steps
@@ -119,7 +119,7 @@ def _hd64_case(device):
     items (one seq_mask row all False: that user's context is its user token alone)."""
     from data.schemas import TokenizedSeqBatch
     dims = dict(E=32, A=128, H=2, n_layers=4, K=32, L1=4, n_max=5, seed=77)
-    model = fused_tests._decoder_model(dims, device)
+    model = bs.decoder_model(dims, device)
     g = gi.rng(78)
     B, n_max, L1, K = 4, 5, 4, 32
     mask = np.zeros((B, n_max * L1), bool)
@@ -135,18 +135,15 @@ def _hd64_case(device):
 
 def _golden_case(golden, device):
     z = golden("generation")
-    return fused_tests._decoder_model(z, device, scale_out=float(z["out_proj_scale"])), fused_tests._tokenized(z, device)
+    return bs.decoder_model(z, device, scale_out=float(z["out_proj_scale"])), bs.tokenized(z, device)
 
 
 _PARENTS = {1: [2, 2, 0], 2: [1, 0, 1]}   # per user, rolled by its index: a duplicated parent and a dropped one
 
 
 def _teacher_forced_logits(model, batch, k):
-    """[(incremental logits, full-forward logits)] per step, the beams chosen by hand. `cur` and the repeated
-    encoder cache are built exactly as _ForwardSteps (modules/model.py) builds them."""
-    from data.schemas import TokenizedSeqBatch
+    """[(incremental logits, full-forward logits)] per step, the beams chosen by hand."""
     from modules.model import BeamDecodeState
-    from ops.jagged import jagged_to_padded_tensor, padded_to_jagged
     K, L1, B = model.num_embeddings, model.sem_id_dim, batch.sem_ids.shape[0]
     dev = batch.sem_ids.device
     model.eval()
@@ -156,9 +153,7 @@ def _teacher_forced_logits(model, batch, k):
     try:
         with torch.no_grad():
             state = BeamDecodeState(model, batch)
-            cur = TokenizedSeqBatch(user_ids=batch.user_ids, sem_ids=batch.sem_ids, sem_ids_fut=None,
-                                    seq_mask=batch.seq_mask, token_type_ids=batch.token_type_ids,
-                                    token_type_ids_fut=None)
+            cur = bs.first_batch(batch)
             generated = parent = None
             for i in range(L1):
                 got = state.step() if i == 0 else state.step(generated[:, :, -1], parent)
@@ -170,25 +165,11 @@ def _teacher_forced_logits(model, batch, k):
                 if i == 0:
                     parent = torch.zeros(B, k, dtype=torch.int32, device=dev)
                     generated = tokens.unsqueeze(-1)
-                    nxt = generated.reshape(-1, 1)
-                    enc = model.transformer.cached_enc_output
-                    n_ctx = cur.sem_ids.shape[1] + 1
-                    padded = jagged_to_padded_tensor(enc, n_ctx).repeat_interleave(k, dim=0)
-                    lengths = enc.offsets().diff().repeat_interleave(k)
-                    model.transformer.cached_enc_output = padded_to_jagged(padded.contiguous(), lengths, n_ctx)
-                    cur = TokenizedSeqBatch(user_ids=cur.user_ids.repeat_interleave(k, dim=0),
-                                            sem_ids=cur.sem_ids.repeat_interleave(k, dim=0), sem_ids_fut=nxt,
-                                            token_type_ids_fut=torch.zeros_like(nxt),
-                                            seq_mask=cur.seq_mask.repeat_interleave(k, dim=0),
-                                            token_type_ids=cur.token_type_ids.repeat_interleave(k, dim=0))
                 else:
                     parent = torch.stack([torch.roll(torch.tensor(_PARENTS[i]), b) for b in range(B)]).to(dev, torch.int32)
                     kept = torch.gather(generated, 1, parent.long().unsqueeze(2).expand(-1, -1, i))
                     generated = torch.cat([kept, tokens.unsqueeze(-1)], dim=-1)
-                    nxt = generated.flatten(end_dim=1)
-                    cur = TokenizedSeqBatch(user_ids=cur.user_ids, sem_ids=cur.sem_ids, sem_ids_fut=nxt,
-                                            token_type_ids_fut=torch.arange(nxt.shape[1], device=dev).repeat(nxt.shape[0], 1),
-                                            seq_mask=cur.seq_mask, token_type_ids=cur.token_type_ids)
+                cur = bs.beams_batch(model, cur, generated, i == 0, k)
     finally:
         model.transformer.cached_enc_output = None
     return pairs
@@ -220,9 +201,9 @@ def test_decode_state_step_logits(golden, device, case, precision):
 # ------------------------------------------------------------------------------------------ generation
 def test_incremental_generation_vs_reference(golden, device):
     z = golden("generation")
-    model = fused_tests._decoder_model(z, device, dropout=0.3, scale_out=float(z["out_proj_scale"]))
+    model = bs.decoder_model(z, device, dropout=0.3, scale_out=float(z["out_proj_scale"]))
     model.enable_generation = True
-    batch = fused_tests._tokenized(z, device)
+    batch = bs.tokenized(z, device)
     for top_k, tag in ((True, "topk"), (False, "greedy")):
         g = model.generate_next_sem_id(batch, temperature=1, top_k=top_k, fused=True, sample=False, incremental=True)
         assert np.array_equal(g.sem_ids.cpu().numpy(), z[f"{tag}_sem_ids"]), tag
@@ -233,13 +214,13 @@ def test_incremental_generation_vs_reference(golden, device):
 @pytest.mark.parametrize("reference_batching", [True, False])
 def test_incremental_generation_prefix_index(golden, device, reference_batching):
     z = golden("generation")
-    tok = fused_tests._corpus_tokenizer(golden("tokenizer"), device)
+    tok = bs.corpus_tokenizer(golden("tokenizer"), device)
     tok.reference_batching = reference_batching
-    model = fused_tests._decoder_model(z, device, dropout=0.3, scale_out=float(z["out_proj_scale"]),
+    model = bs.decoder_model(z, device, dropout=0.3, scale_out=float(z["out_proj_scale"]),
                                        verifier=lambda x: tok.exists_prefix(x))
     model.enable_generation = True
     model.inference_prefix_index = tok
-    batch = fused_tests._tokenized(z, device)
+    batch = bs.tokenized(z, device)
     want = model.generate_next_sem_id(batch, temperature=1, top_k=True, fused=True, sample=False)
     got = model.generate_next_sem_id(batch, temperature=1, top_k=True, fused=True, sample=False, incremental=True)
     assert model.training, "train mode restored"
@@ -250,14 +231,14 @@ def test_incremental_generation_prefix_index(golden, device, reference_batching)
 
 def test_incremental_generation_sampled_properties(golden, device):
     z = golden("generation")
-    tok = fused_tests._corpus_tokenizer(golden("tokenizer"), device)
+    tok = bs.corpus_tokenizer(golden("tokenizer"), device)
     tok.reference_batching = False
-    model = fused_tests._decoder_model(z, device, scale_out=float(z["out_proj_scale"]))
+    model = bs.decoder_model(z, device, scale_out=float(z["out_proj_scale"]))
     model.enable_generation = True
     model.inference_prefix_index = tok
     kw = dict(temperature=1, top_k=True, fused=True, sample=True, incremental=True)
     torch.manual_seed(0)
-    out = model.generate_next_sem_id(fused_tests._tokenized(z, device), **kw)
+    out = model.generate_next_sem_id(bs.tokenized(z, device), **kw)
     ids, lp = out.sem_ids.cpu(), out.log_probas.cpu()
     assert ids.shape == (3, 32, 4) and lp.shape == (3, 32)
     assert torch.all(lp[:, :-1] >= lp[:, 1:]), "beams sorted by cumulative log-probability"
@@ -267,6 +248,6 @@ def test_incremental_generation_sampled_properties(golden, device):
     ok = lp > -5000
     assert all(tuple(r) in corpus for r in ids[ok].tolist())
     torch.manual_seed(1)
-    again = model.generate_next_sem_id(fused_tests._tokenized(z, device), **kw)
+    again = model.generate_next_sem_id(bs.tokenized(z, device), **kw)
     assert not torch.equal(again.sem_ids.cpu(), ids) or not ok.any(), "the draw follows torch's generator"
     assert model.training and model.transformer.cached_enc_output is None

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import beam_support as bs
 import gen_inputs as gi
 
 pytestmark = pytest.mark.gpu
@@ -108,48 +109,14 @@ def test_beam_ops_refuse_bad_arguments(device):
 
 
 # ------------------------------------------------------------------------------------------ beam_select
-def _select_reference(cand_ids, cand_lp, valid, parents, parent_lp, B, k):
-    """CPU: the reference's score expression in fp32 and a stable descending sort."""
-    n_cand = cand_ids.shape[1]
-    ids, lp = cand_ids.reshape(B, -1), cand_lp.reshape(B, -1)
-    score = torch.where(valid.reshape(B, -1), 0.0, -10000.0).float() + lp
-    score = score + (parent_lp.repeat_interleave(n_cand, dim=1) if parent_lp is not None else 0.0)
-    top_lp, idx = torch.sort(score, dim=-1, descending=True, stable=True)
-    top_lp, idx = top_lp[:, :k], idx[:, :k]
-    out = torch.gather(ids, 1, idx).unsqueeze(-1)
-    if parents is not None:
-        P = parents.shape[2]
-        out = torch.cat([torch.gather(parents, 1, (idx // n_cand).unsqueeze(-1).expand(-1, -1, P)), out], dim=-1)
-    return out, top_lp
-
-
 _SEL_SHAPES = [(3, 1, 200, 0, 32), (3, 32, 200, 1, 32), (1, 32, 200, 3, 32), (2, 1, 1, 0, 1), (2, 1, 1, 2, 1)]
-
-
-def _select_inputs(B, kprev, n_cand, P, seed, hi=256):
-    g = torch.Generator().manual_seed(seed)
-    cand_ids = torch.randint(0, hi, (B * kprev, n_cand), generator=g)
-    # log-probabilities on a 0.25 grid: plenty of exact ties, which must come out in flat-index order
-    cand_lp = -(torch.randint(0, 40, (B * kprev, n_cand), generator=g).float() / 4)
-    parents = torch.randint(0, hi, (B, kprev, P), generator=g) if P else None
-    parent_lp = -(torch.randint(0, 20, (B, kprev), generator=g).float() / 4) - 0.1 if P else None
-    return g, cand_ids, cand_lp, parents, parent_lp
-
-
-def _dev(t, device):
-    return None if t is None else t.to(device)
-
-
-def _assert_select(got, want):
-    assert torch.equal(got[0].cpu(), want[0]), "out_ids"
-    assert torch.equal(got[1].cpu().view(torch.int32), want[1].view(torch.int32)), "out_lp bitwise"
 
 
 @pytest.mark.parametrize("few_valid", [False, True], ids=["mask", "few-valid"])
 @pytest.mark.parametrize("B,kprev,n_cand,P,k", _SEL_SHAPES)
 def test_beam_select_mask(device, B, kprev, n_cand, P, k, few_valid):
     from rqvae_hip import ops
-    g, cand_ids, cand_lp, parents, parent_lp = _select_inputs(B, kprev, n_cand, P, 50 + kprev + n_cand + P)
+    g, cand_ids, cand_lp, parents, parent_lp = bs.select_inputs(B, kprev, n_cand, P, 50 + kprev + n_cand + P)
     N = kprev * n_cand
     if few_valid:   # fewer than k valid candidates and one log-probability: the -10000 ties fill the beams in order
         valid = torch.zeros(B, N, dtype=torch.bool)
@@ -157,21 +124,11 @@ def test_beam_select_mask(device, B, kprev, n_cand, P, k, few_valid):
         cand_lp = torch.full_like(cand_lp, -1.5)
     else:
         valid = torch.rand(B, N, generator=g) < 0.7
-    want = _select_reference(cand_ids, cand_lp, valid, parents, parent_lp, B, k)
+    want = bs.select_reference(cand_ids, cand_lp, valid, parents, parent_lp, B, k)
     got = ops.beam_select(cand_ids.to(device), cand_lp.to(device), k, batch=B, valid=valid.to(device),
-                          parents=_dev(parents, device), parent_lp=_dev(parent_lp, device))
+                          parents=bs.dev(parents, device), parent_lp=bs.dev(parent_lp, device))
     assert got[0].shape == (B, k, P + 1) and got[1].shape == (B, k)
-    _assert_select(got, want)
-
-
-def _hand_tokenizer(device, seed=3, n=300, hi=12):
-    """A tokenizer whose corpus ids are set by hand (no RQ-VAE pass): n rows of 4 ids in [0, hi)."""
-    from modules.tokenizer.semids import SemanticIdTokenizer
-    tok = SemanticIdTokenizer(input_dim=8, output_dim=4, hidden_dims=[8], codebook_size=hi, n_layers=3, n_cat_feats=0)
-    g = torch.Generator().manual_seed(seed)
-    tok.cached_ids = torch.randint(0, hi, (n, 4), generator=g).to(device)
-    tok.cached_ids[0, 0] = hi - 1   # base = hi
-    return tok
+    bs.assert_select(got, want)
 
 
 @pytest.mark.parametrize("reference_batching", [True, False])
@@ -181,9 +138,9 @@ def test_beam_select_key_table(device, B, kprev, n_cand, P, k, reference_batchin
     prefixes: corpus prefixes, absent prefixes, ids >= base (out of range), and the unchecked tail of
     reference_batching (B N = 600 -> the last 8 candidates; B N = 2 -> every candidate)."""
     from rqvae_hip import ops
-    tok = _hand_tokenizer(device)
+    tok = bs.hand_tokenizer(device)
     tok.reference_batching = reference_batching
-    g, cand_ids, cand_lp, parents, parent_lp = _select_inputs(B, kprev, n_cand, P, 90 + kprev + n_cand + P, hi=14)
+    g, cand_ids, cand_lp, parents, parent_lp = bs.select_inputs(B, kprev, n_cand, P, 90 + kprev + n_cand + P, hi=14)
     N = kprev * n_cand
     corpus = tok.cached_ids.cpu()
     if P:   # most parents are corpus prefixes (so many candidates are valid), some are not, one is out of range
@@ -200,69 +157,22 @@ def test_beam_select_key_table(device, B, kprev, n_cand, P, k, reference_batchin
         assert not valid[B * N // 16 * 16:].any()
     if N > 1:
         assert valid.any() and not valid.all()
-    want = _select_reference(cand_ids, cand_lp, valid, parents, parent_lp, B, k)
+    want = bs.select_reference(cand_ids, cand_lp, valid, parents, parent_lp, B, k)
     keys, base = tok.prefix_table(P + 1)
     assert base == 12 and (N == 1 or (cand_ids >= base).any())
     got = ops.beam_select(cand_ids.to(device), cand_lp.to(device), k, batch=B, keys=keys, base=base,
                           checked=B * N // 16 * 16 if reference_batching else B * N,
-                          parents=_dev(parents, device), parent_lp=_dev(parent_lp, device))
-    _assert_select(got, want)
+                          parents=bs.dev(parents, device), parent_lp=bs.dev(parent_lp, device))
+    bs.assert_select(got, want)
 
 
 # ------------------------------------------------------------------------------------------ fused generation
-def _decoder_model(z, device, dropout=0.0, scale_out=1.0, verifier=gi.prefix_verifier):
-    from modules.model import EncoderDecoderRetrievalModel
-    E, A, H, nl, K, L1, n_max, seed = (int(z[k]) for k in ("E", "A", "H", "n_layers", "K", "L1", "n_max", "seed"))
-    model = EncoderDecoderRetrievalModel(embedding_dim=E, attn_dim=A, dropout=dropout, num_heads=H, n_layers=nl,
-                                         num_embeddings=K, sem_id_dim=L1, inference_verifier_fn=verifier,
-                                         max_pos=n_max * L1, jagged_mode=True)
-    with torch.no_grad():
-        for name, p in model.named_parameters():
-            v = gi.named_param(name, p.shape, seed)
-            p.copy_(torch.from_numpy(v * scale_out if name == "out_proj.weight" else v))
-    return model.to(device)
-
-
-def _tokenized(z, device):
-    from data.schemas import TokenizedSeqBatch
-    keys = ("user_ids", "sem_ids", "sem_ids_fut", "seq_mask", "token_type_ids", "token_type_ids_fut")
-    return TokenizedSeqBatch(**{k: torch.from_numpy(z[k]).to(device) for k in keys})
-
-
-class _Items:
-    def __init__(self, x):
-        self.x = torch.from_numpy(x)
-
-    def __len__(self):
-        return self.x.shape[0]
-
-    def __getitem__(self, idx):
-        from data.schemas import SeqBatch
-        ids = torch.as_tensor(idx).reshape(1, -1)
-        neg = -torch.ones_like(ids[0])
-        return SeqBatch(neg, ids, neg, self.x[idx], neg, torch.ones_like(ids, dtype=torch.bool))
-
-
-def _corpus_tokenizer(z, device):
-    from modules.tokenizer.semids import SemanticIdTokenizer
-    inp, hid, D, K, L, seed = int(z["inp"]), [int(h) for h in z["hidden"]], int(z["D"]), int(z["K"]), int(z["L"]), int(z["seed"])
-    tok = SemanticIdTokenizer(input_dim=inp, output_dim=D, hidden_dims=hid, codebook_size=K, n_layers=L, n_cat_feats=0)
-    st = {f"encoder.mlp.{2 * j}.weight": w for j, w in enumerate(gi.mlp_weights([inp] + hid + [D], seed))}
-    st.update({f"decoder.mlp.{2 * j}.weight": w for j, w in enumerate(gi.mlp_weights([D] + hid[::-1] + [inp], seed + 1))})
-    st.update({f"layers.{l}.embedding.weight": z["codebooks"][l] for l in range(L)})
-    tok.rq_vae.load_state_dict({k: torch.from_numpy(v) for k, v in st.items()})
-    tok = tok.to(device)
-    ids = tok.precompute_corpus_ids(_Items(gi.items(int(z["n_items"]), inp, seed)))
-    assert np.array_equal(ids.cpu().numpy(), z["corpus_ids"])
-    return tok
-
-
 def test_fused_generation_vs_reference(golden, device):
     """fused=True, sample=False is the reference run with torch.multinomial replaced by the top-n stand-in."""
     z = golden("generation")
-    model = _decoder_model(z, device, dropout=0.3, scale_out=float(z["out_proj_scale"]))
+    model = bs.decoder_model(z, device, dropout=0.3, scale_out=float(z["out_proj_scale"]))
     model.enable_generation = True
-    batch = _tokenized(z, device)
+    batch = bs.tokenized(z, device)
     for top_k, tag in ((True, "topk"), (False, "greedy")):
         g = model.generate_next_sem_id(batch, temperature=1, top_k=top_k, fused=True, sample=False)
         assert np.array_equal(g.sem_ids.cpu().numpy(), z[f"{tag}_sem_ids"]), tag
@@ -276,14 +186,14 @@ def test_fused_generation_prefix_index(golden, device, monkeypatch, reference_ba
     sampler): same beams. The model's ids reach 255, the corpus' base is 759 and its first level has 2 codes, so
     the beams hold verified prefixes, rejected ones and (reference_batching, B = 3) a whole unchecked first step."""
     z = golden("generation")
-    tok = _corpus_tokenizer(golden("tokenizer"), device)
+    tok = bs.corpus_tokenizer(golden("tokenizer"), device)
     tok.reference_batching = reference_batching
-    model = _decoder_model(z, device, dropout=0.3, scale_out=float(z["out_proj_scale"]), verifier=lambda x: tok.exists_prefix(x))
+    model = bs.decoder_model(z, device, dropout=0.3, scale_out=float(z["out_proj_scale"]), verifier=lambda x: tok.exists_prefix(x))
     model.enable_generation = True
     n_params = len(list(model.parameters()))
     model.inference_prefix_index = tok
     assert len(list(model.parameters())) == n_params and "inference_prefix_index" not in dict(model.named_modules())
-    batch = _tokenized(z, device)
+    batch = bs.tokenized(z, device)
     with monkeypatch.context() as m:
         m.setattr(torch, "multinomial", gi.topn_multinomial)
         want = model.generate_next_sem_id(batch, temperature=1, top_k=True)
@@ -297,13 +207,13 @@ def test_fused_generation_prefix_index(golden, device, monkeypatch, reference_ba
 
 def test_fused_generation_sampled_properties(golden, device):
     z = golden("generation")
-    tok = _corpus_tokenizer(golden("tokenizer"), device)
+    tok = bs.corpus_tokenizer(golden("tokenizer"), device)
     tok.reference_batching = False
-    model = _decoder_model(z, device, scale_out=float(z["out_proj_scale"]))
+    model = bs.decoder_model(z, device, scale_out=float(z["out_proj_scale"]))
     model.enable_generation = True
     model.inference_prefix_index = tok
     torch.manual_seed(0)
-    out = model.generate_next_sem_id(_tokenized(z, device), temperature=1, top_k=True, fused=True, sample=True)
+    out = model.generate_next_sem_id(bs.tokenized(z, device), temperature=1, top_k=True, fused=True, sample=True)
     ids, lp = out.sem_ids.cpu(), out.log_probas.cpu()
     assert ids.shape == (3, 32, 4) and lp.shape == (3, 32)
     assert torch.all(lp[:, :-1] >= lp[:, 1:]), "beams sorted by cumulative log-probability"
@@ -313,7 +223,7 @@ def test_fused_generation_sampled_properties(golden, device):
     ok = lp > -5000
     assert all(tuple(r) in corpus for r in ids[ok].tolist())
     torch.manual_seed(1)
-    again = model.generate_next_sem_id(_tokenized(z, device), temperature=1, top_k=True, fused=True, sample=True)
+    again = model.generate_next_sem_id(bs.tokenized(z, device), temperature=1, top_k=True, fused=True, sample=True)
     assert not torch.equal(again.sem_ids.cpu(), ids) or not ok.any(), "the draw follows torch's generator"
 
 

@@ -3,30 +3,12 @@ the corpus rows, its cache, and the argument contracts of generate_next_sem_id(c
 import pytest
 import torch
 
-
-def _tokenizer(ids):
-    """A tokenizer whose corpus ids are set by hand (no RQ-VAE pass), on the CPU."""
-    from modules.tokenizer.semids import SemanticIdTokenizer
-    tok = SemanticIdTokenizer(input_dim=8, output_dim=4, hidden_dims=[8], codebook_size=12, n_layers=ids.shape[1] - 1,
-                              n_cat_feats=0)
-    tok.cached_ids = ids
-    return tok
-
-
-def _random_corpus():
-    g = torch.Generator().manual_seed(3)
-    ids = torch.randint(0, 12, (300, 4), generator=g)
-    ids[0, 0] = 11          # base = 12
-    ids[[7, 250]] = ids[3].clone()  # one row three times: its leaf maps to the lowest index
-    return ids
-
-
-_FIVE = torch.tensor([[3, 1, 4, 0], [3, 1, 4, 1], [0, 2, 2, 0], [3, 0, 9, 0], [0, 2, 2, 0]])
+import beam_support as bs
 
 
 def _check_trie(ids):
     """Walk the trie from the root; at every node compare with the rows that share its path."""
-    trie = _tokenizer(ids).prefix_trie()
+    trie = bs.ids_tokenizer(ids).prefix_trie()
     rows = [tuple(r) for r in ids.tolist()]
     D = ids.shape[1]
     assert trie.depth == D and trie.base == int(ids.max()) + 1
@@ -55,18 +37,18 @@ def _check_trie(ids):
 
 
 def test_prefix_trie_matches_brute_force_random_corpus():
-    _check_trie(_random_corpus())
+    _check_trie(bs.random_corpus())
 
 
 def test_prefix_trie_matches_brute_force_five_rows():
-    _check_trie(_FIVE)
-    trie = _tokenizer(_FIVE).prefix_trie()
+    _check_trie(bs.FIVE)
+    trie = bs.ids_tokenizer(bs.FIVE).prefix_trie()
     assert trie.tok[1].tolist() == [0, 3] and trie.child_off[0].tolist() == [0, 2]
     assert trie.tok[4].tolist() == [0, 0, 0, 1] and trie.leaf_item.tolist() == [2, 3, 0, 1]
 
 
 def test_prefix_trie_cache_and_empty_corpus():
-    tok = _tokenizer(_FIVE)
+    tok = bs.ids_tokenizer(bs.FIVE)
     first = tok.prefix_trie()
     assert tok.prefix_trie() is first, "cached"
     tok.reset()
@@ -75,7 +57,7 @@ def test_prefix_trie_cache_and_empty_corpus():
     with pytest.raises(Exception, match="empty cache"):
         tok.prefix_table(1)
     # a new corpus through precompute_corpus_ids (the RQ-VAE pass replaced by fixed ids: CPU-only)
-    tok.cached_ids = _FIVE
+    tok.cached_ids = bs.FIVE
     old = tok.prefix_trie()
 
     class _Out:
@@ -104,7 +86,7 @@ def test_constrained_generation_argument_errors():
     model.enable_generation = True
     with pytest.raises(ValueError, match="requires fused=True"):
         model.generate_next_sem_id(None, top_k=True, sample=False, constrained=True)
-    model.inference_prefix_index = _tokenizer(_FIVE)
+    model.inference_prefix_index = bs.ids_tokenizer(bs.FIVE)
     with pytest.raises(ValueError, match="sample=False"):
         model.generate_next_sem_id(None, top_k=True, fused=True, constrained=True)   # the default is sample=True
     with pytest.raises(ValueError, match="sample=False"):
@@ -114,11 +96,11 @@ def test_constrained_generation_argument_errors():
         model.generate_next_sem_id(None, top_k=True, fused=True, sample=False, constrained=True)
     with pytest.raises(ValueError, match="inference_prefix_index"):
         model.recommend(None)
-    model.inference_prefix_index = _tokenizer(_FIVE)
-    model.inference_prefix_index.cached_ids = _FIVE[:, :1]
+    model.inference_prefix_index = bs.ids_tokenizer(bs.FIVE)
+    model.inference_prefix_index.cached_ids = bs.FIVE[:, :1]
     with pytest.raises(ValueError, match="depth 1"):
         model.generate_next_sem_id(None, top_k=True, fused=True, sample=False, incremental=True, constrained=True)
-    model.inference_prefix_index = _tokenizer(_FIVE)
+    model.inference_prefix_index = bs.ids_tokenizer(bs.FIVE)
     with pytest.raises(ValueError, match="depth 4"):
         model.recommend(None)       # items are the leaves: the model must generate the whole path
     with pytest.raises(ValueError, match="k <= 32"):
@@ -128,6 +110,6 @@ def test_constrained_generation_argument_errors():
 
 def test_beam_expand_refuses_cpu_tensors():
     from rqvae_hip import ops, RqHipError
-    trie = _tokenizer(_FIVE).prefix_trie()
+    trie = bs.ids_tokenizer(bs.FIVE).prefix_trie()
     with pytest.raises(RqHipError, match="no CPU fallback"):
         ops.beam_expand(torch.zeros(2, 12), 3, batch=2, child_off=trie.child_off[0], tok=trie.tok[1])

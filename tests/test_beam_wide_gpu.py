@@ -8,33 +8,9 @@ import numpy as np
 import pytest
 import torch
 
-import test_beam_expand_gpu as expand_tests
-import test_beam_gpu as fused_tests
-import test_beam_wide_host as wide_host
-from test_exclude_gpu import _items_under, _pad
+import beam_support as bs
 
 pytestmark = pytest.mark.gpu
-
-_NONE = 2 ** 31 - 1
-_NAMES = ("out_ids", "out_lp", "out_parent", "out_node")
-
-
-def _expand(device, tok, c, B, k, P, T=1.0, **kw):
-    from rqvae_hip import ops
-    trie = tok.prefix_trie()
-    d = fused_tests._dev
-    return ops.beam_expand(c["logits"].to(device), k, batch=B, child_off=trie.child_off[P], tok=trie.tok[P + 1],
-                           node=d(c["node"], device), parents=d(c["parents"], device),
-                           parent_lp=d(c["parent_lp"], device), temperature=T, **kw)
-
-
-def _assert_same(got, want, what=""):
-    for g, w, name in zip(got, want, _NAMES):
-        g, w = g.cpu(), w.cpu()
-        assert g.dtype == w.dtype and g.shape == w.shape, f"{what}{name}"
-        if name == "out_lp":
-            g, w = g.view(torch.int32), w.view(torch.int32)
-        assert torch.equal(g, w), f"{what}{name}"
 
 
 def _blocked_from(device, tok, corpus, ids, P):
@@ -43,9 +19,9 @@ def _blocked_from(device, tok, corpus, ids, P):
     lists = []
     for b in range(ids.shape[0]):
         paths = [r for r in ids[b].tolist() if r[0] >= 0]
-        l = [i for r in (0, 2) if r < len(paths) for i in _items_under(corpus, paths[r])]
-        lists.append(l + (_items_under(corpus, paths[1])[:1] if len(paths) > 1 else []) + [7 % len(corpus.rows), 1])
-    return tok.blocked_nodes(_pad(lists).to(device))[P].contiguous()
+        l = [i for r in (0, 2) if r < len(paths) for i in bs.items_under(corpus, paths[r])]
+        lists.append(l + (bs.items_under(corpus, paths[1])[:1] if len(paths) > 1 else []) + [7 % len(corpus.rows), 1])
+    return tok.blocked_nodes(bs.pad(lists).to(device))[P].contiguous()
 
 
 _INPUTS = {}
@@ -54,13 +30,13 @@ _INPUTS = {}
 def _inputs(device, name, B, kprev, V, P, seed=0):
     key = (name, B, kprev, V, P, seed)
     if key not in _INPUTS:
-        tok, corpus = expand_tests._tokenizer(name, device)
-        _INPUTS[key] = (tok, corpus, wide_host.wide_inputs(corpus, B, kprev, V, P, 5000 + 31 * kprev + 3 * P + B + seed))
+        tok, corpus = bs.tokenizer(name, device)
+        _INPUTS[key] = (tok, corpus, bs.wide_inputs(corpus, B, kprev, V, P, 5000 + 31 * kprev + 3 * P + B + seed))
     return _INPUTS[key]
 
 
 # ------------------------------------------------------------------------------------------ 1. the same bits
-_DENSE = expand_tests._SHAPES + [("c300", 2, 64, 12, P, 64) for P in (1, 2, 3)]   # 768 keys, more than 32 beams
+_DENSE = bs.SHAPES + [("c300", 2, 64, 12, P, 64) for P in (1, 2, 3)]   # 768 keys, more than 32 beams
 
 
 @pytest.mark.parametrize("with_blocked", [False, True], ids=["plain", "blocked"])
@@ -70,33 +46,28 @@ def test_wide_equals_narrow_bitwise(device, name, B, kprev, V, P, k, T, with_blo
     if kprev == 64:
         tok, corpus, c = _inputs(device, name, B, kprev, V, P)
     else:
-        c = expand_tests._case(device, name, B, kprev, V, P, k, T)
-        tok, corpus = expand_tests._tokenizer(name, device)
+        c = bs.case(device, name, B, kprev, V, P, k, T)
+        tok, corpus = bs.tokenizer(name, device)
     kw = {}
-    plain = _expand(device, tok, c, B, k, P, T, wide=False)
+    plain = bs.expand(device, tok, c, B, k, P, T, wide=False)
     if with_blocked:
         kw["blocked"] = _blocked_from(device, tok, corpus, plain[0].cpu(), P)
-        assert (kw["blocked"] != _NONE).any(1).all(), "every user has blocked nodes"
-    narrow = _expand(device, tok, c, B, k, P, T, wide=False, **kw)
-    wide = _expand(device, tok, c, B, k, P, T, wide=True, **kw)
-    _assert_same(wide, narrow)
+        assert (kw["blocked"] != bs.NONE).any(1).all(), "every user has blocked nodes"
+    narrow = bs.expand(device, tok, c, B, k, P, T, wide=False, **kw)
+    wide = bs.expand(device, tok, c, B, k, P, T, wide=True, **kw)
+    bs.assert_same(wide, narrow)
     if with_blocked:
         assert all(not torch.equal(narrow[0][b], plain[0][b]) for b in range(B)), "the filter removes top candidates"
-    expand_tests._assert_dead_rows(*(t.cpu() for t in wide))
+    bs.assert_dead_rows(*(t.cpu() for t in wide))
 
 
 # ------------------------------------------------------------------------------------------ 2. beyond the old envelope
 def _narrow_step(device, tok, P, T=1.0, blocked=None):
     """chunk_merge's step function on the narrow kernel; `blocked` (B, H) is repeated for every chunk of a user."""
-    from rqvae_hip import ops
-    trie = tok.prefix_trie()
-    d = fused_tests._dev
-
     def expand(logits, node, parents, plp, batch, kprev, k):
         blk = None if blocked is None else blocked.repeat_interleave(batch // blocked.shape[0], dim=0).contiguous()
-        out = ops.beam_expand(logits.to(device), k, batch=batch, child_off=trie.child_off[P], tok=trie.tok[P + 1],
-                              node=d(node, device), parents=d(parents, device), parent_lp=d(plp, device),
-                              temperature=T, blocked=blk, wide=False)
+        out = bs.expand(device, tok, dict(logits=logits, node=node, parents=parents, parent_lp=plp), batch, k, P, T,
+                        blocked=blk, wide=False)
         return tuple(t.cpu() for t in out)
     return expand
 
@@ -111,31 +82,31 @@ _BEYOND = [(2, 96, 1, 96), (2, 96, 2, 96), (2, 96, 3, 96), (2, 96, 2, 7), (2, 40
 def test_wide_equals_chunk_merge(device, B, kprev, P, k):
     V = 256
     tok, corpus, c = _inputs(device, "c3000", B, kprev, V, P)
-    want = wide_host.chunk_merge(_narrow_step(device, tok, P), c, B, kprev, V, P, k)
-    got = _expand(device, tok, c, B, k, P, wide=True)
+    want = bs.chunk_merge(_narrow_step(device, tok, P), c, B, kprev, V, P, k)
+    got = bs.expand(device, tok, c, B, k, P, wide=True)
     n_live = (want[3] >= 0).sum(1).tolist()
     print(f"c3000 B={B} kprev={kprev} P={P} k={k}: live rows per user {n_live}")
-    _assert_same(got, want)
+    bs.assert_same(got, want)
     if P:
         assert (c["node"] < 0).any() and c["node"][0, 0] == c["node"][0, 1], "dead beams; two beams on one node"
-        auto = _expand(device, tok, c, B, k, P, wide=None)   # kprev V > 8192: the dispatch picks the wide kernel
-        _assert_same(auto, want, "wide=None: ")
+        auto = bs.expand(device, tok, c, B, k, P, wide=None)   # kprev V > 8192: the dispatch picks the wide kernel
+        bs.assert_same(auto, want, "wide=None: ")
     if (kprev, k) == (40, 1024) or P == 0:
         assert all(0 < n < k for n in n_live), "k exceeds the candidates: the tail is dead rows"
         assert P or all(n <= V for n in n_live)
-    expand_tests._assert_dead_rows(*(t.cpu() for t in got))
+    bs.assert_dead_rows(*(t.cpu() for t in got))
 
 
 def test_wide_blocked_equals_chunk_merge(device):
     B, kprev, V, P, k = 2, 96, 256, 2, 96
     tok, corpus, c = _inputs(device, "c3000", B, kprev, V, P)
-    plain = wide_host.chunk_merge(_narrow_step(device, tok, P), c, B, kprev, V, P, k)
+    plain = bs.chunk_merge(_narrow_step(device, tok, P), c, B, kprev, V, P, k)
     blocked = _blocked_from(device, tok, corpus, plain[0], P)
-    want = wide_host.chunk_merge(_narrow_step(device, tok, P, blocked=blocked), c, B, kprev, V, P, k)
+    want = bs.chunk_merge(_narrow_step(device, tok, P, blocked=blocked), c, B, kprev, V, P, k)
     assert all(not torch.equal(want[0][b], plain[0][b]) for b in range(B)), "the filter removes top candidates"
-    _assert_same(_expand(device, tok, c, B, k, P, wide=True, blocked=blocked), want)
+    bs.assert_same(bs.expand(device, tok, c, B, k, P, wide=True, blocked=blocked), want)
     rev = blocked.flip(1).contiguous()   # unsorted: the wrong children are filtered, nothing is read outside the row
-    assert _expand(device, tok, c, B, k, P, wide=True, blocked=rev)[0].shape == (B, k, P + 1)
+    assert bs.expand(device, tok, c, B, k, P, wide=True, blocked=rev)[0].shape == (B, k, P + 1)
     torch.cuda.synchronize()
 
 
@@ -146,14 +117,14 @@ def test_wide_ties_two_beams_on_one_node(device, k, flat):
     """Two beams on node (3,) of the five-row corpus with one logits row and one parent score: children 0 and 1 of
     each, so every score appears twice (random row) or four times (all-equal logits) and the cut falls between equal
     keys: the lower beam's copy, then the lower token, is kept."""
-    tok, corpus = expand_tests._tokenizer("c5", device)
+    tok, corpus = bs.tokenizer("c5", device)
     n3 = corpus.index[1][(3,)]
     row = torch.zeros(16) if flat else 2.0 * torch.randn(16, generator=torch.Generator().manual_seed(3))
     c = dict(logits=row.repeat(2, 1), node=torch.tensor([[n3, n3]], dtype=torch.int32),
              parents=torch.tensor([[[3], [3]]]), parent_lp=torch.full((1, 2), -0.5))
-    narrow = _expand(device, tok, c, 1, k, 1, wide=False)
-    wide = _expand(device, tok, c, 1, k, 1, wide=True)
-    _assert_same(wide, narrow)
+    narrow = bs.expand(device, tok, c, 1, k, 1, wide=False)
+    wide = bs.expand(device, tok, c, 1, k, 1, wide=True)
+    bs.assert_same(wide, narrow)
     ids, lp, parent, node = (t.cpu() for t in wide)
     first = 0 if flat or row[0] >= row[1] else 1
     order = ([(0, 0), (0, 1), (1, 0), (1, 1)] if flat else
@@ -174,18 +145,18 @@ def test_wide_ties_across_chunks(device, k):
         c[key][:, 48:] = c[key][:, :48]
     x = c["logits"].view(B, kprev, V)
     x[:, 48:] = x[:, :48]
-    want = wide_host.chunk_merge(_narrow_step(device, tok, P), c, B, kprev, V, P, k)
+    want = bs.chunk_merge(_narrow_step(device, tok, P), c, B, kprev, V, P, k)
     assert all(want[2][b, 1] == want[2][b, 0] + 48 and want[1][b, 0] == want[1][b, 1] for b in range(B)), "pairs"
-    _assert_same(_expand(device, tok, c, B, k, P, wide=True), want)
+    bs.assert_same(bs.expand(device, tok, c, B, k, P, wide=True), want)
 
 
 def test_wide_underflow_ranks_above_dead_rows(device):
-    tok, corpus = expand_tests._tokenizer("c5", device)
+    tok, corpus = bs.tokenizer("c5", device)
     x = torch.full((1, 16), -200.0)
     x[0, 3] = 0.0
     c = dict(logits=x, node=None, parents=None, parent_lp=None)
-    wide = _expand(device, tok, c, 1, 4, 0, wide=True)
-    _assert_same(wide, _expand(device, tok, c, 1, 4, 0, wide=False))
+    wide = bs.expand(device, tok, c, 1, 4, 0, wide=True)
+    bs.assert_same(wide, bs.expand(device, tok, c, 1, 4, 0, wide=False))
     ids, lp, parent, node = (t.cpu() for t in wide)
     assert ids[0].tolist() == [[3], [0], [-1], [-1]] and lp[0, 0] == 0 and torch.isneginf(lp[0, 1:]).all()
     assert node[0].tolist() == [corpus.index[1][(3,)], corpus.index[1][(0,)], -1, -1] and parent[0].tolist() == [0] * 4
@@ -195,9 +166,9 @@ def test_wide_underflow_ranks_above_dead_rows(device):
 @pytest.mark.parametrize("P", [1, 2])
 def test_wide_vs_fp64(device, P):
     name, B, kprev, V, k, T = "c3000", 2, 96, 256, 40, 1.0
-    c = expand_tests._case(device, name, B, kprev, V, P, k, T)   # its separation rule and redraw loop
+    c = bs.case(device, name, B, kprev, V, P, k, T)   # its separation rule and redraw loop
     want_ids, want_lp, want_parent, want_node, scores = c["ref"]
-    ids, lp, parent, node = (t.cpu() for t in _expand(device, c["tok"], c, B, k, P, T, wide=True))
+    ids, lp, parent, node = (t.cpu() for t in bs.expand(device, c["tok"], c, B, k, P, T, wide=True))
     print(f"{name} B={B} kprev={kprev} V={V} P={P} k={k}: candidates per user {[len(s) for s in scores]}, "
           f"max rel lp err {float(((lp.double() - want_lp).abs() / want_lp.abs())[want_node >= 0].max()):.3e}")
     assert torch.equal(ids, want_ids), "out_ids"
@@ -223,7 +194,7 @@ def test_wide_bad_tables_stay_in_bounds(device):
     args = dict(batch=1, child_off=child_off, tok=tok, node=node, parents=parents.to(device), parent_lp=plp.to(device))
     wide = ops.beam_expand(logits.to(device), k, wide=True, **args)
     torch.cuda.synchronize()
-    _assert_same(wide, ops.beam_expand(logits.to(device), k, wide=False, **args))
+    bs.assert_same(wide, ops.beam_expand(logits.to(device), k, wide=False, **args))
     ids, lp, parent, out_node = (t.cpu() for t in wide)
     assert sorted(zip(parent[0, :4].tolist(), ids[0, :4, 1].tolist(), out_node[0, :4].tolist())) == \
         [(0, 0, 0), (0, 5, 1), (1, 2, 3), (1, 7, 4)]
@@ -244,7 +215,7 @@ def test_wide_bad_tables_stay_in_bounds(device):
 
 def test_wide_refuses_bad_arguments(device):
     from rqvae_hip import ops, RqHipError, _lib
-    tok, _ = expand_tests._tokenizer("c5", device)
+    tok, _ = bs.tokenizer("c5", device)
     trie = tok.prefix_trie()
     lvl0 = dict(child_off=trie.child_off[0], tok=trie.tok[1])
     for wide in (True, None):
@@ -282,7 +253,7 @@ def _calls(monkeypatch, fn):
 
 
 def test_beams_32_is_todays_call(golden, device, monkeypatch):
-    model, batch, corpus, refs = expand_tests._generation_case(golden, device, "c300")
+    model, batch, corpus, refs = bs.generation_case(golden, device, "c300")
     kw = dict(temperature=1, top_k=True, fused=True, sample=False, constrained=True)
     today = model.generate_next_sem_id(batch, **kw)
     got, names = _calls(monkeypatch, lambda: model.generate_next_sem_id(batch, beams=32, **kw))
@@ -304,7 +275,7 @@ _EXHAUSTIVE = {}
 
 def _exhaustive(golden, device, incremental):
     if incremental not in _EXHAUSTIVE:
-        model, batch, corpus, _ = expand_tests._generation_case(golden, device, "c300")
+        model, batch, corpus, _ = bs.generation_case(golden, device, "c300")
         rng = torch.cuda.get_rng_state()
         rec = model.recommend(batch, k=300, beams=512, incremental=incremental)
         assert model.training, "train mode restored"
@@ -318,7 +289,7 @@ def _exhaustive(golden, device, incremental):
 def test_recommend_exhaustive_width(golden, device, incremental):
     """512 beams over the 300-row corpus (no level has more than 300 nodes): nothing is pruned, so the result is every
     distinct row once — its first corpus index — in the order of score_items' scores."""
-    model, batch, corpus, _ = expand_tests._generation_case(golden, device, "c300")
+    model, batch, corpus, _ = bs.generation_case(golden, device, "c300")
     assert max(len(lvl) for lvl in corpus.index) <= 300 and max(max(r) for r in corpus.rows) < model.num_embeddings
     rec = _exhaustive(golden, device, incremental)
     assert rec.item_ids.shape == (3, 300) and rec.sem_ids.shape == (3, 300, 4) and rec.log_probas.shape == (3, 300)
@@ -336,7 +307,7 @@ def test_recommend_exhaustive_width(golden, device, incremental):
 
 
 def test_recommend_exhaustive_excluding_items(golden, device):
-    model, batch, corpus, _ = expand_tests._generation_case(golden, device, "c300")
+    model, batch, corpus, _ = bs.generation_case(golden, device, "c300")
     full = _exhaustive(golden, device, True)
     got = model.recommend(batch, k=295, beams=512, exclude_items=full.item_ids[:, :5].contiguous())
     assert torch.equal(got.item_ids, full.item_ids[:, 5:]) and torch.equal(got.sem_ids, full.sem_ids[:, 5:])
@@ -347,13 +318,13 @@ def test_recommend_exhaustive_excluding_items(golden, device):
 
 
 def test_recommend_wide_vs_fp64_loop(golden, device):
-    """recommend(k=50, beams=W) against test_beam_expand_gpu._reference_constrained at width W: 64, or the first of
+    """recommend(k=50, beams=W) against beam_support.reference_constrained at width W: 64, or the first of
     48, 40, 96 at which that reference's own separation precondition holds on this fixture."""
-    model, batch, corpus, _ = expand_tests._generation_case(golden, device, "c300")
+    model, batch, corpus, _ = bs.generation_case(golden, device, "c300")
     ref = None
     for width in (64, 48, 40, 96):
         try:
-            ref = expand_tests._reference_constrained(model, batch, corpus, width)
+            ref = bs.reference_constrained(model, batch, corpus, width)
             break
         except AssertionError as e:
             assert "precondition" in str(e)

@@ -2,13 +2,14 @@
 from the reference's own class by tests/golden/make_golden_eval.py), a plain-loop brute force, and reduce() under
 data parallelism (gloo, ranks that accumulated different numbers of batches)."""
 import os
-import socket
 
 import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
+
+from beam_support import free_port
 
 
 def _batches(z):
@@ -87,14 +88,6 @@ def test_planted_ranks(golden):
     assert round(m["h@10_pos_2"] * 6) == 5 and round(m["h@5_pos_2"] * 6) == 2        # row 5's column 2 at rank 7
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _dp_worker(rank, world, port, arrays, n_first, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank))
@@ -124,7 +117,7 @@ def test_reduce_data_parallel(golden, n_first):
     want = single.reduce()
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_dp_worker, args=(r, 2, port, arrays, n_first, q)) for r in range(2)]
     for p in procs:
         p.start()

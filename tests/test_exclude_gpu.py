@@ -8,34 +8,15 @@ import numpy as np
 import pytest
 import torch
 
-import test_beam_expand_gpu as expand_tests
-import test_beam_gpu as fused_tests
+import beam_support as bs
 
 pytestmark = pytest.mark.gpu
-
-_NONE = 2 ** 31 - 1
-_Corpus = expand_tests._Corpus
 
 
 def _cpu_twin(tok):
     """A CPU tokenizer over the same corpus ids: blocked_nodes' plain-torch path (checked against the brute force in
     test_exclude_host)."""
-    from modules.tokenizer.semids import SemanticIdTokenizer
-    twin = SemanticIdTokenizer(input_dim=8, output_dim=4, hidden_dims=[8], codebook_size=12, n_layers=3, n_cat_feats=0)
-    twin.cached_ids = tok.cached_ids.cpu()
-    return twin
-
-
-def _items_under(corpus, path):
-    return [i for i, r in enumerate(corpus.rows) if r[:len(path)] == tuple(path)]
-
-
-def _pad(lists, H=None):
-    H = max(1, max(len(l) for l in lists)) if H is None else H
-    out = torch.full((len(lists), H), -1, dtype=torch.int64)
-    for b, l in enumerate(lists):
-        out[b, :len(l)] = torch.tensor(l[:H], dtype=torch.int64)
-    return out
+    return bs.ids_tokenizer(tok.cached_ids.cpu())
 
 
 # ------------------------------------------------------------------------------------------ blocked nodes
@@ -46,7 +27,7 @@ def _histories(corpus, B, H, seed):
     n = corpus.ids.shape[0]
     items = torch.randint(0, n, (B, H), generator=g)
     items[torch.rand(B, H, generator=g) < 0.2] = -1
-    sub = _items_under(corpus, corpus.rows[int(torch.randint(0, n, (1,), generator=g))][:1])
+    sub = bs.items_under(corpus, corpus.rows[int(torch.randint(0, n, (1,), generator=g))][:1])
     items[0, :min(H, len(sub))] = torch.tensor(sub[:H])
     if H >= 4:
         items[1, 1] = items[1, 0]
@@ -57,7 +38,7 @@ def _histories(corpus, B, H, seed):
 @pytest.mark.parametrize("name,H", [("c3000", 1), ("c3000", 5), ("c3000", 64), ("c3000", 65), ("c3000", 200),
                                     ("c3000", 1024), ("c5", 3), ("c5", 8), ("c300", 40), ("c300", 300)])
 def test_trie_blocked_nodes_matches_cpu_path(device, name, H):
-    tok, corpus = expand_tests._tokenizer(name, device)
+    tok, corpus = bs.tokenizer(name, device)
     items, whole, sub = _histories(corpus, 3, H, seed=300 + H)
     if name == "c300" and H == 300:
         items[2] = torch.arange(300)          # everything: every node of every level
@@ -65,7 +46,7 @@ def test_trie_blocked_nodes_matches_cpu_path(device, name, H):
     got = tok.blocked_nodes(items.to(device))
     assert got.is_cuda and got.dtype == torch.int32 and got.shape == (4, 3, H)
     assert torch.equal(got.cpu(), want)
-    n_blocked = (want != _NONE).sum(-1)          # (D, B)
+    n_blocked = (want != bs.NONE).sum(-1)          # (D, B)
     print(f"{name} H={H}: blocked nodes per level and user {n_blocked.tolist()}")
     assert (n_blocked[3] > 0).any(), "listed items block their leaves"
     if H >= 40 or name == "c5":
@@ -76,7 +57,7 @@ def test_trie_blocked_nodes_matches_cpu_path(device, name, H):
 
 def test_trie_blocked_nodes_refusals(device):
     from rqvae_hip import ops, RqHipError
-    tok, _ = expand_tests._tokenizer("c5", device)
+    tok, _ = bs.tokenizer("c5", device)
     idx = tok.trie_index()
     with pytest.raises(RqHipError, match="rc=-22|envelope"):
         tok.blocked_nodes(torch.zeros((2, 1025), dtype=torch.int64, device=device))
@@ -95,8 +76,8 @@ _EXCL = {}
 
 
 def _reduced_reference(corpus, c, items, logits, B, kprev, V, P, k, T):
-    """_expand_reference per user over the _Corpus of the rows that remain; nodes in the full corpus' index."""
-    lp64 = expand_tests._log_softmax64(logits, T)
+    """expand_reference per user over the Corpus of the rows that remain; nodes in the full corpus' index."""
+    lp64 = bs.log_softmax64(logits, T)
     pre = c["parents"].tolist() if P else None
     live = (c["node"] >= 0).tolist() if P else [[True] * kprev] * B
     out = []
@@ -107,24 +88,24 @@ def _reduced_reference(corpus, c, items, logits, B, kprev, V, P, k, T):
         res = (ids, torch.full((1, k), -float("inf"), dtype=torch.float64), torch.zeros((1, k), dtype=torch.int64),
                torch.full((1, k), -1, dtype=torch.int64), [[]])
         if left:
-            res = expand_tests._expand_reference(_Corpus(torch.tensor(left)), lp64[b * kprev:(b + 1) * kprev],
-                                                 None if pre is None else pre[b:b + 1], live[b:b + 1],
-                                                 None if not P else c["parent_lp"][b:b + 1], 1, kprev, V, P, k)
+            res = bs.expand_reference(bs.Corpus(torch.tensor(left)), lp64[b * kprev:(b + 1) * kprev],
+                                      None if pre is None else pre[b:b + 1], live[b:b + 1],
+                                      None if not P else c["parent_lp"][b:b + 1], 1, kprev, V, P, k)
         node = torch.tensor([[corpus.index[P + 1][tuple(r)] if r[0] >= 0 else -1 for r in res[0][0].tolist()]])
         out.append((res[0], res[1], res[2], node, res[4][0]))
     return out
 
 
 def _excl_case(device, name, B, kprev, V, P, k, T=1.0):
-    """test_beam_expand_gpu._case's beams with histories drawn from each user's own best beams: every item under the
+    """beam_support.case's beams with histories drawn from each user's own best beams: every item under the
     node of its unfiltered rank 0 (and rank 2 where it has six candidates or more) — blocked —, one item of rank 1's
-    subtree where that holds several rows — not blocked — and, in the larger corpora, two random items. A user whose top k + 1 scores, before or after the exclusion, are not
-    separated is redrawn from the same stream. Built once."""
+    subtree where that holds several rows — not blocked — and, in the larger corpora, two random items. A user whose
+    top k + 1 scores, before or after the exclusion, are not separated is redrawn from the same stream. Built once."""
     key = (name, B, kprev, V, P, k, T)
     if key in _EXCL:
         return _EXCL[key]
-    c = expand_tests._case(device, name, B, kprev, V, P, k, T)
-    corpus = expand_tests._tokenizer(name, device)[1]
+    c = bs.case(device, name, B, kprev, V, P, k, T)
+    corpus = bs.tokenizer(name, device)[1]
     g = torch.Generator().manual_seed(9000 + 97 * B + 31 * kprev + 7 * V + 3 * P + k)
     logits = c["logits"].clone()
     pre = c["parents"].tolist() if P else None
@@ -133,20 +114,18 @@ def _excl_case(device, name, B, kprev, V, P, k, T=1.0):
     extra = torch.randint(0, n, (B, 2), generator=g).tolist()
     todo = list(range(B))
     for _ in range(200):
-        full = expand_tests._expand_reference(corpus, expand_tests._log_softmax64(logits, T), pre, live, c["parent_lp"],
-                                              B, kprev, V, P, k)
+        full = bs.expand_reference(corpus, bs.log_softmax64(logits, T), pre, live, c["parent_lp"], B, kprev, V, P, k)
         lists = []
         for b in range(B):
             paths = [tuple(r) for r in full[0][b].tolist() if r[0] >= 0]
-            l = [i for r in ((0, 2) if len(full[4][b]) >= 6 else (0,)) for i in _items_under(corpus, paths[r])]
-            under = _items_under(corpus, paths[1]) if len(paths) > 1 else []
+            l = [i for r in ((0, 2) if len(full[4][b]) >= 6 else (0,)) for i in bs.items_under(corpus, paths[r])]
+            under = bs.items_under(corpus, paths[1]) if len(paths) > 1 else []
             if len({corpus.rows[i] for i in under}) > 1:
                 l.append(under[0])
             lists.append(l + (extra[b] if n >= 300 else []))
-        items = _pad(lists)
+        items = bs.pad(lists)
         ref = _reduced_reference(corpus, c, items, logits, B, kprev, V, P, k, T)
-        todo = [b for b in range(B) if not (expand_tests._separated(full[4][b], k) and
-                                            expand_tests._separated(ref[b][4], k))]
+        todo = [b for b in range(B) if not (bs.separated(full[4][b], k) and bs.separated(ref[b][4], k))]
         if not todo:
             break
         for b in todo:
@@ -157,25 +136,16 @@ def _excl_case(device, name, B, kprev, V, P, k, T=1.0):
     return _EXCL[key]
 
 
-def _run(device, c, k, P, T, B, **kw):
-    from rqvae_hip import ops
-    trie = c["tok"].prefix_trie()
-    d = fused_tests._dev
-    return ops.beam_expand(c["logits"].to(device), k, batch=B, child_off=trie.child_off[P], tok=trie.tok[P + 1],
-                           node=d(c["node"], device), parents=d(c["parents"], device),
-                           parent_lp=d(c["parent_lp"], device), temperature=T, **kw)
-
-
-@pytest.mark.parametrize("name,B,kprev,V,P,k", expand_tests._SHAPES)
+@pytest.mark.parametrize("name,B,kprev,V,P,k", bs.SHAPES)
 def test_beam_expand_blocked_equals_postfilter(device, name, B, kprev, V, P, k):
     """Every candidate from the unfiltered kernel (k = kprev V), the rows on a blocked node dropped on the host, the
     first k kept: bitwise what the filtered kernel returns."""
     c = _excl_case(device, name, B, kprev, V, P, k)
-    every = [t.cpu() for t in _run(device, c, kprev * V, P, 1.0, B)]
-    got = [t.cpu() for t in _run(device, c, k, P, 1.0, B, blocked=c["blocked"].to(device))]
+    every = [t.cpu() for t in bs.expand(device, c["tok"], c, B, kprev * V, P)]
+    got = [t.cpu() for t in bs.expand(device, c["tok"], c, B, k, P, blocked=c["blocked"].to(device))]
     removed = []
     for b in range(B):
-        gone = set(c["blocked"][b].tolist()) - {_NONE}
+        gone = set(c["blocked"][b].tolist()) - {bs.NONE}
         keep = torch.tensor([int(v) >= 0 and int(v) not in gone for v in every[3][b]])
         removed.append(int((~keep[:k] & (every[3][b, :k] >= 0)).sum()))
         idx = keep.nonzero().flatten()[:k]
@@ -185,31 +155,28 @@ def test_beam_expand_blocked_equals_postfilter(device, name, B, kprev, V, P, k):
         m = idx.numel()
         want_ids[:m], want_lp[:m], want_parent[:m], want_node[:m] = (every[0][b, idx], every[1][b, idx],
                                                                      every[2][b, idx], every[3][b, idx])
-        assert torch.equal(got[0][b], want_ids), "out_ids"
-        assert torch.equal(got[1][b].view(torch.int32), want_lp.view(torch.int32)), "out_lp bitwise"
-        assert torch.equal(got[2][b], want_parent) and torch.equal(got[3][b], want_node), "out_parent / out_node"
+        bs.assert_same([t[b] for t in got], (want_ids, want_lp, want_parent, want_node), f"user {b}: ")
     print(f"{name} B={B} kprev={kprev} V={V} P={P} k={k}: candidates removed from the top k per user {removed}, "
           f"H={c['items'].shape[1]}")
     assert all(r > 0 for r in removed), "the filter removes candidates from every user's top k"
-    expand_tests._assert_dead_rows(*got)
+    bs.assert_dead_rows(*got)
 
 
-@pytest.mark.parametrize("name,B,kprev,V,P,k", expand_tests._SHAPES)
+@pytest.mark.parametrize("name,B,kprev,V,P,k", bs.SHAPES)
 def test_beam_expand_blocked_noop(device, name, B, kprev, V, P, k):
-    c = expand_tests._case(device, name, B, kprev, V, P, k, 1.0)
-    plain = _run(device, c, k, P, 1.0, B)
-    for blocked in (torch.full((B, 8), _NONE, dtype=torch.int32, device=device),
+    c = bs.case(device, name, B, kprev, V, P, k, 1.0)
+    plain = bs.expand(device, c["tok"], c, B, k, P)
+    for blocked in (torch.full((B, 8), bs.NONE, dtype=torch.int32, device=device),
                     torch.zeros((B, 0), dtype=torch.int32, device=device)):   # n_blocked = 0: a null pointer
-        got = _run(device, c, k, P, 1.0, B, blocked=blocked)
-        assert torch.equal(got[0], plain[0]) and torch.equal(got[1].view(torch.int32), plain[1].view(torch.int32))
-        assert torch.equal(got[2], plain[2]) and torch.equal(got[3], plain[3])
+        got = bs.expand(device, c["tok"], c, B, k, P, blocked=blocked)
+        bs.assert_same(got, plain)
 
 
-@pytest.mark.parametrize("name,B,kprev,V,P,k", expand_tests._SHAPES)
+@pytest.mark.parametrize("name,B,kprev,V,P,k", bs.SHAPES)
 def test_beam_expand_blocked_vs_fp64(device, name, B, kprev, V, P, k):
     c = _excl_case(device, name, B, kprev, V, P, k)
-    assert all(expand_tests._separated(r[4], k) for r in c["ref"]), "precondition: separated scores"
-    ids, lp, parent, node = (t.cpu() for t in _run(device, c, k, P, 1.0, B, blocked=c["blocked"].to(device)))
+    assert all(bs.separated(r[4], k) for r in c["ref"]), "precondition: separated scores"
+    ids, lp, parent, node = (t.cpu() for t in bs.expand(device, c["tok"], c, B, k, P, blocked=c["blocked"].to(device)))
     want_ids, want_lp, want_parent, want_node = (torch.cat([r[j] for r in c["ref"]]) for j in range(4))
     live = want_node >= 0
     print(f"{name} B={B} kprev={kprev} V={V} P={P} k={k}: remaining candidates per user {[len(r[4]) for r in c['ref']]}, "
@@ -218,16 +185,16 @@ def test_beam_expand_blocked_vs_fp64(device, name, B, kprev, V, P, k):
     assert torch.equal(parent.long(), want_parent), "out_parent"
     assert torch.equal(node.long(), want_node), "out_node (full corpus index)"
     np.testing.assert_allclose(lp.double().numpy(), want_lp.numpy(), rtol=1e-5, atol=0)
-    expand_tests._assert_dead_rows(ids, lp, parent, node)
+    bs.assert_dead_rows(ids, lp, parent, node)
 
 
 def test_beam_expand_blocked_refusals(device):
     from rqvae_hip import ops, RqHipError
-    tok, _ = expand_tests._tokenizer("c5", device)
+    tok, _ = bs.tokenizer("c5", device)
     trie = tok.prefix_trie()
     x = torch.zeros(2, 16, device=device)
     lvl0 = dict(child_off=trie.child_off[0], tok=trie.tok[1])
-    ok = torch.full((2, 4), _NONE, dtype=torch.int32, device=device)
+    ok = torch.full((2, 4), bs.NONE, dtype=torch.int32, device=device)
     assert ops.beam_expand(x, 3, batch=2, **lvl0, blocked=ok)[0].shape == (2, 3, 1)
     with pytest.raises(RqHipError, match="no CPU fallback"):
         ops.beam_expand(x, 3, batch=2, **lvl0, blocked=ok.cpu())
@@ -240,56 +207,40 @@ def test_beam_expand_blocked_refusals(device):
     # an unsorted row filters unspecified children but stays inside the row; a whole level blocked leaves dead rows
     rev = torch.tensor([[1, 0], [1, 0]], dtype=torch.int32, device=device)
     assert ops.beam_expand(x, 3, batch=2, **lvl0, blocked=rev)[0].shape == (2, 3, 1)
-    every = torch.tensor([[0, 1], [0, _NONE]], dtype=torch.int32, device=device)
+    every = torch.tensor([[0, 1], [0, bs.NONE]], dtype=torch.int32, device=device)
     ids, lp, parent, node = ops.beam_expand(x, 3, batch=2, **lvl0, blocked=every)
     assert (ids[0] == -1).all() and torch.isneginf(lp[0]).all() and ids[1, :, 0].tolist() == [3, -1, -1]
-    expand_tests._assert_dead_rows(ids.cpu(), lp.cpu(), parent.cpu(), node.cpu())
+    bs.assert_dead_rows(ids.cpu(), lp.cpu(), parent.cpu(), node.cpu())
 
 
 # ------------------------------------------------------------------------------------------ generation
 def _reference_excluded(model, batch, corpus, items, k, T=1.0):
-    """test_beam_expand_gpu._reference_constrained's loop (the model's own forwards, the expansion in fp64 on the CPU)
-    with every user expanded over its own reduced corpus. Returns ids (B, k, L1), fp64 log-probabilities (B, k) — dead
-    rows -1 / -inf — and whether the separation precondition held for every user at every step."""
-    from data.schemas import TokenizedSeqBatch
-    B, L1, V = batch.sem_ids.shape[0], model.sem_id_dim, model.num_embeddings
-    dev = batch.sem_ids.device
+    """beam_support.walk_forwards (the model's own forwards, the expansion in fp64 on the CPU) with every user
+    expanded over its own reduced corpus. Returns ids (B, k, L1), fp64 log-probabilities (B, k) — dead rows -1 / -inf —
+    and whether the separation precondition held for every user at every step."""
+    B, V = batch.sem_ids.shape[0], model.num_embeddings
     left = []
     for b in range(B):
         gone = {corpus.rows[i] for i in items[b].tolist() if i >= 0}
         rows = [r for r in corpus.rows if r not in gone]
-        left.append(_Corpus(torch.tensor(rows)) if rows else None)
-    was_training = model.training
-    model.eval()
-    model.transformer.cached_enc_output = None
-    try:
-        with torch.no_grad():
-            cur = TokenizedSeqBatch(user_ids=batch.user_ids, sem_ids=batch.sem_ids, sem_ids_fut=None,
-                                    seq_mask=batch.seq_mask, token_type_ids=batch.token_type_ids, token_type_ids_fut=None)
-            ids = lp = None
-            separated = True
-            for i in range(L1):
-                kprev = 1 if i == 0 else k
-                lp64 = expand_tests._log_softmax64(model.forward(cur).logits.cpu(), T)
-                assert lp64.shape == (B * kprev, V)
-                new_ids = torch.full((B, k, i + 1), -1, dtype=torch.int64)
-                new_lp = torch.full((B, k), -float("inf"), dtype=torch.float64)
-                for b in range(B):
-                    if left[b] is None:
-                        continue
-                    live = [[True]] if i == 0 else [(ids[b, :, 0] >= 0).tolist()]
-                    r = expand_tests._expand_reference(left[b], lp64[b * kprev:(b + 1) * kprev],
-                                                       None if i == 0 else ids[b:b + 1].tolist(), live,
-                                                       None if i == 0 else lp[b:b + 1], 1, kprev, V, i, k)
-                    separated = separated and expand_tests._separated(r[4][0], k)
-                    new_ids[b], new_lp[b] = r[0][0], r[1][0]
-                first, ids, lp = ids is None, new_ids, new_lp
-                if i + 1 < L1:
-                    cur = model._beams_batch(cur, ids.clamp_min(0).to(dev), first, k)
-    finally:
-        model.transformer.cached_enc_output = None
-        model.train(was_training)
-    return ids, lp, separated
+        left.append(bs.Corpus(torch.tensor(rows)) if rows else None)
+
+    def step(i, logits, state):
+        ids, lp, separated = state
+        kprev = 1 if i == 0 else k
+        lp64 = bs.log_softmax64(logits, T)
+        new_ids = torch.full((B, k, i + 1), -1, dtype=torch.int64)
+        new_lp = torch.full((B, k), -float("inf"), dtype=torch.float64)
+        for b in range(B):
+            if left[b] is None:
+                continue
+            live = [[True]] if i == 0 else [(ids[b, :, 0] >= 0).tolist()]
+            r = bs.expand_reference(left[b], lp64[b * kprev:(b + 1) * kprev], None if i == 0 else ids[b:b + 1].tolist(),
+                                    live, None if i == 0 else lp[b:b + 1], 1, kprev, V, i, k)
+            separated = separated and bs.separated(r[4][0], k)
+            new_ids[b], new_lp[b] = r[0][0], r[1][0]
+        return (new_ids, new_lp, separated), new_ids.clamp_min(0)
+    return bs.walk_forwards(model, batch, k, step, (None, None, True))
 
 
 _GEN = {}
@@ -302,14 +253,14 @@ def _gen_case(golden, device, name):
     ranking until the reference's top k + 1 scores are separated at every step (the precondition, asserted). Built
     once."""
     if name not in _GEN:
-        model, batch, corpus, refs = expand_tests._generation_case(golden, device, name)
+        model, batch, corpus, refs = bs.generation_case(golden, device, name)
         best = refs[32][0]
         n = corpus.ids.shape[0]
         for v in range(8):
-            lists = [[i for r in range(v, v + 3) for i in _items_under(corpus, best[0, r].tolist()) if best[0, r, 0] >= 0],
+            lists = [[i for r in range(v, v + 3) for i in bs.items_under(corpus, best[0, r].tolist()) if best[0, r, 0] >= 0],
                      list(range(n)),
-                     _items_under(corpus, best[2, v if best[2, v, 0] >= 0 else 0, :1].tolist())]
-            items = _pad(lists)
+                     bs.items_under(corpus, best[2, v if best[2, v, 0] >= 0 else 0, :1].tolist())]
+            items = bs.pad(lists)
             ids, lp, separated = _reference_excluded(model, batch, corpus, items, 32)
             if separated:
                 break
@@ -322,7 +273,7 @@ def _gen_case(golden, device, name):
 @pytest.mark.parametrize("name", ["c300", "c5"])
 def test_generation_excluding_items_vs_fp64_loop(golden, device, name):
     model, batch, corpus, items, (want_ids, want_lp) = _gen_case(golden, device, name)
-    plain = expand_tests._generation_case(golden, device, name)[3][32][0]
+    plain = bs.generation_case(golden, device, name)[3][32][0]
     assert not torch.equal(want_ids[0], plain[0]) and (want_ids[0] >= 0).all() == (name == "c300")
     assert (want_ids[1] == -1).all(), "a history that covers the corpus leaves nothing"
     rng = torch.cuda.get_rng_state()

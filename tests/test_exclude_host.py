@@ -6,9 +6,7 @@ import math
 import pytest
 import torch
 
-import test_beam_trie_host as trie_tests
-
-_NONE = 2 ** 31 - 1
+import beam_support as bs
 
 
 def _index(ids):
@@ -24,7 +22,7 @@ def _brute_blocked(ids, items):
     n, D = len(rows), ids.shape[1]
     index = _index(ids)
     B, H = items.shape
-    out = torch.full((D, B, H), _NONE, dtype=torch.int32)
+    out = torch.full((D, B, H), bs.NONE, dtype=torch.int32)
     for b in range(B):
         excluded = {rows[i] for i in items[b].tolist() if 0 <= i < n}
         for q in range(1, D + 1):
@@ -40,30 +38,30 @@ def _subtree_items(ids, first_token):
 
 
 def test_blocked_nodes_five_rows():
-    ids = trie_tests._FIVE
-    tok = trie_tests._tokenizer(ids)
+    ids = bs.FIVE
+    tok = bs.ids_tokenizer(ids)
     index = _index(ids)
     items = torch.tensor([[0, 1, -1], [4, -1, -1], [-1, -1, -1], [1, 1, 0], [7, -5, 3]])
     got = tok.blocked_nodes(items)
     assert got.shape == (4, 5, 3) and got.dtype == torch.int32
     assert torch.equal(got, _brute_blocked(ids, items))
     # history {0, 1}: both leaves under (3, 1, 4), so that node and (3, 1) are blocked; (3,) still has (3, 0, 9, 0)
-    assert got[3, 0].tolist() == [index[4][(3, 1, 4, 0)], index[4][(3, 1, 4, 1)], _NONE]
-    assert got[2, 0].tolist() == [index[3][(3, 1, 4)], _NONE, _NONE]
-    assert got[1, 0].tolist() == [index[2][(3, 1)], _NONE, _NONE]
-    assert got[0, 0].tolist() == [_NONE] * 3
+    assert got[3, 0].tolist() == [index[4][(3, 1, 4, 0)], index[4][(3, 1, 4, 1)], bs.NONE]
+    assert got[2, 0].tolist() == [index[3][(3, 1, 4)], bs.NONE, bs.NONE]
+    assert got[1, 0].tolist() == [index[2][(3, 1)], bs.NONE, bs.NONE]
+    assert got[0, 0].tolist() == [bs.NONE] * 3
     # history {4}: the duplicated row's one leaf is blocked, so item 2 goes with item 4 — and (0,) has no other row
-    assert got[3, 1].tolist() == [index[4][(0, 2, 2, 0)], _NONE, _NONE]
-    assert got[0, 1].tolist() == [index[1][(0,)], _NONE, _NONE]
+    assert got[3, 1].tolist() == [index[4][(0, 2, 2, 0)], bs.NONE, bs.NONE]
+    assert got[0, 1].tolist() == [index[1][(0,)], bs.NONE, bs.NONE]
     assert int(tok.trie_index().item_leaf[2]) == int(tok.trie_index().item_leaf[4])
-    assert (got[:, 2] == _NONE).all(), "all padding"
+    assert (got[:, 2] == bs.NONE).all(), "all padding"
     assert torch.equal(got[:, 3], got[:, 0]), "duplicates and order do not matter"
-    assert got[3, 4].tolist() == [index[4][(3, 0, 9, 0)], _NONE, _NONE], "out-of-range ids count as padding"
+    assert got[3, 4].tolist() == [index[4][(3, 0, 9, 0)], bs.NONE, bs.NONE], "out-of-range ids count as padding"
 
 
 def test_blocked_nodes_random_corpus():
-    ids = trie_tests._random_corpus()
-    tok = trie_tests._tokenizer(ids)
+    ids = bs.random_corpus()
+    tok = bs.ids_tokenizer(ids)
     index = _index(ids)
     n = ids.shape[0]
     g = torch.Generator().manual_seed(17)
@@ -80,24 +78,24 @@ def test_blocked_nodes_random_corpus():
     got = tok.blocked_nodes(items)
     assert torch.equal(got, _brute_blocked(ids, items))
     node1 = index[1][(int(ids[5, 0]),)]
-    assert got[0, 0].tolist() == [node1] + [_NONE] * (H - 1), "the whole-subtree user blocks its level-1 node"
+    assert got[0, 0].tolist() == [node1] + [bs.NONE] * (H - 1), "the whole-subtree user blocks its level-1 node"
     for q in range(1, 5):   # ... and every descendant of it
         want = sorted(v for pre, v in index[q].items() if pre[0] == int(ids[5, 0]))
         assert got[q - 1, 0, :len(want)].tolist() == want
-    assert (got[:, 5] == _NONE).all(), "an empty history blocks nothing"
+    assert (got[:, 5] == bs.NONE).all(), "an empty history blocks nothing"
     for q in range(4):
-        live = got[q][got[q] != _NONE]
+        live = got[q][got[q] != bs.NONE]
         assert (got[q, :, 1:] >= got[q, :, :-1]).all() and live.numel() > 0
     # every item: every node of every level is blocked; H = 0 gives an empty fixed-shape result
     everything = tok.blocked_nodes(torch.arange(n).unsqueeze(0))
     for q in range(1, 5):
         n_q = len(index[q])
-        assert everything[q - 1, 0, :n_q].tolist() == list(range(n_q)) and (everything[q - 1, 0, n_q:] == _NONE).all()
+        assert everything[q - 1, 0, :n_q].tolist() == list(range(n_q)) and (everything[q - 1, 0, n_q:] == bs.NONE).all()
     assert tok.blocked_nodes(torch.zeros((2, 0), dtype=torch.int64)).shape == (4, 2, 0)
 
 
 def test_trie_index_cache_follows_the_trie():
-    tok = trie_tests._tokenizer(trie_tests._FIVE)
+    tok = bs.ids_tokenizer(bs.FIVE)
     idx = tok.trie_index()
     assert tok.trie_index() is idx, "cached"
     assert idx.item_leaf.dtype == torch.int32 and idx.item_leaf.tolist() == [2, 3, 0, 1, 0]
@@ -217,7 +215,6 @@ def _dp_worker(rank, world, port, arrays, n_first, q):
 def test_rank_accumulator_reduce_data_parallel(golden):
     """One all-reduce of the fixed (width + 1) vector: rank 0 holds every batch (two beam widths), rank 1 none."""
     import torch.multiprocessing as mp
-    import test_eval_metrics as metric_tests
     from evaluate.metrics import RankAccumulator
     z = golden("topk_metrics")
     arrays = [(z["actual1"], z["topk1"]), (z["actual2"], z["topk2"]), (z["actual1"][::-1].copy(), z["topk1"][:, :7].copy())]
@@ -228,7 +225,7 @@ def test_rank_accumulator_reduce_data_parallel(golden):
     assert want and len(single.hists) == 3
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = metric_tests._free_port()
+    port = bs.free_port()
     procs = [ctx.Process(target=_dp_worker, args=(r, 2, port, arrays, 3, q)) for r in range(2)]
     for p in procs:
         p.start()
@@ -246,7 +243,7 @@ def test_exclude_items_argument_errors():
     model = EncoderDecoderRetrievalModel(embedding_dim=8, attn_dim=16, dropout=0.0, num_heads=1, n_layers=2,
                                          num_embeddings=12, sem_id_dim=4, inference_verifier_fn=None, max_pos=8)
     model.enable_generation = True
-    model.inference_prefix_index = trie_tests._tokenizer(trie_tests._FIVE)
+    model.inference_prefix_index = bs.ids_tokenizer(bs.FIVE)
     seen = torch.tensor([[0, 1], [4, -1]])
     for kw in (dict(), dict(fused=True), dict(fused=True, sample=False), dict(fused=True, incremental=True)):
         with pytest.raises(ValueError, match="exclude_items requires constrained=True"):
@@ -264,7 +261,7 @@ def test_exclude_items_argument_errors():
 
 def test_exclusion_ops_refuse_cpu_tensors():
     from rqvae_hip import ops, RqHipError
-    tok = trie_tests._tokenizer(trie_tests._FIVE)
+    tok = bs.ids_tokenizer(bs.FIVE)
     idx = tok.trie_index()
     with pytest.raises(RqHipError, match="no CPU fallback"):
         ops.trie_blocked_nodes(torch.zeros(2, 3, dtype=torch.int64), idx.item_leaf, idx.leaf_anc, idx.leaf_count)

@@ -8,8 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-import test_beam_expand_gpu as expand_tests
-import test_beam_gpu as fused_tests
+import beam_support as bs
 
 pytestmark = pytest.mark.gpu
 
@@ -33,7 +32,7 @@ def _kernel_inputs(B, C, V, G, seed):
 
 
 def _score_reference(logits, tokens, present, prev, B, C, V, G, T):
-    lp64 = expand_tests._log_softmax64(logits, T).view(B, G, V).expand(B, C, V)
+    lp64 = bs.log_softmax64(logits, T).view(B, G, V).expand(B, C, V)
     ok = present & (tokens >= 0) & (tokens < V)
     want = lp64.gather(2, tokens.clamp(0, V - 1).unsqueeze(-1)).squeeze(-1)
     if prev is not None:
@@ -75,7 +74,7 @@ def test_score_paths_vs_fp64(device, C, V, per_cand, T, strided, with_prev):
         tdev = tdev.contiguous()
     assert tdev.is_contiguous() == (not strided)
     lp, rank = ops.score_paths(logits.to(device), tdev, present=present.to(device),
-                               prev_lp=fused_tests._dev(prev, device), temperature=T)
+                               prev_lp=bs.dev(prev, device), temperature=T)
     assert rank is None
     _assert_scores(lp, want, f"C={C} V={V} G={G} T={T}:")
     assert torch.isneginf(lp.cpu()[~present]).all(), "padding gives -inf"
@@ -91,7 +90,7 @@ def test_score_paths_dominant_and_underflow_rows(device):
     x[1, 3] = -200.0
     tokens = torch.tensor([[7, 0], [3, 0]])
     lp = ops.score_paths(x.to(device), tokens.to(device))[0].cpu()
-    want = expand_tests._log_softmax64(x, 1.0).gather(1, tokens)
+    want = bs.log_softmax64(x, 1.0).gather(1, tokens)
     assert -5e-12 < float(want[0, 0]) < -1e-12
     np.testing.assert_allclose(lp[0].double().numpy(), want[0].numpy(), rtol=1e-5, atol=0)
     assert lp[1, 0] == _NINF and torch.isfinite(want[1, 0]), "underflow: exactly -inf"
@@ -237,31 +236,16 @@ def test_score_paths_refusals(device):
 
 # ------------------------------------------------------------------------------------------ model vs fp64 loop
 def _reference_scores(model, batch, sem, present, T=1.0):
-    """The teacher-forced walk over the model's own full forwards (batches from _beams_batch, tokens clamped into
+    """The teacher-forced walk over the model's own full forwards (beam_support.walk_forwards, tokens clamped into
     [0, V)), fp64 log-softmax and gather on the CPU. sem (B, C, D), present (B, C) on the CPU."""
-    from data.schemas import TokenizedSeqBatch
     B, C, D = sem.shape
-    V, dev = model.num_embeddings, batch.sem_ids.device
-    was_training = model.training
-    model.eval()
-    model.transformer.cached_enc_output = None
-    try:
-        with torch.no_grad():
-            cur = TokenizedSeqBatch(user_ids=batch.user_ids, sem_ids=batch.sem_ids, sem_ids_fut=None,
-                                    seq_mask=batch.seq_mask, token_type_ids=batch.token_type_ids, token_type_ids_fut=None)
-            lp = torch.zeros(B, C, dtype=torch.float64)
-            for i in range(D):
-                logits = model.forward(cur).logits.cpu()
-                G = 1 if i == 0 else C
-                assert logits.shape == (B * G, V)
-                step, _ = _score_reference(logits, sem[:, :, i], present, None, B, C, V, G, T)
-                lp = lp + step
-                if i + 1 < D:
-                    cur = model._beams_batch(cur, sem[:, :, :i + 1].clamp(0, V - 1).to(dev), i == 0, C)
-    finally:
-        model.transformer.cached_enc_output = None
-        model.train(was_training)
-    return lp
+    V = model.num_embeddings
+    assert D == model.sem_id_dim
+
+    def step(i, logits, lp):
+        return (lp + _score_reference(logits, sem[:, :, i], present, None, B, C, V, 1 if i == 0 else C, T)[0],
+                sem[:, :, :i + 1].clamp(0, V - 1))
+    return bs.walk_forwards(model, batch, C, step, torch.zeros(B, C, dtype=torch.float64))
 
 
 _SCORE = {}
@@ -272,7 +256,7 @@ def _score_case(golden, device, name, C):
     (all ten for C = 40), a duplicate of the first, -1 padding, an index >= N, an item with a token >= V where the
     corpus holds one, random items. The fp64 reference is computed once and shared."""
     if (name, C) not in _SCORE:
-        model, batch, corpus, _ = expand_tests._generation_case(golden, device, name)
+        model, batch, corpus, _ = bs.generation_case(golden, device, name)
         V, n = model.num_embeddings, corpus.ids.shape[0]
         rec = model.recommend(batch, k=10).item_ids.cpu()
         g = torch.Generator().manual_seed(1100 + C + n)
@@ -352,7 +336,7 @@ def test_score_sem_ids_row_outside_the_corpus(golden, device, incremental):
 def test_score_items_agrees_with_recommend(golden, device, name):
     """The separation precondition (asserted when the fixture's references are built) makes recommend's order well
     defined: its items come back with its log-probabilities and with the ranks 0..n_live-1 in order."""
-    model, batch, corpus, refs = expand_tests._generation_case(golden, device, name)
+    model, batch, corpus, refs = bs.generation_case(golden, device, name)
     want_node = refs[32][2][:, :10]
     rec = model.recommend(batch, k=10)
     got = model.score_items(batch, rec.item_ids)
@@ -373,7 +357,7 @@ def test_score_items_agrees_with_recommend(golden, device, name):
 
 
 def test_score_items_refusals(golden, device):
-    model, batch, corpus, _ = expand_tests._generation_case(golden, device, "c5")
+    model, batch, corpus, _ = bs.generation_case(golden, device, "c5")
     items = torch.zeros(3, 4, dtype=torch.int64, device=device)
     with pytest.raises(ValueError, match="1 <= C <= 1024"):
         model.score_items(batch, torch.zeros(3, 1025, dtype=torch.int64, device=device))
@@ -386,7 +370,7 @@ def test_score_items_refusals(golden, device):
     with pytest.raises(ValueError, match="must live on"):
         model.score_sem_ids(batch, torch.zeros(3, 4, 4, dtype=torch.int64))
     index = model.inference_prefix_index
-    narrow = fused_tests._hand_tokenizer(device, n=5)
+    narrow = bs.hand_tokenizer(device, n=5)
     narrow.cached_ids = index.cached_ids[:, :3].contiguous()
     try:
         model.inference_prefix_index = narrow
