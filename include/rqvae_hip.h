@@ -174,6 +174,7 @@ int rq_gemm_bf16x3(const float* A, int64_t lda, int a_kcontig, const float* B, i
 #define RQ_GEMM_NO_WIDE 8     /* never the wide kernel (128- / 64-tile chosen by the model) */
 #define RQ_GEMM_MASKED 16     /* masked k staging even for whole 32-deep stages (bitwise the unmasked path) */
 #define RQ_GEMM_NO_PAIR 32    /* rq_gemm_bf16x3_pair: two launches */
+#define RQ_GEMM_NO_GROUP 64   /* rq_gemm_bf16x3_group: every member in its own launch */
 /* flags | RQ_GEMM_SPLIT(S): split K into S chunks (1..4095; 0 = the planner's count) on the kernel the other
  * flags / the planner pick — a tuned plan for a known shape. S > 1 needs S x M x N fp32 of workspace (which
  * rq_gemm_bf16x3_workspace does not size for a forced S). Bits of a result depend on the chunking. */
@@ -243,6 +244,23 @@ int rq_gemm_bf16x3_pair(const rq_gemm_desc* d, int* splits, void* stream);
 int rq_gemm_bf16x3_plan(const rq_gemm_desc* d, int* splits);
 /* 1 when rq_gemm_bf16x3_pair would run d[0], d[1] in one launch (host-only planning), else 0. */
 int rq_gemm_bf16x3_pair_plan(const rq_gemm_desc* d);
+/* `count` (1..8) independent calls, the weight gradients dW = g^T x of one MLP chain (modules/encoder.py:7-36:
+ * autograd's grad_weight of each nn.Linear). Members that carry an explicit split count (RQ_GEMM_SPLIT(S),
+ * S >= 2) and have split m/n-contiguous operands, the plain epilogue, ldc == N, K % 32 == 0 and no other kernel
+ * policy flag run in ONE wide-tile launch (gemm_x3w_group_kernel), each with its own split-K count over its
+ * share of the grid; every other member runs as rq_gemm_bf16x3_run would run it, bit for bit. A grouped member
+ * writes S slabs to its own workspace (S x M x N fp32) and is reduced in fixed order (rq_reduce_partials layout
+ * 0), here in one launch or, with defer and accumulate, by the caller (splits[i] = S, as rq_gemm_bf16x3_run
+ * reports); with the split count and chunk of its separate launch its bits are that launch's. RQ_GEMM_NO_GROUP
+ * in any member: no grouped launch. */
+int rq_gemm_bf16x3_group(const rq_gemm_desc* d, int count, int* splits, void* stream);
+/* Host-only planning for rq_gemm_bf16x3_group (pointers may be NULL): the number of members that should share
+ * the grouped launch (0: none) and splits[i] = member i's split-K count in it, 0 for a member left out.
+ * Members with explicit counts: what the run does with them. Without: the time model's plan — one step budget
+ * for all members, taken when it beats their separate plans (equal K of at least 32,768 rows) — which the
+ * caller adopts by passing the counts as RQ_GEMM_SPLIT(splits[i]); they differ from the separate plans'
+ * counts, so adopting them changes the fp32 summation order of those results. */
+int rq_gemm_bf16x3_group_plan(const rq_gemm_desc* d, int count, int* splits);
 /* Deferred partial reductions, up to 48 per launch: for each entry i, out_i[j] = (accumulate_i ? out_i[j] :
  * 0) + sum_{s < S_i} P_i[s n_i + j], j < n_i (n_i % 4 == 0, 16-B aligned pointers), in the order of the
  * reduction it replaces (layout 0: rq_gemm_bf16x3_run's slab reduction; layout 1: rq_rmsnorm_dropout_bwd's

@@ -817,17 +817,27 @@ __device__ __forceinline__ bf16x8_t wfrag16(const char* plane, int rb, int lane)
 #define RQ_W_VM6() asm volatile("s_waitcnt vmcnt(6)" ::: "memory")
 #define RQ_W_LGKM0() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 
-template <bool AKC, bool BKC, int EPI, bool DROP>
-__global__ void __launch_bounds__(512, 1)
-gemm_x3w_kernel(const uint16_t* __restrict__ Ah, const uint16_t* __restrict__ Al, int64_t lda,
-                const uint16_t* __restrict__ Bh, const uint16_t* __restrict__ Bl, int64_t ldb, int M, int N, int64_t K,
-                int tiles_n, int tiles, int64_t chunk, float* __restrict__ C, int64_t ldc, X3Epilogue ep) {
-  ep.seed = epoch_seed(ep.seed);
-  __shared__ __attribute__((aligned(16))) char lds[kWLds];   // the kernel's only LDS object (DMA waits)
-  // bijective XCD-major remap: consecutive work items (same A rows, same k chunk) share an L2
+// bijective XCD-major remap of the grid: consecutive work items (same A rows, same k chunk) share an L2
+__device__ __forceinline__ int x3w_work_item() {
   const int nwg = gridDim.x, bid = blockIdx.x;
   const int xq = nwg >> 3, xr = nwg & 7, xcd = bid & 7;
-  const int lw = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (bid >> 3);
+  return (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (bid >> 3);
+}
+
+// One workgroup's share of one problem: work item lw (k chunk lw / tiles, output tile lw % tiles). The body
+// of gemm_x3w_kernel (lw over its own grid) and of gemm_x3w_group_kernel (lw within the workgroup's problem).
+// The __restrict__ parameters matter: inlined, they give the LDS-DMA writes and the fragment reads alias scopes,
+// without which hipcc (ROCm 7.2) puts a vmcnt(0) before each batch of column-image (m/n-contiguous operand)
+// fragment reads — 2 per k step with one such operand, 3 with two, none for k-contiguous x k-contiguous —
+// draining the DMAs that the counted vmcnt(6) waits leave in flight; so it did while the body stood in the
+// kernel, and does again with the qualifiers removed. Nothing pins this to a compiler version: after a change
+// check every instantiation's loop with tools/asm_sync.py (profiles/r07/group_wgrad/README.md).
+template <bool AKC, bool BKC, int EPI, bool DROP>
+__device__ __forceinline__ void
+x3w_body(const uint16_t* __restrict__ Ah, const uint16_t* __restrict__ Al, int64_t lda,
+         const uint16_t* __restrict__ Bh, const uint16_t* __restrict__ Bl, int64_t ldb, int M, int N, int64_t K,
+         int tiles_n, int tiles, int64_t chunk, float* __restrict__ C, int64_t ldc, X3Epilogue ep, int lw) {
+  __shared__ __attribute__((aligned(16))) char lds[kWLds];   // the kernel's only LDS object (DMA waits)
   const int s = lw / tiles, t = lw - s * tiles;
   const int m0 = (t / tiles_n) * kWT2, n0 = (t % tiles_n) * kWT2;
   const int64_t k_lo = (int64_t)s * chunk;
@@ -1011,6 +1021,47 @@ gemm_x3w_kernel(const uint16_t* __restrict__ Ah, const uint16_t* __restrict__ Al
     }
     __syncthreads();
   }
+}
+
+template <bool AKC, bool BKC, int EPI, bool DROP>
+__global__ void __launch_bounds__(512, 1)
+gemm_x3w_kernel(const uint16_t* __restrict__ Ah, const uint16_t* __restrict__ Al, int64_t lda,
+                const uint16_t* __restrict__ Bh, const uint16_t* __restrict__ Bl, int64_t ldb, int M, int N, int64_t K,
+                int tiles_n, int tiles, int64_t chunk, float* __restrict__ C, int64_t ldc, X3Epilogue ep) {
+  ep.seed = epoch_seed(ep.seed);
+  x3w_body<AKC, BKC, EPI, DROP>(Ah, Al, lda, Bh, Bl, ldb, M, N, K, tiles_n, tiles, chunk, C, ldc, ep, x3w_work_item());
+}
+
+// Several weight-gradient problems (m/n-contiguous split operands, plain store to split-K slabs) in one
+// grid: problem p owns work items first[p] .. first[p + 1) of the XCD-remapped grid, tiles[p] x S[p] of
+// them, each the single-problem kernel's work item (k chunk, tile) of that problem with that problem's own
+// chunk, so every member runs the wide tile over a long k loop on its proportional share of the chip.
+constexpr int kX3GroupMax = 8;
+struct X3WProb {
+  const uint16_t* Ah;
+  const uint16_t* Al;
+  int64_t lda;
+  const uint16_t* Bh;
+  const uint16_t* Bl;
+  int64_t ldb;
+  int64_t K, chunk;
+  float* slabs;   // S slabs of M x N fp32 (ld = N)
+  int M, N, tiles_n, tiles, S, pad;
+};
+struct X3WGroup {
+  X3WProb p[kX3GroupMax];
+  int first[kX3GroupMax + 1];
+  int count;
+};
+
+__global__ void __launch_bounds__(512, 1) gemm_x3w_group_kernel(X3WGroup g) {
+  const int lw = x3w_work_item();
+  int e = 0;
+  while (e + 1 < g.count && lw >= g.first[e + 1]) ++e;
+  const X3WProb& q = g.p[e];
+  X3Epilogue ep{};
+  x3w_body<false, false, kEpiStore, false>(q.Ah, q.Al, q.lda, q.Bh, q.Bl, q.ldb, q.M, q.N, q.K, q.tiles_n, q.tiles,
+                                           q.chunk, q.slabs, q.N, ep, lw - g.first[e]);
 }
 #undef RQ_W_BAR
 #undef RQ_W_VM6
@@ -1280,6 +1331,11 @@ static bool x3w_plan(int64_t M, int64_t N, int64_t K, bool allow_split, X3Plan* 
 static int64_t x3w_span(int64_t R, int64_t K, int64_t ld, bool kc, int64_t chunk) {
   return kc ? (int64_t)kWT2 * ld + K : (chunk + 32) * ld + R;
 }
+// Both operands of a wide problem within the DMA's 32-bit byte offsets (the span at the largest chunk, K:
+// a split only shortens it): what x3_prepare and the group planner (x3_group_plan) both require.
+static bool x3w_spans_ok(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, bool a_kc, bool b_kc) {
+  return x3w_span(M, K, lda, a_kc, K) < (1ll << 30) && x3w_span(N, K, ldb, b_kc, K) < (1ll << 30);
+}
 
 // The wide kernel runs when both operands are split planes, the (layout, epilogue) pair is
 // instantiated (every layout for the plain store; the fused MLP chain's layouts otherwise), the shape
@@ -1415,9 +1471,8 @@ static int x3_prepare(const rq_gemm_desc& d, hipStream_t s, X3Call* c, bool dry 
   const int flags = d.flags;
   X3Plan pl = x3_plan(M, N, K, flags, true, epilogue);
   X3Plan pw;
-  // (the span at the largest chunk, K: a forced split count below only shortens it)
   const bool wide = x3w_choose(M, N, K, asp, bsp, a_kcontig, b_kcontig, epilogue, flags, &pw) &&
-                    x3w_span(M, K, lda, a_kcontig, K) < (1ll << 30) && x3w_span(N, K, ldb, b_kcontig, K) < (1ll << 30);
+                    x3w_spans_ok(M, N, K, lda, ldb, a_kcontig, b_kcontig);
   if (wide) pl = pw;
   // a tuned plan: RQ_GEMM_SPLIT(S) forces the split-K count on the kernel the policy picked
   const int forced_s = (flags >> RQ_GEMM_SPLIT_SHIFT) & RQ_GEMM_SPLIT_MASK;
@@ -1661,6 +1716,180 @@ static bool x3_pair_launch(const X3Call& c1, const X3Call& c2, hipStream_t s) {
   return t64 ? x3_pair_ts<64>(k1, c1, c2, grid, pad, s, n1) : x3_pair_ts<128>(k1, c1, c2, grid, 0u, s, n1);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Grouped weight gradients (gemm_x3w_group_kernel): the dW = g^T x problems of one MLP chain share the batch
+// as K and nothing in the backward waits for them, so they can share one launch in which each member takes
+// its proportional share of the chip on the wide tile, instead of each filling 256 CUs alone (the big layer
+// in many short chunks, the small ones on the 128- / 64-tile kernels at 2-4x the LDS fill per MFMA).
+// The plan: one step budget T (k steps of 32 per workgroup) for every member, S_p = ceil(K / 32 T) chunks
+// each, the whole group in one round of workgroups.
+// ---------------------------------------------------------------------------------------------
+// k steps per grouped workgroup at least: the wide loop's prologue and epilogue cost about 20 steps' worth
+// (profiles/r06/gemm_diag/wgrad_policy.jsonl: 512 x 256 x 65,536 at S = 128, 16 steps per workgroup, 65.9 us
+// against 62.4 us on the 128-tile kernel; at 49 steps the wide tile wins), so a budget under 32 steps is
+// mostly ramp. Never below the wide kernel's own kX3WMinSteps.
+constexpr int kX3GMinSteps = 32;
+static_assert(kX3GMinSteps >= kX3WMinSteps, "the group's step budget respects the wide kernel's minimum");
+// Rows (K) from which the model may group. Measured at the RQ-VAE's 65,536 rows only (profiles/r07/group_wgrad);
+// the decoder's 40..11,332-row chains pair each weight gradient with its data gradient (gemm_x3_pair_kernel),
+// which a grouped member gives up and the model does not price: they stay ungrouped until measured.
+constexpr int64_t kX3GMinK = 32768;
+
+struct X3GroupPlan {
+  int n;                       // members sharing the launch (0: no group)
+  bool in[kX3GroupMax];
+  X3Plan pl[kX3GroupMax];      // a member's wide plan (tiles, S, chunk)
+};
+
+// A problem the group kernel can run: split m/n-contiguous operands, plain store, whole k steps, no kernel
+// policy of its own, and the wide kernel's operand conditions (dims % 8 by x3_prepare; x3w_spans_ok).
+static bool x3_group_member(const rq_gemm_desc& d, const X3Call& c) {
+  return !c.trivial && c.asp && c.bsp && !c.a_kc && !c.b_kc && c.epilogue == kEpiStore && (c.flags & 0xFFFF) == 0 &&
+         c.K % 32 == 0 && c.M % 8 == 0 && c.N % 8 == 0 && d.ldc == c.N &&
+         x3w_spans_ok(c.M, c.N, c.K, c.xa.lda, c.xa.ldb, false, false);
+}
+
+// Modelled time (us) of the members `in` at step budget T, with x3_plan_time's constants: one round of wide
+// workgroups of at most T steps each, every member's slabs written and read back, one reduction launch.
+// < 0: the group does not fit one round.
+static double x3_group_time(const X3Call* c, int count, const bool* in, int64_t T, X3Plan* pl) {
+  const int64_t cus = resident_slots() / 2;
+  int64_t wgs = 0, steps = 0;
+  double slab = 0;
+  for (int i = 0; i < count; ++i) {
+    if (!in[i]) continue;
+    const int64_t nk = c[i].K / 32;
+    pl[i] = x3_plan_s(c[i].M, c[i].N, c[i].K, (nk + T - 1) / T, true);
+    wgs += (int64_t)pl[i].tiles * pl[i].S;
+    steps = std::max(steps, pl[i].chunk / 32);
+    slab += (double)(2 * pl[i].S) * (double)(c[i].M * c[i].N) * 4.0;
+  }
+  if (wgs > cus) return -1.0;
+  return (double)kWT2 * kWT2 * 32.0 * (double)steps / (kX3Rate2 * kX3WSpeed * 1e6) + slab / kX3SlabBpus + kX3ReduceUs;
+}
+
+// Best budget for the members `in`: the modelled saving (us) against their separate plans, <= 0 when
+// grouping them does not pay or cannot run in one round.
+static double x3_group_gain(const X3Call* c, int count, const bool* in, X3Plan* best) {
+  int n = 0;
+  int64_t K = -1;
+  double apart = 0;
+  for (int i = 0; i < count; ++i) {
+    if (!in[i]) continue;
+    if (K >= 0 && c[i].K != K) return 0;
+    K = c[i].K;
+    apart += x3_plan_time(c[i].pl, c[i].M, c[i].N, c[i].wide);
+    ++n;
+  }
+  if (n < 2 || K < kX3GMinK) return 0;
+  double tbest = -1;
+  X3Plan pl[kX3GroupMax] = {};
+  for (int64_t T = kX3GMinSteps; T <= K / 32; ++T) {
+    const double t = x3_group_time(c, count, in, T, pl);
+    if (t >= 0 && (tbest < 0 || t < tbest)) {
+      tbest = t;
+      for (int i = 0; i < count; ++i)
+        if (in[i]) best[i] = pl[i];
+    }
+  }
+  return tbest < 0 ? 0 : apart - tbest;
+}
+
+// Which of the problems share one grouped launch. Members that carry an explicit split count (RQ_GEMM_SPLIT)
+// are grouped as told: the only way rq_gemm_bf16x3_group itself groups (model = false). The model's common
+// step budget gives the members other split counts than their separate plans, which changes the fp32
+// summation order of their results (RQ-VAE step: 5.7 % faster, loss after 25 steps 1.1e-4 off the ungrouped
+// run's, profiles/r07/group_wgrad), so taking its plan is the caller's decision: rq_gemm_bf16x3_group_plan
+// reports it (model = true) and the caller passes the counts back as explicit ones. The model drops one
+// member at a time while that raises the modelled saving (a mostly empty tile, 128 x 64, costs the group a
+// whole tile's steps and stays in its own launch), and groups only when the rest beats its separate plans.
+static X3GroupPlan x3_group_plan(const rq_gemm_desc* d, const X3Call* c, int count, bool model) {
+  X3GroupPlan g{};
+  if (count < 2 || count > kX3GroupMax) return g;
+  bool el[kX3GroupMax] = {}, forced = false;
+  for (int i = 0; i < count; ++i) {
+    if (d[i].flags & RQ_GEMM_NO_GROUP) return g;
+    el[i] = x3_group_member(d[i], c[i]);
+    forced = forced || ((d[i].flags >> RQ_GEMM_SPLIT_SHIFT) & RQ_GEMM_SPLIT_MASK) > 0;
+  }
+  if (forced) {
+    for (int i = 0; i < count; ++i) {
+      const int fs = (d[i].flags >> RQ_GEMM_SPLIT_SHIFT) & RQ_GEMM_SPLIT_MASK;
+      if (!el[i] || fs < 2) continue;
+      const X3Plan p = x3_plan_s(c[i].M, c[i].N, c[i].K, fs, true);
+      if (p.S < 2) continue;
+      g.in[i] = true;
+      g.pl[i] = p;
+      ++g.n;
+    }
+  } else if (model) {
+    double gain = x3_group_gain(c, count, el, g.pl);
+    for (;;) {
+      int drop = -1;
+      X3Plan pl[kX3GroupMax] = {};
+      for (int j = 0; j < count; ++j) {
+        if (!el[j]) continue;
+        el[j] = false;
+        const double gj = x3_group_gain(c, count, el, pl);
+        el[j] = true;
+        if (gj > gain) {
+          gain = gj;
+          drop = j;
+        }
+      }
+      if (drop < 0) break;
+      el[drop] = false;
+      gain = x3_group_gain(c, count, el, g.pl);
+    }
+    if (gain > 0)
+      for (int i = 0; i < count; ++i) {
+        g.in[i] = el[i] && g.pl[i].S >= 2;
+        g.n += g.in[i];
+      }
+    if (g.n != (int)std::count(el, el + count, true)) g.n = 0;   // an unsplit member: the plan does not hold
+  }
+  if (g.n < 2) {
+    g.n = 0;
+    for (int i = 0; i < count; ++i) g.in[i] = false;
+  }
+  return g;
+}
+
+static int x3_group_launch(const rq_gemm_desc* d, const X3Call* c, int count, const X3GroupPlan& g, hipStream_t s) {
+  X3WGroup w{};
+  int n = 0, first = 0;
+  for (int i = 0; i < count; ++i) {
+    if (!g.in[i]) continue;
+    const X3Plan& pl = g.pl[i];
+    const size_t need = (size_t)pl.S * (size_t)(c[i].M * c[i].N) * sizeof(float);
+    RQ_CHECK_ARG(d[i].workspace != nullptr && d[i].ws_bytes >= need && ((uintptr_t)d[i].workspace) % 16 == 0,
+                 "rq_gemm_bf16x3_group: member %d needs workspace %zu >= %zu bytes", i, d[i].ws_bytes, need);
+    RQ_CHECK_ARG(pl.chunk % 32 == 0 && (int64_t)(pl.S - 1) * pl.chunk < c[i].K, "rq_gemm_bf16x3_group: bad plan");
+    X3WProb& q = w.p[n];
+    q.Ah = static_cast<const uint16_t*>(c[i].xa.A);
+    q.Al = static_cast<const uint16_t*>(c[i].xa.Al);
+    q.lda = c[i].xa.lda;
+    q.Bh = static_cast<const uint16_t*>(c[i].xa.B);
+    q.Bl = static_cast<const uint16_t*>(c[i].xa.Bl);
+    q.ldb = c[i].xa.ldb;
+    q.K = c[i].K;
+    q.chunk = pl.chunk;
+    q.slabs = static_cast<float*>(d[i].workspace);
+    q.M = (int)c[i].M;
+    q.N = (int)c[i].N;
+    q.tiles_n = pl.tiles_n;
+    q.tiles = pl.tiles;
+    q.S = pl.S;
+    w.first[n++] = first;
+    first += pl.tiles * pl.S;
+  }
+  w.first[n] = first;
+  w.count = n;
+  hipLaunchKernelGGL(gemm_x3w_group_kernel, dim3((unsigned)first), dim3(512), 0, s, w);
+  RQ_LAUNCH_CHECK("gemm_x3w_group_kernel");
+  return 0;
+}
+
 }  // namespace rqhip
 
 extern "C" {
@@ -1733,6 +1962,67 @@ int rq_gemm_bf16x3_pair_plan(const rq_gemm_desc* d) {
     if (x3_prepare(d[i], nullptr, &c[i], true) != 0) return 0;
   }
   return x3_pairable(c[0], c[1]) ? 1 : 0;
+}
+
+// Up to kX3GroupMax independent calls, the weight gradients of one MLP chain: the members that carry explicit
+// split counts (x3_group_plan; the model's counts come from rq_gemm_bf16x3_group_plan)
+// run in ONE gemm_x3w_group_kernel launch, each to split-K slabs in its own workspace; the others run as
+// rq_gemm_bf16x3_run would run them. A grouped member's slabs are reduced here in one rq_reduce_partials
+// launch (layout 0, accumulating where the call accumulates) or, for a deferring accumulating call, left to
+// the caller (splits[i] = its slab count, as rq_gemm_bf16x3_run reports).
+int rq_gemm_bf16x3_group(const rq_gemm_desc* d, int count, int* splits, void* stream) {
+  RQ_CHECK_ARG(d != nullptr && count >= 1 && count <= kX3GroupMax, "rq_gemm_bf16x3_group: 1..%d descriptors",
+               kX3GroupMax);
+  hipStream_t s = (hipStream_t)stream;
+  X3Call c[kX3GroupMax];
+  for (int i = 0; i < count; ++i) {
+    if (splits) splits[i] = 0;
+    const int rc = x3_prepare(d[i], s, &c[i]);
+    if (rc) return rc;
+  }
+  const X3GroupPlan g = x3_group_plan(d, c, count, false);
+  if (g.n) {
+    const int rl = x3_group_launch(d, c, count, g, s);
+    if (rl) return rl;
+  }
+  const float* P[kX3GroupMax];
+  float* out[kX3GroupMax];
+  int64_t n[kX3GroupMax];
+  int S[kX3GroupMax], layout[kX3GroupMax], acc[kX3GroupMax], nr = 0;
+  for (int i = 0; i < count; ++i) {
+    if (c[i].trivial) continue;
+    if (!g.in[i]) {
+      const int rl = x3_launch(c[i], s);
+      if (rl) return rl;
+      const int rp = x3_post(c[i], splits ? splits + i : nullptr, s);
+      if (rp) return rp;
+    } else if (c[i].defer && c[i].accumulate && splits) {
+      splits[i] = g.pl[i].S;
+    } else {
+      P[nr] = static_cast<const float*>(d[i].workspace);
+      out[nr] = c[i].C;
+      n[nr] = c[i].M * c[i].N;
+      S[nr] = g.pl[i].S;
+      layout[nr] = 0;
+      acc[nr++] = c[i].accumulate != 0;
+    }
+  }
+  return nr ? rq_reduce_partials(nr, P, out, n, S, layout, acc, stream) : 0;
+}
+
+int rq_gemm_bf16x3_group_plan(const rq_gemm_desc* d, int count, int* splits) {
+  if (splits)
+    for (int i = 0; i < count && i < kX3GroupMax; ++i) splits[i] = 0;
+  if (!d || count < 2 || count > kX3GroupMax) return 0;
+  X3Call c[kX3GroupMax];
+  for (int i = 0; i < count; ++i) {
+    if (d[i].M <= 0 || d[i].N <= 0 || d[i].K <= 0) return 0;
+    if (x3_prepare(d[i], nullptr, &c[i], true) != 0) return 0;
+  }
+  const X3GroupPlan g = x3_group_plan(d, c, count, true);
+  if (splits)
+    for (int i = 0; i < count; ++i) splits[i] = g.in[i] ? g.pl[i].S : 0;
+  return g.n;
 }
 
 // Deferred partial reductions, many in one launch: out_i[j] (+)= sum_s P_i[s n_i + j] for every entry i,

@@ -55,6 +55,8 @@ _SIGS = {
     "rq_ce_loss_bwd": ([_P, _I64, _I64, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P], _I),
     "rq_gemm_bf16x3_pair": ([_P, _P, _P], _I),
     "rq_gemm_bf16x3_pair_plan": ([_P], _I),
+    "rq_gemm_bf16x3_group": ([_P, _I, _P, _P], _I),
+    "rq_gemm_bf16x3_group_plan": ([_P, _I, _P], _I),
     "rq_segment_sum_multi_workspace": ([_I, _P, _P, _I64], _SZ),
     "rq_segment_sum_multi": ([_I, _P, _P, _P, _P, _P, _I64, _P, _P, _SZ, _P], _I),
     "rq_split_bf16x3": ([_P, _I64, _P, _P, _P], _I),

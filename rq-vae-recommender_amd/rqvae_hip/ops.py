@@ -432,6 +432,7 @@ def _wgrad_result(weight, spec, result):
 # time model's choice): set only by kernel-vs-kernel tests and A/B probes through gemm_policy(); the library
 # itself keeps no state — the flags travel in every descriptor.
 GEMM_ONLY_128, GEMM_ONLY_64, GEMM_FORCE_WIDE, GEMM_NO_WIDE, GEMM_MASKED, GEMM_NO_PAIR = 1, 2, 4, 8, 16, 32
+GEMM_NO_GROUP = 64   # an MLP chain's weight gradients never share a launch (gemm_x3_group)
 GEMM_SPLIT_SHIFT, GEMM_SPLIT_MASK = 16, 0xFFF
 
 
@@ -442,16 +443,16 @@ _GEMM_POLICY = {"flags": 0}
 
 
 class _Policy:
-    def __init__(self, store, flags):
-        self.store, self.flags = store, int(flags)
+    def __init__(self, store, flags, key="flags"):
+        self.store, self.flags, self.key = store, (int(flags) if key == "flags" else flags), key
 
     def __enter__(self):
-        self.prev = self.store["flags"]
-        self.store["flags"] = self.flags
+        self.prev = self.store[self.key]
+        self.store[self.key] = self.flags
         return self
 
     def __exit__(self, *exc):
-        self.store["flags"] = self.prev
+        self.store[self.key] = self.prev
         return False
 
 
@@ -596,6 +597,73 @@ def gemm_x3_pair(spec1: dict, spec2: dict):
     return _x3_result(c1, splits[0]), _x3_result(c2, splits[1])
 
 
+def gemm_x3_group(specs):
+    """The weight gradients of one MLP chain (keyword dicts of gemm_x3's arguments, at most 8) through
+    rq_gemm_bf16x3_group: the members its planner picks — or every member with an explicit split count
+    (flags=gemm_split(S)) — share ONE wide-tile launch, the rest run as gemm_x3 would. Results as gemm_x3's
+    up to the fp32 summation order of the split-K chunks. Returns the list of results."""
+    import ctypes
+    cs = [_x3_setup(**sp) for sp in specs]
+    D = _desc_type()
+    n = len(cs)
+    arr = (D * n)(*[D(*c.fields) for c in cs])
+    splits = (ctypes.c_int * n)(*([0] * n))
+    args = ("rq_gemm_bf16x3_group", arr, n, splits, stream_handle(cs[0].dev))
+    if TIMER.wants("gemm_bf16x3"):
+        TIMER.around("gemm_group:" + "+".join(c.key for c in cs), call, *args)
+    else:
+        call(*args)
+    return [_x3_result(c, splits[i]) for i, c in enumerate(cs)]
+
+
+# Grouping of the chains' weight gradients (_mlp_backward), off by default: "plan" = take the time model's plan
+# (group_wgrads()), "S" = explicit split counts (group_splits()).
+_GROUP = {"S": None, "plan": False}
+_GROUP_CACHE = {}
+
+
+def group_splits(S) -> _Policy:
+    """`with ops.group_splits(S): ...` — every MLP chain backward inside groups its groupable weight
+    gradients with S split-K chunks each (an int, or one count per member in launch order: last layer
+    first), whatever the time model says (tests, probes)."""
+    return _Policy(_GROUP, S, key="S")
+
+
+def group_wgrads(enable: bool = True) -> _Policy:
+    """`with ops.group_wgrads(): ...` — every MLP chain backward inside runs the weight gradients that
+    rq_gemm_bf16x3_group_plan's time model groups (gemm_group_choice) in one launch. Off by default: the plan
+    gives those gradients other split counts than their separate launches, so their fp32 summation order —
+    the last bits of dW — changes (profiles/r07/group_wgrad: the RQ-VAE step 5.7 % faster, the loss after 25
+    steps 1.1e-4 off)."""
+    return _Policy(_GROUP, bool(enable), key="plan")
+
+
+def gemm_group_choice(shapes, K: int):
+    """Split counts rq_gemm_bf16x3_group gives the weight gradients dW_i (M_i, N_i) = shapes[i] over K rows,
+    split m/n-contiguous operands: the explicit counts of group_splits() as the run will use them, else the
+    time model's plan under the current gemm_policy; a list with 0 for a member left out of the grouped launch
+    (all 0: no group). Host-only (rq_gemm_bf16x3_group_plan), memoised."""
+    import ctypes
+    force = _GROUP["S"]
+    n = len(shapes)
+    if isinstance(force, (list, tuple)):
+        force = tuple(int(s) for s in force)
+        if len(force) != n:
+            raise RqHipError(f"group_splits: {len(force)} counts for {n} grouped weight gradients")
+    key = (tuple(shapes), int(K), _GEMM_POLICY["flags"], force)
+    res = _GROUP_CACHE.get(key)
+    if res is None:
+        D = _desc_type()
+        fl = [_GEMM_POLICY["flags"] | (gemm_split(force if isinstance(force, int) else force[i]) if force else 0)
+              for i in range(n)]
+        arr = (D * n)(*[D(A_lo=16, lda=M, B_lo=16, ldb=N, M=M, N=N, K=K, ldc=N, ldh=N, flags=fl[i])
+                        for i, (M, N) in enumerate(shapes)])
+        splits = (ctypes.c_int * n)(*([0] * n))
+        _lib.load().rq_gemm_bf16x3_group_plan(arr, n, splits)
+        res = _GROUP_CACHE[key] = [int(s) for s in splits]
+    return res
+
+
 _PAIR_RESPLIT = True   # False: a paired weight gradient keeps the split count it is planned with alone (A/B)
 _RESPLIT_CACHE = {}
 
@@ -613,7 +681,7 @@ def _bwd_pair(dspec: dict, wspec: dict):
     when that is fewer slabs than its own plan and the pair still spans more than one round of workgroups —
     equal-length workgroups instead of a tail of short ones, and fewer slabs (measured on the paired launches of
     the decoder's 11k-row qkv / MLP-up layers: 152 -> 127 and 93 -> 85 us, tools/pair_split_probe.py)."""
-    if _PAIR_RESPLIT and _GEMM_POLICY["flags"] == 0 and wspec.get("flags") is None and \
+    if _PAIR_RESPLIT and (_GEMM_POLICY["flags"] & ~GEMM_NO_GROUP) == 0 and wspec.get("flags") is None and \
             int(wspec.get("epilogue", EPI_STORE)) == EPI_STORE:
         key = (_spec_key(dspec), _spec_key(wspec))
         S = _RESPLIT_CACHE.get(key)
@@ -822,9 +890,36 @@ def _mlp_backward(gcur, x_in, wsp, zs, hs, rows: int, p: float, seeds, need_w, n
     n = len(wsp)
     dws = [None] * n
     dx = None
+    # the weight gradients that share one grouped launch (gemm_x3_group) under group_wgrads() or
+    # group_splits(): decided from the shapes alone, so a gradient returned to autograd and one added into
+    # its flat bucket take the same path
+    cand = [i for i in reversed(range(n)) if need_w[i] and (i < n - 1 or isinstance(gcur, Split)) and
+            (i > 0 or isinstance(x_in, Split))][:8]
+    grouped, gspecs = {}, []
+    if len(cand) > 1 and not (_GEMM_POLICY["flags"] & GEMM_NO_GROUP) and \
+            (_GROUP["plan"] or _GROUP["S"] is not None):   # opt-in: grouping re-partitions K
+        gs = gemm_group_choice([tuple(wsp[i].hi.shape) for i in cand], rows)
+        grouped = {i: s_ for i, s_ in zip(cand, gs) if s_ > 0}
     for i in reversed(range(n)):
         O, I = wsp[i].hi.shape
         inp = x_in if i == 0 else hs[i - 1]
+        if i in grouped:   # its data gradient alone; the weight gradient waits for the group's last member
+            from . import dp
+            sink = dp.direct_grad(weights[i])
+            spec = dict(a=gcur, a_kcontig=False, b=inp, b_kcontig=False, M=O, N=I, K=rows,
+                        flags=_GEMM_POLICY["flags"] | gemm_split(grouped[i]))
+            if sink is not None:
+                spec.update(out=sink, accumulate=True, defer=dp.defer_ok(weights[i]))
+            gspecs.append((i, spec))
+            if len(gspecs) == len(grouped):
+                for (j, sp), res in zip(gspecs, gemm_x3_group([sp for _, sp in gspecs])):
+                    dws[j] = _wgrad_result(weights[j], sp, res)
+            if i > 0:
+                gcur = gemm_x3(a=gcur, a_kcontig=True, b=wsp[i], b_kcontig=False, M=rows, N=I, K=O,
+                               epilogue=EPI_SILU_BWD, Z=zs[i - 1], p=p, seed=seeds[i - 1])
+            elif need_x:
+                dx = gemm_x3(a=gcur, a_kcontig=True, b=wsp[0], b_kcontig=False, M=rows, N=I, K=O)
+            continue
         if i > 0:
             dspec = dict(a=gcur, a_kcontig=True, b=wsp[i], b_kcontig=False, M=rows, N=I, K=O, epilogue=EPI_SILU_BWD,
                          Z=zs[i - 1], p=p, seed=seeds[i - 1])
