@@ -95,7 +95,12 @@ int rq_rmsnorm_bwd(const float* x, const float* w, const float* rstd, const floa
  * modules/model.py:128-129 `self.do(self.norm(...))`): y = keep * scale * rmsnorm(x), keep drawn from
  * a counter-based generator keyed by `seed` (element e of y keeps iff word e of SplitMix64(seed) >=
  * round(p 2^32); kept values scaled by 1/(1-p)), so the backward regenerates the mask from
- * (seed, e) instead of storing it. p = 0 is plain RMSNorm. */
+ * (seed, e) instead of storing it. p = 0 is plain RMSNorm.
+ * The generator, for every `seed` argument of this header: element e (row-major: r D + c here) takes 32-bit
+ * word e & 1 (low word first) of mix(key + ((e >> 1) + 1) G), mix = SplitMix64's finaliser, G =
+ * 0x9E3779B97F4A7C15, key = seed + epoch * 0xD6E8FEB86659FD93 (rq_seed_epoch_set). Raw seeds that differ by a
+ * multiple of G therefore give the SAME mask shifted by two elements per multiple: pass mixed keys (a 64-bit
+ * finaliser over whatever identifies the mask), as rqvae_hip.ops.next_seed does, never base + i. */
 int rq_rmsnorm_dropout_fwd(const float* x, const float* w, int64_t B, int64_t D, float eps, float p, uint64_t seed,
                            float* y, float* rstd, void* stream);
 /* Its backward, with two fusions and a deferral: gres (NULL or B x D) is added to gx — the gradient that
@@ -126,7 +131,8 @@ int rq_rmsnorm2_dropout_bwd(const float* x, const float* w1, const float* w2, co
  *   rq_silu_dropout_bwd  gz = SiLU'(z) * keep * scale * g
  *   rq_dropout_add_fwd   out = h + Dropout(y)          the block output (modules/transformer/model.py:82)
  *   rq_dropout_bwd       gy = keep * scale * g         (grad of y; h's grad is g itself)
- * rq_dropout_params returns the (threshold, scale) pair the kernels use for p. */
+ * rq_dropout_params returns the (threshold, scale) pair the kernels use for p. Seeds: mixed keys, see
+ * rq_rmsnorm_dropout_fwd (seeds a multiple of G apart give shifted copies of one mask). */
 int rq_dropout_params(float p, uint32_t* thr, float* scale);
 int rq_silu_dropout_fwd(const float* z, int64_t n, float p, uint64_t seed, float* h, void* stream);
 int rq_silu_dropout_bwd(const float* g, const float* z, int64_t n, float p, uint64_t seed, float* gz, void* stream);

@@ -10,6 +10,8 @@ AdamLTy/RQ-VAE-Recommender @ 2025-07-25). Parity of this restatement is PINNED a
 golden vectors produced by importing the reference itself in the build container
 (`tests/golden/make_golden.py`, fixtures `tests/golden/*.npz`), see
 `tests/test_oracle.py`. Floating-point math is float32 numpy unless a docstring says
-otherwise; integer/index work is exact.
+otherwise; integer/index work is exact. One module restates this project instead: `dropout` is the
+kernels' counter-based mask generator (csrc/common.h), which has no counterpart in the reference (it
+draws masks from torch's generator and stores them); it is pinned by a published SplitMix64 sequence.
 """
-from . import quantize, jagged, attention, unique, rqvae, kmeans  # noqa: F401
+from . import quantize, jagged, attention, unique, rqvae, kmeans, dropout  # noqa: F401

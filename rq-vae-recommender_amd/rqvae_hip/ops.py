@@ -1466,19 +1466,40 @@ def rmsnorm(x: torch.Tensor, weight: torch.Tensor, eps: float, p: float = 0.0) -
 _SEED = {"base": None, "n": 0}
 
 
+_M64 = 0xFFFFFFFFFFFFFFFF
+
+
+def _mix64(z: int) -> int:
+    """SplitMix64's finaliser (a bijection of 64-bit words)."""
+    z &= _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
 def next_seed() -> int:
     """Key of the next dropout mask: a counter under torch.initial_seed(), mixed with the
     data-parallel rank so ranks that share a seed draw independent masks on their different shards
     (torch.manual_seed still makes every rank's masks reproducible; the generator is counter-based
     and masks are never stored). Host-only: no device sync. A hipGraph capture freezes the key of
-    each captured call."""
+    each captured call.
+
+    The key is a finalised function of (base, n, rank): each of the three is absorbed through a
+    64-bit mixing finaliser. The kernels draw counter c under key k as mix(k + (c + 1) G), so two keys
+    that differ by a multiple of G = 0x9E3779B97F4A7C15 give the same mask shifted by two elements per
+    counter — a key linear in base, n or rank can line that up (base + 1 did: adjacent torch seeds
+    drew shifted copies of each other's masks). After the finaliser no step in base, n or rank is an
+    additive step in the key (tests/test_dropout_mask_host.py: no two keys of the schedule within 2^32
+    counters)."""
     base = torch.initial_seed()
     if _SEED["base"] != base:
         _SEED["base"], _SEED["n"] = base, 0
     _SEED["n"] += 1
     rank = _dist.get_rank() if _dist.is_available() and _dist.is_initialized() else 0
-    return (base * 0x9E3779B97F4A7C15 + _SEED["n"] * 0xD1B54A32D192ED03 +
-            rank * 0x94D049BB133111EB) & 0x7FFFFFFFFFFFFFFF   # fits int64
+    k = _mix64(base + 0x9E3779B97F4A7C15)
+    k = _mix64(k + _SEED["n"] * 0xD1B54A32D192ED03)
+    k = _mix64(k + rank * 0x94D049BB133111EB)
+    return k & 0x7FFFFFFFFFFFFFFF   # fits int64
 
 
 def seed_epoch_advance(device=None) -> None:

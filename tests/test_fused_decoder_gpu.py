@@ -4,7 +4,9 @@ backward), the segmented-sum embedding backward, and packed-projection attention
 
 Dropout masks are random by design, so the reference recovers the kernel's mask from its output
 (kept elements are exactly value * 1/(1-p), dropped ones exactly 0) and checks the rest of the op
-and its gradient against torch with that mask; the keep rate is checked statistically."""
+and its gradient against torch with that mask; the keep rate is checked statistically.
+The mask itself is pinned in tests/test_dropout_mask_gpu.py (every kernel against the host restatement
+oracle/dropout.py, bit for bit) and tests/test_dropout_mask_host.py (its statistics and the key schedule)."""
 import numpy as np
 import pytest
 import torch
