@@ -533,6 +533,25 @@ int varlen_attn_bwd(const float* q, int64_t sq, const float* k, int64_t sk, cons
  *   longer than V is searched for its first token >= V (a sorted range loses only skipped children), and duplicate
  *   (beam, token) pairs of a bad table give an unspecified choice among them, never an access outside a buffer.
  *   kprev > 1024 or k > 1024: -22.
+ * rq_beam_expand_sampled: one step of stochastic beam search over the trie (Kool, van Hoof and Welling 2019, "Stochastic
+ *   Beams and Where to Find Them", Algorithm 1; the reference has no counterpart — its generate_next_sem_id(sample=True),
+ *   model.py:176-201, draws unconstrained classes and masks them afterwards): after the last level the k rows are k
+ *   distinct corpus rows drawn without replacement from the trie's distribution, in ONE launch per step. The arguments
+ *   are rq_beam_expand_blocked's (blocked may be NULL with n_blocked == 0) with noise (B kprev, V) fp32 Exponential(1)
+ *   draws in rq_beam_candidates' layout, parent_phi / parent_g (B, kprev) fp32 in place of parent_lp (both NULL iff
+ *   P == 0: taken as 0) and out_phi / out_g (B, k) fp32 in place of out_lp. A beam carries phi, its log-probability
+ *   under the locally renormalised trie distribution, and G, its perturbed score. For a live beam j and its candidates
+ *   C_j (the children rq_beam_expand_blocked scores: token in [0, V), not blocked), with l_c the full-V log-softmax
+ *   rq_beam_expand forms (bitwise): Lam_j = log sum_{c in C_j} exp(l_c) (max subtracted); phi_c = phi_j + (l_c - Lam_j);
+ *   Gt_c = phi_c - log(noise[b kprev + j][token_c]) (a noise value that is not a positive finite float is read as
+ *   FLT_MIN; noise is read at candidates only); Z_j = max_c Gt_c; v = G_j - Gt_c + log(1 - exp(Gt_c - Z_j));
+ *   G_c = G_j - max(v, 0) - log1p(exp(-|v|)), so the arg-max child keeps G_j exactly and every G_c <= G_j. l_c, Lam_j,
+ *   phi_j or G_j at -inf gives phi_c = G_c = -inf: still a candidate, above the dead rows. The k candidates of largest
+ *   G_c, ties to the lower beam then the lower token, descending: out_ids, out_parent, out_node and the dead rows as
+ *   rq_beam_expand, out_g, and out_phi = the phi_c that the winner's Gt_c was formed from (dead rows: both -inf). No NaN
+ *   is written for finite logits. V <= 4096, kprev V <= 8192, 1 <= k <= 8192, P < 64, 0 <= n_blocked <= 1024,
+ *   temperature > 0, else -22 (there is no wide form of this step); B == 0 returns 0 without a launch. No allocation,
+ *   no host read: capturable in a graph.
  * rq_trie_blocked_nodes: per user the trie nodes of every level 1..D whose leaves are ALL on the user's exclusion
  *   list, in ONE launch (one workgroup per user). items (B, H) int64 corpus indices, entries outside [0, n_items) are
  *   padding; item_leaf (n_items) int32 = each item's leaf (level-D node; items with equal rows share it, so
@@ -592,6 +611,12 @@ int rq_beam_expand_wide_blocked(const float* logits, float temperature, const in
                                 const float* parent_lp, int64_t B, int64_t kprev, int64_t V, int64_t P, int64_t k,
                                 int64_t* out_ids, float* out_lp, int32_t* out_parent, int32_t* out_node,
                                 const int32_t* blocked, int64_t n_blocked, void* stream);
+int rq_beam_expand_sampled(const float* logits, const float* noise, float temperature, const int32_t* node,
+                           const int32_t* child_off, int64_t n_nodes, const int32_t* tok, int64_t n_children,
+                           const int64_t* parents, const float* parent_phi, const float* parent_g, int64_t B,
+                           int64_t kprev, int64_t V, int64_t P, int64_t k, int64_t* out_ids, float* out_phi,
+                           float* out_g, int32_t* out_parent, int32_t* out_node, const int32_t* blocked,
+                           int64_t n_blocked, void* stream);
 int rq_trie_blocked_nodes(const int64_t* items, int64_t B, int64_t H, const int32_t* item_leaf, int64_t n_items,
                           int64_t n_leaves, const int32_t* const* leaf_anc, const int32_t* const* leaf_count,
                           const int64_t* n_nodes, int64_t D, int32_t* out, void* stream);

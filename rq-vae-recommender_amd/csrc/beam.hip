@@ -15,6 +15,9 @@
 //   beam_expand_wide_kernel the same step for up to 1,024 beams in and out, any kprev * V: the candidates are enumerated
 //                           from the trie instead of kept as a dense key array, the k best come from an exact radix
 //                           select and one LDS sort; bit for bit beam_expand_kernel's outputs where both take the shape.
+//   beam_expand_sampled_kernel  beam_expand_kernel's step for stochastic beam search: the k best by Gumbel-perturbed
+//                           score (the caller's Exponential(1) noise, top-down max conditioning) — after the last level
+//                           a draw of k corpus rows without replacement.
 //   score_paths_kernel     teacher-forced scoring of caller-named candidates: one workgroup per user, per step the
 //                           log-probability of every candidate's token in beam_expand_kernel's arithmetic (bitwise),
 //                           accumulated over the steps; on the last step each candidate's rank among the user's.
@@ -27,6 +30,8 @@
 //                           counters accumulated on the device with one atomic per (wave, counter).
 //   rank_hist_kernel        one wave per batch row: the rank of the first beam equal to the target in every column,
 //                           a workgroup-local histogram, one atomic per non-empty bin.
+#include <float.h>
+
 #include "common.h"
 
 namespace rqhip {
@@ -395,6 +400,206 @@ __global__ void __launch_bounds__(64 * kExpMaxWaves) beam_expand_kernel(
     const int end = min(max(child_off[nd + 1], 0), n_children);
     const int at = lower_bound(tok, min(max(child_off[nd], 0), n_children), end, v);
     out_node[b * k + r] = (at < end && tok[at] == v) ? at : -1;   // -1: an unsorted (bad) table
+  }
+}
+
+// ------------------------------------------------------------------------------------- expand, sampled
+// Stochastic beam search (Kool, van Hoof and Welling 2019): beam_expand_kernel's step with the k best taken by
+// perturbed score instead of by score, which makes the k leaves after the last step a draw of k items without
+// replacement from the trie's own distribution. A beam carries phi (its log-probability under the locally
+// renormalised trie distribution) and G (its perturbed score, a Gumbel(phi) value conditioned top-down on the maximum
+// of its siblings' subtrees). For a live beam j with (phi_j, G_j) and candidates C_j (its children that
+// beam_expand_kernel would score):
+//   l_c     = log_prob(...)                        the full-V log-softmax, beam_expand_kernel's bits
+//   Lam_j   = max l + log(sum_c exp(l_c - max l))  the candidates' mass: phi must sum to the parent's over C_j, or the
+//                                                  truncated-Gumbel step below is not exact
+//   phi_c   = phi_j + (l_c - Lam_j)
+//   Gt_c    = phi_c - log(e_c)                     e_c the caller's Exponential(1) draw: a Gumbel(phi_c) value
+//   Z_j     = max_c Gt_c
+//   v       = G_j - Gt_c + log(1 - exp(Gt_c - Z_j))
+//   G_c     = G_j - max(v, 0) - log1p(exp(-|v|))   the arg-max child: v = -inf, G_c = G_j exactly
+// log(1 - exp(d)) is log(-expm1(d)) for d > -log 2 and log1p(-exp(d)) below (the same quantity, without the
+// cancellation of 1 - exp(d) near d = 0). A child with l_c, Lam_j, phi_j or G_j at -inf carries phi_c = G_c = -inf: a
+// candidate still, above the absent entries. Phase 1 makes four passes over a beam's children (max l; sum; Gt and its
+// max; G), each lane over the same children every time; Gt waits in the child's own key[] slot between the last two.
+// key[] then holds score_key(G_c) and the selection is select_rounds, untouched. out_phi is not kept per candidate
+// (a second array of kprev V floats does not fit beside key[]): after the rounds a wave per output row forms its
+// parent's (statistics, Lam) again with sampled_beam — the one function phase 1 called, so the same bits — and phi_c
+// from them. LDS is beam_expand_kernel's.
+struct SampledBeam {
+  bool live;   // the node is in the level and has a candidate; wave-uniform
+  int lo, hi;  // its child range, clamped
+  RowStats st;
+  float lam, phi, g;
+};
+
+// f(c, v) for the candidates among the children [lo, hi) that this lane owns: c = lo + lane + 64 i, v = tok[c]
+template <bool BLOCKED, typename F>
+__device__ __forceinline__ void sampled_for_children(int lo, int hi, int lane, const int32_t* __restrict__ tok, int V,
+                                                     const int* blk, int n_blocked, F f) {
+  for (int c = lo + lane; c < hi; c += 64) {
+    const int v = tok[c];
+    if (v < 0 || v >= V) continue;
+    if constexpr (BLOCKED) {
+      const int at = lower_bound(blk, 0, n_blocked, c);
+      if (at < n_blocked && blk[at] == c) continue;
+    }
+    f(c, v);
+  }
+}
+
+__device__ __forceinline__ float wave_max(float m) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+  return m;
+}
+
+// Beam j of the user whose beam arrays start at nd0 / phi0 / g0 (NULL on the first step), x its logits row: its child
+// range, row statistics and Lam, formed by one wave. Phase 1 and the output phase both call this, for equal bits.
+template <bool BLOCKED>
+__device__ __forceinline__ SampledBeam sampled_beam(int j, int lane, const float* __restrict__ x, float temperature,
+                                                    const int32_t* __restrict__ nd0,
+                                                    const int32_t* __restrict__ child_off, int n_nodes,
+                                                    const int32_t* __restrict__ tok, int n_children,
+                                                    const float* __restrict__ phi0, const float* __restrict__ g0,
+                                                    int V, const int* blk, int n_blocked) {
+  SampledBeam s = {false, 0, 0, {0.f, 1.f, 0.f}, -INFINITY, -INFINITY, -INFINITY};
+  const int nd = nd0 ? nd0[j] : 0;
+  if (nd < 0 || nd >= n_nodes) return s;
+  s.lo = min(max(child_off[nd], 0), n_children);
+  s.hi = min(max(child_off[nd + 1], 0), n_children);
+  if (s.lo >= s.hi) return s;
+  s.st = row_stats<0>(
+      V, lane, [&](int, int v) { return x[v] / temperature; },
+      [&](int, int v, float m) { return x[v] / temperature - m; });
+  s.phi = phi0 ? phi0[j] : 0.0f;
+  s.g = g0 ? g0[j] : 0.0f;
+  float lmax = -INFINITY;
+  bool any = false;
+  sampled_for_children<BLOCKED>(s.lo, s.hi, lane, tok, V, blk, n_blocked, [&](int, int v) {
+    lmax = fmaxf(lmax, log_prob(x[v] / temperature - s.st.m, s.st));
+    any = true;
+  });
+  if (!__any(any)) return s;
+  s.live = true;
+  lmax = wave_max(lmax);
+  s.lam = -INFINITY;
+  if (lmax != -INFINITY) {   // wave-uniform
+    float sum = 0.f;
+    sampled_for_children<BLOCKED>(s.lo, s.hi, lane, tok, V, blk, n_blocked, [&](int, int v) {
+      sum += expf(log_prob(x[v] / temperature - s.st.m, s.st) - lmax);
+    });
+    s.lam = lmax + logf(group_sum<64>(sum));
+  }
+  return s;
+}
+
+// phi of the child with full-V log-probability l
+__device__ __forceinline__ float sampled_child_phi(float l, const SampledBeam& s) {
+  if (l == -INFINITY || s.lam == -INFINITY || s.phi == -INFINITY || s.g == -INFINITY) return -INFINITY;
+  return s.phi + (l - s.lam);
+}
+
+template <bool BLOCKED>
+__global__ void __launch_bounds__(64 * kExpMaxWaves) beam_expand_sampled_kernel(
+    const float* __restrict__ logits, const float* __restrict__ noise, float temperature,
+    const int32_t* __restrict__ node, const int32_t* __restrict__ child_off, int n_nodes,
+    const int32_t* __restrict__ tok, int n_children, const int64_t* __restrict__ parents,
+    const float* __restrict__ parent_phi, const float* __restrict__ parent_g, int kprev, int V, int P, int k,
+    int64_t* __restrict__ out_ids, float* __restrict__ out_phi, float* __restrict__ out_g,
+    int32_t* __restrict__ out_parent, int32_t* __restrict__ out_node, const int32_t* __restrict__ blocked,
+    int n_blocked) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nthr = blockDim.x, nwave = nthr >> 6;   // 4 or kExpMaxWaves waves (the host picks by kprev)
+  const int N = kprev * V;
+  uint32_t* key = reinterpret_cast<uint32_t*>(smem);   // [N rounded up to 4], then select_rounds' exchange
+  int* blk = reinterpret_cast<int*>(key + (N + 3) / 4 * 4 + 2 * kExpMaxWaves);   // BLOCKED: [n_blocked <= kBlockedMax]
+  const int64_t b = blockIdx.x;
+  const int32_t* nd0 = node ? node + b * kprev : nullptr;
+  const float* phi0 = parent_phi ? parent_phi + b * kprev : nullptr;
+  const float* g0 = parent_g ? parent_g + b * kprev : nullptr;
+
+  for (int e = tid; e < N; e += nthr) key[e] = 0;
+  if constexpr (BLOCKED) {
+    for (int e = tid; e < n_blocked; e += nthr) blk[e] = blocked[b * n_blocked + e];
+  }
+  __syncthreads();
+
+  for (int j = wave; j < kprev; j += nwave) {
+    const float* x = logits + (b * kprev + j) * V;
+    const SampledBeam s = sampled_beam<BLOCKED>(j, lane, x, temperature, nd0, child_off, n_nodes, tok, n_children,
+                                                phi0, g0, V, blk, n_blocked);
+    if (!s.live) continue;   // wave-uniform
+    const float* e = noise + (b * kprev + j) * V;
+    float z = -INFINITY;
+    sampled_for_children<BLOCKED>(s.lo, s.hi, lane, tok, V, blk, n_blocked, [&](int, int v) {
+      const float pc = sampled_child_phi(log_prob(x[v] / temperature - s.st.m, s.st), s);
+      float ev = e[v];
+      if (!(ev > 0.f && ev <= FLT_MAX)) ev = FLT_MIN;
+      const float gt = pc - logf(ev);   // -inf with pc
+      key[j * V + v] = __builtin_bit_cast(uint32_t, gt);
+      z = fmaxf(z, gt);
+    });
+    z = wave_max(z);
+    sampled_for_children<BLOCKED>(s.lo, s.hi, lane, tok, V, blk, n_blocked, [&](int, int v) {
+      const float gt = __builtin_bit_cast(float, key[j * V + v]);
+      float gc = -INFINITY;
+      if (gt != -INFINITY) {   // then s.g and z are finite, z >= gt
+        const float d = gt - z;
+        const float l1me = d > -0.6931472f ? logf(-expm1f(d)) : log1pf(-expf(d));   // -inf at d == 0
+        const float u = (s.g - gt) + l1me;
+        gc = s.g - fmaxf(u, 0.f) - log1pf(expf(-fabsf(u)));
+      }
+      key[j * V + v] = score_key(gc);   // never 0
+    });
+  }
+  __syncthreads();
+
+  select_rounds<kExpMaxWaves>(key, N, k, nthr, [&](int r, uint32_t wk, int wi) {
+    int64_t* o = out_ids + (b * k + r) * (P + 1);
+    if (wk == 0) {   // no candidate left: a dead row
+      if (tid <= P) o[tid] = -1;   // P < 64
+      if (tid == 0) {
+        out_phi[b * k + r] = -INFINITY;
+        out_g[b * k + r] = -INFINITY;
+        out_parent[b * k + r] = 0;
+        out_node[b * k + r] = -1;
+      }
+      return;
+    }
+    const int par = wi / V, v = wi - par * V;
+    if (tid < P) o[tid] = parents[(b * kprev + par) * P + tid];
+    if (tid == 0) {
+      o[P] = v;
+      out_g[b * k + r] = key_score(wk);
+      out_parent[b * k + r] = par;
+    }
+  });
+  __syncthreads();   // thread 0's rows (global) are visible to the workgroup
+  for (int r = tid; r < k; r += nthr) {
+    const int v = (int)out_ids[(b * k + r) * (P + 1) + P];
+    if (v < 0) continue;   // a dead row: its node is already -1
+    const int nd = node ? node[b * kprev + out_parent[b * k + r]] : 0;
+    const int end = min(max(child_off[nd + 1], 0), n_children);
+    const int at = lower_bound(tok, min(max(child_off[nd], 0), n_children), end, v);
+    out_node[b * k + r] = (at < end && tok[at] == v) ? at : -1;   // -1: an unsorted (bad) table
+  }
+  // the winner's phi: the value its Gt was formed from. A wave keeps the beam it formed last: on the first step every
+  // row has the root for its parent, and one formation per wave serves them all.
+  int last = -1;
+  SampledBeam s = {};
+  for (int r = wave; r < k; r += nwave) {
+    const int v = (int)out_ids[(b * k + r) * (P + 1) + P];
+    if (v < 0) continue;   // wave-uniform
+    const int par = out_parent[b * k + r];
+    const float* x = logits + (b * kprev + par) * V;
+    if (par != last) {   // wave-uniform
+      s = sampled_beam<BLOCKED>(par, lane, x, temperature, nd0, child_off, n_nodes, tok, n_children, phi0, g0, V, blk,
+                                n_blocked);
+      last = par;
+    }
+    if (lane == 0) out_phi[b * k + r] = sampled_child_phi(log_prob(x[v] / temperature - s.st.m, s.st), s);
   }
 }
 
@@ -1096,6 +1301,48 @@ int rq_beam_expand_wide_blocked(const float* logits, float temperature, const in
                                     out_node, blocked, n_blocked, stream);
   if (rc != 0 || B == 0) return rc;
   RQ_LAUNCH_CHECK("rq_beam_expand_wide_blocked");
+  return 0;
+}
+
+int rq_beam_expand_sampled(const float* logits, const float* noise, float temperature, const int32_t* node,
+                           const int32_t* child_off, int64_t n_nodes, const int32_t* tok, int64_t n_children,
+                           const int64_t* parents, const float* parent_phi, const float* parent_g, int64_t B,
+                           int64_t kprev, int64_t V, int64_t P, int64_t k, int64_t* out_ids, float* out_phi,
+                           float* out_g, int32_t* out_parent, int32_t* out_node, const int32_t* blocked,
+                           int64_t n_blocked, void* stream) {
+  const char* fn = "rq_beam_expand_sampled";
+  RQ_CHECK_ARG(B >= 0 && kprev >= 1 && V >= 1 && P >= 0 && P < 64, "%s: bad shape", fn);
+  RQ_CHECK_ARG(V <= rqhip::kBeamMaxV && kprev <= rqhip::kBeamMaxN && kprev * V <= rqhip::kBeamMaxN,
+               "%s: need V <= %d and kprev * V <= %d (kprev=%lld, V=%lld); the wide form (more than 32 beams at "
+               "V = 256) is not built for the sampled step",
+               fn, rqhip::kBeamMaxV, rqhip::kBeamMaxN, (long long)kprev, (long long)V);
+  RQ_CHECK_ARG(k >= 1 && k <= rqhip::kBeamMaxN, "%s: need 1 <= k <= %d (k=%lld)", fn, rqhip::kBeamMaxN, (long long)k);
+  RQ_CHECK_ARG(temperature > 0.f && temperature <= 3.0e38f, "%s: temperature must be positive", fn);
+  RQ_CHECK_ARG(n_nodes >= 0 && n_nodes < 0x7fffffff && n_children >= 0 && n_children <= 0x7fffffff,
+               "%s: bad trie level (n_nodes=%lld, n_children=%lld)", fn, (long long)n_nodes, (long long)n_children);
+  RQ_CHECK_ARG((P == 0) ? (!node && !parents && !parent_phi && !parent_g) : (node && parents && parent_phi && parent_g),
+               "%s: node, parents, parent_phi and parent_g are all NULL when P == 0, all given otherwise", fn);
+  RQ_CHECK_ARG(n_blocked >= 0 && n_blocked <= rqhip::kBlockedMax, "%s: need 0 <= n_blocked <= %d (n_blocked=%lld)", fn,
+               rqhip::kBlockedMax, (long long)n_blocked);
+  if (B == 0) return 0;
+  RQ_CHECK_ARG(B <= 0x7fffffff, "%s: too many batch elements", fn);
+  RQ_CHECK_ARG(logits && noise && child_off && (tok || n_children == 0) && out_ids && out_phi && out_g && out_parent &&
+                   out_node && (blocked || n_blocked == 0),
+               "%s: null pointer", fn);
+  const int waves = kprev > 4 ? rqhip::kExpMaxWaves : 4;
+  const size_t lds = (size_t)((kprev * V + 3) / 4 * 4 + 2 * rqhip::kExpMaxWaves) * sizeof(uint32_t);
+  if (n_blocked > 0) {
+    hipLaunchKernelGGL(rqhip::beam_expand_sampled_kernel<true>, dim3((unsigned)B), dim3(64 * waves),
+                       lds + (size_t)n_blocked * sizeof(int32_t), (hipStream_t)stream, logits, noise, temperature, node,
+                       child_off, (int)n_nodes, tok, (int)n_children, parents, parent_phi, parent_g, (int)kprev, (int)V,
+                       (int)P, (int)k, out_ids, out_phi, out_g, out_parent, out_node, blocked, (int)n_blocked);
+  } else {
+    hipLaunchKernelGGL(rqhip::beam_expand_sampled_kernel<false>, dim3((unsigned)B), dim3(64 * waves), lds,
+                       (hipStream_t)stream, logits, noise, temperature, node, child_off, (int)n_nodes, tok,
+                       (int)n_children, parents, parent_phi, parent_g, (int)kprev, (int)V, (int)P, (int)k, out_ids,
+                       out_phi, out_g, out_parent, out_node, (const int32_t*)nullptr, 0);
+  }
+  RQ_LAUNCH_CHECK(fn);
   return 0;
 }
 

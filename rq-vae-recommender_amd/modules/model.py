@@ -56,6 +56,13 @@ class Recommendation(NamedTuple):
     log_probas: Tensor   # (B, k)
 
 
+class SampledItems(NamedTuple):
+    item_ids: Tensor     # (B, k) int64 corpus indices, -1 for dead rows
+    sem_ids: Tensor      # (B, k, D)
+    log_probas: Tensor   # (B, k) fp32: log-probability under the renormalised trie distribution, -inf for dead rows
+    perturbed: Tensor    # (B, k) fp32: the Gumbel-perturbed scores the rows are ordered by, descending; [:, 0] == 0
+
+
 class Scores(NamedTuple):
     log_probas: Tensor   # (B, C) fp32, -inf for padding and for candidates the model cannot generate
     rank: Tensor         # (B, C) int32: each candidate's place among its user's, a permutation of 0..C-1
@@ -348,6 +355,53 @@ class EncoderDecoderRetrievalModel(nn.Module):
         node = node[:, :k].long()
         items = torch.where(node >= 0, trie.leaf_item[node.clamp_min(0)], -1)
         return Recommendation(item_ids=items, sem_ids=generated[:, :k], log_probas=log_probas[:, :k])
+
+    @eval_mode
+    @reset_encoder_cache
+    @torch.no_grad()
+    def sample_items(self, batch: TokenizedSeqBatch, k: int = 10, temperature: int = 1, incremental: bool = True,
+                     exclude_items: Tensor = None, generator: torch.Generator = None) -> SampledItems:
+        """k distinct corpus items per user, drawn without replacement in proportion to the model's own distribution
+        over the corpus: stochastic beam search (Kool, van Hoof and Welling 2019) over the prefix trie, k beams wide,
+        one hip_ops.beam_expand_sampled launch per token. The distribution is the trie's: at every node the model's
+        softmax(logits / temperature) renormalised over the node's children, so the items' probabilities sum to 1.
+        Rows are ordered by `perturbed` descending: row 0 is one exact draw, the first r rows a draw of r items
+        without replacement. A user with fewer than k distinct rows left gets dead rows at the end (item id -1, sem
+        ids -1, -inf). `log_probas` is log of that renormalised probability — NOT the full-V score recommend()
+        returns; score_items(batch, item_ids) gives the raw model score. `perturbed[:, 0]` is exactly 0 (the root's
+        perturbed score is pinned there; the order does not depend on it). exclude_items (B, H) int64, -1 as padding,
+        as recommend: the draw is from the corpus minus the listed rows (and the items sharing them).
+        The draws, part of the contract: at step i, on that step's logits (B, V) / (B * k, V),
+        exactly one torch.empty_like(logits).exponential_(generator=generator), steps in order, nothing else;
+        generator=None is the device's default generator. Needs k * num_embeddings <= 8192."""
+        limit = hip_ops.BEAM_MAX_N // self.num_embeddings
+        if not 1 <= k <= limit:
+            raise ValueError(f"sample_items: need 1 <= k and k * num_embeddings <= {hip_ops.BEAM_MAX_N}, that is "
+                             f"k <= {limit} at num_embeddings = {self.num_embeddings}; got k = {k}")
+        trie = self._constrained_trie("sample_items")
+        if trie.depth != self.sem_id_dim:
+            raise ValueError(f"sample_items: the corpus trie has depth {trie.depth}, the model generates "
+                             f"{self.sem_id_dim} tokens; items are the leaves of the full depth")
+        assert self.enable_generation, "Model generation is not enabled"
+        B = batch.sem_ids.shape[0]
+        blocked = None
+        if exclude_items is not None:
+            if exclude_items.dim() != 2 or exclude_items.shape[0] != B:
+                raise ValueError(f"sample_items: exclude_items must be (B, H) with B = {B} rows, got "
+                                 f"{tuple(exclude_items.shape)}")
+            blocked = self.inference_prefix_index.blocked_nodes(exclude_items)
+        generated, phi, g, parent, node = None, None, None, None, None
+        with self._step_logits(batch, incremental) as step:
+            for i in range(self.sem_id_dim):
+                logits = (step() if generated is None else step(generated.clamp_min(0), parent)).contiguous()
+                noise = torch.empty_like(logits).exponential_(generator=generator)
+                generated, phi, g, parent, node = hip_ops.beam_expand_sampled(
+                    logits, k, batch=B, child_off=trie.child_off[i], tok=trie.tok[i + 1], noise=noise, node=node,
+                    parents=generated, parent_phi=phi, parent_g=g, temperature=temperature,
+                    blocked=None if blocked is None else blocked[i])
+        node = node.long()
+        items = torch.where(node >= 0, trie.leaf_item[node.clamp_min(0)], -1)
+        return SampledItems(item_ids=items, sem_ids=generated, log_probas=phi, perturbed=g)
 
     @eval_mode
     @reset_encoder_cache

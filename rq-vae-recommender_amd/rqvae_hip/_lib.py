@@ -103,6 +103,8 @@ _SIGS = {
                             _I),
     "rq_beam_expand_wide_blocked": ([_P, _F, _P, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P,
                                      _P, _P, _I64, _P], _I),
+    "rq_beam_expand_sampled": ([_P, _P, _F, _P, _P, _I64, _P, _I64, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P,
+                                _P, _P, _P, _I64, _P], _I),
     "rq_trie_blocked_nodes": ([_P, _I64, _I64, _P, _I64, _I64, _P, _P, _P, _I64, _P, _P], _I),
     "rq_rank_hist": ([_P, _P, _I64, _I64, _I64, _P, _P], _I),
     "rq_score_paths": ([_P, _F, _P, _I64, _I64, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _P], _I),

@@ -9,6 +9,7 @@
   beam_candidates / beam_select / topk_hits  decoder evaluation: one beam step in two launches, Hit@k counters
   beam_expand                                constrained decoding: one beam step against the corpus' prefix trie, one launch
                                              (wide=: up to 1,024 beams per user)
+  beam_expand_sampled                        stochastic beam search: the same step by Gumbel-perturbed score, one launch
   trie_blocked_nodes / rank_hist             seen-item exclusion: a batch's blocked trie nodes of every level, one launch;
                                              first-match rank histogram (Recall / NDCG / MRR), one launch
 
@@ -2398,18 +2399,18 @@ def _beam_arg(t, dtype, what, name, shape=None):
     return t
 
 
-def _beam_parents(what, B, kprev, parents, parent_lp, *node) -> int:
+def _beam_parents(what, B, kprev, parents, parent_lp, *node, lp_name="parent_lp") -> int:
     """P of the beams so far — parents (B, kprev, P) int64, parent_lp (B, kprev) fp32 and, for beam_expand, node
     (B, kprev) int32: given together or not at all (P = 0)."""
     given = [t is not None for t in (*node, parents, parent_lp)]
     if any(given) != all(given):
-        raise RqHipError(f"{what}: {'node, ' if node else ''}parents and parent_lp go together")
+        raise RqHipError(f"{what}: {'node, ' if node else ''}parents and {lp_name} go together")
     if parents is None:
         return 0
     if parents.dim() != 3 or tuple(parents.shape[:2]) != (B, kprev):
         raise RqHipError(f"{what}: parents must be (B, kprev, P), got {tuple(parents.shape)}")
     _beam_arg(parents, torch.int64, what, "parents")
-    _beam_arg(parent_lp, torch.float32, what, "parent_lp", (B, kprev))
+    _beam_arg(parent_lp, torch.float32, what, lp_name, (B, kprev))
     if node:
         _beam_arg(node[0], torch.int32, what, "node", (B, kprev))
     return parents.shape[2]
@@ -2545,6 +2546,66 @@ def beam_expand(logits: torch.Tensor, k: int, *, batch: int, child_off: torch.Te
              child_off.numel() - 1, ptr(tok), tok.numel(), ptr(parents), ptr(parent_lp), B, kprev, V, P, int(k),
              ptr(out_ids), ptr(out_lp), ptr(out_parent), ptr(out_node), filt[0], filt[1], stream_handle(dev))
     return out_ids, out_lp, out_parent, out_node
+
+
+def beam_expand_sampled(logits: torch.Tensor, k: int, *, batch: int, child_off: torch.Tensor, tok: torch.Tensor,
+                        noise: torch.Tensor, node: torch.Tensor = None, parents: torch.Tensor = None,
+                        parent_phi: torch.Tensor = None, parent_g: torch.Tensor = None, temperature: float = 1.0,
+                        blocked: torch.Tensor = None):
+    """(out_ids (B, k, P + 1) int64, out_phi (B, k) fp32, out_g (B, k) fp32, out_parent (B, k) int32, out_node (B, k)
+    int32): one step of stochastic beam search against the corpus' prefix trie (rq_beam_expand_sampled; Kool, van Hoof
+    and Welling 2019) — beam_expand's step with the k best taken by Gumbel-perturbed score, so that k beams walked to
+    the leaves are a draw of k distinct corpus rows without replacement. logits, child_off, tok, node, parents,
+    temperature and blocked are beam_expand's. noise (B * kprev, V) fp32: Exponential(1) draws, one per (beam, class),
+    read only where a beam has a candidate. parent_phi / parent_g (B, kprev) fp32: the previous call's out_phi / out_g
+    (None with node and parents on the first step: 0). out_phi: each kept beam's log-probability under the trie
+    distribution renormalised at every node over the candidates (valid, not blocked); out_g: its perturbed score,
+    descending per user, never above its parent's, the best child of a beam inheriting the parent's exactly. Dead rows:
+    ids -1, phi = g = -inf, parent 0, node -1. One launch, no host read. The envelope is beam_expand's narrow one
+    (kprev * V <= 8192); there is no wide form."""
+    what = "beam_expand_sampled"
+    require_gpu(logits, noise, child_off, tok, node, parents, parent_phi, parent_g, blocked, what=what)
+    B = int(batch)
+    if logits.dim() != 2 or B < 0 or (B and logits.shape[0] % B):
+        raise RqHipError(f"{what}: logits must be (B * kprev, V)")
+    _beam_arg(logits, torch.float32, what, "logits")
+    R, V = logits.shape
+    kprev = R // B if B else 1
+    if noise is None:
+        raise RqHipError(f"{what}: noise (Exponential(1) draws, the shape of logits) is required")
+    _beam_arg(noise, torch.float32, what, "noise", (R, V))
+    if (parent_phi is None) != (parent_g is None):
+        raise RqHipError(f"{what}: parent_phi and parent_g go together")
+    P = _beam_parents(what, B, kprev, parents, parent_phi, node, lp_name="parent_phi")
+    if parents is not None and P == 0:
+        raise RqHipError(f"{what}: parents with P == 0; pass node, parents, parent_phi and parent_g as None on the "
+                         "first step")
+    if parent_g is not None:
+        _beam_arg(parent_g, torch.float32, what, "parent_g", (B, kprev))
+    if child_off.dim() != 1 or tok.dim() != 1 or child_off.numel() < 1:
+        raise RqHipError(f"{what}: child_off (n_nodes + 1) and tok (n_children) must be 1-D")
+    _beam_arg(child_off, torch.int32, what, "child_off")
+    _beam_arg(tok, torch.int32, what, "tok")
+    if V < 1 or V > BEAM_MAX_V or kprev * V > BEAM_MAX_N or not 1 <= int(k) <= BEAM_MAX_N:
+        raise RqHipError(f"{what}: outside the supported envelope V <= {BEAM_MAX_V}, kprev * V <= {BEAM_MAX_N}, "
+                         f"1 <= k <= {BEAM_MAX_N} (kprev={kprev}, V={V}, k={k}); the sampled step has no wide form")
+    n_blocked = 0
+    if blocked is not None:
+        if blocked.dim() != 2 or blocked.shape[0] != B or blocked.shape[1] > BLOCKED_MAX:
+            raise RqHipError(f"{what}: blocked must be (B, n_blocked <= {BLOCKED_MAX}), got {tuple(blocked.shape)}")
+        _beam_arg(blocked, torch.int32, what, "blocked")
+        n_blocked = blocked.shape[1]
+    dev = logits.device
+    out_ids = torch.empty((B, int(k), P + 1), device=dev, dtype=torch.int64)
+    out_phi = torch.empty((B, int(k)), device=dev, dtype=torch.float32)
+    out_g = torch.empty((B, int(k)), device=dev, dtype=torch.float32)
+    out_parent = torch.empty((B, int(k)), device=dev, dtype=torch.int32)
+    out_node = torch.empty((B, int(k)), device=dev, dtype=torch.int32)
+    call("rq_beam_expand_sampled", ptr(logits), ptr(noise), float(temperature), ptr(node), ptr(child_off),
+         child_off.numel() - 1, ptr(tok), tok.numel(), ptr(parents), ptr(parent_phi), ptr(parent_g), B, kprev, V, P,
+         int(k), ptr(out_ids), ptr(out_phi), ptr(out_g), ptr(out_parent), ptr(out_node),
+         ptr(blocked) if n_blocked else None, n_blocked, stream_handle(dev))
+    return out_ids, out_phi, out_g, out_parent, out_node
 
 
 BEAM_MAX_T = 8   # RQ_BEAM_MAX_T

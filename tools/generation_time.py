@@ -21,6 +21,8 @@ per beam, 256 classes, 4 sem-ID tokens; model dims of configs/decoder_amazon.gin
                after the first run rq_beam_expand_wide; `wide_excluded`: the same call with `excluded`'s histories;
                `recommend_forced`: `recommend` with every beam_expand call handed to the wide kernel (wide=True), so
                one trace of the two forms times both kernels at the 32-beam shape;
+               `sampled_items`: model.sample_items(k=10) — stochastic beam search, the incremental loop 10 beams wide
+               with one Exponential(1) draw and one rq_beam_expand_sampled launch per step;
   accumulate   TopKAccumulator.accumulate on the device (one rq_topk_hits launch) and the reference's logic
                (evaluate/metrics.py:15-28, restated below: 24 host reads per batch).
 
@@ -83,7 +85,7 @@ def main():
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=2)
     names = ["unfused", "fused", "incremental", "constrained", "excluded", "model", "acc_device", "acc_reference",
-             "recommend", "score", "score_full", "wide", "wide_excluded", "recommend_forced"]
+             "recommend", "score", "score_full", "wide", "wide_excluded", "recommend_forced", "sampled_items"]
     ap.add_argument("--score-candidates", type=int, default=100)
     ap.add_argument("--score-full-candidates", type=int, default=None)
     ap.add_argument("--beams", type=int, default=128, help="width of the `wide` / `wide_excluded` search")
@@ -175,7 +177,7 @@ def main():
              "wide": lambda: model.recommend(batch, k=min(100, args.beams), beams=args.beams),
              "wide_excluded": lambda: model.recommend(batch, k=min(100, args.beams), beams=args.beams,
                                                       exclude_items=seen),
-             "recommend_forced": recommend_forced}
+             "recommend_forced": recommend_forced, "sampled_items": lambda: model.sample_items(batch, k=10)}
     if args.only:
         forms = {args.only: forms[args.only]}
     elif args.forms:
@@ -195,7 +197,7 @@ def main():
            "min_max_ms": {n: [round(min(v), 4), round(max(v), 4)] for n, v in times.items() if v}}
     peak = {}
     for name in ("unfused", "fused", "incremental", "constrained", "excluded", "recommend", "score", "score_full",
-                 "wide", "wide_excluded", "recommend_forced"):
+                 "wide", "wide_excluded", "recommend_forced", "sampled_items"):
         if name in forms and not args.only:   # one more call of each generation form, alone after a peak reset
             torch.cuda.synchronize()
             torch.cuda.reset_peak_memory_stats(device)
