@@ -561,6 +561,27 @@ int varlen_attn_bwd(const float* q, int64_t sq, const float* k, int64_t sk, cons
  *   (D, B, H) int32: out[q - 1][b] = user b's blocked level-q nodes, ascending and distinct, then INT32_MAX. The
  *   ancestors of ascending leaves must be non-decreasing (a level's nodes are in key order). H <= 1024,
  *   D <= RQ_BEAM_MAX_T, else -22; B == 0 or H == 0 returns 0 without a launch.
+ * rq_beam_expand_filtered / rq_beam_expand_wide_filtered / rq_beam_expand_sampled_filtered: rq_beam_expand_blocked /
+ *   rq_beam_expand_wide_blocked / rq_beam_expand_sampled with a second, positive filter (catalogue filters: "only these
+ *   items"). The arguments are the counterpart's, then allowed (G, n_words) int32, n_words, G and group (B) int32.
+ *   allowed is the level-(P + 1) slice of rq_trie_allowed_nodes' bitmaps: bit (c & 31) of word (c >> 5) in row g is set
+ *   iff node c has an allowed item below it in group g. A child c of batch element b is a candidate iff it passes the
+ *   blocked test as before AND (group[b] is outside [0, G) — that user is unfiltered, -1 is the documented spelling —
+ *   OR bit c of row group[b] is set). A word index outside [0, n_words) reads as "not allowed" and is never read.
+ *   Everything else is the counterpart's kernel body, bit for bit (log-softmax, tie rule, dead rows, out_node, table
+ *   clamping, limits; in the sampled step Lam_j runs over the candidates that remain), so a filtered search is the
+ *   unfiltered search over the corpus of the allowed rows. The rows are read from global memory: no LDS is added.
+ *   blocked may be NULL with n_blocked == 0; allowed may be NULL when G n_words == 0; group is required. n_words or
+ *   G negative: -22.
+ * rq_trie_allowed_nodes: the filter tables of an item mask, in TWO launches and no host read. mask (G, n_items) bool:
+ *   mask[g][i] != 0 iff group g may be shown corpus item i. item_leaf (n_items) int32 and leaf_anc[q - 1] (n_leaves)
+ *   int32, q = 1..D, as rq_trie_blocked_nodes takes them (leaf_anc, n_nodes and out_bits are HOST arrays of D entries
+ *   copied into the kernel arguments). out_bits[q - 1]: (G, ceil(n_nodes[q - 1] / 32)) int32, the level-q bitmap of
+ *   every group; out_leaf_item (G, n_leaves) int64: the lowest allowed item whose row is that leaf, -1 if it has none
+ *   (filtering is by item: a row several items share stays reachable while one of them is allowed, and is reported
+ *   under the lowest allowed one). ALL outputs must arrive ZEROED. The reductions are bit OR and index MIN: the result
+ *   does not depend on the order, two runs give the same bits. A leaf outside [0, n_leaves) or an ancestor outside
+ *   [0, n_nodes) is skipped. D <= RQ_BEAM_MAX_T, else -22; G == 0 or n_leaves == 0 returns 0 without a launch.
  * rq_rank_hist: actual (B, D) int64 targets, topk (B, k, D) int64 beams; hist (k + 1) int64 is ACCUMULATED into:
  *   hist[r] += #rows whose first beam equal to the target in all D columns has rank r, hist[k] += #rows without one.
  *   Rows with actual[b][0] < 0 are skipped entirely. D <= 64, k <= 1024. D == 1 serves item ids.
@@ -620,6 +641,28 @@ int rq_beam_expand_sampled(const float* logits, const float* noise, float temper
 int rq_trie_blocked_nodes(const int64_t* items, int64_t B, int64_t H, const int32_t* item_leaf, int64_t n_items,
                           int64_t n_leaves, const int32_t* const* leaf_anc, const int32_t* const* leaf_count,
                           const int64_t* n_nodes, int64_t D, int32_t* out, void* stream);
+int rq_beam_expand_filtered(const float* logits, float temperature, const int32_t* node, const int32_t* child_off,
+                            int64_t n_nodes, const int32_t* tok, int64_t n_children, const int64_t* parents,
+                            const float* parent_lp, int64_t B, int64_t kprev, int64_t V, int64_t P, int64_t k,
+                            int64_t* out_ids, float* out_lp, int32_t* out_parent, int32_t* out_node,
+                            const int32_t* blocked, int64_t n_blocked, const int32_t* allowed, int64_t n_words,
+                            int64_t G, const int32_t* group, void* stream);
+int rq_beam_expand_wide_filtered(const float* logits, float temperature, const int32_t* node, const int32_t* child_off,
+                                 int64_t n_nodes, const int32_t* tok, int64_t n_children, const int64_t* parents,
+                                 const float* parent_lp, int64_t B, int64_t kprev, int64_t V, int64_t P, int64_t k,
+                                 int64_t* out_ids, float* out_lp, int32_t* out_parent, int32_t* out_node,
+                                 const int32_t* blocked, int64_t n_blocked, const int32_t* allowed, int64_t n_words,
+                                 int64_t G, const int32_t* group, void* stream);
+int rq_beam_expand_sampled_filtered(const float* logits, const float* noise, float temperature, const int32_t* node,
+                                    const int32_t* child_off, int64_t n_nodes, const int32_t* tok, int64_t n_children,
+                                    const int64_t* parents, const float* parent_phi, const float* parent_g, int64_t B,
+                                    int64_t kprev, int64_t V, int64_t P, int64_t k, int64_t* out_ids, float* out_phi,
+                                    float* out_g, int32_t* out_parent, int32_t* out_node, const int32_t* blocked,
+                                    int64_t n_blocked, const int32_t* allowed, int64_t n_words, int64_t G,
+                                    const int32_t* group, void* stream);
+int rq_trie_allowed_nodes(const bool* mask, int64_t G, int64_t n_items, const int32_t* item_leaf, int64_t n_leaves,
+                          const int32_t* const* leaf_anc, const int64_t* n_nodes, int64_t D, int32_t* const* out_bits,
+                          int64_t* out_leaf_item, void* stream);
 int rq_rank_hist(const int64_t* actual, const int64_t* topk, int64_t B, int64_t k, int64_t D, int64_t* hist,
                  void* stream);
 int rq_score_paths(const float* logits, float temperature, const int64_t* tokens, int64_t tok_stride_b,

@@ -11,7 +11,8 @@
 //                           element walks the corpus' prefix trie (only valid continuations are scored), the k
 //                           best in stable order, the parent gather and each winner's trie node. A second
 //                           instantiation (BLOCKED) skips the children found in a per-user sorted row of blocked
-//                           nodes (seen-item exclusion).
+//                           nodes (seen-item exclusion); FILTERED keeps only the children whose bit is set in the
+//                           user's row of a per-group node bitmap (catalogue filters), read from global memory.
 //   beam_expand_wide_kernel the same step for up to 1,024 beams in and out, any kprev * V: the candidates are enumerated
 //                           from the trie instead of kept as a dense key array, the k best come from an exact radix
 //                           select and one LDS sort; bit for bit beam_expand_kernel's outputs where both take the shape.
@@ -23,6 +24,8 @@
 //                           accumulated over the steps; on the last step each candidate's rank among the user's.
 //   trie_blocked_kernel     one workgroup per user: the trie nodes of every level whose leaves are all on the
 //                           user's exclusion list, sorted / deduplicated / counted in LDS.
+//   trie_allowed_kernel     catalogue filters: per group of an item mask the bitmap of every level's nodes with an
+//                           allowed item below them (bit OR) and every leaf's lowest allowed item (index MIN).
 //   beam_self_attn_kernel   incremental decoding: the newest token's causal self-attention over its beam's
 //                           ancestors, read in place from every step's packed qkv output through an
 //                           ancestor row table (no per-beam cache is gathered or appended).
@@ -326,15 +329,39 @@ __global__ void __launch_bounds__(kSelThreads) beam_select_kernel(
 // BLOCKED: `blocked` (B, n_blocked) int32 holds per user the level-(P + 1) nodes that are not candidates, ascending
 // and INT32_MAX-padded; the row is staged once into LDS after the exchange area and phase 1 looks every child index
 // up in it (a binary search over [0, n_blocked): an unsorted row filters the wrong children, never reads outside).
+// FILTERED: `allowed` holds G rows of n_words words, bit (c & 31) of word (c >> 5) set iff the level-(P + 1) node c has
+// an allowed item below it in that group; batch element b reads row group[b], or is unfiltered when group[b] is outside
+// [0, G). The rows stay in global memory (a level's row is a few KB at most, shared by the users of a group and
+// L2-resident): the LDS layout does not grow. A word outside [0, n_words) reads as "not allowed". Both filters may be
+// given: a candidate passes both.
 constexpr int kExpMaxWaves = 16;
 
-template <bool BLOCKED>
+struct AllowedBits {   // FILTERED's arguments; never read otherwise
+  const int32_t* bits;    // (G, n_words)
+  const int32_t* group;   // (B)
+  int n_words, G;
+};
+// batch element b's row of the bitmap and its length in words; -1 words: b is not filtered
+__device__ __forceinline__ int allowed_row(const AllowedBits& a, int64_t b, const int32_t*& row) {
+  const int g = a.group[b];
+  if (g < 0 || g >= a.G) return -1;
+  row = a.bits + (int64_t)g * a.n_words;
+  return a.n_words;
+}
+// c >= 0: a child index
+__device__ __forceinline__ bool allowed_child(const int32_t* __restrict__ row, int n_words, int c) {
+  if (n_words < 0) return true;
+  const int w = c >> 5;
+  return w < n_words && (((uint32_t)row[w] >> (c & 31)) & 1u);
+}
+
+template <bool BLOCKED, bool FILTERED>
 __global__ void __launch_bounds__(64 * kExpMaxWaves) beam_expand_kernel(
     const float* __restrict__ logits, float temperature, const int32_t* __restrict__ node,
     const int32_t* __restrict__ child_off, int n_nodes, const int32_t* __restrict__ tok, int n_children,
     const int64_t* __restrict__ parents, const float* __restrict__ parent_lp, int kprev, int V, int P, int k,
     int64_t* __restrict__ out_ids, float* __restrict__ out_lp, int32_t* __restrict__ out_parent,
-    int32_t* __restrict__ out_node, const int32_t* __restrict__ blocked, int n_blocked) {
+    int32_t* __restrict__ out_node, const int32_t* __restrict__ blocked, int n_blocked, AllowedBits allowed) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nthr = blockDim.x, nwave = nthr >> 6;   // 4 or kExpMaxWaves waves (the host picks by kprev)
@@ -342,6 +369,9 @@ __global__ void __launch_bounds__(64 * kExpMaxWaves) beam_expand_kernel(
   uint32_t* key = reinterpret_cast<uint32_t*>(smem);   // [N rounded up to 4], then select_rounds' exchange
   int* blk = reinterpret_cast<int*>(key + (N + 3) / 4 * 4 + 2 * kExpMaxWaves);   // BLOCKED: [n_blocked <= kBlockedMax]
   const int64_t b = blockIdx.x;
+  const int32_t* arow = nullptr;   // FILTERED: the user's bitmap row
+  int n_words = -1;
+  if constexpr (FILTERED) n_words = allowed_row(allowed, b, arow);
 
   for (int e = tid; e < N; e += nthr) key[e] = 0;
   if constexpr (BLOCKED) {
@@ -366,6 +396,9 @@ __global__ void __launch_bounds__(64 * kExpMaxWaves) beam_expand_kernel(
       if constexpr (BLOCKED) {
         const int at = lower_bound(blk, 0, n_blocked, c);
         if (at < n_blocked && blk[at] == c) continue;   // every leaf below this child is excluded for the user
+      }
+      if constexpr (FILTERED) {
+        if (!allowed_child(arow, n_words, c)) continue;   // no allowed item below this child
       }
       key[j * V + v] = score_key(log_prob(x[v] / temperature - st.m, st) + plp);
     }
@@ -434,15 +467,19 @@ struct SampledBeam {
 };
 
 // f(c, v) for the candidates among the children [lo, hi) that this lane owns: c = lo + lane + 64 i, v = tok[c]
-template <bool BLOCKED, typename F>
+template <bool BLOCKED, bool FILTERED, typename F>
 __device__ __forceinline__ void sampled_for_children(int lo, int hi, int lane, const int32_t* __restrict__ tok, int V,
-                                                     const int* blk, int n_blocked, F f) {
+                                                     const int* blk, int n_blocked, const int32_t* arow, int n_words,
+                                                     F f) {
   for (int c = lo + lane; c < hi; c += 64) {
     const int v = tok[c];
     if (v < 0 || v >= V) continue;
     if constexpr (BLOCKED) {
       const int at = lower_bound(blk, 0, n_blocked, c);
       if (at < n_blocked && blk[at] == c) continue;
+    }
+    if constexpr (FILTERED) {
+      if (!allowed_child(arow, n_words, c)) continue;
     }
     f(c, v);
   }
@@ -454,15 +491,27 @@ __device__ __forceinline__ float wave_max(float m) {
   return m;
 }
 
+// the position of the n-th set bit of m (n from 0); n >= popcount(m): some position below 64
+__device__ __forceinline__ int nth_set_bit(uint64_t m, int n) {
+  int pos = 0;
+#pragma unroll
+  for (int w = 32; w >= 1; w >>= 1) {
+    const int cnt = __popcll((unsigned long long)((m >> pos) & ((1ull << w) - 1)));
+    if (n >= cnt) { n -= cnt; pos += w; }
+  }
+  return pos;
+}
+
 // Beam j of the user whose beam arrays start at nd0 / phi0 / g0 (NULL on the first step), x its logits row: its child
 // range, row statistics and Lam, formed by one wave. Phase 1 and the output phase both call this, for equal bits.
-template <bool BLOCKED>
+template <bool BLOCKED, bool FILTERED>
 __device__ __forceinline__ SampledBeam sampled_beam(int j, int lane, const float* __restrict__ x, float temperature,
                                                     const int32_t* __restrict__ nd0,
                                                     const int32_t* __restrict__ child_off, int n_nodes,
                                                     const int32_t* __restrict__ tok, int n_children,
                                                     const float* __restrict__ phi0, const float* __restrict__ g0,
-                                                    int V, const int* blk, int n_blocked) {
+                                                    int V, const int* blk, int n_blocked, const int32_t* arow,
+                                                    int n_words) {
   SampledBeam s = {false, 0, 0, {0.f, 1.f, 0.f}, -INFINITY, -INFINITY, -INFINITY};
   const int nd = nd0 ? nd0[j] : 0;
   if (nd < 0 || nd >= n_nodes) return s;
@@ -476,7 +525,7 @@ __device__ __forceinline__ SampledBeam sampled_beam(int j, int lane, const float
   s.g = g0 ? g0[j] : 0.0f;
   float lmax = -INFINITY;
   bool any = false;
-  sampled_for_children<BLOCKED>(s.lo, s.hi, lane, tok, V, blk, n_blocked, [&](int, int v) {
+  sampled_for_children<BLOCKED, FILTERED>(s.lo, s.hi, lane, tok, V, blk, n_blocked, arow, n_words, [&](int, int v) {
     lmax = fmaxf(lmax, log_prob(x[v] / temperature - s.st.m, s.st));
     any = true;
   });
@@ -486,9 +535,37 @@ __device__ __forceinline__ SampledBeam sampled_beam(int j, int lane, const float
   s.lam = -INFINITY;
   if (lmax != -INFINITY) {   // wave-uniform
     float sum = 0.f;
-    sampled_for_children<BLOCKED>(s.lo, s.hi, lane, tok, V, blk, n_blocked, [&](int, int v) {
-      sum += expf(log_prob(x[v] / temperature - s.st.m, s.st) - lmax);
-    });
+    if constexpr (FILTERED) {
+      // The one place where a child's position matters: a lane's partial sum. Here lane t adds the terms of the ALLOWED
+      // children of rank t, t + 64, ... among the node's allowed children — the lanes on which the trie of the allowed
+      // rows alone holds the same children — so Lam (and with it phi and G) is bitwise that trie's. A child that is
+      // allowed but no candidate (blocked, token outside [0, V)) adds 0 on its lane, as it does there.
+      int before = 0;   // allowed children in the chunks so far
+      for (int c0 = s.lo; c0 < s.hi; c0 += 64) {   // wave-uniform
+        const int c = c0 + lane;
+        const bool in = c < s.hi && allowed_child(arow, n_words, c);
+        float term = 0.f;
+        if (in) {
+          const int v = tok[c];
+          bool cand = v >= 0 && v < V;
+          if constexpr (BLOCKED) {
+            const int at = lower_bound(blk, 0, n_blocked, c);
+            cand = cand && !(at < n_blocked && blk[at] == c);
+          }
+          if (cand) term = expf(log_prob(x[v] / temperature - s.st.m, s.st) - lmax);
+        }
+        const uint64_t m = __ballot(in);
+        const int n = __popcll((unsigned long long)m);
+        const int j = (lane - before) & 63;   // this lane takes the chunk's j-th allowed child, if it has one
+        const float t = __shfl(term, nth_set_bit(m, j), 64);
+        if (j < n) sum += t;
+        before += n;
+      }
+    } else {
+      sampled_for_children<BLOCKED, FILTERED>(s.lo, s.hi, lane, tok, V, blk, n_blocked, arow, n_words, [&](int, int v) {
+        sum += expf(log_prob(x[v] / temperature - s.st.m, s.st) - lmax);
+      });
+    }
     s.lam = lmax + logf(group_sum<64>(sum));
   }
   return s;
@@ -500,7 +577,7 @@ __device__ __forceinline__ float sampled_child_phi(float l, const SampledBeam& s
   return s.phi + (l - s.lam);
 }
 
-template <bool BLOCKED>
+template <bool BLOCKED, bool FILTERED>
 __global__ void __launch_bounds__(64 * kExpMaxWaves) beam_expand_sampled_kernel(
     const float* __restrict__ logits, const float* __restrict__ noise, float temperature,
     const int32_t* __restrict__ node, const int32_t* __restrict__ child_off, int n_nodes,
@@ -508,7 +585,7 @@ __global__ void __launch_bounds__(64 * kExpMaxWaves) beam_expand_sampled_kernel(
     const float* __restrict__ parent_phi, const float* __restrict__ parent_g, int kprev, int V, int P, int k,
     int64_t* __restrict__ out_ids, float* __restrict__ out_phi, float* __restrict__ out_g,
     int32_t* __restrict__ out_parent, int32_t* __restrict__ out_node, const int32_t* __restrict__ blocked,
-    int n_blocked) {
+    int n_blocked, AllowedBits allowed) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nthr = blockDim.x, nwave = nthr >> 6;   // 4 or kExpMaxWaves waves (the host picks by kprev)
@@ -519,6 +596,9 @@ __global__ void __launch_bounds__(64 * kExpMaxWaves) beam_expand_sampled_kernel(
   const int32_t* nd0 = node ? node + b * kprev : nullptr;
   const float* phi0 = parent_phi ? parent_phi + b * kprev : nullptr;
   const float* g0 = parent_g ? parent_g + b * kprev : nullptr;
+  const int32_t* arow = nullptr;   // FILTERED: the user's bitmap row
+  int n_words = -1;
+  if constexpr (FILTERED) n_words = allowed_row(allowed, b, arow);
 
   for (int e = tid; e < N; e += nthr) key[e] = 0;
   if constexpr (BLOCKED) {
@@ -528,12 +608,12 @@ __global__ void __launch_bounds__(64 * kExpMaxWaves) beam_expand_sampled_kernel(
 
   for (int j = wave; j < kprev; j += nwave) {
     const float* x = logits + (b * kprev + j) * V;
-    const SampledBeam s = sampled_beam<BLOCKED>(j, lane, x, temperature, nd0, child_off, n_nodes, tok, n_children,
-                                                phi0, g0, V, blk, n_blocked);
+    const SampledBeam s = sampled_beam<BLOCKED, FILTERED>(j, lane, x, temperature, nd0, child_off, n_nodes, tok,
+                                                          n_children, phi0, g0, V, blk, n_blocked, arow, n_words);
     if (!s.live) continue;   // wave-uniform
     const float* e = noise + (b * kprev + j) * V;
     float z = -INFINITY;
-    sampled_for_children<BLOCKED>(s.lo, s.hi, lane, tok, V, blk, n_blocked, [&](int, int v) {
+    sampled_for_children<BLOCKED, FILTERED>(s.lo, s.hi, lane, tok, V, blk, n_blocked, arow, n_words, [&](int, int v) {
       const float pc = sampled_child_phi(log_prob(x[v] / temperature - s.st.m, s.st), s);
       float ev = e[v];
       if (!(ev > 0.f && ev <= FLT_MAX)) ev = FLT_MIN;
@@ -542,7 +622,7 @@ __global__ void __launch_bounds__(64 * kExpMaxWaves) beam_expand_sampled_kernel(
       z = fmaxf(z, gt);
     });
     z = wave_max(z);
-    sampled_for_children<BLOCKED>(s.lo, s.hi, lane, tok, V, blk, n_blocked, [&](int, int v) {
+    sampled_for_children<BLOCKED, FILTERED>(s.lo, s.hi, lane, tok, V, blk, n_blocked, arow, n_words, [&](int, int v) {
       const float gt = __builtin_bit_cast(float, key[j * V + v]);
       float gc = -INFINITY;
       if (gt != -INFINITY) {   // then s.g and z are finite, z >= gt
@@ -595,8 +675,8 @@ __global__ void __launch_bounds__(64 * kExpMaxWaves) beam_expand_sampled_kernel(
     const int par = out_parent[b * k + r];
     const float* x = logits + (b * kprev + par) * V;
     if (par != last) {   // wave-uniform
-      s = sampled_beam<BLOCKED>(par, lane, x, temperature, nd0, child_off, n_nodes, tok, n_children, phi0, g0, V, blk,
-                                n_blocked);
+      s = sampled_beam<BLOCKED, FILTERED>(par, lane, x, temperature, nd0, child_off, n_nodes, tok, n_children, phi0, g0,
+                                          V, blk, n_blocked, arow, n_words);
       last = par;
     }
     if (lane == 0) out_phi[b * k + r] = sampled_child_phi(log_prob(x[v] / temperature - s.st.m, s.st), s);
@@ -631,9 +711,9 @@ struct WideBeams {   // LDS, per beam
 };
 
 // f(key, c) for every candidate of the user that thread tid owns: c its level-(P + 1) node
-template <bool BLOCKED, typename F>
+template <bool BLOCKED, bool FILTERED, typename F>
 __device__ __forceinline__ void wide_for_candidates(const WideBeams& s, const int* blk, int n_blocked,
-                                                    const float* __restrict__ x, float temperature,
+                                                    const int32_t* arow, int n_words, const float* __restrict__ x, float temperature,
                                                     const int32_t* __restrict__ tok, int kprev, int V, F f) {
   const int M = s.off[kprev];
   for (int e = threadIdx.x; e < M; e += kWideThreads) {
@@ -645,19 +725,22 @@ __device__ __forceinline__ void wide_for_candidates(const WideBeams& s, const in
       const int at = lower_bound(blk, 0, n_blocked, c);
       if (at < n_blocked && blk[at] == c) continue;
     }
+    if constexpr (FILTERED) {
+      if (!allowed_child(arow, n_words, c)) continue;
+    }
     const RowStats st = {s.m[j], s.sum[j], s.log_norm[j]};
     const uint32_t sk = score_key(log_prob(x[(int64_t)j * V + v] / temperature - st.m, st) + s.plp[j]);
     f(((uint64_t)sk << 32) | (uint32_t)~(uint32_t)(j * V + v), c);
   }
 }
 
-template <bool BLOCKED>
+template <bool BLOCKED, bool FILTERED>
 __global__ void __launch_bounds__(kWideThreads) beam_expand_wide_kernel(
     const float* __restrict__ logits, float temperature, const int32_t* __restrict__ node,
     const int32_t* __restrict__ child_off, int n_nodes, const int32_t* __restrict__ tok, int n_children,
     const int64_t* __restrict__ parents, const float* __restrict__ parent_lp, int kprev, int V, int P, int k,
     int64_t* __restrict__ out_ids, float* __restrict__ out_lp, int32_t* __restrict__ out_parent,
-    int32_t* __restrict__ out_node, const int32_t* __restrict__ blocked, int n_blocked) {
+    int32_t* __restrict__ out_node, const int32_t* __restrict__ blocked, int n_blocked, AllowedBits allowed) {
   __shared__ WideBeams s;
   __shared__ int hist[256];
   __shared__ uint64_t wkey[kWideMax];
@@ -669,6 +752,9 @@ __global__ void __launch_bounds__(kWideThreads) beam_expand_wide_kernel(
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t b = blockIdx.x;
   const float* x = logits + b * kprev * V;
+  const int32_t* arow = nullptr;   // FILTERED: the user's bitmap row
+  int n_words = -1;
+  if constexpr (FILTERED) n_words = allowed_row(allowed, b, arow);
 
   // 1. child ranges and their scan
   int lo = 0, cnt = 0;
@@ -716,7 +802,8 @@ __global__ void __launch_bounds__(kWideThreads) beam_expand_wide_kernel(
     if (tid < 256) hist[tid] = 0;
     __syncthreads();   // also: the statistics are written
     const uint64_t above = shift == 56 ? 0 : ~0ull << (shift + 8);   // the digits already fixed
-    wide_for_candidates<BLOCKED>(s, blk, n_blocked, x, temperature, tok, kprev, V, [&](uint64_t key, int) {
+    wide_for_candidates<BLOCKED, FILTERED>(s, blk, n_blocked, arow, n_words, x, temperature, tok, kprev, V,
+                                           [&](uint64_t key, int) {
       if ((key & above) == cut) atomicAdd(&hist[(int)(key >> shift) & 255], 1);
     });
     __syncthreads();
@@ -753,7 +840,8 @@ __global__ void __launch_bounds__(kWideThreads) beam_expand_wide_kernel(
   }
 
   // 3. collect, sort, write
-  wide_for_candidates<BLOCKED>(s, blk, n_blocked, x, temperature, tok, kprev, V, [&](uint64_t key, int c) {
+  wide_for_candidates<BLOCKED, FILTERED>(s, blk, n_blocked, arow, n_words, x, temperature, tok, kprev, V,
+                                         [&](uint64_t key, int c) {
     if (key >= cut) {
       const int at = atomicAdd(&n_won, 1);
       if (at < kWideMax) { wkey[at] = key; wnode[at] = c; }
@@ -1133,6 +1221,73 @@ __global__ void __launch_bounds__(kBlkThreads) trie_blocked_kernel(const int64_t
   }
 }
 
+// ------------------------------------------------------------------------------------- allowed trie nodes
+// Catalogue filters: mask (G, N) bool says which corpus items group g may be shown. Per group, level q = 1..D gets a
+// bitmap over its nodes (bit c & 31 of word c >> 5: node c has an allowed item below it) and every leaf the lowest
+// allowed item whose row it is. Both are reductions that do not depend on the order (bit OR, index MIN), so the result
+// is the same in every run. The outputs arrive zeroed.
+//   trie_allowed_kernel  a thread per 4 consecutive mask bytes (one dword load where the mask is 4-byte aligned), grid
+//                        stride. For an allowed item i of group g with leaf l: atomicMax of ~i into lowest[g][l] (the
+//                        largest ~i is the lowest i, and the zero it starts from is ~(-1): "none"), and for every level
+//                        the bit of l's ancestor — tested with a plain load first, the atomic OR only where it is still
+//                        clear: the upper levels have a handful of words per group, which every allowed item below
+//                        them would otherwise hit.
+//   trie_allowed_finish_kernel  lowest[g][l] = ~lowest[g][l] in place: the item, or -1.
+// Table values are never trusted for addressing: a leaf outside [0, n_leaves) or an ancestor outside [0, n_nodes) is
+// skipped.
+struct AllowedLevels {
+  const int32_t* anc[RQ_BEAM_MAX_T];   // (n_leaves): each leaf's level-q ancestor
+  int32_t* bits[RQ_BEAM_MAX_T];        // (G, n_words[q - 1]), zeroed
+  int n_nodes[RQ_BEAM_MAX_T];
+  int n_words[RQ_BEAM_MAX_T];          // ceil(n_nodes / 32)
+};
+
+constexpr int kAllowThreads = 256;
+constexpr int kAllowMaxBlocks = 2048;
+
+__global__ void __launch_bounds__(kAllowThreads) trie_allowed_kernel(const uint8_t* __restrict__ mask, int64_t G,
+                                                                    int64_t n_items,
+                                                                    const int32_t* __restrict__ item_leaf,
+                                                                    int n_leaves, AllowedLevels lv, int D,
+                                                                    unsigned long long* __restrict__ lowest) {
+  const int64_t total = G * n_items;
+  const bool aligned = (reinterpret_cast<uintptr_t>(mask) & 3) == 0;
+  const int64_t stride = (int64_t)gridDim.x * kAllowThreads * 4;
+  for (int64_t e0 = ((int64_t)blockIdx.x * kAllowThreads + threadIdx.x) * 4; e0 < total; e0 += stride) {
+    uint32_t m = 0;   // byte t: mask[e0 + t]
+    if (aligned && e0 + 4 <= total) {
+      m = *reinterpret_cast<const uint32_t*>(mask + e0);
+    } else {
+      for (int t = 0; t < 4; ++t)
+        if (e0 + t < total) m |= (uint32_t)mask[e0 + t] << (8 * t);
+    }
+    if (m == 0) continue;
+    for (int t = 0; t < 4; ++t) {
+      if (((m >> (8 * t)) & 0xffu) == 0) continue;
+      const int64_t g = (e0 + t) / n_items, item = (e0 + t) - g * n_items;
+      const int leaf = item_leaf[item];
+      if (leaf < 0 || leaf >= n_leaves) continue;
+      unsigned long long* lw = lowest + g * n_leaves + leaf;
+      const unsigned long long enc = ~(unsigned long long)item;
+      if (__atomic_load_n(lw, __ATOMIC_RELAXED) < enc) atomicMax(lw, enc);
+#pragma unroll 1
+      for (int q = 0; q < D; ++q) {
+        const int a = lv.anc[q][leaf];
+        if (a < 0 || a >= lv.n_nodes[q]) continue;
+        int32_t* w = lv.bits[q] + g * lv.n_words[q] + (a >> 5);
+        const int32_t bit = (int32_t)(1u << (a & 31));
+        if (!(__atomic_load_n(w, __ATOMIC_RELAXED) & bit)) atomicOr(w, bit);
+      }
+    }
+  }
+}
+
+__global__ void __launch_bounds__(kAllowThreads) trie_allowed_finish_kernel(unsigned long long* __restrict__ lowest,
+                                                                           int64_t n) {
+  const int64_t stride = (int64_t)gridDim.x * kAllowThreads;
+  for (int64_t i = (int64_t)blockIdx.x * kAllowThreads + threadIdx.x; i < n; i += stride) lowest[i] = ~lowest[i];
+}
+
 }  // namespace rqhip
 
 extern "C" {
@@ -1196,11 +1351,13 @@ int rq_beam_select(const int64_t* cand_ids, const float* cand_lp, const bool* va
                                n_cand, P, k, out_ids, out_lp, nullptr, stream);
 }
 
+// filtered: the _filtered entry points, whose bitmap arguments are checked here; the others pass false and nothing
 static int beam_expand_launch(const char* fn, bool wide, const float* logits, float temperature, const int32_t* node,
                               const int32_t* child_off, int64_t n_nodes, const int32_t* tok, int64_t n_children,
                               const int64_t* parents, const float* parent_lp, int64_t B, int64_t kprev, int64_t V,
                               int64_t P, int64_t k, int64_t* out_ids, float* out_lp, int32_t* out_parent,
-                              int32_t* out_node, const int32_t* blocked, int64_t n_blocked, void* stream) {
+                              int32_t* out_node, const int32_t* blocked, int64_t n_blocked, bool filtered,
+                              const int32_t* allowed, int64_t n_words, int64_t G, const int32_t* group, void* stream) {
   RQ_CHECK_ARG(B >= 0 && kprev >= 1 && V >= 1 && P >= 0 && P < 64, "%s: bad shape", fn);
   if (wide) {
     RQ_CHECK_ARG(V <= rqhip::kBeamMaxV && kprev <= rqhip::kWideMax && k >= 1 && k <= rqhip::kWideMax,
@@ -1219,37 +1376,41 @@ static int beam_expand_launch(const char* fn, bool wide, const float* logits, fl
                "%s: node, parents and parent_lp are all NULL when P == 0, all given otherwise", fn);
   RQ_CHECK_ARG(n_blocked >= 0 && n_blocked <= rqhip::kBlockedMax, "%s: need 0 <= n_blocked <= %d (n_blocked=%lld)", fn,
                rqhip::kBlockedMax, (long long)n_blocked);
+  RQ_CHECK_ARG(!filtered || (n_words >= 0 && n_words <= 0x7fffffff / 32 && G >= 0 && G <= 0x7fffffff),
+               "%s: bad bitmap (n_words=%lld, G=%lld)", fn, (long long)n_words, (long long)G);
   if (B == 0) return 0;
   RQ_CHECK_ARG(B <= 0x7fffffff, "%s: too many batch elements", fn);
   RQ_CHECK_ARG(logits && child_off && (tok || n_children == 0) && out_ids && out_lp && out_parent && out_node &&
-                   (blocked || n_blocked == 0),
+                   (blocked || n_blocked == 0) && (!filtered || (group && (allowed || n_words * G == 0))),
                "%s: null pointer", fn);
+  const rqhip::AllowedBits ab = {allowed, group, (int)n_words, (int)G};
+  const bool blk = n_blocked > 0;
+  if (!blk) { blocked = nullptr; n_blocked = 0; }
   if (wide) {   // static LDS, one shape of workgroup
-    if (n_blocked > 0) {
-      hipLaunchKernelGGL(rqhip::beam_expand_wide_kernel<true>, dim3((unsigned)B), dim3(rqhip::kWideThreads), 0,
-                         (hipStream_t)stream, logits, temperature, node, child_off, (int)n_nodes, tok, (int)n_children,
-                         parents, parent_lp, (int)kprev, (int)V, (int)P, (int)k, out_ids, out_lp, out_parent, out_node,
-                         blocked, (int)n_blocked);
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(rqhip::kWideThreads), 0, (hipStream_t)stream, logits,
+                         temperature, node, child_off, (int)n_nodes, tok, (int)n_children, parents, parent_lp, (int)kprev,
+                         (int)V, (int)P, (int)k, out_ids, out_lp, out_parent, out_node, blocked, (int)n_blocked, ab);
+    };
+    if (filtered) {
+      if (blk) launch(rqhip::beam_expand_wide_kernel<true, true>); else launch(rqhip::beam_expand_wide_kernel<false, true>);
     } else {
-      hipLaunchKernelGGL(rqhip::beam_expand_wide_kernel<false>, dim3((unsigned)B), dim3(rqhip::kWideThreads), 0,
-                         (hipStream_t)stream, logits, temperature, node, child_off, (int)n_nodes, tok, (int)n_children,
-                         parents, parent_lp, (int)kprev, (int)V, (int)P, (int)k, out_ids, out_lp, out_parent, out_node,
-                         (const int32_t*)nullptr, 0);
+      if (blk) launch(rqhip::beam_expand_wide_kernel<true, false>); else launch(rqhip::beam_expand_wide_kernel<false, false>);
     }
     return 0;
   }
   const int waves = kprev > 4 ? rqhip::kExpMaxWaves : 4;
-  const size_t lds = (size_t)((kprev * V + 3) / 4 * 4 + 2 * rqhip::kExpMaxWaves) * sizeof(uint32_t);
-  if (n_blocked > 0) {
-    hipLaunchKernelGGL(rqhip::beam_expand_kernel<true>, dim3((unsigned)B), dim3(64 * waves),
-                       lds + (size_t)n_blocked * sizeof(int32_t), (hipStream_t)stream, logits, temperature, node,
+  const size_t lds = (size_t)((kprev * V + 3) / 4 * 4 + 2 * rqhip::kExpMaxWaves) * sizeof(uint32_t) +
+                     (size_t)n_blocked * sizeof(int32_t);
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(64 * waves), lds, (hipStream_t)stream, logits, temperature, node,
                        child_off, (int)n_nodes, tok, (int)n_children, parents, parent_lp, (int)kprev, (int)V, (int)P,
-                       (int)k, out_ids, out_lp, out_parent, out_node, blocked, (int)n_blocked);
+                       (int)k, out_ids, out_lp, out_parent, out_node, blocked, (int)n_blocked, ab);
+  };
+  if (filtered) {
+    if (blk) launch(rqhip::beam_expand_kernel<true, true>); else launch(rqhip::beam_expand_kernel<false, true>);
   } else {
-    hipLaunchKernelGGL(rqhip::beam_expand_kernel<false>, dim3((unsigned)B), dim3(64 * waves), lds, (hipStream_t)stream,
-                       logits, temperature, node, child_off, (int)n_nodes, tok, (int)n_children, parents, parent_lp,
-                       (int)kprev, (int)V, (int)P, (int)k, out_ids, out_lp, out_parent, out_node,
-                       (const int32_t*)nullptr, 0);
+    if (blk) launch(rqhip::beam_expand_kernel<true, false>); else launch(rqhip::beam_expand_kernel<false, false>);
   }
   return 0;
 }
@@ -1260,7 +1421,7 @@ int rq_beam_expand(const float* logits, float temperature, const int32_t* node, 
                    float* out_lp, int32_t* out_parent, int32_t* out_node, void* stream) {
   const int rc = beam_expand_launch("rq_beam_expand", false, logits, temperature, node, child_off, n_nodes, tok, n_children,
                                     parents, parent_lp, B, kprev, V, P, k, out_ids, out_lp, out_parent, out_node,
-                                    nullptr, 0, stream);
+                                    nullptr, 0, false, nullptr, 0, 0, nullptr, stream);
   if (rc != 0 || B == 0) return rc;
   RQ_LAUNCH_CHECK("rq_beam_expand");
   return 0;
@@ -1273,7 +1434,7 @@ int rq_beam_expand_blocked(const float* logits, float temperature, const int32_t
                            const int32_t* blocked, int64_t n_blocked, void* stream) {
   const int rc = beam_expand_launch("rq_beam_expand_blocked", false, logits, temperature, node, child_off, n_nodes, tok,
                                     n_children, parents, parent_lp, B, kprev, V, P, k, out_ids, out_lp, out_parent,
-                                    out_node, blocked, n_blocked, stream);
+                                    out_node, blocked, n_blocked, false, nullptr, 0, 0, nullptr, stream);
   if (rc != 0 || B == 0) return rc;
   RQ_LAUNCH_CHECK("rq_beam_expand_blocked");
   return 0;
@@ -1285,7 +1446,7 @@ int rq_beam_expand_wide(const float* logits, float temperature, const int32_t* n
                         int64_t* out_ids, float* out_lp, int32_t* out_parent, int32_t* out_node, void* stream) {
   const int rc = beam_expand_launch("rq_beam_expand_wide", true, logits, temperature, node, child_off, n_nodes, tok,
                                     n_children, parents, parent_lp, B, kprev, V, P, k, out_ids, out_lp, out_parent,
-                                    out_node, nullptr, 0, stream);
+                                    out_node, nullptr, 0, false, nullptr, 0, 0, nullptr, stream);
   if (rc != 0 || B == 0) return rc;
   RQ_LAUNCH_CHECK("rq_beam_expand_wide");
   return 0;
@@ -1298,19 +1459,48 @@ int rq_beam_expand_wide_blocked(const float* logits, float temperature, const in
                                 const int32_t* blocked, int64_t n_blocked, void* stream) {
   const int rc = beam_expand_launch("rq_beam_expand_wide_blocked", true, logits, temperature, node, child_off, n_nodes,
                                     tok, n_children, parents, parent_lp, B, kprev, V, P, k, out_ids, out_lp, out_parent,
-                                    out_node, blocked, n_blocked, stream);
+                                    out_node, blocked, n_blocked, false, nullptr, 0, 0, nullptr, stream);
   if (rc != 0 || B == 0) return rc;
   RQ_LAUNCH_CHECK("rq_beam_expand_wide_blocked");
   return 0;
 }
 
-int rq_beam_expand_sampled(const float* logits, const float* noise, float temperature, const int32_t* node,
-                           const int32_t* child_off, int64_t n_nodes, const int32_t* tok, int64_t n_children,
-                           const int64_t* parents, const float* parent_phi, const float* parent_g, int64_t B,
-                           int64_t kprev, int64_t V, int64_t P, int64_t k, int64_t* out_ids, float* out_phi,
-                           float* out_g, int32_t* out_parent, int32_t* out_node, const int32_t* blocked,
-                           int64_t n_blocked, void* stream) {
-  const char* fn = "rq_beam_expand_sampled";
+int rq_beam_expand_filtered(const float* logits, float temperature, const int32_t* node, const int32_t* child_off,
+                            int64_t n_nodes, const int32_t* tok, int64_t n_children, const int64_t* parents,
+                            const float* parent_lp, int64_t B, int64_t kprev, int64_t V, int64_t P, int64_t k,
+                            int64_t* out_ids, float* out_lp, int32_t* out_parent, int32_t* out_node,
+                            const int32_t* blocked, int64_t n_blocked, const int32_t* allowed, int64_t n_words,
+                            int64_t G, const int32_t* group, void* stream) {
+  const int rc = beam_expand_launch("rq_beam_expand_filtered", false, logits, temperature, node, child_off, n_nodes, tok,
+                                    n_children, parents, parent_lp, B, kprev, V, P, k, out_ids, out_lp, out_parent,
+                                    out_node, blocked, n_blocked, true, allowed, n_words, G, group, stream);
+  if (rc != 0 || B == 0) return rc;
+  RQ_LAUNCH_CHECK("rq_beam_expand_filtered");
+  return 0;
+}
+
+int rq_beam_expand_wide_filtered(const float* logits, float temperature, const int32_t* node, const int32_t* child_off,
+                                 int64_t n_nodes, const int32_t* tok, int64_t n_children, const int64_t* parents,
+                                 const float* parent_lp, int64_t B, int64_t kprev, int64_t V, int64_t P, int64_t k,
+                                 int64_t* out_ids, float* out_lp, int32_t* out_parent, int32_t* out_node,
+                                 const int32_t* blocked, int64_t n_blocked, const int32_t* allowed, int64_t n_words,
+                                 int64_t G, const int32_t* group, void* stream) {
+  const int rc = beam_expand_launch("rq_beam_expand_wide_filtered", true, logits, temperature, node, child_off, n_nodes,
+                                    tok, n_children, parents, parent_lp, B, kprev, V, P, k, out_ids, out_lp, out_parent,
+                                    out_node, blocked, n_blocked, true, allowed, n_words, G, group, stream);
+  if (rc != 0 || B == 0) return rc;
+  RQ_LAUNCH_CHECK("rq_beam_expand_wide_filtered");
+  return 0;
+}
+
+static int beam_expand_sampled_launch(const char* fn, const float* logits, const float* noise, float temperature,
+                                      const int32_t* node, const int32_t* child_off, int64_t n_nodes,
+                                      const int32_t* tok, int64_t n_children, const int64_t* parents,
+                                      const float* parent_phi, const float* parent_g, int64_t B, int64_t kprev,
+                                      int64_t V, int64_t P, int64_t k, int64_t* out_ids, float* out_phi, float* out_g,
+                                      int32_t* out_parent, int32_t* out_node, const int32_t* blocked, int64_t n_blocked,
+                                      bool filtered, const int32_t* allowed, int64_t n_words, int64_t G,
+                                      const int32_t* group, void* stream) {
   RQ_CHECK_ARG(B >= 0 && kprev >= 1 && V >= 1 && P >= 0 && P < 64, "%s: bad shape", fn);
   RQ_CHECK_ARG(V <= rqhip::kBeamMaxV && kprev <= rqhip::kBeamMaxN && kprev * V <= rqhip::kBeamMaxN,
                "%s: need V <= %d and kprev * V <= %d (kprev=%lld, V=%lld); the wide form (more than 32 beams at "
@@ -1324,26 +1514,58 @@ int rq_beam_expand_sampled(const float* logits, const float* noise, float temper
                "%s: node, parents, parent_phi and parent_g are all NULL when P == 0, all given otherwise", fn);
   RQ_CHECK_ARG(n_blocked >= 0 && n_blocked <= rqhip::kBlockedMax, "%s: need 0 <= n_blocked <= %d (n_blocked=%lld)", fn,
                rqhip::kBlockedMax, (long long)n_blocked);
+  RQ_CHECK_ARG(!filtered || (n_words >= 0 && n_words <= 0x7fffffff / 32 && G >= 0 && G <= 0x7fffffff),
+               "%s: bad bitmap (n_words=%lld, G=%lld)", fn, (long long)n_words, (long long)G);
   if (B == 0) return 0;
   RQ_CHECK_ARG(B <= 0x7fffffff, "%s: too many batch elements", fn);
   RQ_CHECK_ARG(logits && noise && child_off && (tok || n_children == 0) && out_ids && out_phi && out_g && out_parent &&
-                   out_node && (blocked || n_blocked == 0),
+                   out_node && (blocked || n_blocked == 0) &&
+                   (!filtered || (group && (allowed || n_words * G == 0))),
                "%s: null pointer", fn);
+  const rqhip::AllowedBits ab = {allowed, group, (int)n_words, (int)G};
+  const bool blk = n_blocked > 0;
+  if (!blk) { blocked = nullptr; n_blocked = 0; }
   const int waves = kprev > 4 ? rqhip::kExpMaxWaves : 4;
-  const size_t lds = (size_t)((kprev * V + 3) / 4 * 4 + 2 * rqhip::kExpMaxWaves) * sizeof(uint32_t);
-  if (n_blocked > 0) {
-    hipLaunchKernelGGL(rqhip::beam_expand_sampled_kernel<true>, dim3((unsigned)B), dim3(64 * waves),
-                       lds + (size_t)n_blocked * sizeof(int32_t), (hipStream_t)stream, logits, noise, temperature, node,
-                       child_off, (int)n_nodes, tok, (int)n_children, parents, parent_phi, parent_g, (int)kprev, (int)V,
-                       (int)P, (int)k, out_ids, out_phi, out_g, out_parent, out_node, blocked, (int)n_blocked);
+  const size_t lds = (size_t)((kprev * V + 3) / 4 * 4 + 2 * rqhip::kExpMaxWaves) * sizeof(uint32_t) +
+                     (size_t)n_blocked * sizeof(int32_t);
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(64 * waves), lds, (hipStream_t)stream, logits, noise, temperature,
+                       node, child_off, (int)n_nodes, tok, (int)n_children, parents, parent_phi, parent_g, (int)kprev,
+                       (int)V, (int)P, (int)k, out_ids, out_phi, out_g, out_parent, out_node, blocked, (int)n_blocked, ab);
+  };
+  if (filtered) {
+    if (blk) launch(rqhip::beam_expand_sampled_kernel<true, true>);
+    else launch(rqhip::beam_expand_sampled_kernel<false, true>);
   } else {
-    hipLaunchKernelGGL(rqhip::beam_expand_sampled_kernel<false>, dim3((unsigned)B), dim3(64 * waves), lds,
-                       (hipStream_t)stream, logits, noise, temperature, node, child_off, (int)n_nodes, tok,
-                       (int)n_children, parents, parent_phi, parent_g, (int)kprev, (int)V, (int)P, (int)k, out_ids,
-                       out_phi, out_g, out_parent, out_node, (const int32_t*)nullptr, 0);
+    if (blk) launch(rqhip::beam_expand_sampled_kernel<true, false>);
+    else launch(rqhip::beam_expand_sampled_kernel<false, false>);
   }
   RQ_LAUNCH_CHECK(fn);
   return 0;
+}
+
+int rq_beam_expand_sampled(const float* logits, const float* noise, float temperature, const int32_t* node,
+                           const int32_t* child_off, int64_t n_nodes, const int32_t* tok, int64_t n_children,
+                           const int64_t* parents, const float* parent_phi, const float* parent_g, int64_t B,
+                           int64_t kprev, int64_t V, int64_t P, int64_t k, int64_t* out_ids, float* out_phi,
+                           float* out_g, int32_t* out_parent, int32_t* out_node, const int32_t* blocked,
+                           int64_t n_blocked, void* stream) {
+  return beam_expand_sampled_launch("rq_beam_expand_sampled", logits, noise, temperature, node, child_off, n_nodes, tok,
+                                    n_children, parents, parent_phi, parent_g, B, kprev, V, P, k, out_ids, out_phi, out_g,
+                                    out_parent, out_node, blocked, n_blocked, false, nullptr, 0, 0, nullptr, stream);
+}
+
+int rq_beam_expand_sampled_filtered(const float* logits, const float* noise, float temperature, const int32_t* node,
+                                    const int32_t* child_off, int64_t n_nodes, const int32_t* tok, int64_t n_children,
+                                    const int64_t* parents, const float* parent_phi, const float* parent_g, int64_t B,
+                                    int64_t kprev, int64_t V, int64_t P, int64_t k, int64_t* out_ids, float* out_phi,
+                                    float* out_g, int32_t* out_parent, int32_t* out_node, const int32_t* blocked,
+                                    int64_t n_blocked, const int32_t* allowed, int64_t n_words, int64_t G,
+                                    const int32_t* group, void* stream) {
+  return beam_expand_sampled_launch("rq_beam_expand_sampled_filtered", logits, noise, temperature, node, child_off,
+                                    n_nodes, tok, n_children, parents, parent_phi, parent_g, B, kprev, V, P, k, out_ids,
+                                    out_phi, out_g, out_parent, out_node, blocked, n_blocked, true, allowed, n_words, G,
+                                    group, stream);
 }
 
 int rq_score_paths(const float* logits, float temperature, const int64_t* tokens, int64_t tok_stride_b,
@@ -1398,6 +1620,43 @@ int rq_trie_blocked_nodes(const int64_t* items, int64_t B, int64_t H, const int3
   hipLaunchKernelGGL(rqhip::trie_blocked_kernel, dim3((unsigned)B), dim3(rqhip::kBlkThreads), 0, (hipStream_t)stream,
                      items, (int)H, Hp, item_leaf, n_items, (int)n_leaves, lv, (int)D, B, out);
   RQ_LAUNCH_CHECK("rq_trie_blocked_nodes");
+  return 0;
+}
+
+int rq_trie_allowed_nodes(const bool* mask, int64_t G, int64_t n_items, const int32_t* item_leaf, int64_t n_leaves,
+                          const int32_t* const* leaf_anc, const int64_t* n_nodes, int64_t D, int32_t* const* out_bits,
+                          int64_t* out_leaf_item, void* stream) {
+  RQ_CHECK_ARG(G >= 0 && D >= 1 && D <= RQ_BEAM_MAX_T, "rq_trie_allowed_nodes: need G >= 0, 1 <= D <= %d (G=%lld, D=%lld)",
+               RQ_BEAM_MAX_T, (long long)G, (long long)D);
+  RQ_CHECK_ARG(n_items >= 0 && n_leaves >= 0 && n_leaves < 0x7fffffff, "rq_trie_allowed_nodes: bad corpus size");
+  RQ_CHECK_ARG(n_items == 0 || G <= INT64_MAX / 8 / n_items, "rq_trie_allowed_nodes: mask too large");
+  RQ_CHECK_ARG(leaf_anc && n_nodes && out_bits, "rq_trie_allowed_nodes: null level array");
+  rqhip::AllowedLevels lv = {};
+  for (int64_t q = 0; q < D; ++q) {
+    RQ_CHECK_ARG(n_nodes[q] >= 0 && n_nodes[q] < 0x7fffffff, "rq_trie_allowed_nodes: level %lld has %lld nodes",
+                 (long long)(q + 1), (long long)n_nodes[q]);
+    RQ_CHECK_ARG((leaf_anc[q] || n_leaves == 0) && (out_bits[q] || n_nodes[q] == 0 || G == 0),
+                 "rq_trie_allowed_nodes: null table at level %lld", (long long)(q + 1));
+    lv.anc[q] = leaf_anc[q];
+    lv.bits[q] = out_bits[q];
+    lv.n_nodes[q] = (int)n_nodes[q];
+    lv.n_words[q] = (int)((n_nodes[q] + 31) / 32);
+  }
+  if (G == 0 || n_leaves == 0) return 0;
+  RQ_CHECK_ARG(out_leaf_item && (n_items == 0 || (mask && item_leaf)), "rq_trie_allowed_nodes: null pointer");
+  hipStream_t hs = (hipStream_t)stream;
+  auto blocks = [](int64_t threads) {
+    return (unsigned)std::min<int64_t>((threads + rqhip::kAllowThreads - 1) / rqhip::kAllowThreads,
+                                       rqhip::kAllowMaxBlocks);
+  };
+  unsigned long long* lowest = reinterpret_cast<unsigned long long*>(out_leaf_item);
+  if (n_items > 0) {
+    hipLaunchKernelGGL(rqhip::trie_allowed_kernel, dim3(blocks((G * n_items + 3) / 4)), dim3(rqhip::kAllowThreads), 0, hs,
+                       reinterpret_cast<const uint8_t*>(mask), G, n_items, item_leaf, (int)n_leaves, lv, (int)D, lowest);
+  }
+  hipLaunchKernelGGL(rqhip::trie_allowed_finish_kernel, dim3(blocks(G * n_leaves)), dim3(rqhip::kAllowThreads), 0, hs,
+                     lowest, G * n_leaves);
+  RQ_LAUNCH_CHECK("rq_trie_allowed_nodes");
   return 0;
 }
 

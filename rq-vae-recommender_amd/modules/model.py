@@ -232,7 +232,8 @@ class EncoderDecoderRetrievalModel(nn.Module):
     def generate_next_sem_id(self, batch: TokenizedSeqBatch, temperature: int = 1, top_k: bool = True, *,
                              fused: bool = False, sample: bool = True,
                              incremental: bool = False, constrained: bool = False,
-                             exclude_items: Tensor = None, beams: int = 32) -> GenerationOutput:
+                             exclude_items: Tensor = None, beams: int = 32, item_filter=None,
+                             filter_group: Tensor = None) -> GenerationOutput:
         """Beam-style decoding of the next item's L+1 sem-ID tokens (reference :149-245): per step
         sample 200 candidates per beam from softmax(logits / T), drop prefixes the verifier
         rejects (-10000), keep the top 32 cumulative log-probabilities. The encoder output is
@@ -254,7 +255,13 @@ class EncoderDecoderRetrievalModel(nn.Module):
         applied by beam_expand at every level, so no beam is spent on a prefix that only leads to listed items.
         beams (needs constrained=True and top_k=True): the search's width, 1..1024 beams per user instead of 32 — the
         returned tensors are (B, beams, L+1) / (B, beams); past 32 beams at V = 256 the steps run the wide expand
-        kernel (hip_ops.beam_expand(wide=None)), at 32 they are the launches they were."""
+        kernel (hip_ops.beam_expand(wide=None)), at 32 they are the launches they were.
+        item_filter (needs constrained=True): a catalogue filter — the search runs over the sub-corpus of the ALLOWED
+        items ("only what is in stock"), without a trie per filter. An ItemFilter (the tokenizer's item_filter(mask),
+        built once and reused) or a bool mask (N,) / (G, N) over corpus indices, turned into one per call. filter_group
+        (B,) integer: each user's group (row of the mask); -1 leaves a user unfiltered; None is group 0 for everyone,
+        which needs a one-group filter. Step i's beam_expand keeps only the children whose bit is set in
+        item_filter.bits[i]; it composes with exclude_items (a candidate passes both), beams and incremental."""
         if not 1 <= beams <= hip_ops.BEAM_WIDE_MAX:
             raise ValueError(f"generate_next_sem_id: need 1 <= beams <= {hip_ops.BEAM_WIDE_MAX}, got {beams}")
         if beams != 32 and not (constrained and top_k):
@@ -264,6 +271,8 @@ class EncoderDecoderRetrievalModel(nn.Module):
             raise ValueError("generate_next_sem_id: incremental=True requires fused=True")
         if exclude_items is not None and not constrained:
             raise ValueError("generate_next_sem_id: exclude_items requires constrained=True")
+        if (item_filter is not None or filter_group is not None) and not constrained:
+            raise ValueError("generate_next_sem_id: item_filter / filter_group require constrained=True")
         if constrained:
             if not fused:
                 raise ValueError("generate_next_sem_id: constrained=True requires fused=True")
@@ -273,7 +282,8 @@ class EncoderDecoderRetrievalModel(nn.Module):
         assert self.enable_generation, "Model generation is not enabled"
         if constrained:
             generated, log_probas, _ = self._generate_constrained(batch, temperature, beams if top_k else 1,
-                                                                  incremental, exclude_items)
+                                                                  incremental, exclude_items, item_filter,
+                                                                  filter_group)
             return GenerationOutput(sem_ids=generated.squeeze(), log_probas=log_probas.squeeze())
         if fused:
             return self._generate_sampled(batch, temperature, top_k, sample, incremental)
@@ -333,17 +343,55 @@ class EncoderDecoderRetrievalModel(nn.Module):
             raise ValueError(f"{what}: the corpus trie has depth {trie.depth} < sem_id_dim = {self.sem_id_dim}")
         return trie
 
+    def _item_filter(self, what: str, item_filter, filter_group, B: int, device):
+        """(ItemFilter, group (B,) int32 on the device) of a call's item_filter / filter_group arguments, or (None,
+        None) without a filter. A bool mask becomes an ItemFilter through the tokenizer (built per call); the groups
+        are converted on the device, nothing is read back."""
+        if item_filter is None:
+            if filter_group is not None:
+                raise ValueError(f"{what}: filter_group without item_filter")
+            return None, None
+        if isinstance(item_filter, Tensor):
+            item_filter = self.inference_prefix_index.item_filter(item_filter)
+        if filter_group is None:
+            if item_filter.groups != 1:
+                raise ValueError(f"{what}: item_filter has {item_filter.groups} groups; filter_group (B,) must say "
+                                 "which one every user reads (-1: unfiltered)")
+            return item_filter, torch.zeros(B, dtype=torch.int32, device=device)
+        if filter_group.dim() != 1 or filter_group.shape[0] != B or filter_group.dtype.is_floating_point or \
+                filter_group.dtype == torch.bool:
+            raise ValueError(f"{what}: filter_group must be (B,) integer with B = {B}, got {filter_group.dtype} "
+                             f"{tuple(filter_group.shape)}")
+        return item_filter, filter_group.to(device=device, dtype=torch.int32).contiguous()
+
+    @staticmethod
+    def _leaf_items(trie, item_filter, group, node: Tensor) -> Tensor:
+        """The corpus index of every leaf node (B, k), -1 for dead rows: the trie's lowest index for an unfiltered user,
+        the filter's lowest ALLOWED index for a filtered one."""
+        node = node.long()
+        at = node.clamp_min(0)
+        items = trie.leaf_item[at]
+        if item_filter is not None:
+            g = group.long().unsqueeze(1)
+            filtered = (g >= 0) & (g < item_filter.groups)
+            if item_filter.groups > 0:
+                items = torch.where(filtered, item_filter.leaf_item[g.clamp(0, item_filter.groups - 1), at], items)
+        return torch.where(node >= 0, items, -1)
+
     @eval_mode
     @reset_encoder_cache
     @torch.no_grad()
     def recommend(self, batch: TokenizedSeqBatch, k: int = 10, temperature: int = 1,
-                  incremental: bool = True, exclude_items: Tensor = None, beams: int = 32) -> Recommendation:
+                  incremental: bool = True, exclude_items: Tensor = None, beams: int = 32, item_filter=None,
+                  filter_group: Tensor = None) -> Recommendation:
         """The k <= beams most probable corpus items for every user: the constrained beam search (`beams` wide, 32
         by default and up to 1024; sample=False; generate_next_sem_id(constrained=True, beams=beams)) with each kept
         beam mapped back to its corpus index through the trie's leaves. A user with fewer than k valid beams gets
         item id -1 (sem ids -1, log-probability -inf) in the remaining places. exclude_items (B, H) int64, -1 as padding: corpus items (and
         the items sharing their sem-ID rows) that are never returned — the k best of the REMAINING corpus, see
-        generate_next_sem_id."""
+        generate_next_sem_id. item_filter / filter_group: a catalogue filter, see generate_next_sem_id — the k best of the
+        ALLOWED items of each user's group; every returned id is an allowed item (a row that several items share is
+        reported under its lowest allowed index), never a disallowed one."""
         if not 1 <= k <= beams <= hip_ops.BEAM_WIDE_MAX:
             raise ValueError(f"recommend: need 1 <= k <= {beams} beams <= {hip_ops.BEAM_WIDE_MAX}, got k = {k}")
         trie = self._constrained_trie("recommend")
@@ -351,16 +399,19 @@ class EncoderDecoderRetrievalModel(nn.Module):
             raise ValueError(f"recommend: the corpus trie has depth {trie.depth}, the model generates {self.sem_id_dim} "
                              "tokens; items are the leaves of the full depth")
         assert self.enable_generation, "Model generation is not enabled"
-        generated, log_probas, node = self._generate_constrained(batch, temperature, beams, incremental, exclude_items)
-        node = node[:, :k].long()
-        items = torch.where(node >= 0, trie.leaf_item[node.clamp_min(0)], -1)
+        B, dev = batch.sem_ids.shape[0], batch.sem_ids.device
+        item_filter, group = self._item_filter("recommend", item_filter, filter_group, B, dev)
+        generated, log_probas, node = self._generate_constrained(batch, temperature, beams, incremental, exclude_items,
+                                                                 item_filter, group)
+        items = self._leaf_items(trie, item_filter, group, node[:, :k])
         return Recommendation(item_ids=items, sem_ids=generated[:, :k], log_probas=log_probas[:, :k])
 
     @eval_mode
     @reset_encoder_cache
     @torch.no_grad()
     def sample_items(self, batch: TokenizedSeqBatch, k: int = 10, temperature: int = 1, incremental: bool = True,
-                     exclude_items: Tensor = None, generator: torch.Generator = None) -> SampledItems:
+                     exclude_items: Tensor = None, generator: torch.Generator = None, item_filter=None,
+                     filter_group: Tensor = None) -> SampledItems:
         """k distinct corpus items per user, drawn without replacement in proportion to the model's own distribution
         over the corpus: stochastic beam search (Kool, van Hoof and Welling 2019) over the prefix trie, k beams wide,
         one hip_ops.beam_expand_sampled launch per token. The distribution is the trie's: at every node the model's
@@ -370,7 +421,9 @@ class EncoderDecoderRetrievalModel(nn.Module):
         ids -1, -inf). `log_probas` is log of that renormalised probability — NOT the full-V score recommend()
         returns; score_items(batch, item_ids) gives the raw model score. `perturbed[:, 0]` is exactly 0 (the root's
         perturbed score is pinned there; the order does not depend on it). exclude_items (B, H) int64, -1 as padding,
-        as recommend: the draw is from the corpus minus the listed rows (and the items sharing them).
+        as recommend: the draw is from the corpus minus the listed rows (and the items sharing them). item_filter /
+        filter_group, as recommend: the draw is from the allowed items of each user's group, the distribution
+        renormalised over the children that still lead to one.
         The draws, part of the contract: at step i, on that step's logits (B, V) / (B * k, V),
         exactly one torch.empty_like(logits).exponential_(generator=generator), steps in order, nothing else;
         generator=None is the device's default generator. Needs k * num_embeddings <= 8192."""
@@ -390,6 +443,7 @@ class EncoderDecoderRetrievalModel(nn.Module):
                 raise ValueError(f"sample_items: exclude_items must be (B, H) with B = {B} rows, got "
                                  f"{tuple(exclude_items.shape)}")
             blocked = self.inference_prefix_index.blocked_nodes(exclude_items)
+        item_filter, group = self._item_filter("sample_items", item_filter, filter_group, B, batch.sem_ids.device)
         generated, phi, g, parent, node = None, None, None, None, None
         with self._step_logits(batch, incremental) as step:
             for i in range(self.sem_id_dim):
@@ -398,9 +452,9 @@ class EncoderDecoderRetrievalModel(nn.Module):
                 generated, phi, g, parent, node = hip_ops.beam_expand_sampled(
                     logits, k, batch=B, child_off=trie.child_off[i], tok=trie.tok[i + 1], noise=noise, node=node,
                     parents=generated, parent_phi=phi, parent_g=g, temperature=temperature,
-                    blocked=None if blocked is None else blocked[i])
-        node = node.long()
-        items = torch.where(node >= 0, trie.leaf_item[node.clamp_min(0)], -1)
+                    blocked=None if blocked is None else blocked[i],
+                    allowed=None if item_filter is None else item_filter.bits[i], group=group)
+        items = self._leaf_items(trie, item_filter, group, node)
         return SampledItems(item_ids=items, sem_ids=generated, log_probas=phi, perturbed=g)
 
     @eval_mode
@@ -482,17 +536,20 @@ class EncoderDecoderRetrievalModel(nn.Module):
         return Scores(log_probas=lp, rank=rank)
 
     def _generate_constrained(self, batch: TokenizedSeqBatch, temperature, k: int, incremental: bool,
-                              exclude_items: Tensor = None):
+                              exclude_items: Tensor = None, item_filter=None, filter_group: Tensor = None):
         """_generate_sampled's loop with beam_candidates + _beam_verify + beam_select replaced by one
         hip_ops.beam_expand per step: a beam carries its trie node, the node's children are the
         only candidates. Returns (sem_ids (B, k, L+1), log_probas (B, k), the beams' leaf nodes (B, k) int32), dead
         beams as beam_expand marks them. Tokens handed back to the model for dead beams are clamped to 0 (row
         counts stay B * k: static shapes, no negative index reaches an embedding kernel); whatever they compute is
         never read, a dead beam has no children. exclude_items (B, H): step i's beam_expand skips the user's blocked
-        level-(i + 1) nodes (the tokenizer's blocked_nodes, one launch for the whole call). Runs under the caller's
-        decorators."""
+        level-(i + 1) nodes (the tokenizer's blocked_nodes, one launch for the whole call). item_filter / filter_group
+        (_item_filter's arguments): step i's beam_expand keeps only the children set in item_filter.bits[i], row
+        filter_group[b]. Runs under the caller's decorators."""
         trie = self._constrained_trie("generate_next_sem_id")
         B = batch.sem_ids.shape[0]
+        item_filter, group = self._item_filter("generate_next_sem_id", item_filter, filter_group, B,
+                                               batch.sem_ids.device)
         blocked = None
         if exclude_items is not None:
             if exclude_items.dim() != 2 or exclude_items.shape[0] != B:
@@ -506,7 +563,8 @@ class EncoderDecoderRetrievalModel(nn.Module):
                 generated, log_probas, parent, node = hip_ops.beam_expand(
                     logits.contiguous(), k, batch=B, child_off=trie.child_off[i], tok=trie.tok[i + 1], node=node,
                     parents=generated, parent_lp=log_probas, temperature=temperature,
-                    blocked=None if blocked is None else blocked[i], wide=None)
+                    blocked=None if blocked is None else blocked[i], wide=None,
+                    allowed=None if item_filter is None else item_filter.bits[i], group=group)
         return generated, log_probas, node
 
     def _beams_batch(self, cur: TokenizedSeqBatch, generated: Tensor, first: bool, k: int) -> TokenizedSeqBatch:

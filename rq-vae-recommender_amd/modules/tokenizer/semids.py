@@ -16,7 +16,10 @@ MI355X path:
     behaviour;
   * `prefix_trie` / `trie_index` / `blocked_nodes` (this build's additions): the corpus ids as a level-by-level CSR
     trie for constrained decoding, and per batch of item-id histories the trie nodes whose leaves are all listed
-    (seen-item exclusion) — one HIP launch on the device, plain torch on the CPU.
+    (seen-item exclusion) — one HIP launch on the device, plain torch on the CPU;
+  * `item_filter` (this build's addition): per group of a bool item mask the ItemFilter tables — every level's bitmap
+    of nodes that still lead to an allowed item, and every leaf's lowest allowed item (catalogue filters: "only what
+    is in stock") — two HIP launches on the device, plain torch on the CPU.
 """
 import math
 from typing import List, NamedTuple, Optional
@@ -76,6 +79,15 @@ class TrieIndex(NamedTuple):
     leaf_anc: tuple     # leaf_anc[q - 1], q = 1..depth: int32 (n_depth), each leaf's level-q ancestor (non-decreasing;
                         # the last one is the leaf itself)
     leaf_count: tuple   # leaf_count[q - 1], q = 1..depth: int32 (n_q), each level-q node's number of leaves
+
+
+class ItemFilter(NamedTuple):
+    """A catalogue filter over the PrefixTrie (SemanticIdTokenizer.item_filter): per group of an item mask, which
+    nodes of every level still lead to an allowed item. Built once, reused across calls."""
+    bits: tuple         # bits[q - 1], q = 1..depth: int32 (G, ceil(n_q / 32)); bit c & 31 of word c >> 5 in row g is
+                        # set iff the level-q node c has at least one allowed item below it in group g
+    leaf_item: Tensor   # int64 (G, n_depth): the lowest ALLOWED corpus index whose row is that leaf, -1 if none
+    groups: int         # G
 
 
 _NO_NODE = torch.iinfo(torch.int32).max   # padding of blocked_nodes' rows
@@ -239,6 +251,46 @@ class SemanticIdTokenizer(nn.Module):
             full = head & (listed[row, a] == idx.leaf_count[q].long()[a])
             out[q] = torch.where(full, a, _NO_NODE).sort(dim=1).values.to(torch.int32)
         return out
+
+    @torch.no_grad()
+    def item_filter(self, mask: Tensor) -> ItemFilter:
+        """The ItemFilter of `mask`, bool (N,) or (G, N) over corpus indices: mask[g][i] says whether group g (a
+        region, a category, a user) may be shown item i. A constrained search that keeps only the children whose bit
+        is set at every level (rqvae_hip.ops.beam_expand(allowed=..., group=...)) is exactly the search over the
+        sub-corpus of the allowed items, without a trie per filter. Filtering is by item, not by row: a row that
+        several items share stays reachable while one of them is allowed and is reported under the lowest allowed
+        index. Device tensors: two HIP launches for all levels (rqvae_hip.ops.trie_allowed_nodes), no host read; CPU
+        tensors: the same tables with plain torch. Nothing is cached: build once, reuse across calls."""
+        idx = self.trie_index()
+        N = idx.item_leaf.numel()
+        if mask.dtype != torch.bool or mask.dim() not in (1, 2) or mask.shape[-1] != N:
+            raise ValueError(f"item_filter: mask must be bool (N,) or (G, N) with N = {N} corpus items, got "
+                             f"{mask.dtype} {tuple(mask.shape)}")
+        if mask.device != idx.item_leaf.device:
+            raise ValueError(f"item_filter: mask must live on the corpus ids' device {idx.item_leaf.device}, got "
+                             f"{mask.device}")
+        if mask.dim() == 1:
+            mask = mask.unsqueeze(0)
+        G, n_leaves = mask.shape[0], idx.leaf_anc[0].numel()
+        n_nodes = [c.numel() for c in idx.leaf_count]
+        if mask.is_cuda:
+            from rqvae_hip import ops as hip_ops
+            bits, leaf_item = hip_ops.trie_allowed_nodes(mask.contiguous(), idx.item_leaf, idx.leaf_anc, n_nodes)
+            return ItemFilter(bits=bits, leaf_item=leaf_item, groups=G)
+        none = torch.iinfo(torch.int64).max
+        leaf = idx.item_leaf.long().expand(G, N)
+        lowest = torch.full((G, n_leaves), none, dtype=torch.int64)
+        lowest.scatter_reduce_(1, leaf, torch.where(mask, torch.arange(N), none), "amin")
+        leaf_ok = lowest != none
+        shifts = torch.arange(32, dtype=torch.int64)
+        bits = []
+        for q, n_q in enumerate(n_nodes):
+            W = (n_q + 31) // 32
+            below = torch.zeros((G, W * 32), dtype=torch.int64)
+            below.scatter_add_(1, idx.leaf_anc[q].long().expand(G, n_leaves), leaf_ok.long())   # allowed leaves below
+            words = ((below > 0).view(G, W, 32).long() << shifts).sum(-1)                       # in [0, 2^32)
+            bits.append(torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32))
+        return ItemFilter(bits=tuple(bits), leaf_item=torch.where(leaf_ok, lowest, -1), groups=G)
 
     @torch.no_grad()
     @eval_mode

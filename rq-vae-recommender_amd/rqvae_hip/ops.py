@@ -12,6 +12,8 @@
   beam_expand_sampled                        stochastic beam search: the same step by Gumbel-perturbed score, one launch
   trie_blocked_nodes / rank_hist             seen-item exclusion: a batch's blocked trie nodes of every level, one launch;
                                              first-match rank histogram (Recall / NDCG / MRR), one launch
+  trie_allowed_nodes                         catalogue filters: per group of an item mask every level's bitmap of nodes
+                                             that lead to an allowed item (beam_expand's allowed=), two launches
 
 All kernels run on torch's current HIP stream; tensors must be on the GPU (no CPU path).
 """
@@ -2483,9 +2485,25 @@ BEAM_MAX_V, BEAM_MAX_N = 4096, 8192   # kBeamMaxV, kBeamMaxN (csrc/beam.hip)
 BEAM_WIDE_MAX = 1024   # kWideMax (csrc/beam.hip): most beams in / out of the wide kernel
 
 
+def _beam_allowed(what, B, allowed, group) -> tuple:
+    """The (allowed, n_words, G, group) arguments of the _filtered entry points — allowed (G, n_words) int32 and group
+    (B) int32, given together — or () with neither."""
+    if (allowed is None) != (group is None):
+        raise RqHipError(f"{what}: allowed and group go together")
+    if allowed is None:
+        return ()
+    if allowed.dim() != 2:
+        raise RqHipError(f"{what}: allowed must be (G, n_words), got {tuple(allowed.shape)}")
+    _beam_arg(allowed, torch.int32, what, "allowed")
+    _beam_arg(group, torch.int32, what, "group", (B,))
+    G, n_words = allowed.shape
+    return (ptr(allowed) if G * n_words else None, n_words, G, ptr(group))
+
+
 def beam_expand(logits: torch.Tensor, k: int, *, batch: int, child_off: torch.Tensor, tok: torch.Tensor,
                 node: torch.Tensor = None, parents: torch.Tensor = None, parent_lp: torch.Tensor = None,
-                temperature: float = 1.0, blocked: torch.Tensor = None, wide: bool = False):
+                temperature: float = 1.0, blocked: torch.Tensor = None, wide: bool = False,
+                allowed: torch.Tensor = None, group: torch.Tensor = None):
     """(out_ids (B, k, P + 1) int64, out_lp (B, k) fp32, out_parent (B, k) int32, out_node (B, k) int32): one
     constrained beam step against the corpus' prefix trie (rq_beam_expand) — the k best of the valid continuations of
     the B * kprev beams whose logits (B * kprev, V) these are, with beam_candidates' log-probabilities. child_off
@@ -2498,9 +2516,13 @@ def beam_expand(logits: torch.Tensor, k: int, *, batch: int, child_off: torch.Te
     wide: False (the default: a plain call refuses what it always refused) — that kernel, whose envelope is
     kprev * V <= 8192; True — rq_beam_expand_wide(_blocked), the same contract and, where both take the shape, the
     same bits, for kprev <= 1024 and k <= 1024 at any kprev * V; None (what the model's search passes) — the first
-    wherever its envelope holds, so results and timings there are what they were, else the wide one."""
+    wherever its envelope holds, so results and timings there are what they were, else the wide one.
+    allowed (G, n_words) int32 with group (B) int32, given together (rq_beam_expand_filtered /
+    rq_beam_expand_wide_filtered): a catalogue filter — slice P of trie_allowed_nodes' bitmaps (ItemFilter.bits[P]), bit
+    c of row group[b] set iff the level-(P + 1) node c leads to an item batch element b may be shown; a group outside
+    [0, G) (-1) leaves that element unfiltered. Composes with blocked: a candidate passes both."""
     what = "beam_expand"
-    require_gpu(logits, child_off, tok, node, parents, parent_lp, blocked, what=what)
+    require_gpu(logits, child_off, tok, node, parents, parent_lp, blocked, allowed, group, what=what)
     B = int(batch)
     if logits.dim() != 2 or B < 0 or (B and logits.shape[0] % B):
         raise RqHipError(f"{what}: logits must be (B * kprev, V)")
@@ -2527,13 +2549,19 @@ def beam_expand(logits: torch.Tensor, k: int, *, batch: int, child_off: torch.Te
         if blocked.dim() != 2 or blocked.shape[0] != B or blocked.shape[1] > BLOCKED_MAX:
             raise RqHipError(f"{what}: blocked must be (B, n_blocked <= {BLOCKED_MAX}), got {tuple(blocked.shape)}")
         _beam_arg(blocked, torch.int32, what, "blocked")
+    bitmap = _beam_allowed(what, B, allowed, group)
     dev = logits.device
     out_ids = torch.empty((B, int(k), P + 1), device=dev, dtype=torch.int64)
     out_lp = torch.empty((B, int(k)), device=dev, dtype=torch.float32)
     out_parent = torch.empty((B, int(k)), device=dev, dtype=torch.int32)
     out_node = torch.empty((B, int(k)), device=dev, dtype=torch.int32)
     filt = () if blocked is None else (ptr(blocked) if blocked.shape[1] else None, blocked.shape[1])
-    if not wide:
+    if bitmap:
+        call("rq_beam_expand_wide_filtered" if wide else "rq_beam_expand_filtered", ptr(logits), float(temperature),
+             ptr(node), ptr(child_off), child_off.numel() - 1, ptr(tok), tok.numel(), ptr(parents), ptr(parent_lp), B,
+             kprev, V, P, int(k), ptr(out_ids), ptr(out_lp), ptr(out_parent), ptr(out_node), *(filt or (None, 0)),
+             *bitmap, stream_handle(dev))
+    elif not wide:
         call("rq_beam_expand" if blocked is None else "rq_beam_expand_blocked", ptr(logits), float(temperature),
              ptr(node), ptr(child_off), child_off.numel() - 1, ptr(tok), tok.numel(), ptr(parents), ptr(parent_lp), B,
              kprev, V, P, int(k), ptr(out_ids), ptr(out_lp), ptr(out_parent), ptr(out_node), *filt, stream_handle(dev))
@@ -2551,7 +2579,7 @@ def beam_expand(logits: torch.Tensor, k: int, *, batch: int, child_off: torch.Te
 def beam_expand_sampled(logits: torch.Tensor, k: int, *, batch: int, child_off: torch.Tensor, tok: torch.Tensor,
                         noise: torch.Tensor, node: torch.Tensor = None, parents: torch.Tensor = None,
                         parent_phi: torch.Tensor = None, parent_g: torch.Tensor = None, temperature: float = 1.0,
-                        blocked: torch.Tensor = None):
+                        blocked: torch.Tensor = None, allowed: torch.Tensor = None, group: torch.Tensor = None):
     """(out_ids (B, k, P + 1) int64, out_phi (B, k) fp32, out_g (B, k) fp32, out_parent (B, k) int32, out_node (B, k)
     int32): one step of stochastic beam search against the corpus' prefix trie (rq_beam_expand_sampled; Kool, van Hoof
     and Welling 2019) — beam_expand's step with the k best taken by Gumbel-perturbed score, so that k beams walked to
@@ -2562,9 +2590,10 @@ def beam_expand_sampled(logits: torch.Tensor, k: int, *, batch: int, child_off: 
     distribution renormalised at every node over the candidates (valid, not blocked); out_g: its perturbed score,
     descending per user, never above its parent's, the best child of a beam inheriting the parent's exactly. Dead rows:
     ids -1, phi = g = -inf, parent 0, node -1. One launch, no host read. The envelope is beam_expand's narrow one
-    (kprev * V <= 8192); there is no wide form."""
+    (kprev * V <= 8192); there is no wide form. allowed (G, n_words) int32 with group (B) int32: beam_expand's catalogue
+    filter (rq_beam_expand_sampled_filtered) — the renormalisation then runs over the candidates that remain."""
     what = "beam_expand_sampled"
-    require_gpu(logits, noise, child_off, tok, node, parents, parent_phi, parent_g, blocked, what=what)
+    require_gpu(logits, noise, child_off, tok, node, parents, parent_phi, parent_g, blocked, allowed, group, what=what)
     B = int(batch)
     if logits.dim() != 2 or B < 0 or (B and logits.shape[0] % B):
         raise RqHipError(f"{what}: logits must be (B * kprev, V)")
@@ -2595,16 +2624,17 @@ def beam_expand_sampled(logits: torch.Tensor, k: int, *, batch: int, child_off: 
             raise RqHipError(f"{what}: blocked must be (B, n_blocked <= {BLOCKED_MAX}), got {tuple(blocked.shape)}")
         _beam_arg(blocked, torch.int32, what, "blocked")
         n_blocked = blocked.shape[1]
+    bitmap = _beam_allowed(what, B, allowed, group)
     dev = logits.device
     out_ids = torch.empty((B, int(k), P + 1), device=dev, dtype=torch.int64)
     out_phi = torch.empty((B, int(k)), device=dev, dtype=torch.float32)
     out_g = torch.empty((B, int(k)), device=dev, dtype=torch.float32)
     out_parent = torch.empty((B, int(k)), device=dev, dtype=torch.int32)
     out_node = torch.empty((B, int(k)), device=dev, dtype=torch.int32)
-    call("rq_beam_expand_sampled", ptr(logits), ptr(noise), float(temperature), ptr(node), ptr(child_off),
-         child_off.numel() - 1, ptr(tok), tok.numel(), ptr(parents), ptr(parent_phi), ptr(parent_g), B, kprev, V, P,
-         int(k), ptr(out_ids), ptr(out_phi), ptr(out_g), ptr(out_parent), ptr(out_node),
-         ptr(blocked) if n_blocked else None, n_blocked, stream_handle(dev))
+    call("rq_beam_expand_sampled_filtered" if bitmap else "rq_beam_expand_sampled", ptr(logits), ptr(noise),
+         float(temperature), ptr(node), ptr(child_off), child_off.numel() - 1, ptr(tok), tok.numel(), ptr(parents),
+         ptr(parent_phi), ptr(parent_g), B, kprev, V, P, int(k), ptr(out_ids), ptr(out_phi), ptr(out_g), ptr(out_parent),
+         ptr(out_node), ptr(blocked) if n_blocked else None, n_blocked, *bitmap, stream_handle(dev))
     return out_ids, out_phi, out_g, out_parent, out_node
 
 
@@ -2645,6 +2675,40 @@ def trie_blocked_nodes(items: torch.Tensor, item_leaf: torch.Tensor, leaf_anc, l
          P(*[t.data_ptr() for t in leaf_anc]), P(*[t.data_ptr() for t in leaf_count]),
          (ctypes.c_int64 * D)(*[t.numel() for t in leaf_count]), D, ptr(out), stream_handle(items.device))
     return out
+
+
+def trie_allowed_nodes(mask: torch.Tensor, item_leaf: torch.Tensor, leaf_anc, n_nodes):
+    """(bits, leaf_item) of a catalogue filter (rq_trie_allowed_nodes): bits, a tuple of D int32 tensors, bits[q - 1]
+    (G, ceil(n_q / 32)) with bit c & 31 of word c >> 5 in row g set iff the level-q trie node c has an item below it
+    that mask[g] allows — beam_expand's `allowed` of step q - 1; leaf_item (G, n_leaves) int64, the lowest allowed
+    corpus index whose row is that leaf, -1 if none. mask (G, N) bool; item_leaf (N) int32 and leaf_anc, D int32 tensors
+    (n_leaves) — SemanticIdTokenizer.trie_index(); n_nodes: the D level sizes n_q. Two launches, no host read; the
+    reductions are bit OR and index MIN, so the result does not depend on the order."""
+    import ctypes
+    what = "trie_allowed_nodes"
+    leaf_anc, n_nodes = list(leaf_anc), [int(n) for n in n_nodes]
+    require_gpu(mask, item_leaf, *leaf_anc, what=what)
+    D = len(leaf_anc)
+    if mask.dim() != 2:
+        raise RqHipError(f"{what}: mask must be (G, N), got {tuple(mask.shape)}")
+    G, N = mask.shape
+    if not 1 <= D <= BEAM_MAX_T or len(n_nodes) != D:
+        raise RqHipError(f"{what}: outside the supported envelope 1 <= D <= {BEAM_MAX_T} with D level sizes (D={D}, "
+                         f"{len(n_nodes)} sizes)")
+    _beam_arg(mask, torch.bool, what, "mask")
+    _beam_arg(item_leaf, torch.int32, what, "item_leaf", (N,))
+    n_leaves = leaf_anc[0].numel()
+    for q in range(D):
+        _beam_arg(leaf_anc[q], torch.int32, what, f"leaf_anc[{q}]", (n_leaves,))
+        if n_nodes[q] < 0:
+            raise RqHipError(f"{what}: n_nodes[{q}] = {n_nodes[q]}")
+    dev = mask.device
+    bits = tuple(torch.zeros((G, (n + 31) // 32), device=dev, dtype=torch.int32) for n in n_nodes)
+    leaf_item = torch.zeros((G, n_leaves), device=dev, dtype=torch.int64)
+    P = ctypes.c_void_p * D
+    call("rq_trie_allowed_nodes", ptr(mask), G, N, ptr(item_leaf), n_leaves, P(*[t.data_ptr() for t in leaf_anc]),
+         (ctypes.c_int64 * D)(*n_nodes), D, P(*[t.data_ptr() for t in bits]), ptr(leaf_item), stream_handle(dev))
+    return bits, leaf_item
 
 
 def beam_self_attention(q: torch.Tensor, kv_steps, anc: torch.Tensor, num_heads: int, scale: float = None):

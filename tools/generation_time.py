@@ -23,6 +23,15 @@ per beam, 256 classes, 4 sem-ID tokens; model dims of configs/decoder_amazon.gin
                one trace of the two forms times both kernels at the 32-beam shape;
                `sampled_items`: model.sample_items(k=10) — stochastic beam search, the incremental loop 10 beams wide
                with one Exponential(1) draw and one rq_beam_expand_sampled launch per step;
+  filters      `filtered_shared`: model.recommend(k=10, item_filter=F) with F one ItemFilter over a 50 % mask of the
+               corpus that every user shares, built once before the loop (rq_beam_expand_filtered per step);
+               `filtered_groups`: the same call with one 50 % mask per user (G = B groups, filter_group = 0..B-1);
+               `filter_build`: the one-off tokenizer.item_filter(mask) of the shared mask, `filter_build_groups` of
+               the G = B masks (rq_trie_allowed_nodes: two launches). The over-fetch alternative is `wide`. One run
+               for the comparison:
+                 --forms recommend,filtered_shared,filtered_groups,wide,filter_build,filter_build_groups
+               (the JSON then carries `filtered_vs_recommend`: each filtered form's median over `recommend`'s, next
+               to `recommend`'s own min..max spread);
   accumulate   TopKAccumulator.accumulate on the device (one rq_topk_hits launch) and the reference's logic
                (evaluate/metrics.py:15-28, restated below: 24 host reads per batch).
 
@@ -85,7 +94,8 @@ def main():
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=2)
     names = ["unfused", "fused", "incremental", "constrained", "excluded", "model", "acc_device", "acc_reference",
-             "recommend", "score", "score_full", "wide", "wide_excluded", "recommend_forced", "sampled_items"]
+             "recommend", "score", "score_full", "wide", "wide_excluded", "recommend_forced", "sampled_items",
+             "filtered_shared", "filtered_groups", "filter_build", "filter_build_groups"]
     ap.add_argument("--score-candidates", type=int, default=100)
     ap.add_argument("--score-full-candidates", type=int, default=None)
     ap.add_argument("--beams", type=int, default=128, help="width of the `wide` / `wide_excluded` search")
@@ -157,6 +167,14 @@ def main():
     def score(incremental, c):
         return model.score_items(batch, cands[:, :c].contiguous(), incremental=incremental)
 
+    # catalogue filters: about half the corpus allowed — one mask for everyone, and one per user
+    gm = torch.Generator().manual_seed(13)
+    n_corpus = tok.cached_ids.shape[0]
+    shared_mask = (torch.rand(n_corpus, generator=gm) < 0.5).to(device)
+    user_masks = (torch.rand(args.batch, n_corpus, generator=gm) < 0.5).to(device)
+    shared_filter, user_filter = tok.item_filter(shared_mask), tok.item_filter(user_masks)
+    own_group = torch.arange(args.batch, device=device)
+
     top = gen(True).sem_ids.contiguous()
     actual = batch.sem_ids_fut.contiguous()
     top[::3, 4] = actual[::3]          # some hits, as a trained model has
@@ -177,7 +195,11 @@ def main():
              "wide": lambda: model.recommend(batch, k=min(100, args.beams), beams=args.beams),
              "wide_excluded": lambda: model.recommend(batch, k=min(100, args.beams), beams=args.beams,
                                                       exclude_items=seen),
-             "recommend_forced": recommend_forced, "sampled_items": lambda: model.sample_items(batch, k=10)}
+             "recommend_forced": recommend_forced, "sampled_items": lambda: model.sample_items(batch, k=10),
+             "filtered_shared": lambda: model.recommend(batch, k=10, item_filter=shared_filter),
+             "filtered_groups": lambda: model.recommend(batch, k=10, item_filter=user_filter, filter_group=own_group),
+             "filter_build": lambda: tok.item_filter(shared_mask),
+             "filter_build_groups": lambda: tok.item_filter(user_masks)}
     if args.only:
         forms = {args.only: forms[args.only]}
     elif args.forms:
@@ -197,7 +219,7 @@ def main():
            "min_max_ms": {n: [round(min(v), 4), round(max(v), 4)] for n, v in times.items() if v}}
     peak = {}
     for name in ("unfused", "fused", "incremental", "constrained", "excluded", "recommend", "score", "score_full",
-                 "wide", "wide_excluded", "recommend_forced", "sampled_items"):
+                 "wide", "wide_excluded", "recommend_forced", "sampled_items", "filtered_shared", "filtered_groups"):
         if name in forms and not args.only:   # one more call of each generation form, alone after a peak reset
             torch.cuda.synchronize()
             torch.cuda.reset_peak_memory_stats(device)
@@ -220,6 +242,13 @@ def main():
         out["excluded_vs_constrained"] = dict(delta_ms=round(med["excluded"] - med["constrained"], 4),
                                               constrained_spread_ms=round(spread, 4), history=n_hist,
                                               within_spread=med["excluded"] - med["constrained"] <= spread)
+    if "recommend" in med and {"filtered_shared", "filtered_groups"} & set(med):
+        # the yardstick is the unfiltered call of the same run: the ratio, next to that call's own spread
+        lo, hi = min(times["recommend"]), max(times["recommend"])
+        out["filtered_vs_recommend"] = dict(
+            ratio={n: round(med[n] / med["recommend"], 4) for n in ("filtered_shared", "filtered_groups") if n in med},
+            recommend_min_max_over_median=[round(lo / med["recommend"], 4), round(hi / med["recommend"], 4)],
+            groups=dict(filtered_shared=1, filtered_groups=args.batch), allowed_fraction=0.5)
     if {"wide", "wide_excluded"} & set(med):
         out["wide"] = dict(beams=args.beams, k=min(100, args.beams))
     if {"score", "score_full"} & set(med):
