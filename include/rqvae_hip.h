@@ -519,15 +519,24 @@ int varlen_attn_bwd(const float* q, int64_t sq, const float* k, int64_t sk, cons
  *   tables are the caller's contract, but a bad one never reads outside a buffer: child_off is clamped into
  *   [0, n_children], tokens outside [0, V) are skipped (an unsorted range gives an unspecified out_node or -1).
  *   V <= 4096, kprev V <= 8192, 1 <= k <= 8192, P < 64, temperature > 0; outside that -22, never a truncated result.
- * rq_beam_expand_blocked: rq_beam_expand with a per-user filter (seen-item exclusion). blocked (B, n_blocked) int32:
- *   row b holds the level-(P + 1) nodes that are not candidates for batch element b, ascending and padded with
- *   INT32_MAX (a slice of rq_trie_blocked_nodes' output); a child c found in row b is skipped, everything else is
- *   rq_beam_expand (the same kernel body: scores, tie rule, dead rows, out_node, table clamping, limits). An unsorted
- *   row may filter the wrong children but is never read outside [0, n_blocked). 0 <= n_blocked <= 1024; n_blocked == 0
- *   (blocked may be NULL) is rq_beam_expand.
- * rq_beam_expand_wide / rq_beam_expand_wide_blocked: rq_beam_expand / rq_beam_expand_blocked (the same arguments, one
- *   launch, one workgroup per batch element) for 1 <= kprev <= 1024 and 1 <= k <= 1024 with V <= 4096 and NO bound on
- *   kprev V: the candidates are enumerated from the trie, never stored, and the k best are found by an exact radix
+ *   The two optional filters come last, before the stream: blocked, n_blocked, allowed, n_words, G, group.
+ *   blocked (seen-item exclusion; NULL with n_blocked == 0: no exclusion): (B, n_blocked) int32, row b holds the
+ *   level-(P + 1) nodes that are not candidates for batch element b, ascending and padded with INT32_MAX (a slice of
+ *   rq_trie_blocked_nodes' output); a child c found in row b is skipped, everything else is as without it (the same
+ *   kernel body: scores, tie rule, dead rows, out_node, table clamping, limits). An unsorted row may filter the wrong
+ *   children but is never read outside [0, n_blocked). 0 <= n_blocked <= 1024.
+ *   group (catalogue filters, "only these items"; NULL: no catalogue filter, allowed / n_words / G are then not looked
+ *   at): (B) int32, with allowed (G, n_words) int32 the level-(P + 1) slice of rq_trie_allowed_nodes' bitmaps: bit
+ *   (c & 31) of word (c >> 5) in row g is set iff node c has an allowed item below it in group g. A child c of batch
+ *   element b is a candidate iff it passes the blocked test AND (group[b] is outside [0, G) — that user is
+ *   unfiltered, -1 is the documented spelling — OR bit c of row group[b] is set). A word index outside [0, n_words)
+ *   reads as "not allowed" and is never read. Everything else is the unfiltered kernel body, bit for bit (log-softmax,
+ *   tie rule, dead rows, out_node, table clamping, limits), so a filtered search is the unfiltered search over the
+ *   corpus of the allowed rows. The rows are read from global memory: no LDS is added. With group given, allowed may
+ *   be NULL only when G n_words == 0; n_words or G negative: -22. Both filters may be given: a candidate passes both.
+ * rq_beam_expand_wide: rq_beam_expand (the same arguments, NULL meaning the same, one launch, one workgroup per batch
+ *   element) for 1 <= kprev <= 1024 and 1 <= k <= 1024 with V <= 4096 and NO bound on kprev V: the candidates
+ *   are enumerated from the trie, never stored, and the k best are found by an exact radix
  *   select over (score, beam, token). Wherever both accept a shape the four outputs are bit for bit the same — ids,
  *   out_lp, parents, nodes, the dead rows after the last candidate, the tie rule, the table clamping; a child range
  *   longer than V is searched for its first token >= V (a sorted range loses only skipped children), and duplicate
@@ -537,12 +546,14 @@ int varlen_attn_bwd(const float* q, int64_t sq, const float* k, int64_t sk, cons
  *   Beams and Where to Find Them", Algorithm 1; the reference has no counterpart — its generate_next_sem_id(sample=True),
  *   model.py:176-201, draws unconstrained classes and masks them afterwards): after the last level the k rows are k
  *   distinct corpus rows drawn without replacement from the trie's distribution, in ONE launch per step. The arguments
- *   are rq_beam_expand_blocked's (blocked may be NULL with n_blocked == 0) with noise (B kprev, V) fp32 Exponential(1)
+ *   are rq_beam_expand's (the filters included: blocked NULL with n_blocked == 0 and group NULL mean what they mean
+ *   there) with noise (B kprev, V) fp32 Exponential(1)
  *   draws in rq_beam_candidates' layout, parent_phi / parent_g (B, kprev) fp32 in place of parent_lp (both NULL iff
  *   P == 0: taken as 0) and out_phi / out_g (B, k) fp32 in place of out_lp. A beam carries phi, its log-probability
  *   under the locally renormalised trie distribution, and G, its perturbed score. For a live beam j and its candidates
- *   C_j (the children rq_beam_expand_blocked scores: token in [0, V), not blocked), with l_c the full-V log-softmax
- *   rq_beam_expand forms (bitwise): Lam_j = log sum_{c in C_j} exp(l_c) (max subtracted); phi_c = phi_j + (l_c - Lam_j);
+ *   C_j (the children rq_beam_expand scores: token in [0, V), not blocked, allowed), with l_c the full-V log-softmax
+ *   rq_beam_expand forms (bitwise): Lam_j = log sum_{c in C_j} exp(l_c) (max subtracted; with a catalogue
+ *   filter it runs over the candidates that remain); phi_c = phi_j + (l_c - Lam_j);
  *   Gt_c = phi_c - log(noise[b kprev + j][token_c]) (a noise value that is not a positive finite float is read as
  *   FLT_MIN; noise is read at candidates only); Z_j = max_c Gt_c; v = G_j - Gt_c + log(1 - exp(Gt_c - Z_j));
  *   G_c = G_j - max(v, 0) - log1p(exp(-|v|)), so the arg-max child keeps G_j exactly and every G_c <= G_j. l_c, Lam_j,
@@ -561,18 +572,6 @@ int varlen_attn_bwd(const float* q, int64_t sq, const float* k, int64_t sk, cons
  *   (D, B, H) int32: out[q - 1][b] = user b's blocked level-q nodes, ascending and distinct, then INT32_MAX. The
  *   ancestors of ascending leaves must be non-decreasing (a level's nodes are in key order). H <= 1024,
  *   D <= RQ_BEAM_MAX_T, else -22; B == 0 or H == 0 returns 0 without a launch.
- * rq_beam_expand_filtered / rq_beam_expand_wide_filtered / rq_beam_expand_sampled_filtered: rq_beam_expand_blocked /
- *   rq_beam_expand_wide_blocked / rq_beam_expand_sampled with a second, positive filter (catalogue filters: "only these
- *   items"). The arguments are the counterpart's, then allowed (G, n_words) int32, n_words, G and group (B) int32.
- *   allowed is the level-(P + 1) slice of rq_trie_allowed_nodes' bitmaps: bit (c & 31) of word (c >> 5) in row g is set
- *   iff node c has an allowed item below it in group g. A child c of batch element b is a candidate iff it passes the
- *   blocked test as before AND (group[b] is outside [0, G) — that user is unfiltered, -1 is the documented spelling —
- *   OR bit c of row group[b] is set). A word index outside [0, n_words) reads as "not allowed" and is never read.
- *   Everything else is the counterpart's kernel body, bit for bit (log-softmax, tie rule, dead rows, out_node, table
- *   clamping, limits; in the sampled step Lam_j runs over the candidates that remain), so a filtered search is the
- *   unfiltered search over the corpus of the allowed rows. The rows are read from global memory: no LDS is added.
- *   blocked may be NULL with n_blocked == 0; allowed may be NULL when G n_words == 0; group is required. n_words or
- *   G negative: -22.
  * rq_trie_allowed_nodes: the filter tables of an item mask, in TWO launches and no host read. mask (G, n_items) bool:
  *   mask[g][i] != 0 iff group g may be shown corpus item i. item_leaf (n_items) int32 and leaf_anc[q - 1] (n_leaves)
  *   int32, q = 1..D, as rq_trie_blocked_nodes takes them (leaf_anc, n_nodes and out_bits are HOST arrays of D entries
@@ -615,51 +614,26 @@ int rq_beam_self_attn(const float* q, int64_t sq, const float* const* k_steps, c
 int rq_beam_expand(const float* logits, float temperature, const int32_t* node, const int32_t* child_off,
                    int64_t n_nodes, const int32_t* tok, int64_t n_children, const int64_t* parents,
                    const float* parent_lp, int64_t B, int64_t kprev, int64_t V, int64_t P, int64_t k, int64_t* out_ids,
-                   float* out_lp, int32_t* out_parent, int32_t* out_node, void* stream);
+                   float* out_lp, int32_t* out_parent, int32_t* out_node, const int32_t* blocked, int64_t n_blocked,
+                   const int32_t* allowed, int64_t n_words, int64_t G, const int32_t* group, void* stream);
 int rq_topk_hits(const int64_t* actual, const int64_t* topk, int64_t B, int64_t k, int64_t D, const int* ks,
                  int64_t n_ks, int64_t* counts, void* stream);
-int rq_beam_expand_blocked(const float* logits, float temperature, const int32_t* node, const int32_t* child_off,
-                           int64_t n_nodes, const int32_t* tok, int64_t n_children, const int64_t* parents,
-                           const float* parent_lp, int64_t B, int64_t kprev, int64_t V, int64_t P, int64_t k,
-                           int64_t* out_ids, float* out_lp, int32_t* out_parent, int32_t* out_node,
-                           const int32_t* blocked, int64_t n_blocked, void* stream);
 int rq_beam_expand_wide(const float* logits, float temperature, const int32_t* node, const int32_t* child_off,
                         int64_t n_nodes, const int32_t* tok, int64_t n_children, const int64_t* parents,
                         const float* parent_lp, int64_t B, int64_t kprev, int64_t V, int64_t P, int64_t k,
-                        int64_t* out_ids, float* out_lp, int32_t* out_parent, int32_t* out_node, void* stream);
-int rq_beam_expand_wide_blocked(const float* logits, float temperature, const int32_t* node, const int32_t* child_off,
-                                int64_t n_nodes, const int32_t* tok, int64_t n_children, const int64_t* parents,
-                                const float* parent_lp, int64_t B, int64_t kprev, int64_t V, int64_t P, int64_t k,
-                                int64_t* out_ids, float* out_lp, int32_t* out_parent, int32_t* out_node,
-                                const int32_t* blocked, int64_t n_blocked, void* stream);
+                        int64_t* out_ids, float* out_lp, int32_t* out_parent, int32_t* out_node,
+                        const int32_t* blocked, int64_t n_blocked, const int32_t* allowed, int64_t n_words, int64_t G,
+                        const int32_t* group, void* stream);
 int rq_beam_expand_sampled(const float* logits, const float* noise, float temperature, const int32_t* node,
                            const int32_t* child_off, int64_t n_nodes, const int32_t* tok, int64_t n_children,
                            const int64_t* parents, const float* parent_phi, const float* parent_g, int64_t B,
                            int64_t kprev, int64_t V, int64_t P, int64_t k, int64_t* out_ids, float* out_phi,
                            float* out_g, int32_t* out_parent, int32_t* out_node, const int32_t* blocked,
-                           int64_t n_blocked, void* stream);
+                           int64_t n_blocked, const int32_t* allowed, int64_t n_words, int64_t G, const int32_t* group,
+                           void* stream);
 int rq_trie_blocked_nodes(const int64_t* items, int64_t B, int64_t H, const int32_t* item_leaf, int64_t n_items,
                           int64_t n_leaves, const int32_t* const* leaf_anc, const int32_t* const* leaf_count,
                           const int64_t* n_nodes, int64_t D, int32_t* out, void* stream);
-int rq_beam_expand_filtered(const float* logits, float temperature, const int32_t* node, const int32_t* child_off,
-                            int64_t n_nodes, const int32_t* tok, int64_t n_children, const int64_t* parents,
-                            const float* parent_lp, int64_t B, int64_t kprev, int64_t V, int64_t P, int64_t k,
-                            int64_t* out_ids, float* out_lp, int32_t* out_parent, int32_t* out_node,
-                            const int32_t* blocked, int64_t n_blocked, const int32_t* allowed, int64_t n_words,
-                            int64_t G, const int32_t* group, void* stream);
-int rq_beam_expand_wide_filtered(const float* logits, float temperature, const int32_t* node, const int32_t* child_off,
-                                 int64_t n_nodes, const int32_t* tok, int64_t n_children, const int64_t* parents,
-                                 const float* parent_lp, int64_t B, int64_t kprev, int64_t V, int64_t P, int64_t k,
-                                 int64_t* out_ids, float* out_lp, int32_t* out_parent, int32_t* out_node,
-                                 const int32_t* blocked, int64_t n_blocked, const int32_t* allowed, int64_t n_words,
-                                 int64_t G, const int32_t* group, void* stream);
-int rq_beam_expand_sampled_filtered(const float* logits, const float* noise, float temperature, const int32_t* node,
-                                    const int32_t* child_off, int64_t n_nodes, const int32_t* tok, int64_t n_children,
-                                    const int64_t* parents, const float* parent_phi, const float* parent_g, int64_t B,
-                                    int64_t kprev, int64_t V, int64_t P, int64_t k, int64_t* out_ids, float* out_phi,
-                                    float* out_g, int32_t* out_parent, int32_t* out_node, const int32_t* blocked,
-                                    int64_t n_blocked, const int32_t* allowed, int64_t n_words, int64_t G,
-                                    const int32_t* group, void* stream);
 int rq_trie_allowed_nodes(const bool* mask, int64_t G, int64_t n_items, const int32_t* item_leaf, int64_t n_leaves,
                           const int32_t* const* leaf_anc, const int64_t* n_nodes, int64_t D, int32_t* const* out_bits,
                           int64_t* out_leaf_item, void* stream);

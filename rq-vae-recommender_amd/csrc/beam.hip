@@ -35,6 +35,8 @@
 //                           a workgroup-local histogram, one atomic per non-empty bin.
 #include <float.h>
 
+#include <type_traits>
+
 #include "common.h"
 
 namespace rqhip {
@@ -341,24 +343,133 @@ struct AllowedBits {   // FILTERED's arguments; never read otherwise
   const int32_t* group;   // (B)
   int n_words, G;
 };
-// batch element b's row of the bitmap and its length in words; -1 words: b is not filtered
-__device__ __forceinline__ int allowed_row(const AllowedBits& a, int64_t b, const int32_t*& row) {
-  const int g = a.group[b];
-  if (g < 0 || g >= a.G) return -1;
-  row = a.bits + (int64_t)g * a.n_words;
-  return a.n_words;
+
+// One level of the trie: the nodes' child offsets and the next level's tokens, as the caller passed them.
+struct TrieLevel {
+  const int32_t* __restrict__ child_off;
+  int n_nodes;
+  const int32_t* __restrict__ tok;
+  int n_children;
+  // node nd's child range [lo, hi), clamped into [0, n_children]; false (no range) for a node outside [0, n_nodes)
+  __device__ __forceinline__ bool children(int nd, int& lo, int& hi) const {
+    if (nd < 0 || nd >= n_nodes) return false;
+    lo = min(max(child_off[nd], 0), n_children);
+    hi = min(max(child_off[nd + 1], 0), n_children);
+    return true;
+  }
+};
+
+// One user's filters on a level's children: which of them are candidates is stated here and nowhere else.
+struct ChildFilter {
+  const int* blk;        // BLOCKED: the user's blocked row, staged in LDS
+  int n_blocked;
+  const int32_t* arow;   // FILTERED: the user's bitmap row (global memory)
+  int n_words;           // < 0: the user is not filtered
+  // c >= 0, a child index: it has an allowed item below it
+  template <bool BLOCKED, bool FILTERED>
+  __device__ __forceinline__ bool allowed(int c) const {
+    if constexpr (FILTERED) {
+      if (n_words < 0) return true;
+      const int w = c >> 5;
+      return w < n_words && (((uint32_t)arow[w] >> (c & 31)) & 1u);
+    }
+    return true;
+  }
+  // child c with token v is a candidate: a class the model can generate (not e.g. a dedup count >= V), not every leaf
+  // below it excluded for the user, an allowed item below it
+  template <bool BLOCKED, bool FILTERED>
+  __device__ __forceinline__ bool candidate(int c, int v, int V) const {
+    if (v < 0 || v >= V) return false;
+    if constexpr (BLOCKED) {
+      const int at = lower_bound(blk, 0, n_blocked, c);
+      if (at < n_blocked && blk[at] == c) return false;
+    }
+    return allowed<BLOCKED, FILTERED>(c);
+  }
+};
+// batch element b's filters over the staged row blk; a group outside [0, G) leaves b unfiltered
+template <bool FILTERED>
+__device__ __forceinline__ ChildFilter child_filter(const int* blk, int n_blocked, const AllowedBits& a, int64_t b) {
+  ChildFilter f = {blk, n_blocked, nullptr, -1};
+  if constexpr (FILTERED) {
+    const int g = a.group[b];
+    if (g >= 0 && g < a.G) {
+      f.arow = a.bits + (int64_t)g * a.n_words;
+      f.n_words = a.n_words;
+    }
+  }
+  return f;
 }
-// c >= 0: a child index
-__device__ __forceinline__ bool allowed_child(const int32_t* __restrict__ row, int n_words, int c) {
-  if (n_words < 0) return true;
-  const int w = c >> 5;
-  return w < n_words && (((uint32_t)row[w] >> (c & 31)) & 1u);
+
+// The dense kernels' LDS: key[N rounded up to 4], select_rounds' exchange, then (BLOCKED)
+// blk[n_blocked <= kBlockedMax]. Zeroes key[], stages batch element b's blocked row and ends on a barrier.
+template <bool BLOCKED, bool FILTERED>
+__device__ __forceinline__ ChildFilter expand_prologue(char* smem, int N, int64_t b,
+                                                       const int32_t* __restrict__ blocked, int n_blocked,
+                                                       const AllowedBits& allowed, uint32_t*& key) {
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  key = reinterpret_cast<uint32_t*>(smem);
+  int* blk = reinterpret_cast<int*>(key + (N + 3) / 4 * 4 + 2 * kExpMaxWaves);
+  for (int e = tid; e < N; e += nthr) key[e] = 0;
+  if constexpr (BLOCKED) {
+    for (int e = tid; e < n_blocked; e += nthr) blk[e] = blocked[b * n_blocked + e];
+  }
+  __syncthreads();
+  return child_filter<FILTERED>(blk, n_blocked, allowed, b);
+}
+
+// A dense kernel's output rows of batch element b, (k) each: beam 0 of the user is row 0 of every array here.
+struct ExpandRows {
+  int64_t* ids;      // (k, P + 1)
+  float* score;      // the selection's score: key_score of the winner's key
+  float* later;      // sampled: out_phi, -inf in a dead row and written after the rounds in a live one; else NULL
+  int32_t* parent;
+  int32_t* node;
+};
+// select_rounds' out() of the dense kernels: round r's row — dead (ids -1, -inf, parent 0, node -1) when no candidate
+// is left, else the parent's prefix, the token, the score and the parent's index; its node follows in expand_nodes.
+__device__ __forceinline__ void expand_write_row(const ExpandRows& o, int r, uint32_t wk, int wi,
+                                                 const int64_t* __restrict__ parents, int V, int P) {
+  const int tid = threadIdx.x;
+  int64_t* row = o.ids + (int64_t)r * (P + 1);
+  if (wk == 0) {   // no candidate left: a dead row
+    if (tid <= P) row[tid] = -1;   // P < 64
+    if (tid == 0) {
+      if (o.later) o.later[r] = -INFINITY;
+      o.score[r] = -INFINITY;
+      o.parent[r] = 0;
+      o.node[r] = -1;
+    }
+    return;
+  }
+  const int par = wi / V, v = wi - par * V;
+  if (tid < P) row[tid] = parents[(int64_t)par * P + tid];
+  if (tid == 0) {
+    row[P] = v;
+    o.score[r] = key_score(wk);
+    o.parent[r] = par;
+  }
+}
+// After the rounds, a thread per row: the winner's node, the child of its parent's node (nd0[parent], the root without
+// nd0) that carries its token — the first entry >= v of the node's ascending range; -1: an unsorted (bad) table.
+__device__ __forceinline__ void expand_nodes(const ExpandRows& o, int k, int P, const int32_t* __restrict__ nd0,
+                                             const TrieLevel& lvl) {
+  __syncthreads();   // thread 0's rows (global) are visible to the workgroup
+  for (int r = threadIdx.x; r < k; r += blockDim.x) {
+    const int v = (int)o.ids[(int64_t)r * (P + 1) + P];
+    if (v < 0) continue;   // a dead row: its node is already -1
+    int lo, hi, at = -1;
+    if (lvl.children(nd0 ? nd0[o.parent[r]] : 0, lo, hi)) {
+      at = lower_bound(lvl.tok, lo, hi, v);
+      if (!(at < hi && lvl.tok[at] == v)) at = -1;
+    }
+    o.node[r] = at;
+  }
 }
 
 template <bool BLOCKED, bool FILTERED>
 __global__ void __launch_bounds__(64 * kExpMaxWaves) beam_expand_kernel(
-    const float* __restrict__ logits, float temperature, const int32_t* __restrict__ node,
-    const int32_t* __restrict__ child_off, int n_nodes, const int32_t* __restrict__ tok, int n_children,
+    const float* __restrict__ logits, float temperature, const int32_t* __restrict__ node, TrieLevel lvl,
     const int64_t* __restrict__ parents, const float* __restrict__ parent_lp, int kprev, int V, int P, int k,
     int64_t* __restrict__ out_ids, float* __restrict__ out_lp, int32_t* __restrict__ out_parent,
     int32_t* __restrict__ out_node, const int32_t* __restrict__ blocked, int n_blocked, AllowedBits allowed) {
@@ -366,74 +477,32 @@ __global__ void __launch_bounds__(64 * kExpMaxWaves) beam_expand_kernel(
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nthr = blockDim.x, nwave = nthr >> 6;   // 4 or kExpMaxWaves waves (the host picks by kprev)
   const int N = kprev * V;
-  uint32_t* key = reinterpret_cast<uint32_t*>(smem);   // [N rounded up to 4], then select_rounds' exchange
-  int* blk = reinterpret_cast<int*>(key + (N + 3) / 4 * 4 + 2 * kExpMaxWaves);   // BLOCKED: [n_blocked <= kBlockedMax]
   const int64_t b = blockIdx.x;
-  const int32_t* arow = nullptr;   // FILTERED: the user's bitmap row
-  int n_words = -1;
-  if constexpr (FILTERED) n_words = allowed_row(allowed, b, arow);
-
-  for (int e = tid; e < N; e += nthr) key[e] = 0;
-  if constexpr (BLOCKED) {
-    for (int e = tid; e < n_blocked; e += nthr) blk[e] = blocked[b * n_blocked + e];
-  }
-  __syncthreads();
+  const int32_t* nd0 = node ? node + b * kprev : nullptr;
+  uint32_t* key;
+  const ChildFilter flt = expand_prologue<BLOCKED, FILTERED>(smem, N, b, blocked, n_blocked, allowed, key);
 
   for (int j = wave; j < kprev; j += nwave) {
-    const int nd = node ? node[b * kprev + j] : 0;
-    if (nd < 0 || nd >= n_nodes) continue;   // dead beam (wave-uniform)
-    const int lo = min(max(child_off[nd], 0), n_children);
-    const int hi = min(max(child_off[nd + 1], 0), n_children);
-    if (lo >= hi) continue;
+    int lo, hi;
+    if (!lvl.children(nd0 ? nd0[j] : 0, lo, hi) || lo >= hi) continue;   // dead beam (wave-uniform)
     const float* x = logits + (b * kprev + j) * V;
     const RowStats st = row_stats<0>(
         V, lane, [&](int, int v) { return x[v] / temperature; },
         [&](int, int v, float m) { return x[v] / temperature - m; });
     const float plp = parent_lp ? parent_lp[b * kprev + j] : 0.0f;
     for (int c = lo + lane; c < hi; c += 64) {
-      const int v = tok[c];
-      if (v < 0 || v >= V) continue;   // a class the model cannot generate (e.g. a dedup count >= V)
-      if constexpr (BLOCKED) {
-        const int at = lower_bound(blk, 0, n_blocked, c);
-        if (at < n_blocked && blk[at] == c) continue;   // every leaf below this child is excluded for the user
-      }
-      if constexpr (FILTERED) {
-        if (!allowed_child(arow, n_words, c)) continue;   // no allowed item below this child
-      }
+      const int v = lvl.tok[c];
+      if (!flt.candidate<BLOCKED, FILTERED>(c, v, V)) continue;
       key[j * V + v] = score_key(log_prob(x[v] / temperature - st.m, st) + plp);
     }
   }
   __syncthreads();
 
+  const ExpandRows rows = {out_ids + b * k * (P + 1), out_lp + b * k, nullptr, out_parent + b * k, out_node + b * k};
   select_rounds<kExpMaxWaves>(key, N, k, nthr, [&](int r, uint32_t wk, int wi) {
-    int64_t* o = out_ids + (b * k + r) * (P + 1);
-    if (wk == 0) {   // no candidate left: a dead row
-      if (tid <= P) o[tid] = -1;   // P < 64
-      if (tid == 0) {
-        out_lp[b * k + r] = -INFINITY;
-        out_parent[b * k + r] = 0;
-        out_node[b * k + r] = -1;
-      }
-      return;
-    }
-    const int par = wi / V, v = wi - par * V;
-    if (tid < P) o[tid] = parents[(b * kprev + par) * P + tid];
-    if (tid == 0) {
-      o[P] = v;
-      out_lp[b * k + r] = key_score(wk);
-      out_parent[b * k + r] = par;
-    }
+    expand_write_row(rows, r, wk, wi, parents + b * kprev * P, V, P);
   });
-  __syncthreads();   // thread 0's rows (global) are visible to the workgroup
-  for (int r = tid; r < k; r += nthr) {
-    const int v = (int)out_ids[(b * k + r) * (P + 1) + P];
-    if (v < 0) continue;   // a dead row: its node is already -1
-    // the child of the parent's node that carries token v: the first entry >= v of its ascending range
-    const int nd = node ? node[b * kprev + out_parent[b * k + r]] : 0;
-    const int end = min(max(child_off[nd + 1], 0), n_children);
-    const int at = lower_bound(tok, min(max(child_off[nd], 0), n_children), end, v);
-    out_node[b * k + r] = (at < end && tok[at] == v) ? at : -1;   // -1: an unsorted (bad) table
-  }
+  expand_nodes(rows, k, P, nd0, lvl);
 }
 
 // ------------------------------------------------------------------------------------- expand, sampled
@@ -468,20 +537,11 @@ struct SampledBeam {
 
 // f(c, v) for the candidates among the children [lo, hi) that this lane owns: c = lo + lane + 64 i, v = tok[c]
 template <bool BLOCKED, bool FILTERED, typename F>
-__device__ __forceinline__ void sampled_for_children(int lo, int hi, int lane, const int32_t* __restrict__ tok, int V,
-                                                     const int* blk, int n_blocked, const int32_t* arow, int n_words,
-                                                     F f) {
+__device__ __forceinline__ void sampled_for_children(int lo, int hi, int lane, const TrieLevel& lvl, int V,
+                                                     const ChildFilter& flt, F f) {
   for (int c = lo + lane; c < hi; c += 64) {
-    const int v = tok[c];
-    if (v < 0 || v >= V) continue;
-    if constexpr (BLOCKED) {
-      const int at = lower_bound(blk, 0, n_blocked, c);
-      if (at < n_blocked && blk[at] == c) continue;
-    }
-    if constexpr (FILTERED) {
-      if (!allowed_child(arow, n_words, c)) continue;
-    }
-    f(c, v);
+    const int v = lvl.tok[c];
+    if (flt.candidate<BLOCKED, FILTERED>(c, v, V)) f(c, v);
   }
 }
 
@@ -506,18 +566,11 @@ __device__ __forceinline__ int nth_set_bit(uint64_t m, int n) {
 // range, row statistics and Lam, formed by one wave. Phase 1 and the output phase both call this, for equal bits.
 template <bool BLOCKED, bool FILTERED>
 __device__ __forceinline__ SampledBeam sampled_beam(int j, int lane, const float* __restrict__ x, float temperature,
-                                                    const int32_t* __restrict__ nd0,
-                                                    const int32_t* __restrict__ child_off, int n_nodes,
-                                                    const int32_t* __restrict__ tok, int n_children,
+                                                    const int32_t* __restrict__ nd0, const TrieLevel& lvl,
                                                     const float* __restrict__ phi0, const float* __restrict__ g0,
-                                                    int V, const int* blk, int n_blocked, const int32_t* arow,
-                                                    int n_words) {
+                                                    int V, const ChildFilter& flt) {
   SampledBeam s = {false, 0, 0, {0.f, 1.f, 0.f}, -INFINITY, -INFINITY, -INFINITY};
-  const int nd = nd0 ? nd0[j] : 0;
-  if (nd < 0 || nd >= n_nodes) return s;
-  s.lo = min(max(child_off[nd], 0), n_children);
-  s.hi = min(max(child_off[nd + 1], 0), n_children);
-  if (s.lo >= s.hi) return s;
+  if (!lvl.children(nd0 ? nd0[j] : 0, s.lo, s.hi) || s.lo >= s.hi) return s;
   s.st = row_stats<0>(
       V, lane, [&](int, int v) { return x[v] / temperature; },
       [&](int, int v, float m) { return x[v] / temperature - m; });
@@ -525,7 +578,7 @@ __device__ __forceinline__ SampledBeam sampled_beam(int j, int lane, const float
   s.g = g0 ? g0[j] : 0.0f;
   float lmax = -INFINITY;
   bool any = false;
-  sampled_for_children<BLOCKED, FILTERED>(s.lo, s.hi, lane, tok, V, blk, n_blocked, arow, n_words, [&](int, int v) {
+  sampled_for_children<BLOCKED, FILTERED>(s.lo, s.hi, lane, lvl, V, flt, [&](int, int v) {
     lmax = fmaxf(lmax, log_prob(x[v] / temperature - s.st.m, s.st));
     any = true;
   });
@@ -539,20 +592,17 @@ __device__ __forceinline__ SampledBeam sampled_beam(int j, int lane, const float
       // The one place where a child's position matters: a lane's partial sum. Here lane t adds the terms of the ALLOWED
       // children of rank t, t + 64, ... among the node's allowed children — the lanes on which the trie of the allowed
       // rows alone holds the same children — so Lam (and with it phi and G) is bitwise that trie's. A child that is
-      // allowed but no candidate (blocked, token outside [0, V)) adds 0 on its lane, as it does there.
+      // allowed but no candidate (blocked, token outside [0, V)) adds 0 on its lane, as it does there. So this is the
+      // one caller that asks allowed() apart from candidate(): the first places a child, the second gives its term.
       int before = 0;   // allowed children in the chunks so far
       for (int c0 = s.lo; c0 < s.hi; c0 += 64) {   // wave-uniform
         const int c = c0 + lane;
-        const bool in = c < s.hi && allowed_child(arow, n_words, c);
+        const bool in = c < s.hi && flt.allowed<BLOCKED, FILTERED>(c);
         float term = 0.f;
         if (in) {
-          const int v = tok[c];
-          bool cand = v >= 0 && v < V;
-          if constexpr (BLOCKED) {
-            const int at = lower_bound(blk, 0, n_blocked, c);
-            cand = cand && !(at < n_blocked && blk[at] == c);
-          }
-          if (cand) term = expf(log_prob(x[v] / temperature - s.st.m, s.st) - lmax);
+          const int v = lvl.tok[c];
+          if (flt.candidate<BLOCKED, FILTERED>(c, v, V))
+            term = expf(log_prob(x[v] / temperature - s.st.m, s.st) - lmax);
         }
         const uint64_t m = __ballot(in);
         const int n = __popcll((unsigned long long)m);
@@ -562,7 +612,7 @@ __device__ __forceinline__ SampledBeam sampled_beam(int j, int lane, const float
         before += n;
       }
     } else {
-      sampled_for_children<BLOCKED, FILTERED>(s.lo, s.hi, lane, tok, V, blk, n_blocked, arow, n_words, [&](int, int v) {
+      sampled_for_children<BLOCKED, FILTERED>(s.lo, s.hi, lane, lvl, V, flt, [&](int, int v) {
         sum += expf(log_prob(x[v] / temperature - s.st.m, s.st) - lmax);
       });
     }
@@ -580,8 +630,7 @@ __device__ __forceinline__ float sampled_child_phi(float l, const SampledBeam& s
 template <bool BLOCKED, bool FILTERED>
 __global__ void __launch_bounds__(64 * kExpMaxWaves) beam_expand_sampled_kernel(
     const float* __restrict__ logits, const float* __restrict__ noise, float temperature,
-    const int32_t* __restrict__ node, const int32_t* __restrict__ child_off, int n_nodes,
-    const int32_t* __restrict__ tok, int n_children, const int64_t* __restrict__ parents,
+    const int32_t* __restrict__ node, TrieLevel lvl, const int64_t* __restrict__ parents,
     const float* __restrict__ parent_phi, const float* __restrict__ parent_g, int kprev, int V, int P, int k,
     int64_t* __restrict__ out_ids, float* __restrict__ out_phi, float* __restrict__ out_g,
     int32_t* __restrict__ out_parent, int32_t* __restrict__ out_node, const int32_t* __restrict__ blocked,
@@ -590,30 +639,20 @@ __global__ void __launch_bounds__(64 * kExpMaxWaves) beam_expand_sampled_kernel(
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nthr = blockDim.x, nwave = nthr >> 6;   // 4 or kExpMaxWaves waves (the host picks by kprev)
   const int N = kprev * V;
-  uint32_t* key = reinterpret_cast<uint32_t*>(smem);   // [N rounded up to 4], then select_rounds' exchange
-  int* blk = reinterpret_cast<int*>(key + (N + 3) / 4 * 4 + 2 * kExpMaxWaves);   // BLOCKED: [n_blocked <= kBlockedMax]
   const int64_t b = blockIdx.x;
   const int32_t* nd0 = node ? node + b * kprev : nullptr;
   const float* phi0 = parent_phi ? parent_phi + b * kprev : nullptr;
   const float* g0 = parent_g ? parent_g + b * kprev : nullptr;
-  const int32_t* arow = nullptr;   // FILTERED: the user's bitmap row
-  int n_words = -1;
-  if constexpr (FILTERED) n_words = allowed_row(allowed, b, arow);
-
-  for (int e = tid; e < N; e += nthr) key[e] = 0;
-  if constexpr (BLOCKED) {
-    for (int e = tid; e < n_blocked; e += nthr) blk[e] = blocked[b * n_blocked + e];
-  }
-  __syncthreads();
+  uint32_t* key;
+  const ChildFilter flt = expand_prologue<BLOCKED, FILTERED>(smem, N, b, blocked, n_blocked, allowed, key);
 
   for (int j = wave; j < kprev; j += nwave) {
     const float* x = logits + (b * kprev + j) * V;
-    const SampledBeam s = sampled_beam<BLOCKED, FILTERED>(j, lane, x, temperature, nd0, child_off, n_nodes, tok,
-                                                          n_children, phi0, g0, V, blk, n_blocked, arow, n_words);
+    const SampledBeam s = sampled_beam<BLOCKED, FILTERED>(j, lane, x, temperature, nd0, lvl, phi0, g0, V, flt);
     if (!s.live) continue;   // wave-uniform
     const float* e = noise + (b * kprev + j) * V;
     float z = -INFINITY;
-    sampled_for_children<BLOCKED, FILTERED>(s.lo, s.hi, lane, tok, V, blk, n_blocked, arow, n_words, [&](int, int v) {
+    sampled_for_children<BLOCKED, FILTERED>(s.lo, s.hi, lane, lvl, V, flt, [&](int, int v) {
       const float pc = sampled_child_phi(log_prob(x[v] / temperature - s.st.m, s.st), s);
       float ev = e[v];
       if (!(ev > 0.f && ev <= FLT_MAX)) ev = FLT_MIN;
@@ -622,7 +661,7 @@ __global__ void __launch_bounds__(64 * kExpMaxWaves) beam_expand_sampled_kernel(
       z = fmaxf(z, gt);
     });
     z = wave_max(z);
-    sampled_for_children<BLOCKED, FILTERED>(s.lo, s.hi, lane, tok, V, blk, n_blocked, arow, n_words, [&](int, int v) {
+    sampled_for_children<BLOCKED, FILTERED>(s.lo, s.hi, lane, lvl, V, flt, [&](int, int v) {
       const float gt = __builtin_bit_cast(float, key[j * V + v]);
       float gc = -INFINITY;
       if (gt != -INFINITY) {   // then s.g and z are finite, z >= gt
@@ -636,35 +675,12 @@ __global__ void __launch_bounds__(64 * kExpMaxWaves) beam_expand_sampled_kernel(
   }
   __syncthreads();
 
+  const ExpandRows rows = {out_ids + b * k * (P + 1), out_g + b * k, out_phi + b * k, out_parent + b * k,
+                           out_node + b * k};
   select_rounds<kExpMaxWaves>(key, N, k, nthr, [&](int r, uint32_t wk, int wi) {
-    int64_t* o = out_ids + (b * k + r) * (P + 1);
-    if (wk == 0) {   // no candidate left: a dead row
-      if (tid <= P) o[tid] = -1;   // P < 64
-      if (tid == 0) {
-        out_phi[b * k + r] = -INFINITY;
-        out_g[b * k + r] = -INFINITY;
-        out_parent[b * k + r] = 0;
-        out_node[b * k + r] = -1;
-      }
-      return;
-    }
-    const int par = wi / V, v = wi - par * V;
-    if (tid < P) o[tid] = parents[(b * kprev + par) * P + tid];
-    if (tid == 0) {
-      o[P] = v;
-      out_g[b * k + r] = key_score(wk);
-      out_parent[b * k + r] = par;
-    }
+    expand_write_row(rows, r, wk, wi, parents + b * kprev * P, V, P);
   });
-  __syncthreads();   // thread 0's rows (global) are visible to the workgroup
-  for (int r = tid; r < k; r += nthr) {
-    const int v = (int)out_ids[(b * k + r) * (P + 1) + P];
-    if (v < 0) continue;   // a dead row: its node is already -1
-    const int nd = node ? node[b * kprev + out_parent[b * k + r]] : 0;
-    const int end = min(max(child_off[nd + 1], 0), n_children);
-    const int at = lower_bound(tok, min(max(child_off[nd], 0), n_children), end, v);
-    out_node[b * k + r] = (at < end && tok[at] == v) ? at : -1;   // -1: an unsorted (bad) table
-  }
+  expand_nodes(rows, k, P, nd0, lvl);
   // the winner's phi: the value its Gt was formed from. A wave keeps the beam it formed last: on the first step every
   // row has the root for its parent, and one formation per wave serves them all.
   int last = -1;
@@ -675,8 +691,7 @@ __global__ void __launch_bounds__(64 * kExpMaxWaves) beam_expand_sampled_kernel(
     const int par = out_parent[b * k + r];
     const float* x = logits + (b * kprev + par) * V;
     if (par != last) {   // wave-uniform
-      s = sampled_beam<BLOCKED, FILTERED>(par, lane, x, temperature, nd0, child_off, n_nodes, tok, n_children, phi0, g0,
-                                          V, blk, n_blocked, arow, n_words);
+      s = sampled_beam<BLOCKED, FILTERED>(par, lane, x, temperature, nd0, lvl, phi0, g0, V, flt);
       last = par;
     }
     if (lane == 0) out_phi[b * k + r] = sampled_child_phi(log_prob(x[v] / temperature - s.st.m, s.st), s);
@@ -712,22 +727,15 @@ struct WideBeams {   // LDS, per beam
 
 // f(key, c) for every candidate of the user that thread tid owns: c its level-(P + 1) node
 template <bool BLOCKED, bool FILTERED, typename F>
-__device__ __forceinline__ void wide_for_candidates(const WideBeams& s, const int* blk, int n_blocked,
-                                                    const int32_t* arow, int n_words, const float* __restrict__ x, float temperature,
+__device__ __forceinline__ void wide_for_candidates(const WideBeams& s, const ChildFilter& flt,
+                                                    const float* __restrict__ x, float temperature,
                                                     const int32_t* __restrict__ tok, int kprev, int V, F f) {
   const int M = s.off[kprev];
   for (int e = threadIdx.x; e < M; e += kWideThreads) {
     const int j = upper_bound(s.off, 0, kprev, e) - 1;
     const int c = s.lo[j] + (e - s.off[j]);
     const int v = tok[c];
-    if (v < 0 || v >= V) continue;
-    if constexpr (BLOCKED) {
-      const int at = lower_bound(blk, 0, n_blocked, c);
-      if (at < n_blocked && blk[at] == c) continue;
-    }
-    if constexpr (FILTERED) {
-      if (!allowed_child(arow, n_words, c)) continue;
-    }
+    if (!flt.candidate<BLOCKED, FILTERED>(c, v, V)) continue;
     const RowStats st = {s.m[j], s.sum[j], s.log_norm[j]};
     const uint32_t sk = score_key(log_prob(x[(int64_t)j * V + v] / temperature - st.m, st) + s.plp[j]);
     f(((uint64_t)sk << 32) | (uint32_t)~(uint32_t)(j * V + v), c);
@@ -736,8 +744,7 @@ __device__ __forceinline__ void wide_for_candidates(const WideBeams& s, const in
 
 template <bool BLOCKED, bool FILTERED>
 __global__ void __launch_bounds__(kWideThreads) beam_expand_wide_kernel(
-    const float* __restrict__ logits, float temperature, const int32_t* __restrict__ node,
-    const int32_t* __restrict__ child_off, int n_nodes, const int32_t* __restrict__ tok, int n_children,
+    const float* __restrict__ logits, float temperature, const int32_t* __restrict__ node, TrieLevel lvl,
     const int64_t* __restrict__ parents, const float* __restrict__ parent_lp, int kprev, int V, int P, int k,
     int64_t* __restrict__ out_ids, float* __restrict__ out_lp, int32_t* __restrict__ out_parent,
     int32_t* __restrict__ out_node, const int32_t* __restrict__ blocked, int n_blocked, AllowedBits allowed) {
@@ -752,18 +759,14 @@ __global__ void __launch_bounds__(kWideThreads) beam_expand_wide_kernel(
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t b = blockIdx.x;
   const float* x = logits + b * kprev * V;
-  const int32_t* arow = nullptr;   // FILTERED: the user's bitmap row
-  int n_words = -1;
-  if constexpr (FILTERED) n_words = allowed_row(allowed, b, arow);
+  const ChildFilter flt = child_filter<FILTERED>(blk, n_blocked, allowed, b);
 
   // 1. child ranges and their scan
   int lo = 0, cnt = 0;
   if (tid < kprev) {
-    const int nd = node ? node[b * kprev + tid] : 0;
-    if (nd >= 0 && nd < n_nodes) {
-      lo = min(max(child_off[nd], 0), n_children);
-      int hi = min(max(child_off[nd + 1], 0), n_children);
-      if (hi - lo > V) hi = min(lower_bound(tok, lo, hi, V), lo + V);
+    int hi;
+    if (lvl.children(node ? node[b * kprev + tid] : 0, lo, hi)) {
+      if (hi - lo > V) hi = min(lower_bound(lvl.tok, lo, hi, V), lo + V);
       cnt = max(hi - lo, 0);
     }
     s.lo[tid] = lo;
@@ -802,8 +805,7 @@ __global__ void __launch_bounds__(kWideThreads) beam_expand_wide_kernel(
     if (tid < 256) hist[tid] = 0;
     __syncthreads();   // also: the statistics are written
     const uint64_t above = shift == 56 ? 0 : ~0ull << (shift + 8);   // the digits already fixed
-    wide_for_candidates<BLOCKED, FILTERED>(s, blk, n_blocked, arow, n_words, x, temperature, tok, kprev, V,
-                                           [&](uint64_t key, int) {
+    wide_for_candidates<BLOCKED, FILTERED>(s, flt, x, temperature, lvl.tok, kprev, V, [&](uint64_t key, int) {
       if ((key & above) == cut) atomicAdd(&hist[(int)(key >> shift) & 255], 1);
     });
     __syncthreads();
@@ -840,8 +842,7 @@ __global__ void __launch_bounds__(kWideThreads) beam_expand_wide_kernel(
   }
 
   // 3. collect, sort, write
-  wide_for_candidates<BLOCKED, FILTERED>(s, blk, n_blocked, arow, n_words, x, temperature, tok, kprev, V,
-                                         [&](uint64_t key, int c) {
+  wide_for_candidates<BLOCKED, FILTERED>(s, flt, x, temperature, lvl.tok, kprev, V, [&](uint64_t key, int c) {
     if (key >= cut) {
       const int at = atomicAdd(&n_won, 1);
       if (at < kWideMax) { wkey[at] = key; wnode[at] = c; }
@@ -1288,6 +1289,17 @@ __global__ void __launch_bounds__(kAllowThreads) trie_allowed_finish_kernel(unsi
   for (int64_t i = (int64_t)blockIdx.x * kAllowThreads + threadIdx.x; i < n; i += stride) lowest[i] = ~lowest[i];
 }
 
+// Host side of the expand kernels: f(BLOCKED, FILTERED), the two as std::bool_constant values — the instantiation that
+// the filters given ask for
+template <typename F>
+static void with_filters(bool blocked, bool filtered, F f) {
+  if (filtered) {
+    if (blocked) f(std::true_type{}, std::true_type{}); else f(std::false_type{}, std::true_type{});
+  } else {
+    if (blocked) f(std::true_type{}, std::false_type{}); else f(std::false_type{}, std::false_type{});
+  }
+}
+
 }  // namespace rqhip
 
 extern "C" {
@@ -1351,197 +1363,101 @@ int rq_beam_select(const int64_t* cand_ids, const float* cand_lp, const bool* va
                                n_cand, P, k, out_ids, out_lp, nullptr, stream);
 }
 
-// filtered: the _filtered entry points, whose bitmap arguments are checked here; the others pass false and nothing
-static int beam_expand_launch(const char* fn, bool wide, const float* logits, float temperature, const int32_t* node,
-                              const int32_t* child_off, int64_t n_nodes, const int32_t* tok, int64_t n_children,
-                              const int64_t* parents, const float* parent_lp, int64_t B, int64_t kprev, int64_t V,
-                              int64_t P, int64_t k, int64_t* out_ids, float* out_lp, int32_t* out_parent,
-                              int32_t* out_node, const int32_t* blocked, int64_t n_blocked, bool filtered,
-                              const int32_t* allowed, int64_t n_words, int64_t G, const int32_t* group, void* stream) {
+// The argument checks of the three expand entry points, in one order; fn is the entry point's name for the message.
+// beams_ok / beam_names: the P == 0 rule over the entry point's own beam arrays; own_ptrs: its logits and outputs.
+// After a 0 the caller still returns at once when B == 0 (nothing is dereferenced, NULL is fine then).
+enum class ExpandForm { kDense, kWide, kSampled };
+static int beam_expand_check(const char* fn, ExpandForm form, float temperature, int64_t n_nodes, const int32_t* tok,
+                             int64_t n_children, bool beams_ok, const char* beam_names, int64_t B, int64_t kprev,
+                             int64_t V, int64_t P, int64_t k, bool own_ptrs, const int32_t* blocked, int64_t n_blocked,
+                             const int32_t* allowed, int64_t n_words, int64_t G, const int32_t* group) {
   RQ_CHECK_ARG(B >= 0 && kprev >= 1 && V >= 1 && P >= 0 && P < 64, "%s: bad shape", fn);
-  if (wide) {
+  if (form == ExpandForm::kWide) {
     RQ_CHECK_ARG(V <= rqhip::kBeamMaxV && kprev <= rqhip::kWideMax && k >= 1 && k <= rqhip::kWideMax,
                  "%s: need V <= %d, kprev <= %d and 1 <= k <= %d (kprev=%lld, V=%lld, k=%lld)", fn, rqhip::kBeamMaxV,
                  rqhip::kWideMax, rqhip::kWideMax, (long long)kprev, (long long)V, (long long)k);
   } else {
     RQ_CHECK_ARG(V <= rqhip::kBeamMaxV && kprev <= rqhip::kBeamMaxN && kprev * V <= rqhip::kBeamMaxN,
-                 "%s: need V <= %d and kprev * V <= %d (kprev=%lld, V=%lld)", fn, rqhip::kBeamMaxV, rqhip::kBeamMaxN,
-                 (long long)kprev, (long long)V);
+                 "%s: need V <= %d and kprev * V <= %d (kprev=%lld, V=%lld)%s", fn, rqhip::kBeamMaxV, rqhip::kBeamMaxN,
+                 (long long)kprev, (long long)V,
+                 form == ExpandForm::kSampled
+                     ? "; the wide form (more than 32 beams at V = 256) is not built for the sampled step"
+                     : "");
     RQ_CHECK_ARG(k >= 1 && k <= rqhip::kBeamMaxN, "%s: need 1 <= k <= %d (k=%lld)", fn, rqhip::kBeamMaxN, (long long)k);
   }
   RQ_CHECK_ARG(temperature > 0.f && temperature <= 3.0e38f, "%s: temperature must be positive", fn);
   RQ_CHECK_ARG(n_nodes >= 0 && n_nodes < 0x7fffffff && n_children >= 0 && n_children <= 0x7fffffff,
                "%s: bad trie level (n_nodes=%lld, n_children=%lld)", fn, (long long)n_nodes, (long long)n_children);
-  RQ_CHECK_ARG((P == 0) ? (!node && !parents && !parent_lp) : (node && parents && parent_lp),
-               "%s: node, parents and parent_lp are all NULL when P == 0, all given otherwise", fn);
+  RQ_CHECK_ARG(beams_ok, "%s: %s are all NULL when P == 0, all given otherwise", fn, beam_names);
   RQ_CHECK_ARG(n_blocked >= 0 && n_blocked <= rqhip::kBlockedMax, "%s: need 0 <= n_blocked <= %d (n_blocked=%lld)", fn,
                rqhip::kBlockedMax, (long long)n_blocked);
-  RQ_CHECK_ARG(!filtered || (n_words >= 0 && n_words <= 0x7fffffff / 32 && G >= 0 && G <= 0x7fffffff),
+  RQ_CHECK_ARG(!group || (n_words >= 0 && n_words <= 0x7fffffff / 32 && G >= 0 && G <= 0x7fffffff),
                "%s: bad bitmap (n_words=%lld, G=%lld)", fn, (long long)n_words, (long long)G);
   if (B == 0) return 0;
   RQ_CHECK_ARG(B <= 0x7fffffff, "%s: too many batch elements", fn);
-  RQ_CHECK_ARG(logits && child_off && (tok || n_children == 0) && out_ids && out_lp && out_parent && out_node &&
-                   (blocked || n_blocked == 0) && (!filtered || (group && (allowed || n_words * G == 0))),
+  RQ_CHECK_ARG(own_ptrs && (tok || n_children == 0) && (blocked || n_blocked == 0) &&
+                   (!group || allowed || n_words * G == 0),
                "%s: null pointer", fn);
+  return 0;
+}
+
+static size_t beam_expand_lds(int64_t kprev, int64_t V, int64_t n_blocked) {   // expand_prologue's layout
+  return (size_t)((kprev * V + 3) / 4 * 4 + 2 * rqhip::kExpMaxWaves) * sizeof(uint32_t) +
+         (size_t)n_blocked * sizeof(int32_t);
+}
+
+static int beam_expand_launch(const char* fn, bool wide, const float* logits, float temperature, const int32_t* node,
+                              const int32_t* child_off, int64_t n_nodes, const int32_t* tok, int64_t n_children,
+                              const int64_t* parents, const float* parent_lp, int64_t B, int64_t kprev, int64_t V,
+                              int64_t P, int64_t k, int64_t* out_ids, float* out_lp, int32_t* out_parent,
+                              int32_t* out_node, const int32_t* blocked, int64_t n_blocked, const int32_t* allowed,
+                              int64_t n_words, int64_t G, const int32_t* group, void* stream) {
+  const int rc = beam_expand_check(
+      fn, wide ? ExpandForm::kWide : ExpandForm::kDense, temperature, n_nodes, tok, n_children,
+      (P == 0) ? (!node && !parents && !parent_lp) : (node && parents && parent_lp), "node, parents and parent_lp", B,
+      kprev, V, P, k, logits && child_off && out_ids && out_lp && out_parent && out_node, blocked, n_blocked, allowed,
+      n_words, G, group);
+  if (rc != 0 || B == 0) return rc;
+  const rqhip::TrieLevel lvl = {child_off, (int)n_nodes, tok, (int)n_children};
   const rqhip::AllowedBits ab = {allowed, group, (int)n_words, (int)G};
-  const bool blk = n_blocked > 0;
-  if (!blk) { blocked = nullptr; n_blocked = 0; }
-  if (wide) {   // static LDS, one shape of workgroup
-    auto launch = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(rqhip::kWideThreads), 0, (hipStream_t)stream, logits,
-                         temperature, node, child_off, (int)n_nodes, tok, (int)n_children, parents, parent_lp, (int)kprev,
-                         (int)V, (int)P, (int)k, out_ids, out_lp, out_parent, out_node, blocked, (int)n_blocked, ab);
+  if (n_blocked == 0) blocked = nullptr;
+  rqhip::with_filters(n_blocked > 0, group != nullptr, [&](auto blk, auto flt) {
+    constexpr bool kBlk = decltype(blk)::value, kFlt = decltype(flt)::value;
+    auto launch = [&](auto kernel, int threads, size_t lds) {
+      hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(threads), lds, (hipStream_t)stream, logits, temperature, node,
+                         lvl, parents, parent_lp, (int)kprev, (int)V, (int)P, (int)k, out_ids, out_lp, out_parent,
+                         out_node, blocked, (int)n_blocked, ab);
     };
-    if (filtered) {
-      if (blk) launch(rqhip::beam_expand_wide_kernel<true, true>); else launch(rqhip::beam_expand_wide_kernel<false, true>);
+    if (wide) {   // static LDS, one shape of workgroup
+      launch(rqhip::beam_expand_wide_kernel<kBlk, kFlt>, rqhip::kWideThreads, 0);
     } else {
-      if (blk) launch(rqhip::beam_expand_wide_kernel<true, false>); else launch(rqhip::beam_expand_wide_kernel<false, false>);
+      launch(rqhip::beam_expand_kernel<kBlk, kFlt>, kprev > 4 ? 64 * rqhip::kExpMaxWaves : 64 * 4,
+             beam_expand_lds(kprev, V, n_blocked));
     }
-    return 0;
-  }
-  const int waves = kprev > 4 ? rqhip::kExpMaxWaves : 4;
-  const size_t lds = (size_t)((kprev * V + 3) / 4 * 4 + 2 * rqhip::kExpMaxWaves) * sizeof(uint32_t) +
-                     (size_t)n_blocked * sizeof(int32_t);
-  auto launch = [&](auto kernel) {
-    hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(64 * waves), lds, (hipStream_t)stream, logits, temperature, node,
-                       child_off, (int)n_nodes, tok, (int)n_children, parents, parent_lp, (int)kprev, (int)V, (int)P,
-                       (int)k, out_ids, out_lp, out_parent, out_node, blocked, (int)n_blocked, ab);
-  };
-  if (filtered) {
-    if (blk) launch(rqhip::beam_expand_kernel<true, true>); else launch(rqhip::beam_expand_kernel<false, true>);
-  } else {
-    if (blk) launch(rqhip::beam_expand_kernel<true, false>); else launch(rqhip::beam_expand_kernel<false, false>);
-  }
+  });
+  RQ_LAUNCH_CHECK(fn);
   return 0;
 }
 
 int rq_beam_expand(const float* logits, float temperature, const int32_t* node, const int32_t* child_off,
                    int64_t n_nodes, const int32_t* tok, int64_t n_children, const int64_t* parents,
                    const float* parent_lp, int64_t B, int64_t kprev, int64_t V, int64_t P, int64_t k, int64_t* out_ids,
-                   float* out_lp, int32_t* out_parent, int32_t* out_node, void* stream) {
-  const int rc = beam_expand_launch("rq_beam_expand", false, logits, temperature, node, child_off, n_nodes, tok, n_children,
-                                    parents, parent_lp, B, kprev, V, P, k, out_ids, out_lp, out_parent, out_node,
-                                    nullptr, 0, false, nullptr, 0, 0, nullptr, stream);
-  if (rc != 0 || B == 0) return rc;
-  RQ_LAUNCH_CHECK("rq_beam_expand");
-  return 0;
-}
-
-int rq_beam_expand_blocked(const float* logits, float temperature, const int32_t* node, const int32_t* child_off,
-                           int64_t n_nodes, const int32_t* tok, int64_t n_children, const int64_t* parents,
-                           const float* parent_lp, int64_t B, int64_t kprev, int64_t V, int64_t P, int64_t k,
-                           int64_t* out_ids, float* out_lp, int32_t* out_parent, int32_t* out_node,
-                           const int32_t* blocked, int64_t n_blocked, void* stream) {
-  const int rc = beam_expand_launch("rq_beam_expand_blocked", false, logits, temperature, node, child_off, n_nodes, tok,
-                                    n_children, parents, parent_lp, B, kprev, V, P, k, out_ids, out_lp, out_parent,
-                                    out_node, blocked, n_blocked, false, nullptr, 0, 0, nullptr, stream);
-  if (rc != 0 || B == 0) return rc;
-  RQ_LAUNCH_CHECK("rq_beam_expand_blocked");
-  return 0;
+                   float* out_lp, int32_t* out_parent, int32_t* out_node, const int32_t* blocked, int64_t n_blocked,
+                   const int32_t* allowed, int64_t n_words, int64_t G, const int32_t* group, void* stream) {
+  return beam_expand_launch("rq_beam_expand", false, logits, temperature, node, child_off, n_nodes, tok, n_children,
+                            parents, parent_lp, B, kprev, V, P, k, out_ids, out_lp, out_parent, out_node, blocked,
+                            n_blocked, allowed, n_words, G, group, stream);
 }
 
 int rq_beam_expand_wide(const float* logits, float temperature, const int32_t* node, const int32_t* child_off,
                         int64_t n_nodes, const int32_t* tok, int64_t n_children, const int64_t* parents,
                         const float* parent_lp, int64_t B, int64_t kprev, int64_t V, int64_t P, int64_t k,
-                        int64_t* out_ids, float* out_lp, int32_t* out_parent, int32_t* out_node, void* stream) {
-  const int rc = beam_expand_launch("rq_beam_expand_wide", true, logits, temperature, node, child_off, n_nodes, tok,
-                                    n_children, parents, parent_lp, B, kprev, V, P, k, out_ids, out_lp, out_parent,
-                                    out_node, nullptr, 0, false, nullptr, 0, 0, nullptr, stream);
-  if (rc != 0 || B == 0) return rc;
-  RQ_LAUNCH_CHECK("rq_beam_expand_wide");
-  return 0;
-}
-
-int rq_beam_expand_wide_blocked(const float* logits, float temperature, const int32_t* node, const int32_t* child_off,
-                                int64_t n_nodes, const int32_t* tok, int64_t n_children, const int64_t* parents,
-                                const float* parent_lp, int64_t B, int64_t kprev, int64_t V, int64_t P, int64_t k,
-                                int64_t* out_ids, float* out_lp, int32_t* out_parent, int32_t* out_node,
-                                const int32_t* blocked, int64_t n_blocked, void* stream) {
-  const int rc = beam_expand_launch("rq_beam_expand_wide_blocked", true, logits, temperature, node, child_off, n_nodes,
-                                    tok, n_children, parents, parent_lp, B, kprev, V, P, k, out_ids, out_lp, out_parent,
-                                    out_node, blocked, n_blocked, false, nullptr, 0, 0, nullptr, stream);
-  if (rc != 0 || B == 0) return rc;
-  RQ_LAUNCH_CHECK("rq_beam_expand_wide_blocked");
-  return 0;
-}
-
-int rq_beam_expand_filtered(const float* logits, float temperature, const int32_t* node, const int32_t* child_off,
-                            int64_t n_nodes, const int32_t* tok, int64_t n_children, const int64_t* parents,
-                            const float* parent_lp, int64_t B, int64_t kprev, int64_t V, int64_t P, int64_t k,
-                            int64_t* out_ids, float* out_lp, int32_t* out_parent, int32_t* out_node,
-                            const int32_t* blocked, int64_t n_blocked, const int32_t* allowed, int64_t n_words,
-                            int64_t G, const int32_t* group, void* stream) {
-  const int rc = beam_expand_launch("rq_beam_expand_filtered", false, logits, temperature, node, child_off, n_nodes, tok,
-                                    n_children, parents, parent_lp, B, kprev, V, P, k, out_ids, out_lp, out_parent,
-                                    out_node, blocked, n_blocked, true, allowed, n_words, G, group, stream);
-  if (rc != 0 || B == 0) return rc;
-  RQ_LAUNCH_CHECK("rq_beam_expand_filtered");
-  return 0;
-}
-
-int rq_beam_expand_wide_filtered(const float* logits, float temperature, const int32_t* node, const int32_t* child_off,
-                                 int64_t n_nodes, const int32_t* tok, int64_t n_children, const int64_t* parents,
-                                 const float* parent_lp, int64_t B, int64_t kprev, int64_t V, int64_t P, int64_t k,
-                                 int64_t* out_ids, float* out_lp, int32_t* out_parent, int32_t* out_node,
-                                 const int32_t* blocked, int64_t n_blocked, const int32_t* allowed, int64_t n_words,
-                                 int64_t G, const int32_t* group, void* stream) {
-  const int rc = beam_expand_launch("rq_beam_expand_wide_filtered", true, logits, temperature, node, child_off, n_nodes,
-                                    tok, n_children, parents, parent_lp, B, kprev, V, P, k, out_ids, out_lp, out_parent,
-                                    out_node, blocked, n_blocked, true, allowed, n_words, G, group, stream);
-  if (rc != 0 || B == 0) return rc;
-  RQ_LAUNCH_CHECK("rq_beam_expand_wide_filtered");
-  return 0;
-}
-
-static int beam_expand_sampled_launch(const char* fn, const float* logits, const float* noise, float temperature,
-                                      const int32_t* node, const int32_t* child_off, int64_t n_nodes,
-                                      const int32_t* tok, int64_t n_children, const int64_t* parents,
-                                      const float* parent_phi, const float* parent_g, int64_t B, int64_t kprev,
-                                      int64_t V, int64_t P, int64_t k, int64_t* out_ids, float* out_phi, float* out_g,
-                                      int32_t* out_parent, int32_t* out_node, const int32_t* blocked, int64_t n_blocked,
-                                      bool filtered, const int32_t* allowed, int64_t n_words, int64_t G,
-                                      const int32_t* group, void* stream) {
-  RQ_CHECK_ARG(B >= 0 && kprev >= 1 && V >= 1 && P >= 0 && P < 64, "%s: bad shape", fn);
-  RQ_CHECK_ARG(V <= rqhip::kBeamMaxV && kprev <= rqhip::kBeamMaxN && kprev * V <= rqhip::kBeamMaxN,
-               "%s: need V <= %d and kprev * V <= %d (kprev=%lld, V=%lld); the wide form (more than 32 beams at "
-               "V = 256) is not built for the sampled step",
-               fn, rqhip::kBeamMaxV, rqhip::kBeamMaxN, (long long)kprev, (long long)V);
-  RQ_CHECK_ARG(k >= 1 && k <= rqhip::kBeamMaxN, "%s: need 1 <= k <= %d (k=%lld)", fn, rqhip::kBeamMaxN, (long long)k);
-  RQ_CHECK_ARG(temperature > 0.f && temperature <= 3.0e38f, "%s: temperature must be positive", fn);
-  RQ_CHECK_ARG(n_nodes >= 0 && n_nodes < 0x7fffffff && n_children >= 0 && n_children <= 0x7fffffff,
-               "%s: bad trie level (n_nodes=%lld, n_children=%lld)", fn, (long long)n_nodes, (long long)n_children);
-  RQ_CHECK_ARG((P == 0) ? (!node && !parents && !parent_phi && !parent_g) : (node && parents && parent_phi && parent_g),
-               "%s: node, parents, parent_phi and parent_g are all NULL when P == 0, all given otherwise", fn);
-  RQ_CHECK_ARG(n_blocked >= 0 && n_blocked <= rqhip::kBlockedMax, "%s: need 0 <= n_blocked <= %d (n_blocked=%lld)", fn,
-               rqhip::kBlockedMax, (long long)n_blocked);
-  RQ_CHECK_ARG(!filtered || (n_words >= 0 && n_words <= 0x7fffffff / 32 && G >= 0 && G <= 0x7fffffff),
-               "%s: bad bitmap (n_words=%lld, G=%lld)", fn, (long long)n_words, (long long)G);
-  if (B == 0) return 0;
-  RQ_CHECK_ARG(B <= 0x7fffffff, "%s: too many batch elements", fn);
-  RQ_CHECK_ARG(logits && noise && child_off && (tok || n_children == 0) && out_ids && out_phi && out_g && out_parent &&
-                   out_node && (blocked || n_blocked == 0) &&
-                   (!filtered || (group && (allowed || n_words * G == 0))),
-               "%s: null pointer", fn);
-  const rqhip::AllowedBits ab = {allowed, group, (int)n_words, (int)G};
-  const bool blk = n_blocked > 0;
-  if (!blk) { blocked = nullptr; n_blocked = 0; }
-  const int waves = kprev > 4 ? rqhip::kExpMaxWaves : 4;
-  const size_t lds = (size_t)((kprev * V + 3) / 4 * 4 + 2 * rqhip::kExpMaxWaves) * sizeof(uint32_t) +
-                     (size_t)n_blocked * sizeof(int32_t);
-  auto launch = [&](auto kernel) {
-    hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(64 * waves), lds, (hipStream_t)stream, logits, noise, temperature,
-                       node, child_off, (int)n_nodes, tok, (int)n_children, parents, parent_phi, parent_g, (int)kprev,
-                       (int)V, (int)P, (int)k, out_ids, out_phi, out_g, out_parent, out_node, blocked, (int)n_blocked, ab);
-  };
-  if (filtered) {
-    if (blk) launch(rqhip::beam_expand_sampled_kernel<true, true>);
-    else launch(rqhip::beam_expand_sampled_kernel<false, true>);
-  } else {
-    if (blk) launch(rqhip::beam_expand_sampled_kernel<true, false>);
-    else launch(rqhip::beam_expand_sampled_kernel<false, false>);
-  }
-  RQ_LAUNCH_CHECK(fn);
-  return 0;
+                        int64_t* out_ids, float* out_lp, int32_t* out_parent, int32_t* out_node,
+                        const int32_t* blocked, int64_t n_blocked, const int32_t* allowed, int64_t n_words, int64_t G,
+                        const int32_t* group, void* stream) {
+  return beam_expand_launch("rq_beam_expand_wide", true, logits, temperature, node, child_off, n_nodes, tok, n_children,
+                            parents, parent_lp, B, kprev, V, P, k, out_ids, out_lp, out_parent, out_node, blocked,
+                            n_blocked, allowed, n_words, G, group, stream);
 }
 
 int rq_beam_expand_sampled(const float* logits, const float* noise, float temperature, const int32_t* node,
@@ -1549,23 +1465,28 @@ int rq_beam_expand_sampled(const float* logits, const float* noise, float temper
                            const int64_t* parents, const float* parent_phi, const float* parent_g, int64_t B,
                            int64_t kprev, int64_t V, int64_t P, int64_t k, int64_t* out_ids, float* out_phi,
                            float* out_g, int32_t* out_parent, int32_t* out_node, const int32_t* blocked,
-                           int64_t n_blocked, void* stream) {
-  return beam_expand_sampled_launch("rq_beam_expand_sampled", logits, noise, temperature, node, child_off, n_nodes, tok,
-                                    n_children, parents, parent_phi, parent_g, B, kprev, V, P, k, out_ids, out_phi, out_g,
-                                    out_parent, out_node, blocked, n_blocked, false, nullptr, 0, 0, nullptr, stream);
-}
-
-int rq_beam_expand_sampled_filtered(const float* logits, const float* noise, float temperature, const int32_t* node,
-                                    const int32_t* child_off, int64_t n_nodes, const int32_t* tok, int64_t n_children,
-                                    const int64_t* parents, const float* parent_phi, const float* parent_g, int64_t B,
-                                    int64_t kprev, int64_t V, int64_t P, int64_t k, int64_t* out_ids, float* out_phi,
-                                    float* out_g, int32_t* out_parent, int32_t* out_node, const int32_t* blocked,
-                                    int64_t n_blocked, const int32_t* allowed, int64_t n_words, int64_t G,
-                                    const int32_t* group, void* stream) {
-  return beam_expand_sampled_launch("rq_beam_expand_sampled_filtered", logits, noise, temperature, node, child_off,
-                                    n_nodes, tok, n_children, parents, parent_phi, parent_g, B, kprev, V, P, k, out_ids,
-                                    out_phi, out_g, out_parent, out_node, blocked, n_blocked, true, allowed, n_words, G,
-                                    group, stream);
+                           int64_t n_blocked, const int32_t* allowed, int64_t n_words, int64_t G, const int32_t* group,
+                           void* stream) {
+  const char* fn = "rq_beam_expand_sampled";
+  const int rc = beam_expand_check(
+      fn, ExpandForm::kSampled, temperature, n_nodes, tok, n_children,
+      (P == 0) ? (!node && !parents && !parent_phi && !parent_g) : (node && parents && parent_phi && parent_g),
+      "node, parents, parent_phi and parent_g", B, kprev, V, P, k,
+      logits && noise && child_off && out_ids && out_phi && out_g && out_parent && out_node, blocked, n_blocked,
+      allowed, n_words, G, group);
+  if (rc != 0 || B == 0) return rc;
+  const rqhip::TrieLevel lvl = {child_off, (int)n_nodes, tok, (int)n_children};
+  const rqhip::AllowedBits ab = {allowed, group, (int)n_words, (int)G};
+  if (n_blocked == 0) blocked = nullptr;
+  rqhip::with_filters(n_blocked > 0, group != nullptr, [&](auto blk, auto flt) {
+    hipLaunchKernelGGL((rqhip::beam_expand_sampled_kernel<decltype(blk)::value, decltype(flt)::value>),
+                       dim3((unsigned)B), dim3(kprev > 4 ? 64 * rqhip::kExpMaxWaves : 64 * 4),
+                       beam_expand_lds(kprev, V, n_blocked), (hipStream_t)stream, logits, noise, temperature, node, lvl,
+                       parents, parent_phi, parent_g, (int)kprev, (int)V, (int)P, (int)k, out_ids, out_phi, out_g,
+                       out_parent, out_node, blocked, (int)n_blocked, ab);
+  });
+  RQ_LAUNCH_CHECK(fn);
+  return 0;
 }
 
 int rq_score_paths(const float* logits, float temperature, const int64_t* tokens, int64_t tok_stride_b,

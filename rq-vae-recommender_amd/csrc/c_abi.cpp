@@ -23,7 +23,7 @@ extern "C" {
 
 const char* rq_last_error(void) { return rqhip::g_err; }
 
-int rq_abi_version(void) { return 3; }
+int rq_abi_version(void) { return 4; }
 
 // Dropout epoch (common.h): the three translation units' device copies, resolved once per device
 // (the symbol addresses differ per device) and cached; resolving costs three runtime lookups, and the

@@ -68,6 +68,20 @@ class Scores(NamedTuple):
     rank: Tensor         # (B, C) int32: each candidate's place among its user's, a permutation of 0..C-1
 
 
+class _TrieSearch(NamedTuple):
+    """A trie search's per-call tables (EncoderDecoderRetrievalModel._trie_search)."""
+    trie: object
+    blocked: Tensor       # (D, B, H) int32 blocked nodes of every level, or None
+    item_filter: object   # ItemFilter or None
+    group: Tensor         # (B,) int32 with item_filter, else None
+
+    def level(self, i: int) -> dict:
+        """Step i's trie and filter arguments of hip_ops.beam_expand / beam_expand_sampled."""
+        return dict(child_off=self.trie.child_off[i], tok=self.trie.tok[i + 1],
+                    blocked=None if self.blocked is None else self.blocked[i],
+                    allowed=None if self.item_filter is None else self.item_filter.bits[i], group=self.group)
+
+
 class EncoderDecoderRetrievalModel(nn.Module):
     def __init__(self, embedding_dim, attn_dim, dropout, num_heads, n_layers, num_embeddings, sem_id_dim,
                  inference_verifier_fn, max_pos=2048, jagged_mode: bool = True) -> None:
@@ -291,10 +305,9 @@ class EncoderDecoderRetrievalModel(nn.Module):
         generated, log_probas = None, 0
         k = 32 if top_k else 1
         n_cand = 200 if top_k else 1
-        cur = TokenizedSeqBatch(user_ids=batch.user_ids, sem_ids=batch.sem_ids, sem_ids_fut=None,
-                                seq_mask=batch.seq_mask, token_type_ids=batch.token_type_ids, token_type_ids_fut=None)
+        step = _ForwardSteps(self, batch)
         for i in range(self.sem_id_dim):
-            logits = self.forward(cur).logits
+            logits = step() if generated is None else step(generated)
             probas = F.softmax(logits / temperature, dim=-1)
             samples_b = torch.multinomial(probas, num_samples=n_cand)
             if generated is None:
@@ -311,37 +324,39 @@ class EncoderDecoderRetrievalModel(nn.Module):
             top_samples = torch.gather(samples, 1, top_idx)
             if generated is not None:
                 parent = torch.gather(generated, 1, (top_idx // n_cand).unsqueeze(2).expand(-1, -1, i))
-                top_samples = torch.cat([parent, top_samples.unsqueeze(-1)], axis=-1)
-                nxt = top_samples.flatten(end_dim=1)
-                cur = TokenizedSeqBatch(user_ids=cur.user_ids, sem_ids=cur.sem_ids, sem_ids_fut=nxt,
-                                        token_type_ids_fut=torch.arange(nxt.shape[1], device=nxt.device).repeat(nxt.shape[0], 1),
-                                        seq_mask=cur.seq_mask, token_type_ids=cur.token_type_ids)
-                generated = top_samples.detach().clone()
-                log_probas = top_lp.detach().clone()
+                generated = torch.cat([parent, top_samples.unsqueeze(-1)], axis=-1).detach().clone()
             else:
-                nxt = top_samples.reshape(-1, 1)
-                enc = self.transformer.cached_enc_output
-                n_ctx = cur.sem_ids.shape[1] + 1
-                padded = jagged_to_padded_tensor(enc, n_ctx).repeat_interleave(k, dim=0)
-                lengths = enc.offsets().diff().repeat_interleave(k)
-                self.transformer.cached_enc_output = padded_to_jagged(padded.contiguous(), lengths, n_ctx)
-                cur = TokenizedSeqBatch(user_ids=cur.user_ids.repeat_interleave(k, dim=0),
-                                        sem_ids=cur.sem_ids.repeat_interleave(k, dim=0), sem_ids_fut=nxt,
-                                        token_type_ids_fut=torch.zeros_like(nxt),
-                                        seq_mask=cur.seq_mask.repeat_interleave(k, dim=0),
-                                        token_type_ids=cur.token_type_ids.repeat_interleave(k, dim=0))
                 generated = top_samples.unsqueeze(-1)
-                log_probas = top_lp.detach().clone()
+            log_probas = top_lp.detach().clone()
         return GenerationOutput(sem_ids=generated.squeeze(), log_probas=log_probas.squeeze())
 
-    def _constrained_trie(self, what: str):
+    def _constrained_trie(self, what: str, items: bool = False):
+        """The tokenizer's prefix trie, deep enough for the search; items: its leaves must be the corpus items."""
         index = getattr(self, "inference_prefix_index", None)
         if index is None:
             raise ValueError(f"{what}: constrained decoding requires inference_prefix_index (the tokenizer)")
         trie = index.prefix_trie()
         if trie.depth < self.sem_id_dim:
             raise ValueError(f"{what}: the corpus trie has depth {trie.depth} < sem_id_dim = {self.sem_id_dim}")
+        if items and trie.depth != self.sem_id_dim:
+            raise ValueError(f"{what}: the corpus trie has depth {trie.depth}, the model generates {self.sem_id_dim} "
+                             "tokens; items are the leaves of the full depth")
         return trie
+
+    def _trie_search(self, what: str, batch: TokenizedSeqBatch, exclude_items, item_filter, filter_group):
+        """The per-call tables of a search over the trie, errors under the caller's name `what`: the trie, the users'
+        blocked nodes of every level (exclude_items (B, H); the tokenizer's blocked_nodes, one launch for the whole
+        call) and the catalogue filter (_item_filter's arguments). _TrieSearch.level(i) hands step i its slices."""
+        trie = self._constrained_trie(what)
+        B = batch.sem_ids.shape[0]
+        item_filter, group = self._item_filter(what, item_filter, filter_group, B, batch.sem_ids.device)
+        blocked = None
+        if exclude_items is not None:
+            if exclude_items.dim() != 2 or exclude_items.shape[0] != B:
+                raise ValueError(f"{what}: exclude_items must be (B, H) with B = {B} rows, got "
+                                 f"{tuple(exclude_items.shape)}")
+            blocked = self.inference_prefix_index.blocked_nodes(exclude_items)
+        return _TrieSearch(trie, blocked, item_filter, group)
 
     def _item_filter(self, what: str, item_filter, filter_group, B: int, device):
         """(ItemFilter, group (B,) int32 on the device) of a call's item_filter / filter_group arguments, or (None,
@@ -394,10 +409,7 @@ class EncoderDecoderRetrievalModel(nn.Module):
         reported under its lowest allowed index), never a disallowed one."""
         if not 1 <= k <= beams <= hip_ops.BEAM_WIDE_MAX:
             raise ValueError(f"recommend: need 1 <= k <= {beams} beams <= {hip_ops.BEAM_WIDE_MAX}, got k = {k}")
-        trie = self._constrained_trie("recommend")
-        if trie.depth != self.sem_id_dim:
-            raise ValueError(f"recommend: the corpus trie has depth {trie.depth}, the model generates {self.sem_id_dim} "
-                             "tokens; items are the leaves of the full depth")
+        trie = self._constrained_trie("recommend", items=True)
         assert self.enable_generation, "Model generation is not enabled"
         B, dev = batch.sem_ids.shape[0], batch.sem_ids.device
         item_filter, group = self._item_filter("recommend", item_filter, filter_group, B, dev)
@@ -431,30 +443,19 @@ class EncoderDecoderRetrievalModel(nn.Module):
         if not 1 <= k <= limit:
             raise ValueError(f"sample_items: need 1 <= k and k * num_embeddings <= {hip_ops.BEAM_MAX_N}, that is "
                              f"k <= {limit} at num_embeddings = {self.num_embeddings}; got k = {k}")
-        trie = self._constrained_trie("sample_items")
-        if trie.depth != self.sem_id_dim:
-            raise ValueError(f"sample_items: the corpus trie has depth {trie.depth}, the model generates "
-                             f"{self.sem_id_dim} tokens; items are the leaves of the full depth")
+        self._constrained_trie("sample_items", items=True)
         assert self.enable_generation, "Model generation is not enabled"
         B = batch.sem_ids.shape[0]
-        blocked = None
-        if exclude_items is not None:
-            if exclude_items.dim() != 2 or exclude_items.shape[0] != B:
-                raise ValueError(f"sample_items: exclude_items must be (B, H) with B = {B} rows, got "
-                                 f"{tuple(exclude_items.shape)}")
-            blocked = self.inference_prefix_index.blocked_nodes(exclude_items)
-        item_filter, group = self._item_filter("sample_items", item_filter, filter_group, B, batch.sem_ids.device)
+        search = self._trie_search("sample_items", batch, exclude_items, item_filter, filter_group)
         generated, phi, g, parent, node = None, None, None, None, None
         with self._step_logits(batch, incremental) as step:
             for i in range(self.sem_id_dim):
                 logits = (step() if generated is None else step(generated.clamp_min(0), parent)).contiguous()
                 noise = torch.empty_like(logits).exponential_(generator=generator)
                 generated, phi, g, parent, node = hip_ops.beam_expand_sampled(
-                    logits, k, batch=B, child_off=trie.child_off[i], tok=trie.tok[i + 1], noise=noise, node=node,
-                    parents=generated, parent_phi=phi, parent_g=g, temperature=temperature,
-                    blocked=None if blocked is None else blocked[i],
-                    allowed=None if item_filter is None else item_filter.bits[i], group=group)
-        items = self._leaf_items(trie, item_filter, group, node)
+                    logits, k, batch=B, noise=noise, node=node, parents=generated, parent_phi=phi, parent_g=g,
+                    temperature=temperature, **search.level(i))
+        items = self._leaf_items(search.trie, search.item_filter, search.group, node)
         return SampledItems(item_ids=items, sem_ids=generated, log_probas=phi, perturbed=g)
 
     @eval_mode
@@ -546,25 +547,15 @@ class EncoderDecoderRetrievalModel(nn.Module):
         level-(i + 1) nodes (the tokenizer's blocked_nodes, one launch for the whole call). item_filter / filter_group
         (_item_filter's arguments): step i's beam_expand keeps only the children set in item_filter.bits[i], row
         filter_group[b]. Runs under the caller's decorators."""
-        trie = self._constrained_trie("generate_next_sem_id")
         B = batch.sem_ids.shape[0]
-        item_filter, group = self._item_filter("generate_next_sem_id", item_filter, filter_group, B,
-                                               batch.sem_ids.device)
-        blocked = None
-        if exclude_items is not None:
-            if exclude_items.dim() != 2 or exclude_items.shape[0] != B:
-                raise ValueError(f"generate_next_sem_id: exclude_items must be (B, H) with B = {B} rows, got "
-                                 f"{tuple(exclude_items.shape)}")
-            blocked = self.inference_prefix_index.blocked_nodes(exclude_items)
+        search = self._trie_search("generate_next_sem_id", batch, exclude_items, item_filter, filter_group)
         generated, log_probas, parent, node = None, None, None, None
         with self._step_logits(batch, incremental) as step:
             for i in range(self.sem_id_dim):
                 logits = step() if generated is None else step(generated.clamp_min(0), parent)
                 generated, log_probas, parent, node = hip_ops.beam_expand(
-                    logits.contiguous(), k, batch=B, child_off=trie.child_off[i], tok=trie.tok[i + 1], node=node,
-                    parents=generated, parent_lp=log_probas, temperature=temperature,
-                    blocked=None if blocked is None else blocked[i], wide=None,
-                    allowed=None if item_filter is None else item_filter.bits[i], group=group)
+                    logits.contiguous(), k, batch=B, node=node, parents=generated, parent_lp=log_probas,
+                    temperature=temperature, wide=None, **search.level(i))
         return generated, log_probas, node
 
     def _beams_batch(self, cur: TokenizedSeqBatch, generated: Tensor, first: bool, k: int) -> TokenizedSeqBatch:

@@ -95,23 +95,14 @@ _SIGS = {
     "rq_beam_select_parent": ([_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P],
                               _I),
     "rq_beam_self_attn": ([_P, _I64, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _F, _P, _I64, _P], _I),
-    "rq_beam_expand": ([_P, _F, _P, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P], _I),
+    "rq_beam_expand": ([_P, _F, _P, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P, _I64,
+                        _P, _I64, _I64, _P, _P], _I),
     "rq_topk_hits": ([_P, _P, _I64, _I64, _I64, _P, _I64, _P, _P], _I),
-    "rq_beam_expand_blocked": ([_P, _F, _P, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P,
-                                _P, _I64, _P], _I),
-    "rq_beam_expand_wide": ([_P, _F, _P, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P],
-                            _I),
-    "rq_beam_expand_wide_blocked": ([_P, _F, _P, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P,
-                                     _P, _P, _I64, _P], _I),
+    "rq_beam_expand_wide": ([_P, _F, _P, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P,
+                             _I64, _P, _I64, _I64, _P, _P], _I),
     "rq_beam_expand_sampled": ([_P, _P, _F, _P, _P, _I64, _P, _I64, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P,
-                                _P, _P, _P, _I64, _P], _I),
+                                _P, _P, _P, _I64, _P, _I64, _I64, _P, _P], _I),
     "rq_trie_blocked_nodes": ([_P, _I64, _I64, _P, _I64, _I64, _P, _P, _P, _I64, _P, _P], _I),
-    "rq_beam_expand_filtered": ([_P, _F, _P, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P,
-                                 _P, _I64, _P, _I64, _I64, _P, _P], _I),
-    "rq_beam_expand_wide_filtered": ([_P, _F, _P, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P,
-                                      _P, _P, _I64, _P, _I64, _I64, _P, _P], _I),
-    "rq_beam_expand_sampled_filtered": ([_P, _P, _F, _P, _P, _I64, _P, _I64, _P, _P, _P, _I64, _I64, _I64, _I64, _I64,
-                                         _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _I64, _P, _P], _I),
     "rq_trie_allowed_nodes": ([_P, _I64, _I64, _P, _I64, _P, _P, _I64, _P, _P, _P], _I),
     "rq_rank_hist": ([_P, _P, _I64, _I64, _I64, _P, _P], _I),
     "rq_score_paths": ([_P, _F, _P, _I64, _I64, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _P], _I),

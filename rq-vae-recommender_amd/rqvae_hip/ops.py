@@ -2486,18 +2486,68 @@ BEAM_WIDE_MAX = 1024   # kWideMax (csrc/beam.hip): most beams in / out of the wi
 
 
 def _beam_allowed(what, B, allowed, group) -> tuple:
-    """The (allowed, n_words, G, group) arguments of the _filtered entry points — allowed (G, n_words) int32 and group
-    (B) int32, given together — or () with neither."""
+    """The (allowed, n_words, G, group) arguments of the expand entry points — allowed (G, n_words) int32 and group
+    (B) int32, given together — or the NULLs that say "no catalogue filter" with neither."""
     if (allowed is None) != (group is None):
         raise RqHipError(f"{what}: allowed and group go together")
     if allowed is None:
-        return ()
+        return (None, 0, 0, None)
     if allowed.dim() != 2:
         raise RqHipError(f"{what}: allowed must be (G, n_words), got {tuple(allowed.shape)}")
     _beam_arg(allowed, torch.int32, what, "allowed")
     _beam_arg(group, torch.int32, what, "group", (B,))
     G, n_words = allowed.shape
     return (ptr(allowed) if G * n_words else None, n_words, G, ptr(group))
+
+
+class _ExpandCall(NamedTuple):
+    """What beam_expand and beam_expand_sampled share once their arguments are checked (_beam_expand_setup)."""
+    kprev: int
+    V: int
+    trie: tuple    # node, child_off, n_nodes, tok, n_children
+    shape: tuple   # B, kprev, V, P, k
+    out_ids: torch.Tensor      # (B, k, P + 1) int64
+    out_parent: torch.Tensor   # (B, k) int32
+    out_node: torch.Tensor     # (B, k) int32
+    tail: tuple    # blocked, n_blocked, allowed, n_words, G, group, stream
+
+    def scores(self) -> torch.Tensor:
+        """A (B, k) fp32 output: out_lp, out_phi or out_g."""
+        return torch.empty(self.out_parent.shape, device=self.out_parent.device, dtype=torch.float32)
+
+
+def _beam_expand_setup(what, logits, k, batch, child_off, tok, node, parents, parent_lp, blocked, allowed, group, *more,
+                       lp_name="parent_lp", first_step="node, parents and parent_lp") -> _ExpandCall:
+    """The argument checks, the outputs and the trailing arguments common to the expand steps. more: the caller's own
+    tensors, checked for residence only; the envelope is the caller's to check (the wide form has its own)."""
+    require_gpu(logits, child_off, tok, node, parents, parent_lp, blocked, allowed, group, *more, what=what)
+    B = int(batch)
+    if logits.dim() != 2 or B < 0 or (B and logits.shape[0] % B):
+        raise RqHipError(f"{what}: logits must be (B * kprev, V)")
+    _beam_arg(logits, torch.float32, what, "logits")
+    R, V = logits.shape
+    kprev = R // B if B else 1
+    P = _beam_parents(what, B, kprev, parents, parent_lp, node, lp_name=lp_name)
+    if parents is not None and P == 0:
+        raise RqHipError(f"{what}: parents with P == 0; pass {first_step} as None on the first step")
+    if child_off.dim() != 1 or tok.dim() != 1 or child_off.numel() < 1:
+        raise RqHipError(f"{what}: child_off (n_nodes + 1) and tok (n_children) must be 1-D")
+    _beam_arg(child_off, torch.int32, what, "child_off")
+    _beam_arg(tok, torch.int32, what, "tok")
+    n_blocked = 0
+    if blocked is not None:
+        if blocked.dim() != 2 or blocked.shape[0] != B or blocked.shape[1] > BLOCKED_MAX:
+            raise RqHipError(f"{what}: blocked must be (B, n_blocked <= {BLOCKED_MAX}), got {tuple(blocked.shape)}")
+        _beam_arg(blocked, torch.int32, what, "blocked")
+        n_blocked = blocked.shape[1]
+    bitmap = _beam_allowed(what, B, allowed, group)
+    dev = logits.device
+    return _ExpandCall(
+        kprev, V, (ptr(node), ptr(child_off), child_off.numel() - 1, ptr(tok), tok.numel()), (B, kprev, V, P, int(k)),
+        torch.empty((B, int(k), P + 1), device=dev, dtype=torch.int64),
+        torch.empty((B, int(k)), device=dev, dtype=torch.int32),
+        torch.empty((B, int(k)), device=dev, dtype=torch.int32),
+        (ptr(blocked) if n_blocked else None, n_blocked, *bitmap, stream_handle(dev)))
 
 
 def beam_expand(logits: torch.Tensor, k: int, *, batch: int, child_off: torch.Tensor, tok: torch.Tensor,
@@ -2512,30 +2562,18 @@ def beam_expand(logits: torch.Tensor, k: int, *, batch: int, child_off: torch.Te
     out_node, out_ids and out_lp — all None on the first step (every beam on the root). With fewer than k valid
     continuations the remaining rows are dead: ids -1, -inf, parent 0, node -1. One launch, no host read.
     blocked (B, n_blocked <= 1024) int32: per batch element the level-(P + 1) nodes that are not candidates, ascending
-    and INT32_MAX-padded — slice P of trie_blocked_nodes' result (rq_beam_expand_blocked); None: no filter.
+    and INT32_MAX-padded — slice P of trie_blocked_nodes' result; None: no exclusion (the entry point's NULL).
     wide: False (the default: a plain call refuses what it always refused) — that kernel, whose envelope is
-    kprev * V <= 8192; True — rq_beam_expand_wide(_blocked), the same contract and, where both take the shape, the
+    kprev * V <= 8192; True — rq_beam_expand_wide, the same arguments and contract and, where both take the shape, the
     same bits, for kprev <= 1024 and k <= 1024 at any kprev * V; None (what the model's search passes) — the first
     wherever its envelope holds, so results and timings there are what they were, else the wide one.
-    allowed (G, n_words) int32 with group (B) int32, given together (rq_beam_expand_filtered /
-    rq_beam_expand_wide_filtered): a catalogue filter — slice P of trie_allowed_nodes' bitmaps (ItemFilter.bits[P]), bit
+    allowed (G, n_words) int32 with group (B) int32, given together (neither: the entry point's NULL group): a
+    catalogue filter — slice P of trie_allowed_nodes' bitmaps (ItemFilter.bits[P]), bit
     c of row group[b] set iff the level-(P + 1) node c leads to an item batch element b may be shown; a group outside
     [0, G) (-1) leaves that element unfiltered. Composes with blocked: a candidate passes both."""
     what = "beam_expand"
-    require_gpu(logits, child_off, tok, node, parents, parent_lp, blocked, allowed, group, what=what)
-    B = int(batch)
-    if logits.dim() != 2 or B < 0 or (B and logits.shape[0] % B):
-        raise RqHipError(f"{what}: logits must be (B * kprev, V)")
-    _beam_arg(logits, torch.float32, what, "logits")
-    R, V = logits.shape
-    kprev = R // B if B else 1
-    P = _beam_parents(what, B, kprev, parents, parent_lp, node)
-    if parents is not None and P == 0:
-        raise RqHipError(f"{what}: parents with P == 0; pass node, parents and parent_lp as None on the first step")
-    if child_off.dim() != 1 or tok.dim() != 1 or child_off.numel() < 1:
-        raise RqHipError(f"{what}: child_off (n_nodes + 1) and tok (n_children) must be 1-D")
-    _beam_arg(child_off, torch.int32, what, "child_off")
-    _beam_arg(tok, torch.int32, what, "tok")
+    c = _beam_expand_setup(what, logits, k, batch, child_off, tok, node, parents, parent_lp, blocked, allowed, group)
+    kprev, V = c.kprev, c.V
     if wide is None:
         wide = kprev * V > BEAM_MAX_N
     if wide:
@@ -2545,35 +2583,10 @@ def beam_expand(logits: torch.Tensor, k: int, *, batch: int, child_off: torch.Te
     elif V < 1 or V > BEAM_MAX_V or kprev * V > BEAM_MAX_N or not 1 <= int(k) <= BEAM_MAX_N:
         raise RqHipError(f"{what}: outside the supported envelope V <= {BEAM_MAX_V}, kprev * V <= {BEAM_MAX_N}, "
                          f"1 <= k <= {BEAM_MAX_N} (kprev={kprev}, V={V}, k={k})")
-    if blocked is not None:
-        if blocked.dim() != 2 or blocked.shape[0] != B or blocked.shape[1] > BLOCKED_MAX:
-            raise RqHipError(f"{what}: blocked must be (B, n_blocked <= {BLOCKED_MAX}), got {tuple(blocked.shape)}")
-        _beam_arg(blocked, torch.int32, what, "blocked")
-    bitmap = _beam_allowed(what, B, allowed, group)
-    dev = logits.device
-    out_ids = torch.empty((B, int(k), P + 1), device=dev, dtype=torch.int64)
-    out_lp = torch.empty((B, int(k)), device=dev, dtype=torch.float32)
-    out_parent = torch.empty((B, int(k)), device=dev, dtype=torch.int32)
-    out_node = torch.empty((B, int(k)), device=dev, dtype=torch.int32)
-    filt = () if blocked is None else (ptr(blocked) if blocked.shape[1] else None, blocked.shape[1])
-    if bitmap:
-        call("rq_beam_expand_wide_filtered" if wide else "rq_beam_expand_filtered", ptr(logits), float(temperature),
-             ptr(node), ptr(child_off), child_off.numel() - 1, ptr(tok), tok.numel(), ptr(parents), ptr(parent_lp), B,
-             kprev, V, P, int(k), ptr(out_ids), ptr(out_lp), ptr(out_parent), ptr(out_node), *(filt or (None, 0)),
-             *bitmap, stream_handle(dev))
-    elif not wide:
-        call("rq_beam_expand" if blocked is None else "rq_beam_expand_blocked", ptr(logits), float(temperature),
-             ptr(node), ptr(child_off), child_off.numel() - 1, ptr(tok), tok.numel(), ptr(parents), ptr(parent_lp), B,
-             kprev, V, P, int(k), ptr(out_ids), ptr(out_lp), ptr(out_parent), ptr(out_node), *filt, stream_handle(dev))
-    elif blocked is None:
-        call("rq_beam_expand_wide", ptr(logits), float(temperature), ptr(node), ptr(child_off), child_off.numel() - 1,
-             ptr(tok), tok.numel(), ptr(parents), ptr(parent_lp), B, kprev, V, P, int(k), ptr(out_ids), ptr(out_lp),
-             ptr(out_parent), ptr(out_node), stream_handle(dev))
-    else:
-        call("rq_beam_expand_wide_blocked", ptr(logits), float(temperature), ptr(node), ptr(child_off),
-             child_off.numel() - 1, ptr(tok), tok.numel(), ptr(parents), ptr(parent_lp), B, kprev, V, P, int(k),
-             ptr(out_ids), ptr(out_lp), ptr(out_parent), ptr(out_node), filt[0], filt[1], stream_handle(dev))
-    return out_ids, out_lp, out_parent, out_node
+    out_lp = c.scores()
+    call("rq_beam_expand_wide" if wide else "rq_beam_expand", ptr(logits), float(temperature), *c.trie, ptr(parents),
+         ptr(parent_lp), *c.shape, ptr(c.out_ids), ptr(out_lp), ptr(c.out_parent), ptr(c.out_node), *c.tail)
+    return c.out_ids, out_lp, c.out_parent, c.out_node
 
 
 def beam_expand_sampled(logits: torch.Tensor, k: int, *, batch: int, child_off: torch.Tensor, tok: torch.Tensor,
@@ -2591,51 +2604,26 @@ def beam_expand_sampled(logits: torch.Tensor, k: int, *, batch: int, child_off: 
     descending per user, never above its parent's, the best child of a beam inheriting the parent's exactly. Dead rows:
     ids -1, phi = g = -inf, parent 0, node -1. One launch, no host read. The envelope is beam_expand's narrow one
     (kprev * V <= 8192); there is no wide form. allowed (G, n_words) int32 with group (B) int32: beam_expand's catalogue
-    filter (rq_beam_expand_sampled_filtered) — the renormalisation then runs over the candidates that remain."""
+    filter — the renormalisation then runs over the candidates that remain."""
     what = "beam_expand_sampled"
-    require_gpu(logits, noise, child_off, tok, node, parents, parent_phi, parent_g, blocked, allowed, group, what=what)
-    B = int(batch)
-    if logits.dim() != 2 or B < 0 or (B and logits.shape[0] % B):
-        raise RqHipError(f"{what}: logits must be (B * kprev, V)")
-    _beam_arg(logits, torch.float32, what, "logits")
-    R, V = logits.shape
-    kprev = R // B if B else 1
-    if noise is None:
-        raise RqHipError(f"{what}: noise (Exponential(1) draws, the shape of logits) is required")
-    _beam_arg(noise, torch.float32, what, "noise", (R, V))
     if (parent_phi is None) != (parent_g is None):
         raise RqHipError(f"{what}: parent_phi and parent_g go together")
-    P = _beam_parents(what, B, kprev, parents, parent_phi, node, lp_name="parent_phi")
-    if parents is not None and P == 0:
-        raise RqHipError(f"{what}: parents with P == 0; pass node, parents, parent_phi and parent_g as None on the "
-                         "first step")
+    c = _beam_expand_setup(what, logits, k, batch, child_off, tok, node, parents, parent_phi, blocked, allowed, group,
+                           noise, parent_g, lp_name="parent_phi",
+                           first_step="node, parents, parent_phi and parent_g")
+    B, kprev, V = c.shape[:3]
+    if noise is None:
+        raise RqHipError(f"{what}: noise (Exponential(1) draws, the shape of logits) is required")
+    _beam_arg(noise, torch.float32, what, "noise", tuple(logits.shape))
     if parent_g is not None:
         _beam_arg(parent_g, torch.float32, what, "parent_g", (B, kprev))
-    if child_off.dim() != 1 or tok.dim() != 1 or child_off.numel() < 1:
-        raise RqHipError(f"{what}: child_off (n_nodes + 1) and tok (n_children) must be 1-D")
-    _beam_arg(child_off, torch.int32, what, "child_off")
-    _beam_arg(tok, torch.int32, what, "tok")
     if V < 1 or V > BEAM_MAX_V or kprev * V > BEAM_MAX_N or not 1 <= int(k) <= BEAM_MAX_N:
         raise RqHipError(f"{what}: outside the supported envelope V <= {BEAM_MAX_V}, kprev * V <= {BEAM_MAX_N}, "
                          f"1 <= k <= {BEAM_MAX_N} (kprev={kprev}, V={V}, k={k}); the sampled step has no wide form")
-    n_blocked = 0
-    if blocked is not None:
-        if blocked.dim() != 2 or blocked.shape[0] != B or blocked.shape[1] > BLOCKED_MAX:
-            raise RqHipError(f"{what}: blocked must be (B, n_blocked <= {BLOCKED_MAX}), got {tuple(blocked.shape)}")
-        _beam_arg(blocked, torch.int32, what, "blocked")
-        n_blocked = blocked.shape[1]
-    bitmap = _beam_allowed(what, B, allowed, group)
-    dev = logits.device
-    out_ids = torch.empty((B, int(k), P + 1), device=dev, dtype=torch.int64)
-    out_phi = torch.empty((B, int(k)), device=dev, dtype=torch.float32)
-    out_g = torch.empty((B, int(k)), device=dev, dtype=torch.float32)
-    out_parent = torch.empty((B, int(k)), device=dev, dtype=torch.int32)
-    out_node = torch.empty((B, int(k)), device=dev, dtype=torch.int32)
-    call("rq_beam_expand_sampled_filtered" if bitmap else "rq_beam_expand_sampled", ptr(logits), ptr(noise),
-         float(temperature), ptr(node), ptr(child_off), child_off.numel() - 1, ptr(tok), tok.numel(), ptr(parents),
-         ptr(parent_phi), ptr(parent_g), B, kprev, V, P, int(k), ptr(out_ids), ptr(out_phi), ptr(out_g), ptr(out_parent),
-         ptr(out_node), ptr(blocked) if n_blocked else None, n_blocked, *bitmap, stream_handle(dev))
-    return out_ids, out_phi, out_g, out_parent, out_node
+    out_phi, out_g = c.scores(), c.scores()
+    call("rq_beam_expand_sampled", ptr(logits), ptr(noise), float(temperature), *c.trie, ptr(parents), ptr(parent_phi),
+         ptr(parent_g), *c.shape, ptr(c.out_ids), ptr(out_phi), ptr(out_g), ptr(c.out_parent), ptr(c.out_node), *c.tail)
+    return c.out_ids, out_phi, out_g, c.out_parent, c.out_node
 
 
 BEAM_MAX_T = 8   # RQ_BEAM_MAX_T

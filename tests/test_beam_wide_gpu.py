@@ -1,5 +1,5 @@
-"""Wide constrained beam search on the device: rq_beam_expand_wide(_blocked) bit for bit against rq_beam_expand(_blocked)
-where both take the shape, against the chunk-merge of narrow-kernel calls beyond that (test_beam_wide_host checks the
+"""Wide constrained beam search on the device: rq_beam_expand_wide bit for bit against rq_beam_expand (with and without
+blocked rows) where both take the shape, against the chunk-merge of narrow-kernel calls beyond that (test_beam_wide_host checks the
 merge itself), its ties / underflow / bad-table behaviour and refusals, an fp64 reference at 96 beams; then
 generate_next_sem_id / recommend(beams=...) up to an exhaustive search of the corpus, and the evaluator's switches."""
 import glob
@@ -234,11 +234,12 @@ def test_wide_refuses_bad_arguments(device):
     typed = _lib.load()
     for kprev, V, k in ((1025, 16, 3), (4, 16, 1025), (1, 4097, 3)):
         rc = typed.rq_beam_expand_wide(None, 1.0, None, None, 1, None, 0, None, None, 1, kprev, V, 0, k, None, None, None,
-                                       None, None)
+                                       None, None, 0, None, 0, 0, None, None)
         assert rc == -22 and b"rq_beam_expand_wide: need V <= 4096" in typed.rq_last_error()
-        rc = typed.rq_beam_expand_wide_blocked(None, 1.0, None, None, 1, None, 0, None, None, 1, kprev, V, 0, k, None,
-                                               None, None, None, None, 0, None)
-        assert rc == -22 and b"rq_beam_expand_wide_blocked: need V <= 4096" in typed.rq_last_error()
+        # a blocked row announced but NULL: the envelope is checked before the pointers
+        rc = typed.rq_beam_expand_wide(None, 1.0, None, None, 1, None, 0, None, None, 1, kprev, V, 0, k, None, None, None,
+                                       None, None, 4, None, 0, 0, None, None)
+        assert rc == -22 and b"rq_beam_expand_wide: need V <= 4096" in typed.rq_last_error()
 
 
 # ------------------------------------------------------------------------------------------ 6. the model

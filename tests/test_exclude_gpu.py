@@ -1,4 +1,4 @@
-"""Seen-item exclusion on the device: rq_trie_blocked_nodes against the tokenizer's CPU path, rq_beam_expand_blocked
+"""Seen-item exclusion on the device: rq_trie_blocked_nodes against the tokenizer's CPU path, rq_beam_expand's blocked rows
 against the unfiltered kernel with a host post-filter (bitwise) and against an fp64 reference over each user's
 reduced corpus, generate_next_sem_id / recommend(exclude_items=...) against the fp64 loop over the reduced corpora,
 rq_rank_hist against the CPU accumulator, and the evaluator's item-level switches."""

@@ -1,5 +1,5 @@
-"""Catalogue filters on the device: the _filtered expand entry points (narrow, wide, sampled) against the existing
-kernels on the trie of the allowed rows alone — the sub-corpus the filtered search must equal, bit for bit — the group
+"""Catalogue filters on the device: the expand entry points' allowed / group arguments (narrow, wide, sampled) against
+the unfiltered kernels on the trie of the allowed rows alone — the sub-corpus the filtered search must equal, bit for bit — the group
 rules, the equivalence with seen-item exclusion, the device table build against the CPU tables, and an fp64 cross-check."""
 import numpy as np
 import pytest
@@ -200,7 +200,7 @@ def _excluded(corpus, c, B, V, P):
                          ids=lambda a: "-".join(map(str, a)))
 def test_complement_of_an_exclusion_list(device, case_args, kind):
     """Per-user groups whose masks are the complement of an exclusion list (by row, as exclusion works) against the
-    _blocked entry point on that list: every output bit for bit, out_node too. Both filters together: the sub-corpus
+    blocked argument on that list: every output bit for bit, out_node too. Both filters together: the sub-corpus
     with the union removed — exact here because the list is a whole subtree of the level the step selects from, so no
     node of that level has its allowed rows all excluded while other rows keep it unblocked."""
     name, B, kprev, V, P, k = case_args

@@ -9,7 +9,7 @@ per beam, 256 classes, 4 sem-ID tokens; model dims of configs/decoder_amazon.gin
                incremental loop with the beam step replaced by one rq_beam_expand launch that walks the corpus'
                prefix trie) and the same call with exclude_items (`excluded`: H = the batch's history length of 20
                items per user, drawn from the corpus, padded where the sequence is; one rq_trie_blocked_nodes launch
-               per call and the filtered rq_beam_expand_blocked per step), verifier = a tokenizer over a 12,101-item
+               per call and rq_beam_expand with its blocked rows per step), verifier = a tokenizer over a 12,101-item
                corpus; and with the beam step
                stubbed out (`model`: the four forwards and the encoder cache repeat alone), which gives the
                beam logic's share of the first two forms;
@@ -24,7 +24,7 @@ per beam, 256 classes, 4 sem-ID tokens; model dims of configs/decoder_amazon.gin
                `sampled_items`: model.sample_items(k=10) — stochastic beam search, the incremental loop 10 beams wide
                with one Exponential(1) draw and one rq_beam_expand_sampled launch per step;
   filters      `filtered_shared`: model.recommend(k=10, item_filter=F) with F one ItemFilter over a 50 % mask of the
-               corpus that every user shares, built once before the loop (rq_beam_expand_filtered per step);
+               corpus that every user shares, built once before the loop (rq_beam_expand with allowed / group per step);
                `filtered_groups`: the same call with one 50 % mask per user (G = B groups, filter_group = 0..B-1);
                `filter_build`: the one-off tokenizer.item_filter(mask) of the shared mask, `filter_build_groups` of
                the G = B masks (rq_trie_allowed_nodes: two launches). The over-fetch alternative is `wide`. One run
