@@ -654,6 +654,33 @@ int rq_adamw_step(const int64_t* segs, int64_t nseg, float lr, float beta1, floa
                   float weight_decay, float bias_correction1, float bias_correction2_sqrt, void* stream);
 size_t rq_adamw_chunk_elems(void);
 
+/* Codebook usage and dead-code revival (csrc/codebook.hip). EXTENSIONS: the nearest reference counterpart is
+ * the `codebook_usage_{l}` log at checkpoint time (train_rqvae.py:232-239); the reference never counts usage
+ * during training and has no countermeasure against codebook collapse beyond its one-shot k-means init.
+ *
+ * rq_code_usage: counts[l][k] += #{b : ids[b][l] == k}. ids (B, L) int64 row-major; counts (L, K) int64,
+ *   ACCUMULATED in place (the caller zeroes it). Ids outside [0, K) are skipped. B == 0 is a no-op. Integer
+ *   atomics only (exact, order-free): the histogram is privatised in LDS while L K <= 8192 bins (one 64-bit
+ *   global add per non-zero bin per workgroup), else global adds aggregated per wave. One launch, no workspace,
+ *   no host sync, graph-capturable. L K < 2^31, B L <= 2^40.
+ * rq_codebook_revive: re-seat dead codewords on data residuals. codebooks / exp_avg / exp_avg_sq: HOST arrays of
+ *   L device pointers to (K, D) fp32, 16-byte aligned (the per-level parameters and their AdamW moments; the two
+ *   moment arrays may be NULL together), copied into the kernel arguments. res (L, B, D) fp32 = each level's input
+ *   residuals. The rule: for level l the dead codes are {k : counts[l][k] < min_count} in ascending k; the j-th
+ *   (0-based) takes donor row r = (s_l + j) mod B, s_l = SplitMix64(seed, l) mod B (unsigned 64-bit; the mix of
+ *   rq_rmsnorm_dropout_fwd's generator: counter l under key seed); codebook_l[k][:] becomes a bit copy of
+ *   res[l][r][:], row k of both moments +0.0, revived[l][k] = 1 (else 0), n_revived[l] = the number of dead
+ *   codes. revived (L, K) uint8 and n_revived (L) int64 are fully written; counts (L, K) int64 is only read.
+ *   B >= K is required (-22 otherwise): the donors of a level are then distinct rows and nothing is capped.
+ *   1 <= L <= 16, 1 <= K <= 2^20, D % 4 == 0, D <= 1024, min_count >= 0 (0: nothing is dead). Two launches
+ *   (dead flags + 256-code chunk totals into the workspace; ranks from the chunk totals, one wave per dead code
+ *   copying 16 bytes per lane); workspace >= rq_codebook_revive_workspace(L, K) bytes. */
+int rq_code_usage(const int64_t* ids, int64_t B, int64_t L, int64_t K, int64_t* counts, void* stream);
+size_t rq_codebook_revive_workspace(int64_t L, int64_t K);
+int rq_codebook_revive(float* const* codebooks, float* const* exp_avg, float* const* exp_avg_sq, int64_t L, int64_t K,
+                       int64_t D, const int64_t* counts, int64_t min_count, const float* res, int64_t B, uint64_t seed,
+                       uint8_t* revived, int64_t* n_revived, void* workspace, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

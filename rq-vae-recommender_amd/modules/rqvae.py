@@ -83,6 +83,7 @@ class RqVae(nn.Module):
                            normalize=True)
         self.reconstruction_loss = (CategoricalReconstuctionLoss(n_cat_features) if n_cat_features != 0
                                     else ReconstructionLoss())
+        self.code_usage = None   # (L, K) int64 usage counters while track_usage() is on; never a buffer
 
     @property
     def config(self) -> dict:
@@ -180,5 +181,65 @@ class RqVae(nn.Module):
         with torch.no_grad():
             embs_norm = emb_norms.T
             p_unique_ids = hip_ops.unique_fraction(ids, self.codebook_size)
+            if self.code_usage is not None and self.training:
+                hip_ops.code_usage(ids, self.code_usage)
         return RqVaeComputedLosses(loss=loss, reconstruction_loss=recon_mean, rqvae_loss=rq_mean,
                                    embs_norm=embs_norm, p_unique_ids=p_unique_ids)
+
+    # ------------------------------------------------- codebook usage and dead-code revival (extensions)
+    def track_usage(self, enable: bool = True) -> None:
+        """Count, per level, how often each code is selected by TRAINING forwards (eval forwards do not count):
+        `self.code_usage`, int64 (L, K) on the model's device, grows by one rq_code_usage launch per forward
+        (captured with a graphed step). The counters are allocated here, never inside a step, and are a plain
+        attribute, not a registered buffer: state_dict() keeps the reference's keys. enable=False drops them."""
+        self.code_usage = (torch.zeros((self.n_layers, self.codebook_size), dtype=torch.int64, device=self.device)
+                           if enable else None)
+
+    def usage_stats(self):
+        """(used, perplexity), two lists of L floats: the fraction of each level's codes with a non-zero count and
+        exp(H) of the level's normalised counts (K for a uniformly used codebook, 1 for a collapsed one, 0 before
+        anything was counted). Plain torch, for log time."""
+        if self.code_usage is None:
+            raise ValueError("usage_stats: call track_usage() first")
+        c = self.code_usage.to(torch.float64)
+        p = c / c.sum(1, keepdim=True).clamp_min(1.0)
+        ent = -(p * torch.log(p.clamp_min(1e-300))).sum(1)
+        ppl = torch.where(c.sum(1) > 0, torch.exp(ent), torch.zeros_like(ent))
+        return (c > 0).to(torch.float64).mean(1).tolist(), ppl.tolist()
+
+    def revive_dead_codes(self, x: Tensor, *, min_count: int = 1, seed: int, optimizer=None) -> Tensor:
+        """Re-seat every codeword counted fewer than min_count times since the counters were last zeroed on the
+        residual of a row of x (modules.codebook_revival.revive_: the rule, the data-parallel protocol) ->
+        n_revived (L,) int64; zeroes the counters. x (B >= K, input_dim): data rows; their level inputs come from
+        one eval-mode, no-grad quantize_levels(encode(x)) under the PRE-revival codebooks — the residuals of deeper
+        levels are knowingly not recomputed after a shallower level is re-seated, so a deeper donor is a residual
+        the old shallower codebook left. optimizer: when given, the exp_avg / exp_avg_sq rows of the re-seated
+        codewords are zeroed too (if that state exists yet). Parameters and moments are written through their
+        existing storage, so captured graphs stay valid. L2-distance levels without out_proj only."""
+        from modules.codebook_revival import revive_
+        if self.code_usage is None:
+            raise ValueError("revive_dead_codes: call track_usage() first")
+        for layer in self.layers:
+            if not all(isinstance(m, nn.Identity) for m in layer.out_proj):
+                raise ValueError("revive_dead_codes: codebooks with an out_proj (sim_vq / codebook_normalize) are not "
+                                 "supported")
+            if layer.distance_mode != QuantizeDistance.L2 or layer.needs_init():
+                raise ValueError("revive_dead_codes: needs L2-distance levels whose k-means init is done")
+        if x.dim() != 2 or x.shape[0] < self.codebook_size:
+            raise ValueError(f"revive_dead_codes: x must hold at least K = {self.codebook_size} rows, got "
+                             f"{tuple(x.shape)}")
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                res = self.quantize_levels(self.encode(x), 0.001)[1].contiguous()
+        finally:
+            self.train(was_training)
+        weights = [layer.embedding.weight for layer in self.layers]
+        moments = None
+        if optimizer is not None:
+            states = [optimizer.state.get(w, {}) for w in weights]
+            if all("exp_avg" in st and "exp_avg_sq" in st for st in states):
+                moments = ([st["exp_avg"] for st in states], [st["exp_avg_sq"] for st in states])
+        return revive_(weights, self.code_usage, res, min_count=min_count, seed=seed,
+                       exp_avg=moments and moments[0], exp_avg_sq=moments and moments[1])

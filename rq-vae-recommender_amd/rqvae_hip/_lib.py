@@ -108,6 +108,9 @@ _SIGS = {
     "rq_score_paths": ([_P, _F, _P, _I64, _I64, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _P], _I),
     "rq_adamw_step": ([_P, _I64, _F, _F, _F, _F, _F, _F, _F, _P], _I),
     "rq_adamw_chunk_elems": ([], _SZ),
+    "rq_code_usage": ([_P, _I64, _I64, _I64, _P, _P], _I),
+    "rq_codebook_revive_workspace": ([_I64, _I64], _SZ),
+    "rq_codebook_revive": ([_P, _P, _P, _I64, _I64, _I64, _P, _I64, _P, _I64, _U64, _P, _P, _P, _SZ, _P], _I),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -14,6 +14,8 @@
                                              first-match rank histogram (Recall / NDCG / MRR), one launch
   trie_allowed_nodes                         catalogue filters: per group of an item mask every level's bitmap of nodes
                                              that lead to an allowed item (beam_expand's allowed=), two launches
+  code_usage / codebook_revive               tokenizer health: per-level code histogram added into device counters, one launch;
+                                             dead codewords re-seated on data residuals (bit copies, moments zeroed), two launches
 
 All kernels run on torch's current HIP stream; tensors must be on the GPU (no CPU path).
 """
@@ -2849,3 +2851,84 @@ def score_paths(logits: torch.Tensor, tokens: torch.Tensor, *, present: torch.Te
          tokens.stride(1) if C > 1 else 0, ptr(present), ptr(prev_lp), B, C, V, G, ptr(lp), ptr(rank),
          stream_handle(dev))
     return lp, rank
+
+
+# ------------------------------------------------------------------ codebook usage / dead-code revival
+REVIVE_MAX_L, REVIVE_MAX_K, REVIVE_MAX_D = 16, 1 << 20, 1024   # kReviveMaxL and the limits of rq_codebook_revive
+
+
+def code_usage(ids: torch.Tensor, counts: torch.Tensor) -> torch.Tensor:
+    """counts (L, K) int64 += the per-level histogram of ids (B, L) int64 (rq_code_usage): counts[l][k] grows by the
+    rows whose level-l id is k; ids outside [0, K) are skipped. Integer atomics only, so the result is exact. One
+    launch, no allocation, no host read (graph-capturable); the caller zeroes counts once."""
+    what = "code_usage"
+    require_gpu(ids, counts, what=what)
+    if ids.dim() != 2 or counts.dim() != 2 or counts.shape[0] != ids.shape[1]:
+        raise ValueError(f"{what}: need ids (B, L) and counts (L, K), got {tuple(ids.shape)}, {tuple(counts.shape)}")
+    B, L = ids.shape
+    K = counts.shape[1]
+    if L < 1 or K < 1 or L * K >= 1 << 31:
+        raise ValueError(f"{what}: need L >= 1, K >= 1 and L K < 2^31 (L={L}, K={K})")
+    _beam_arg(ids, torch.int64, what, "ids")
+    _beam_arg(counts, torch.int64, what, "counts")
+    if counts.device != ids.device:
+        raise RqHipError(f"{what}: ids and counts must be on one device, got {ids.device}, {counts.device}")
+    call("rq_code_usage", ptr(ids), B, L, K, ptr(counts), stream_handle(ids.device))
+    return counts
+
+
+def revive_check_args(L: int, K: int, D: int, B: int, min_count: int, what: str = "codebook_revive") -> None:
+    """The argument limits of rq_codebook_revive (ValueError outside them), shared with the CPU path of
+    modules.codebook_revival.revive_."""
+    if not 1 <= L <= REVIVE_MAX_L:
+        raise ValueError(f"{what}: need 1 <= L <= {REVIVE_MAX_L} levels, got {L}")
+    if not 1 <= K <= REVIVE_MAX_K:
+        raise ValueError(f"{what}: need 1 <= K <= 2^20, got {K}")
+    if D < 4 or D % 4 != 0 or D > REVIVE_MAX_D:
+        raise ValueError(f"{what}: need D % 4 == 0 and 4 <= D <= {REVIVE_MAX_D}, got {D}")
+    if min_count < 0:
+        raise ValueError(f"{what}: min_count must be >= 0, got {min_count}")
+    if B < K:
+        raise ValueError(f"{what}: need at least K donor rows per level (B={B} < K={K})")
+
+
+def codebook_revive(weights, counts: torch.Tensor, res: torch.Tensor, min_count: int, seed: int, exp_avg=None,
+                    exp_avg_sq=None):
+    """Re-seat the dead codewords of every level IN PLACE (rq_codebook_revive) -> (revived (L, K) bool, n_revived (L,)
+    int64). weights: L fp32 (K, D) tensors (the levels' codebook parameters), exp_avg / exp_avg_sq: their AdamW moments
+    (both or neither); counts (L, K) int64 is only read; res (L, B, D) fp32 holds each level's input residuals, B >= K.
+    Level l's codes with counts[l][k] < min_count, ascending, take rows (s_l + j) mod B of res[l], s_l =
+    SplitMix64(seed, l) mod B: a bit copy into the weight row, +0.0 into both moment rows. Two launches, no host read."""
+    import ctypes
+    what = "codebook_revive"
+    weights = list(weights)
+    moments = [None if m is None else list(m) for m in (exp_avg, exp_avg_sq)]
+    if (moments[0] is None) != (moments[1] is None):
+        raise ValueError(f"{what}: exp_avg and exp_avg_sq go together (both or neither)")
+    if not weights or weights[0].dim() != 2:
+        raise ValueError(f"{what}: weights must be a non-empty list of (K, D) tensors")
+    tensors = weights + [t for m in moments if m is not None for t in m]
+    require_gpu(*tensors, counts, res, what=what)
+    L, (K, D) = len(weights), weights[0].shape
+    if res.dim() != 3 or res.shape[0] != L or res.shape[2] != D:
+        raise ValueError(f"{what}: res must be (L, B, D) = ({L}, B, {D}), got {tuple(res.shape)}")
+    B, min_count = res.shape[1], int(min_count)
+    revive_check_args(L, K, D, B, min_count, what)
+    if any(m is not None and len(m) != L for m in moments):
+        raise ValueError(f"{what}: need one moment tensor per level")
+    for t in tensors:
+        _beam_arg(t.detach(), torch.float32, what, "every weight / moment", (K, D))
+    _beam_arg(counts, torch.int64, what, "counts", (L, K))
+    _beam_arg(res, torch.float32, what, "res")
+    dev = res.device
+    if any(t.device != dev for t in tensors + [counts]):
+        raise RqHipError(f"{what}: every tensor must be on {dev}")
+    revived = torch.empty((L, K), device=dev, dtype=torch.uint8)
+    n_revived = torch.empty((L,), device=dev, dtype=torch.int64)
+    nbytes = _lib.load().rq_codebook_revive_workspace(L, K)
+    ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+    P = ctypes.c_void_p * L
+    tabs = [P(*[t.data_ptr() for t in weights])] + [None if m is None else P(*[t.data_ptr() for t in m]) for m in moments]
+    call("rq_codebook_revive", tabs[0], tabs[1], tabs[2], L, K, D, ptr(counts), min_count, ptr(res), B,
+         int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(revived), ptr(n_revived), ptr(ws), nbytes, stream_handle(dev))
+    return revived.view(torch.bool), n_revived

@@ -14,7 +14,10 @@ Differences from the reference loop (train_rqvae.py:24-250), all on the MI355X p
     AdamW step (host-side bias corrections) runs after the replay;
   * checkpoints are plain state dicts {"iter", "model", "model_config", "optimizer"} (loadable with
     weights_only=True); swanlab logging is replaced by printed JSON lines (out of scope);
-  * the loop runs `iterations + 1` times like the reference (SURVEY A-4).
+  * the loop runs `iterations + 1` times like the reference (SURVEY A-4);
+  * opt-in extension (REVIVE_EVERY, off by default): per-level code usage counted inside the step and dead codewords
+    re-seated on data residuals between steps (modules/codebook_revival.py); rank 0 prints one JSON line per revival,
+    {"iter", "revived", "codebook_used", "codebook_perplexity"} (the last two from its own counters).
 Data: `data.processed.ItemData` (seeded synthetic corpus unless `data_path` names a feature file).
 """
 import contextlib
@@ -29,6 +32,7 @@ import torch
 
 from data.processed import ItemData, RecDataset
 from data.schemas import SeqBatch
+from modules.codebook_revival import splitmix64
 from modules.ginlite import gin
 from modules.quantize import QuantizeForwardMode
 from modules.rqvae import RqVae
@@ -46,6 +50,14 @@ def sample_batch_indices(gen: torch.Generator, n_items: int, global_batch: int, 
     substitute the reference's recorded batch order."""
     return torch.randint(0, n_items, (global_batch,), generator=gen, device=device)
 
+
+
+# Dead-code revival (modules/codebook_revival.py, DESIGN §5; an extension, off by default): every REVIVE_EVERY-th
+# iteration, after the optimiser step, the codewords selected fewer than REVIVE_MIN_COUNT times since the last
+# revival are re-seated on encoder residuals of max(K, local batch) items drawn from a generator of their own (the
+# batch stream of a run is the same with the feature on or off). 0: off — no counter launch, no extra state.
+REVIVE_EVERY = 0
+REVIVE_MIN_COUNT = 1
 
 
 # Last train() call: steady-state time per iteration (CUDA-synchronised once at the start and once at
@@ -135,6 +147,9 @@ def train(iterations=50000, batch_size=64, learning_rate=0.0001, weight_decay=0.
         return torch.stack([total, out.reconstruction_loss.detach(), out.rqvae_loss.detach(),
                             out.p_unique_ids.detach()])
 
+    if REVIVE_EVERY > 0:
+        model.track_usage()   # before the first step: the counter launch is captured with it
+        revive_gen = torch.Generator(device=device).manual_seed(seed + 29)   # same stream on every rank
     graphed = GraphedSteps(step_body, lambda idx: 0, buckets, run_backward=False) if cuda_graphs else None
     gen = torch.Generator(device=device).manual_seed(seed + 17)   # same stream on every rank
     hist = []
@@ -155,6 +170,15 @@ def train(iterations=50000, batch_size=64, learning_rate=0.0001, weight_decay=0.
             stats = step_body(idx)
         buckets.synchronize()
         opt.step()
+        if REVIVE_EVERY > 0 and (it + 1) % REVIVE_EVERY == 0:
+            # eager, between replays: parameters and moments are written through their existing storage
+            ridx = torch.randint(0, n_items, (max(vae_codebook_size, hi - lo),), generator=revive_gen, device=device)
+            used, ppl = model.usage_stats()
+            n_rev = model.revive_dead_codes(items[ridx], min_count=REVIVE_MIN_COUNT, seed=splitmix64(seed, it),
+                                            optimizer=opt)
+            if rank == 0:
+                print(json.dumps({"iter": it, "revived": n_rev.tolist(), "codebook_used": used,
+                                  "codebook_perplexity": ppl}), flush=True)
         hist.append(stats)
         if it == last_it - 1 and t_mark is not None:
             torch.cuda.synchronize()
