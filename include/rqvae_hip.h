@@ -464,6 +464,66 @@ int varlen_attn_bwd(const float* q, int64_t sq, const float* k, int64_t sk, cons
                     float scale, float* dq, int64_t sdq, float* dk, int64_t sdk, float* dv, int64_t sdv, int64_t Tk,
                     float* delta, float* ws, int64_t ws_elems, int flags, void* stream);
 
+/* Host-only planning of one varlen_attn_fwd (backward = 0) or varlen_attn_bwd (backward = 1) call: the
+ * launches the call issues, in order, and how it lays out its workspace. The entry points above launch from
+ * this same plan (csrc/attention_plan.h; DESIGN.md "Attention dispatch" tabulates the rules), so a test can
+ * ask which kernel form a shape dispatches. No launch, no allocation; the only device access is the cached
+ * CU-count query of the backward's query splits and persistent few-query walk (256, the MI355X count,
+ * without a GPU: plans are the same on a machine without one).
+ *   ws_elems: the floats of scratch the call would bring, < 0 for none (ws == NULL); Tk: as varlen_attn_bwd's,
+ *   or < 0 as for varlen_attn_bwd_ws_elems (a plan without query splits); the forward ignores it.
+ * One launch: the kernel family and the family's integer template arguments, 0 where it has none —
+ *   hd (head dim), nw (waves per workgroup), r (staged rows R / chunk CH / key block KB), x3 (split-bf16
+ *   products) — then grid and block. RQ_ATTN_K_BWD_FUSED with x3 = 1 is attn_bwd_fused_x3_kernel. */
+enum {
+  RQ_ATTN_K_ORDER = 1,        /* attn_order_kernel: longest-first ranking of order_src's segments */
+  RQ_ATTN_K_FWD,              /* attn_fwd_kernel<hd, nw, x3>: the chunked forward */
+  RQ_ATTN_K_FWD_SHORT,        /* attn_fwd_short_kernel<hd, nw, r> */
+  RQ_ATTN_K_FWD_DMA,          /* attn_fwd_dma_kernel<nw, r> */
+  RQ_ATTN_K_FWD_SHORT_X3,     /* attn_fwd_short_x3_kernel<r> */
+  RQ_ATTN_K_FWD_FEWQ,         /* attn_fwd_fewq_kernel<nw> */
+  RQ_ATTN_K_FWD_SPLIT,        /* attn_fwd_split_kernel<hd, r> */
+  RQ_ATTN_K_FWD_KVSPLIT,      /* attn_fwd_kvsplit_kernel<hd, nw, r, x3> */
+  RQ_ATTN_K_FWD_COMBINE,      /* attn_fwd_combine_kernel<hd, r> */
+  RQ_ATTN_K_BWD_DQ,           /* attn_bwd_dq_kernel<hd, nw>: the chunked dQ pass */
+  RQ_ATTN_K_BWD_DKDV,         /* attn_bwd_dkdv_kernel<hd, nw>: the chunked dK / dV pass */
+  RQ_ATTN_K_BWD_DQ_SHORT,     /* attn_bwd_dq_short_kernel<hd, nw, r> */
+  RQ_ATTN_K_BWD_DKDV_SHORT,   /* attn_bwd_dkdv_short_kernel<hd, nw, r> */
+  RQ_ATTN_K_BWD_DQ_DMA,       /* attn_bwd_dq_dma_kernel<nw, r> */
+  RQ_ATTN_K_BWD_DKDV_DMA,     /* attn_bwd_dkdv_dma_kernel<nw, r> */
+  RQ_ATTN_K_BWD_DQ_FEWQ,      /* attn_bwd_dq_fewq_kernel<nw> */
+  RQ_ATTN_K_BWD_FEWQ_FUSED,   /* attn_bwd_fewq_fused_kernel<nw> */
+  RQ_ATTN_K_BWD_FEWQ_STREAM,  /* attn_bwd_fewq_stream_kernel<r> */
+  RQ_ATTN_K_BWD_SHORT_FUSED,  /* attn_bwd_short_fused_kernel<nw, r> */
+  RQ_ATTN_K_DELTA,            /* attn_delta_kernel<hd> */
+  RQ_ATTN_K_BWD_FUSED,        /* attn_bwd_fused_kernel<hd, nw, r> / attn_bwd_fused_x3_kernel<nw, r> */
+  RQ_ATTN_K_KV_REDUCE,        /* attn_kv_reduce_kernel<hd> */
+  RQ_ATTN_K_DQ_REDUCE         /* attn_dq_reduce_kernel<hd, r> */
+};
+enum { RQ_ATTN_ORDER_SRC_NONE = 0, RQ_ATTN_ORDER_SRC_CU_Q, RQ_ATTN_ORDER_SRC_CU_K, RQ_ATTN_ORDER_SRC_GIVEN };
+#define RQ_ATTN_MAX_LAUNCHES 6
+typedef struct rq_attn_launch {
+  int family;  /* RQ_ATTN_K_* */
+  int hd, nw, r, x3;
+  int block;
+  unsigned grid[3];
+} rq_attn_launch;
+typedef struct rq_attn_plan {
+  int n_launches;
+  int qsplit;     /* query splits of the fused backward (1 = none) */
+  int order_src;  /* RQ_ATTN_ORDER_SRC_*: the offsets array the order ranks, or GIVEN (RQ_ATTN_ORDER_GIVEN) */
+  int reserved;   /* 0 */
+  int64_t ws_total;  /* = varlen_attn_{fwd,bwd}_ws_elems(...) floats, whatever ws_elems is */
+  int64_t ws_need;   /* a call that brings a workspace must bring this many floats (backward: ws_total
+                        without the query splits' dK / dV partials) */
+  /* float offsets into the workspace, -1 = absent: the order (B int32), the forward's split partials or
+   * the fused backward's dQ partials, the query splits' dK / dV partials */
+  int64_t order_off, part_off, kvpart_off;
+  rq_attn_launch launch[RQ_ATTN_MAX_LAUNCHES];
+} rq_attn_plan;
+int varlen_attn_plan(int backward, int64_t B, int64_t H, int64_t hd, int64_t max_q, int64_t max_k, int64_t Tq,
+                     int64_t Tk, int causal, int flags, int64_t ws_elems, rq_attn_plan* plan);
+
 /* Decoder evaluation (csrc/beam.hip): one beam step of EncoderDecoderRetrievalModel.generate_next_sem_id
  * (modules/model.py:176-201) in two launches, and the Hit@k counters of TopKAccumulator.accumulate
  * (evaluate/metrics.py:15-28). No call allocates or synchronises; all are graph-capturable.

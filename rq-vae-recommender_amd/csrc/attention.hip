@@ -3016,106 +3016,18 @@ __global__ void __launch_bounds__(64 * NW, 2) attn_bwd_short_fused_kernel(
   }
 }
 
-constexpr int kShortMaxStaged = 32;   // longest staged range served by the short forms (A/B: 32 / 128)
-constexpr int kShortMax = 128;   // longest staged range of the short forms
+}  // namespace rqhip
 
-// (waves, staged rows) of a short-form launch whose tiles run over `rows` (queries for fwd / dQ, keys
-// for dK/dV) against a staged range of `staged` rows; false when the chunked kernels serve it
-static bool short_plan(int64_t rows, int64_t staged, int* nw, int* ch) {
-  if (rows > kShortMax || staged > kShortMax) return false;
-  // Measured on MI355X (decoder Amazon step, rocprofv3): the short forms win where the staged range
-  // is one 32-row chunk (decoder self-attention 5 x 5: fwd 11.6 -> 6.4 us, dQ 15.6 -> 8.9 us; the
-  // cross-attention dK/dV over 5 staged queries 41 -> 24 us) and lose at 96 staged rows (encoder
-  // self-attention, n <= 81: fwd 35 -> 39 us, dQ 54 -> 59 us, dK/dV 41 -> 64 us: 52 KB of LDS per
-  // workgroup leaves 3 workgroups per CU, and a one-wave workgroup would hold it alone), so longer
-  // staged ranges keep the chunked kernels.
-  if (staged > kShortMaxStaged) return false;
-  *nw = rows <= 16 ? 1 : 4;
-  *ch = staged <= 32 ? 32 : (staged <= 64 ? 64 : (staged <= 96 ? 96 : 128));
-  return true;
-}
+// Host dispatch. attention_plan.h decides, once per call, which launches serve it and where their scratch
+// lives; attn_run_fwd / attn_run_bwd below issue that plan and decide nothing.
+#include "attention_plan.h"
 
-#define RQ_SHORT_SWITCH(NW_, CH_, LAUNCH)                          \
-  do {                                                           \
-    if ((NW_) == 1) {                                            \
-      LAUNCH(1, 32);                                             \
-    } else {                                                     \
-      switch (CH_) {                                             \
-        case 32: LAUNCH(4, 32); break;                           \
-        case 64: LAUNCH(4, 64); break;                           \
-        case 96: LAUNCH(4, 96); break;                           \
-        default: LAUNCH(4, 128); break;                          \
-      }                                                          \
-    }                                                            \
-  } while (0)
+#include <type_traits>
 
-// Waves per workgroup by the longest row count: 16 rows per wave; short sequences (the Amazon
-// decoder's contexts <= 81 tokens, its 5-6 future tokens) use narrow workgroups so few waves idle
-// on padding, long ones (ML-32M <= 801, C5 <= 1281) share each staged 64-row chunk between 4 waves.
-static int waves_for(int64_t rows) { return rows <= 16 ? 1 : (rows <= 96 ? 2 : 4); }
+namespace rqhip {
 
-// LPT order where a workgroup's run time varies enough with the sequence to leave a straggler tail
-static bool lpt_plan(int64_t B, int64_t max_len) { return B >= 2 && B <= kOrderMax && max_len > 128; }
+static_assert(kAttnOrderMax == kOrderMax, "the plan's order bound is attn_order_kernel's");
 
-// split-key forward: one query tile per sequence (<= 16 queries), non-causal, long key ranges (cross-attention)
-constexpr int kSplitMinK = 129;   // key ranges from here use the split-key forward (A/B: at the Amazon
-                                  // contexts, <= 81 keys in 32-key blocks, it ties the chunked form)
-// The kernel policy of one call, from its `flags` argument (RQ_ATTN_* in include/rqvae_hip.h; 0 = the
-// measured-best forms): LDS-DMA short forms, one-pass backwards, split-key / key-split forwards, and the
-// fused backward's query splits (0 = automatic).
-struct AttnPolicy {
-  bool dma, fused, split;
-  int qsplit;
-  bool x3;   // RQ_ATTN_SPLIT_BF16: the long-range forwards multiply in split-bf16 (matmul precision 'high')
-  bool lpt_short;   // RQ_ATTN_LPT_SHORT: longest-first sequence order for the short / few-query forms too
-  bool order_given;   // RQ_ATTN_ORDER_GIVEN: ws[0, B) already holds the LPT order of cu_k (no order launch)
-  bool fewq_stream;   // !RQ_ATTN_FEWQ_WG: the 4-wave few-query backward as the persistent LDS-DMA-staged walk
-};
-static AttnPolicy attn_policy(int flags) {
-  return AttnPolicy{!(flags & RQ_ATTN_NO_DMA), !(flags & RQ_ATTN_TWO_PASS), !(flags & RQ_ATTN_NO_SPLIT),
-                    (flags >> RQ_ATTN_QSPLIT_SHIFT) & 15, (flags & RQ_ATTN_SPLIT_BF16) != 0,
-                    (flags & RQ_ATTN_LPT_SHORT) != 0, (flags & RQ_ATTN_ORDER_GIVEN) != 0,
-                    !(flags & RQ_ATTN_FEWQ_WG)};
-}
-// LPT order of the short / few-query forms (by key length: their work per workgroup grows with it)
-static bool short_lpt_plan(int64_t B, const AttnPolicy& pol) { return pol.lpt_short && B >= 2 && B <= kOrderMax; }
-
-static bool split_plan(int64_t hd, int64_t max_q, int64_t max_k, int causal, const AttnPolicy& pol) {
-  return pol.split && hd == 64 && !causal && max_q <= 16 && max_k >= kSplitMinK;
-}
-static int split_kb(int64_t max_k) { return max_k <= 128 ? 32 : 128; }   // 32: for a kSplitMinK <= 128
-// key-split forward for many queries over long keys at low occupancy (attn_fwd_kvsplit_kernel): the C4
-// per-rank config (8 sequences x 6 heads x <= 13 query blocks); RQ_ATTN_NO_SPLIT disables it (A/B)
-constexpr int kKvSplitMaxWg = 1024;   // unsplit workgroups (B x H x 64-query blocks) up to which it applies
-constexpr int kKvSplitKB = 128;
-static bool kvsplit_plan(int64_t B, int64_t H, int64_t hd, int64_t max_q, int64_t max_k, int causal,
-                         const AttnPolicy& pol) {
-  return pol.split && hd == 64 && !causal && max_q > 16 && max_k > 2 * kKvSplitKB &&
-         B * H * ((max_q + 63) / 64) <= kKvSplitMaxWg;
-}
-static int64_t split_ws_elems(int64_t B, int64_t H, int64_t hd, int64_t max_q, int64_t max_k, int64_t Tq, int causal,
-                              const AttnPolicy& pol) {
-  if (kvsplit_plan(B, H, hd, max_q, max_k, causal, pol)) return (max_k + kKvSplitKB - 1) / kKvSplitKB * Tq * H * (hd + 2);
-  if (!split_plan(hd, max_q, max_k, causal, pol)) return 0;
-  const int kb = split_kb(max_k);
-  return (max_k + kb - 1) / kb * Tq * H * (hd + 2);
-}
-
-// LDS-DMA short forms (attn_fwd_dma_kernel): self-attention style launches (more than one query tile)
-// whose key range fits 128 staged rows; RQ_ATTN_NO_DMA keeps the register-staged kernels (A/B).
-static int dma_rows_for(int64_t max_k) { return max_k <= 32 ? 32 : (max_k <= 64 ? 64 : (max_k <= 96 ? 96 : 128)); }
-static bool dma_fwd_plan(int64_t hd, int64_t max_q, int64_t max_k, const AttnPolicy& pol) {   // also the dQ pass
-  return pol.dma && hd == 64 && max_q > 16 && max_k <= 128;
-}
-static bool dma_kv_plan(int64_t hd, int64_t max_q, int64_t max_k, const AttnPolicy& pol) {    // dK / dV: queries staged
-  return pol.dma && hd == 64 && max_k > 16 && max_q <= 128;
-}
-// one query tile over <= 128 keys (cross-attention, the decoder's short causal self-attention): forward and
-// dQ with the key tiles split over the waves (attn_fwd_fewq_kernel / attn_bwd_dq_fewq_kernel)
-static bool fewq_plan(int64_t hd, int64_t max_q, int64_t max_k, const AttnPolicy& pol) {
-  return pol.dma && hd == 64 && max_q <= 16 && max_k <= 128;
-}
-static int fewq_waves(int64_t max_k) { return max_k <= 16 ? 1 : (max_k <= 32 ? 2 : 4); }
 static int attn_cus() {
   static int cus = 0;
   if (cus == 0) {
@@ -3126,392 +3038,184 @@ static int attn_cus() {
   }
   return cus;
 }
-// one-pass backward of the self-attention style short launches (attn_bwd_short_fused_kernel) and of the
-// few-query launches (attn_bwd_fewq_fused_kernel); RQ_ATTN_TWO_PASS keeps the two-pass dQ + dK/dV kernels
-static bool short_fused_plan(int64_t hd, int64_t max_q, int64_t max_k, const AttnPolicy& pol) {
-  return pol.dma && pol.fused && hd == 64 && max_q > 16 && max_q <= 128 && max_k <= 128;
+
+// f(std::integral_constant<int, V>) for the V among Vs that equals v: the instantiations of one template
+// argument. false when v is none of them (a plan entry the launcher does not build: an error, never a fallback).
+template <int... Vs, typename F>
+static bool with_int(int v, F&& f) {
+  return ((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
 }
 
-template <int HD, int NW>
-static void fwd_nw(int64_t B, int64_t H, int64_t max_q, hipStream_t st, const float* q, int64_t sq, const float* k,
-                   int64_t sk, const float* v, int64_t sv, const int64_t* cq, const int64_t* ck, int causal, float scale,
-                   float* out, int64_t so, float* lse, int64_t Tq, const int* order, bool x3) {
-  dim3 g((unsigned)std::max<int64_t>(1, (max_q + 16 * NW - 1) / (16 * NW)), (unsigned)H, (unsigned)B + 1);   // + tail slice
-  if constexpr (HD == 64 && NW == 4) {
-    if (x3) {
-      hipLaunchKernelGGL((attn_fwd_kernel<HD, NW, true>), g, dim3(64 * NW), 0, st, q, sq, k, sk, v, sv, cq, ck, causal,
-                         scale, out, so, lse, Tq, order);
-      return;
+// the chunked kernels: every head dim x 1 / 2 / 4 waves
+template <typename F>
+static bool with_hd_nw(const rq_attn_launch& l, F&& f) {
+  bool ok = false;
+  with_int<16, 32, 64, 128>(l.hd, [&](auto HD) { ok = with_int<1, 2, 4>(l.nw, [&](auto NW) { f(HD, NW); }); });
+  return ok;
+}
+
+template <typename... KArgs, typename... Args>
+static void launch(void (*kern)(KArgs...), const rq_attn_launch& l, hipStream_t st, Args... args) {
+  hipLaunchKernelGGL(kern, dim3(l.grid[0], l.grid[1], l.grid[2]), dim3(l.block), 0, st, static_cast<KArgs>(args)...);
+}
+
+struct AttnFwdArgs {
+  const float *q, *k, *v;
+  int64_t sq, sk, sv;
+  const int64_t *cq, *ck;
+  int64_t B, H, Tq, max_k;
+  int causal;
+  float scale;
+  float* out;
+  int64_t so;
+  float *lse, *ws;
+  hipStream_t st;
+};
+
+// Issues the plan's launches in order, selecting each template instantiation from (family, hd, nw, r, x3).
+static bool attn_run_fwd(const rq_attn_plan& p, const AttnFwdArgs& a) {
+  int* order = p.order_off >= 0 ? reinterpret_cast<int*>(a.ws + p.order_off) : nullptr;
+  float* part = p.part_off >= 0 ? a.ws + p.part_off : nullptr;
+  bool ok = true;
+  for (int i = 0; i < p.n_launches && ok; ++i) {
+    const rq_attn_launch& l = p.launch[i];
+    const int nsplit = l.r > 0 ? (int)((a.max_k + l.r - 1) / l.r) : 0;   // key blocks of the split forms
+    auto plain = [&](auto kern) {
+      launch(kern, l, a.st, a.q, a.sq, a.k, a.sk, a.v, a.sv, a.cq, a.ck, a.causal, a.scale, a.out, a.so, a.lse, a.Tq);
+    };
+    auto ordered = [&](auto kern) {
+      launch(kern, l, a.st, a.q, a.sq, a.k, a.sk, a.v, a.sv, a.cq, a.ck, a.causal, a.scale, a.out, a.so, a.lse, a.Tq, order);
+    };
+    auto split = [&](auto kern) {
+      launch(kern, l, a.st, a.q, a.sq, a.k, a.sk, a.v, a.sv, a.cq, a.ck, a.scale, a.Tq, part, nsplit);
+    };
+    switch (l.family) {
+      case RQ_ATTN_K_ORDER: launch(attn_order_kernel, l, a.st, a.ck, (int)a.B, order); break;
+      case RQ_ATTN_K_FWD:   // split-bf16 only at hd 64, 4 waves
+        if (l.x3) ok = l.hd == 64 && l.nw == 4 && (ordered(attn_fwd_kernel<64, 4, true>), true);
+        else ok = with_hd_nw(l, [&](auto HD, auto NW) { ordered(attn_fwd_kernel<HD(), NW()>); });
+        break;
+      case RQ_ATTN_K_FWD_SHORT:   // CH == 32 only: kShortMaxStaged (attention_plan.h)
+        ok = l.hd == 64 && l.r == 32 && with_int<1, 4>(l.nw, [&](auto NW) { plain(attn_fwd_short_kernel<64, NW(), 32>); });
+        break;
+      case RQ_ATTN_K_FWD_DMA:
+        ok = l.nw == 4 && with_int<32, 64, 96, 128>(l.r, [&](auto R) { plain(attn_fwd_dma_kernel<4, R()>); });
+        break;
+      case RQ_ATTN_K_FWD_SHORT_X3:
+        ok = with_int<64, 96, 128>(l.r, [&](auto R) { ordered(attn_fwd_short_x3_kernel<R()>); });
+        break;
+      case RQ_ATTN_K_FWD_FEWQ:
+        ok = with_int<1, 2, 4>(l.nw, [&](auto NW) { ordered(attn_fwd_fewq_kernel<NW()>); });
+        break;
+      case RQ_ATTN_K_FWD_SPLIT:
+        ok = l.hd == 64 && with_int<32, 128>(l.r, [&](auto KB) { split(attn_fwd_split_kernel<64, KB()>); });
+        break;
+      case RQ_ATTN_K_FWD_KVSPLIT:
+        ok = l.hd == 64 && l.nw == 4 && l.r == kKvSplitKB;
+        if (ok && l.x3) split(attn_fwd_kvsplit_kernel<64, 4, kKvSplitKB, true>);
+        else if (ok) split(attn_fwd_kvsplit_kernel<64, 4, kKvSplitKB>);
+        break;
+      case RQ_ATTN_K_FWD_COMBINE:
+        ok = l.hd == 64 && with_int<32, 128>(l.r, [&](auto KB) {
+               launch(attn_fwd_combine_kernel<64, KB()>, l, a.st, part, nsplit, a.cq, a.ck, a.Tq, a.out, a.so, a.lse);
+             });
+        break;
+      default: ok = false;
     }
   }
-  hipLaunchKernelGGL((attn_fwd_kernel<HD, NW>), g, dim3(64 * NW), 0, st, q, sq, k, sk, v, sv, cq, ck, causal, scale, out,
-                     so, lse, Tq, order);
+  return ok;
 }
 
-template <int HD>
-static void launch_fwd(int64_t B, int64_t H, int64_t max_q, int64_t max_k, hipStream_t st, const float* q, int64_t sq,
-                       const float* k,
-                       int64_t sk, const float* v, int64_t sv, const int64_t* cq, const int64_t* ck, int causal,
-                       float scale, float* out, int64_t so, float* lse, int64_t Tq, int* order, float* split_ws,
-                       const AttnPolicy& pol) {
-  if constexpr (HD == 64) {
-    if (split_ws && kvsplit_plan(B, H, HD, max_q, max_k, causal, pol)) {
-      const int nsplit = (int)((max_k + kKvSplitKB - 1) / kKvSplitKB);
-      constexpr int RPB = 256 / (HD / 4);
-      const dim3 gs((unsigned)(((max_q + 63) / 64) * nsplit), (unsigned)H, (unsigned)B);
-      const dim3 gc((unsigned)std::max<int64_t>(1, (max_q + RPB - 1) / RPB), (unsigned)H, (unsigned)B + 1);
-      if (pol.x3)
-        hipLaunchKernelGGL((attn_fwd_kvsplit_kernel<HD, 4, kKvSplitKB, true>), gs, dim3(256), 0, st, q, sq, k, sk, v, sv,
-                           cq, ck, scale, Tq, split_ws, nsplit);
-      else
-        hipLaunchKernelGGL((attn_fwd_kvsplit_kernel<HD, 4, kKvSplitKB>), gs, dim3(256), 0, st, q, sq, k, sk, v, sv, cq,
-                           ck, scale, Tq, split_ws, nsplit);
-      hipLaunchKernelGGL((attn_fwd_combine_kernel<HD, kKvSplitKB>), gc, dim3(256), 0, st, split_ws, nsplit, cq, ck, Tq, out,
-                         so, lse);
-      return;
-    }
-    if (split_ws && split_plan(HD, max_q, max_k, causal, pol)) {
-      const int kb = split_kb(max_k);
-      const int nsplit = (int)((max_k + kb - 1) / kb);
-      constexpr int RPB = 256 / (HD / 4);
-      const dim3 gs((unsigned)nsplit, (unsigned)H, (unsigned)B);
-      const dim3 gc((unsigned)std::max<int64_t>(1, (max_q + RPB - 1) / RPB), (unsigned)H, (unsigned)B + 1);
-      if (pol.x3 && kb == kKvSplitKB) {   // split-bf16: the key-split form (4 waves stage each 128-key block)
-        hipLaunchKernelGGL((attn_fwd_kvsplit_kernel<HD, 4, kKvSplitKB, true>), gs, dim3(256), 0, st, q, sq, k, sk, v,
-                           sv, cq, ck, scale, Tq, split_ws, nsplit);
-        hipLaunchKernelGGL((attn_fwd_combine_kernel<HD, kKvSplitKB>), gc, dim3(256), 0, st, split_ws, nsplit, cq, ck, Tq,
-                           out, so, lse);
-        return;
-      }
-#define RQ_SPL(KB_)                                                                                                \
-  hipLaunchKernelGGL((attn_fwd_split_kernel<HD, KB_>), gs, dim3(64), 0, st, q, sq, k, sk, v, sv, cq, ck, scale, Tq, \
-                     split_ws, nsplit);                                                                            \
-  hipLaunchKernelGGL((attn_fwd_combine_kernel<HD, KB_>), gc, dim3(256), 0, st, split_ws, nsplit, cq, ck, Tq, out, so, lse)
-      if (kb == 32) { RQ_SPL(32); } else { RQ_SPL(128); }
-#undef RQ_SPL
-      return;
-    }
-    const int* sord = nullptr;   // LPT order of the short / few-query forms
-    if (order && short_lpt_plan(B, pol) && (fewq_plan(HD, max_q, max_k, pol) || dma_fwd_plan(HD, max_q, max_k, pol))) {
-      if (!pol.order_given) hipLaunchKernelGGL(attn_order_kernel, dim3(1), dim3(1024), 0, st, ck, (int)B, order);
-      sord = order;
-    }
-    if (fewq_plan(HD, max_q, max_k, pol)) {
-      const dim3 g(1, (unsigned)H, (unsigned)B + 1);   // + tail slice
-      switch (fewq_waves(max_k)) {
-        case 1: hipLaunchKernelGGL((attn_fwd_fewq_kernel<1>), g, dim3(64), 0, st, q, sq, k, sk, v, sv, cq, ck, causal, scale, out, so, lse, Tq, sord); break;
-        case 2: hipLaunchKernelGGL((attn_fwd_fewq_kernel<2>), g, dim3(128), 0, st, q, sq, k, sk, v, sv, cq, ck, causal, scale, out, so, lse, Tq, sord); break;
-        default: hipLaunchKernelGGL((attn_fwd_fewq_kernel<4>), g, dim3(256), 0, st, q, sq, k, sk, v, sv, cq, ck, causal, scale, out, so, lse, Tq, sord); break;
-      }
-      return;
-    }
-    if (dma_fwd_plan(HD, max_q, max_k, pol)) {
-      const dim3 g(1, (unsigned)H, (unsigned)B + 1);   // + tail slice
-      if (pol.x3 && max_k > 32) {   // split-bf16 form at matmul 'high'
-#define RQ_FX(R_)                                                                                                \
-  hipLaunchKernelGGL((attn_fwd_short_x3_kernel<R_>), g, dim3(256), 0, st, q, sq, k, sk, v, sv, cq, ck, causal, scale, \
-                     out, so, lse, Tq, sord)
-        switch (dma_rows_for(max_k)) {
-          case 64: RQ_FX(64); break;
-          case 96: RQ_FX(96); break;
-          default: RQ_FX(128); break;
-        }
-#undef RQ_FX
-        return;
-      }
-#define RQ_FD(R_)                                                                                              \
-  hipLaunchKernelGGL((attn_fwd_dma_kernel<4, R_>), g, dim3(256), 0, st, q, sq, k, sk, v, sv, cq, ck, causal, scale, \
-                     out, so, lse, Tq)
-      switch (dma_rows_for(max_k)) {
-        case 32: RQ_FD(32); break;
-        case 64: RQ_FD(64); break;
-        case 96: RQ_FD(96); break;
-        default: RQ_FD(128); break;
-      }
-#undef RQ_FD
-      return;
-    }
-    int nw = 0, ch = 0;
-    if (short_plan(max_q, max_k, &nw, &ch)) {
-      const dim3 g(1, (unsigned)H, (unsigned)B + 1);   // + tail slice
-#define RQ_FS(NW_, CH_)                                                                                            \
-  hipLaunchKernelGGL((attn_fwd_short_kernel<HD, NW_, CH_>), g, dim3(64 * NW_), 0, st, q, sq, k, sk, v, sv, cq, ck, \
-                     causal, scale, out, so, lse, Tq)
-      RQ_SHORT_SWITCH(nw, ch, RQ_FS);
-#undef RQ_FS
-      return;
+struct AttnBwdArgs {
+  const float *q, *k, *v, *out, *dout, *lse;
+  int64_t sq, sk, sv, so, sdo;
+  const int64_t *cq, *ck;
+  int64_t B, H, Tq, Tk;
+  int causal;
+  float scale;
+  float *dq, *dk, *dv;
+  int64_t sdq, sdk, sdv;
+  float *delta, *ws;
+  hipStream_t st;
+};
+
+static bool attn_run_bwd(const rq_attn_plan& p, const AttnBwdArgs& a) {
+  int* order = p.order_off >= 0 ? reinterpret_cast<int*>(a.ws + p.order_off) : nullptr;
+  float* kvpart = p.kvpart_off >= 0 ? a.ws + p.kvpart_off : nullptr;
+  bool ok = true;
+  for (int i = 0; i < p.n_launches && ok; ++i) {
+    const rq_attn_launch& l = p.launch[i];
+    auto dq_pass = [&](auto kern) {   // also writes delta
+      launch(kern, l, a.st, a.q, a.sq, a.k, a.sk, a.v, a.sv, a.out, a.so, a.dout, a.sdo, a.lse, a.Tq, a.cq, a.ck, a.causal,
+             a.scale, a.dq, a.sdq, a.delta);
+    };
+    auto kv_pass = [&](auto kern) {
+      launch(kern, l, a.st, a.q, a.sq, a.k, a.sk, a.v, a.sv, a.dout, a.sdo, a.lse, a.delta, a.Tq, a.cq, a.ck, a.causal,
+             a.scale, a.dk, a.sdk, a.dv, a.sdv, a.Tk);
+    };
+    auto one_pass = [&](auto kern, auto... more) {
+      launch(kern, l, a.st, a.q, a.sq, a.k, a.sk, a.v, a.sv, a.out, a.so, a.dout, a.sdo, a.lse, a.Tq, a.cq, a.ck, a.causal,
+             a.scale, a.dq, a.sdq, a.dk, a.sdk, a.dv, a.sdv, a.Tk, a.delta, order, more...);
+    };
+    auto fused = [&](auto kern) {   // the dQ partials open the workspace
+      launch(kern, l, a.st, a.q, a.sq, a.k, a.sk, a.v, a.sv, a.dout, a.sdo, a.lse, a.delta, a.Tq, a.cq, a.ck, a.causal,
+             a.scale, a.dq, a.sdq, a.ws, a.dk, a.sdk, a.dv, a.sdv, a.Tk, order, p.qsplit, kvpart);
+    };
+    switch (l.family) {
+      case RQ_ATTN_K_ORDER:
+        launch(attn_order_kernel, l, a.st, p.order_src == RQ_ATTN_ORDER_SRC_CU_Q ? a.cq : a.ck, (int)a.B, order);
+        break;
+      case RQ_ATTN_K_BWD_DQ:
+        ok = with_hd_nw(l, [&](auto HD, auto NW) { dq_pass(attn_bwd_dq_kernel<HD(), NW()>); });
+        break;
+      case RQ_ATTN_K_BWD_DKDV:
+        ok = with_hd_nw(l, [&](auto HD, auto NW) { kv_pass(attn_bwd_dkdv_kernel<HD(), NW()>); });
+        break;
+      case RQ_ATTN_K_BWD_DQ_SHORT:   // CH == 32 only: kShortMaxStaged (attention_plan.h)
+        ok = l.hd == 64 && l.r == 32 && with_int<1, 4>(l.nw, [&](auto NW) { dq_pass(attn_bwd_dq_short_kernel<64, NW(), 32>); });
+        break;
+      case RQ_ATTN_K_BWD_DKDV_SHORT:
+        ok = l.hd == 64 && l.r == 32 && with_int<1, 4>(l.nw, [&](auto NW) { kv_pass(attn_bwd_dkdv_short_kernel<64, NW(), 32>); });
+        break;
+      case RQ_ATTN_K_BWD_DQ_DMA:
+        ok = l.nw == 4 && with_int<32, 64, 96, 128>(l.r, [&](auto R) { dq_pass(attn_bwd_dq_dma_kernel<4, R()>); });
+        break;
+      case RQ_ATTN_K_BWD_DKDV_DMA:
+        ok = l.nw == 4 && with_int<32, 64, 96, 128>(l.r, [&](auto R) { kv_pass(attn_bwd_dkdv_dma_kernel<4, R()>); });
+        break;
+      case RQ_ATTN_K_BWD_DQ_FEWQ:
+        ok = with_int<1, 2, 4>(l.nw, [&](auto NW) { dq_pass(attn_bwd_dq_fewq_kernel<NW()>); });
+        break;
+      case RQ_ATTN_K_BWD_FEWQ_FUSED:
+        ok = with_int<1, 2, 4>(l.nw, [&](auto NW) { one_pass(attn_bwd_fewq_fused_kernel<NW()>); });
+        break;
+      case RQ_ATTN_K_BWD_FEWQ_STREAM:
+        ok = with_int<64, 96, 128>(l.r, [&](auto R) { one_pass(attn_bwd_fewq_stream_kernel<R()>, (int)a.B, (int)a.H); });
+        break;
+      case RQ_ATTN_K_BWD_SHORT_FUSED:
+        if (l.nw == 2 && l.r == 32) one_pass(attn_bwd_short_fused_kernel<2, 32>);
+        else ok = l.nw == 4 && with_int<64, 96, 128>(l.r, [&](auto R) { one_pass(attn_bwd_short_fused_kernel<4, R()>); });
+        break;
+      case RQ_ATTN_K_DELTA:
+        ok = l.hd == 64 && (launch(attn_delta_kernel<64>, l, a.st, a.out, a.so, a.dout, a.sdo, a.Tq, a.H, a.delta), true);
+        break;
+      case RQ_ATTN_K_BWD_FUSED:
+        ok = l.hd == 64 && l.nw == kFusedNW && l.r == kFusedCH;
+        if (ok && l.x3) fused(attn_bwd_fused_x3_kernel<kFusedNW, kFusedCH>);
+        else if (ok) fused(attn_bwd_fused_kernel<64, kFusedNW, kFusedCH>);
+        break;
+      case RQ_ATTN_K_KV_REDUCE:
+        ok = l.hd == 64 && (launch(attn_kv_reduce_kernel<64>, l, a.st, kvpart, p.qsplit, a.Tk, a.H, a.ck, (int)a.B, a.scale,
+                                   a.dk, a.sdk, a.dv, a.sdv), true);
+        break;
+      case RQ_ATTN_K_DQ_REDUCE:
+        ok = l.hd == 64 && l.r == kFusedKB &&
+             (launch(attn_dq_reduce_kernel<64, kFusedKB>, l, a.st, a.ws, a.Tq, a.cq, a.ck, a.causal, a.scale, a.dq, a.sdq), true);
+        break;
+      default: ok = false;
     }
   }
-  const int* ord = nullptr;
-  if (order && lpt_plan(B, max_k)) {
-    if (!pol.order_given) hipLaunchKernelGGL(attn_order_kernel, dim3(1), dim3(1024), 0, st, ck, (int)B, order);
-    ord = order;
-  }
-  switch (waves_for(max_q)) {
-    case 1: fwd_nw<HD, 1>(B, H, max_q, st, q, sq, k, sk, v, sv, cq, ck, causal, scale, out, so, lse, Tq, ord, false); break;
-    case 2: fwd_nw<HD, 2>(B, H, max_q, st, q, sq, k, sk, v, sv, cq, ck, causal, scale, out, so, lse, Tq, ord, false); break;
-    default: fwd_nw<HD, 4>(B, H, max_q, st, q, sq, k, sk, v, sv, cq, ck, causal, scale, out, so, lse, Tq, ord, pol.x3); break;
-  }
-}
-
-template <int HD, int NW>
-static void dq_nw(int64_t B, int64_t H, int64_t max_q, hipStream_t st, const float* q, int64_t sq, const float* k,
-                  int64_t sk, const float* v, int64_t sv, const float* out, int64_t so, const float* dout, int64_t sdo,
-                  const float* lse, int64_t Tq, const int64_t* cq, const int64_t* ck, int causal, float scale, float* dq,
-                  int64_t sdq, float* delta) {
-  dim3 g((unsigned)std::max<int64_t>(1, (max_q + 16 * NW - 1) / (16 * NW)), (unsigned)H, (unsigned)B + 1);   // + tail slice
-  hipLaunchKernelGGL((attn_bwd_dq_kernel<HD, NW>), g, dim3(64 * NW), 0, st, q, sq, k, sk, v, sv, out, so, dout, sdo, lse,
-                     Tq, cq, ck, causal, scale, dq, sdq, delta);
-}
-
-template <int HD, int NW>
-static void dkdv_nw(int64_t B, int64_t H, int64_t max_k, hipStream_t st, const float* q, int64_t sq, const float* k,
-                    int64_t sk, const float* v, int64_t sv, const float* dout, int64_t sdo, const float* lse,
-                    const float* delta, int64_t Tq, const int64_t* cq, const int64_t* ck, int causal, float scale,
-                    float* dk, int64_t sdk, float* dv, int64_t sdv, int64_t Tk) {
-  dim3 g((unsigned)std::max<int64_t>(1, (max_k + 16 * NW - 1) / (16 * NW)), (unsigned)H, (unsigned)B + 1);   // + tail slice
-  hipLaunchKernelGGL((attn_bwd_dkdv_kernel<HD, NW>), g, dim3(64 * NW), 0, st, q, sq, k, sk, v, sv, dout, sdo, lse, delta,
-                     Tq, cq, ck, causal, scale, dk, sdk, dv, sdv, Tk);
-}
-
-template <int HD>
-static void launch_dq_chunked(int64_t B, int64_t H, int64_t max_q, hipStream_t st, const float* q, int64_t sq,
-                              const float* k, int64_t sk, const float* v, int64_t sv, const float* out, int64_t so,
-                              const float* dout, int64_t sdo, const float* lse, int64_t Tq, const int64_t* cq,
-                              const int64_t* ck, int causal, float scale, float* dq, int64_t sdq, float* delta) {
-  switch (waves_for(max_q)) {
-    case 1: dq_nw<HD, 1>(B, H, max_q, st, q, sq, k, sk, v, sv, out, so, dout, sdo, lse, Tq, cq, ck, causal, scale, dq, sdq, delta); break;
-    case 2: dq_nw<HD, 2>(B, H, max_q, st, q, sq, k, sk, v, sv, out, so, dout, sdo, lse, Tq, cq, ck, causal, scale, dq, sdq, delta); break;
-    default: dq_nw<HD, 4>(B, H, max_q, st, q, sq, k, sk, v, sv, out, so, dout, sdo, lse, Tq, cq, ck, causal, scale, dq, sdq, delta); break;
-  }
-}
-
-template <int HD>
-static void launch_bwd(int64_t B, int64_t H, int64_t max_q, int64_t max_k, hipStream_t st, const float* q, int64_t sq,
-                       const float* k, int64_t sk, const float* v, int64_t sv, const float* out, int64_t so,
-                       const float* dout, int64_t sdo, const float* lse, int64_t Tq, const int64_t* cq, const int64_t* ck,
-                       int causal, float scale, float* dq, int64_t sdq, float* dk, int64_t sdk, float* dv, int64_t sdv,
-                       int64_t Tk, float* delta, const AttnPolicy& pol, const int* order = nullptr) {
-  // dQ pass first: it also writes delta_q = dO.O, which the dK/dV pass reads per query chunk
-  bool dq_done = false, kv_done = false;
-  if constexpr (HD == 64) {
-    int nw = 0, ch = 0;
-    const dim3 g(1, (unsigned)H, (unsigned)B + 1);   // + tail slice
-    if (short_fused_plan(HD, max_q, max_k, pol)) {
-#define RQ_SHF(NW_, R_)                                                                                              \
-  hipLaunchKernelGGL((attn_bwd_short_fused_kernel<NW_, R_>), g, dim3(64 * NW_), 0, st, q, sq, k, sk, v, sv, out, so, \
-                     dout, sdo, lse, Tq, cq, ck, causal, scale, dq, sdq, dk, sdk, dv, sdv, Tk, delta, order)
-      // 4 waves with up to two key tiles each (one key tile per wave, R / 16 waves, measured slower on the
-      // Amazon step: 6.20-6.22 vs 6.10-6.15 ms, profiles/r03/short_tpw_ab.txt — more waves idle on short
-      // sequences)
-      switch (dma_rows_for(std::max(max_q, max_k))) {
-        case 32: RQ_SHF(2, 32); break;
-        case 64: RQ_SHF(4, 64); break;
-        case 96: RQ_SHF(4, 96); break;
-        default: RQ_SHF(4, 128); break;
-      }
-#undef RQ_SHF
-      return;
-    }
-    if (fewq_plan(HD, max_q, max_k, pol) && pol.fused && fewq_waves(max_k) == 4 && pol.fewq_stream && Tq > 0 &&
-        Tk > 0) {   // persistent workgroups, the next unit staged by LDS-DMA
-      const int64_t slots = (int64_t)attn_cus() * (max_k <= 96 ? 2 : 1);
-      const dim3 gs((unsigned)std::max<int64_t>(1, std::min<int64_t>(B * H, slots)));
-#define RQ_FQS(R_)                                                                                                 \
-  hipLaunchKernelGGL((attn_bwd_fewq_stream_kernel<R_>), gs, dim3(256), 0, st, q, sq, k, sk, v, sv, out, so, dout, sdo, \
-                     lse, Tq, cq, ck, causal, scale, dq, sdq, dk, sdk, dv, sdv, Tk, delta, order, (int)B, (int)H)
-      if (max_k <= 64) { RQ_FQS(64); } else if (max_k <= 96) { RQ_FQS(96); } else { RQ_FQS(128); }
-#undef RQ_FQS
-      return;
-    }
-    if (fewq_plan(HD, max_q, max_k, pol) && pol.fused) {
-#define RQ_FQF(NW_)                                                                                                   \
-  hipLaunchKernelGGL((attn_bwd_fewq_fused_kernel<NW_>), g, dim3(64 * NW_), 0, st, q, sq, k, sk, v, sv, out, so, dout, \
-                     sdo, lse, Tq, cq, ck, causal, scale, dq, sdq, dk, sdk, dv, sdv, Tk, delta, order)
-      switch (fewq_waves(max_k)) {
-        case 1: RQ_FQF(1); break;
-        case 2: RQ_FQF(2); break;
-        default: RQ_FQF(4); break;
-      }
-#undef RQ_FQF
-      return;
-    }
-    if (fewq_plan(HD, max_q, max_k, pol)) {
-#define RQ_DQF(NW_)                                                                                                   \
-  hipLaunchKernelGGL((attn_bwd_dq_fewq_kernel<NW_>), g, dim3(64 * NW_), 0, st, q, sq, k, sk, v, sv, out, so, dout, sdo, \
-                     lse, Tq, cq, ck, causal, scale, dq, sdq, delta)
-      switch (fewq_waves(max_k)) {
-        case 1: RQ_DQF(1); break;
-        case 2: RQ_DQF(2); break;
-        default: RQ_DQF(4); break;
-      }
-#undef RQ_DQF
-      dq_done = true;
-    } else if (dma_fwd_plan(HD, max_q, max_k, pol)) {
-#define RQ_DQD(R_)                                                                                                  \
-  hipLaunchKernelGGL((attn_bwd_dq_dma_kernel<4, R_>), g, dim3(256), 0, st, q, sq, k, sk, v, sv, out, so, dout, sdo, lse, \
-                     Tq, cq, ck, causal, scale, dq, sdq, delta)
-      switch (dma_rows_for(max_k)) {
-        case 32: RQ_DQD(32); break;
-        case 64: RQ_DQD(64); break;
-        case 96: RQ_DQD(96); break;
-        default: RQ_DQD(128); break;
-      }
-#undef RQ_DQD
-      dq_done = true;
-    } else if (short_plan(max_q, max_k, &nw, &ch)) {
-#define RQ_DQS(NW_, CH_)                                                                                              \
-  hipLaunchKernelGGL((attn_bwd_dq_short_kernel<HD, NW_, CH_>), g, dim3(64 * NW_), 0, st, q, sq, k, sk, v, sv, out, so, \
-                     dout, sdo, lse, Tq, cq, ck, causal, scale, dq, sdq, delta)
-      RQ_SHORT_SWITCH(nw, ch, RQ_DQS);
-#undef RQ_DQS
-      dq_done = true;
-    }
-    if (dma_kv_plan(HD, max_q, max_k, pol)) {
-      if (!dq_done) {   // the dK/dV pass reads delta: chunked dQ first
-        launch_dq_chunked<HD>(B, H, max_q, st, q, sq, k, sk, v, sv, out, so, dout, sdo, lse, Tq, cq, ck, causal, scale, dq,
-                              sdq, delta);
-        dq_done = true;
-      }
-#define RQ_KVD(R_)                                                                                                     \
-  hipLaunchKernelGGL((attn_bwd_dkdv_dma_kernel<4, R_>), g, dim3(256), 0, st, q, sq, k, sk, v, sv, dout, sdo, lse, delta, \
-                     Tq, cq, ck, causal, scale, dk, sdk, dv, sdv, Tk)
-      switch (dma_rows_for(max_q)) {
-        case 32: RQ_KVD(32); break;
-        case 64: RQ_KVD(64); break;
-        case 96: RQ_KVD(96); break;
-        default: RQ_KVD(128); break;
-      }
-#undef RQ_KVD
-      kv_done = true;
-    } else if (short_plan(max_k, max_q, &nw, &ch)) {
-      if (!dq_done) {   // the dK/dV pass reads delta: chunked dQ first
-        launch_dq_chunked<HD>(B, H, max_q, st, q, sq, k, sk, v, sv, out, so, dout, sdo, lse, Tq, cq, ck, causal, scale, dq,
-                              sdq, delta);
-        dq_done = true;
-      }
-#define RQ_KVS(NW_, CH_)                                                                                                \
-  hipLaunchKernelGGL((attn_bwd_dkdv_short_kernel<HD, NW_, CH_>), g, dim3(64 * NW_), 0, st, q, sq, k, sk, v, sv, dout, \
-                     sdo, lse, delta, Tq, cq, ck, causal, scale, dk, sdk, dv, sdv, Tk)
-      RQ_SHORT_SWITCH(nw, ch, RQ_KVS);
-#undef RQ_KVS
-      kv_done = true;
-    }
-  }
-  if (!dq_done)
-    launch_dq_chunked<HD>(B, H, max_q, st, q, sq, k, sk, v, sv, out, so, dout, sdo, lse, Tq, cq, ck, causal, scale, dq, sdq,
-                          delta);
-  if (kv_done) return;
-  switch (waves_for(max_k)) {
-    case 1: dkdv_nw<HD, 1>(B, H, max_k, st, q, sq, k, sk, v, sv, dout, sdo, lse, delta, Tq, cq, ck, causal, scale, dk, sdk, dv, sdv, Tk); break;
-    case 2: dkdv_nw<HD, 2>(B, H, max_k, st, q, sq, k, sk, v, sv, dout, sdo, lse, delta, Tq, cq, ck, causal, scale, dk, sdk, dv, sdv, Tk); break;
-    default: dkdv_nw<HD, 4>(B, H, max_k, st, q, sq, k, sk, v, sv, dout, sdo, lse, delta, Tq, cq, ck, causal, scale, dk, sdk, dv, sdv, Tk); break;
-  }
-}
-
-// Fused backward (one launch for dQ, dK, dV: attn_bwd_fused_kernel) where the two-pass form would use the
-// chunked dK/dV kernel; the short forms keep the decoder's 5-token self- and cross-attention.
-constexpr int kFusedNW = 4;           // waves per workgroup = key block / 16
-constexpr int kFusedCH = 32;          // staged query rows per LDS round trip (A/B on MI355X: 32 beats 64 by 4-5 %)
-constexpr int kFusedMinK = 129;       // shorter key ranges keep the two-pass form (Amazon n <= 81: 0.25 vs 0.30 ms)
-constexpr int kFusedMinKFewq = 129;   // the same threshold for <= 16 queries per sequence (cross-attention;
-                                      // A/B from 33 keys: Amazon decoder step 6.53 -> 6.60 ms, fewq_ab.txt)
-constexpr int kFusedKB = 16 * kFusedNW;
-
-static bool fused_plan(int64_t hd, int64_t max_q, int64_t max_k, const AttnPolicy& pol) {
-  if (!pol.fused || hd != 64) return false;
-  if (max_q <= 16) return max_k >= kFusedMinKFewq;   // few queries (cross-attention): own threshold
-  if (max_k < kFusedMinK) return false;
-  int nw = 0, ch = 0;
-  return !short_plan(max_k, max_q, &nw, &ch);
-}
-
-// Query splits of the fused backward: when (sequences x heads x key blocks) workgroups cannot fill the
-// chip twice over (ML-32M at 8 sequences per GPU: ~300 workgroups, each walking up to 801 queries), each
-// key block's query range is split over up to 4 workgroups (whole 32-query chunks, >= 2 per split);
-// their dK / dV partials are summed by attn_kv_reduce_kernel. A call's RQ_ATTN_QSPLIT(n) forces n (1 = off).
-static int fused_qsplit(int64_t B, int64_t H, int64_t max_q, int64_t max_k, const AttnPolicy& pol) {
-  const int forced = pol.qsplit;
-  if (max_q <= 16) return 1;
-  const int64_t max_by_len = std::max<int64_t>(1, max_q / (2 * kFusedCH));
-  if (forced > 0) return (int)std::min<int64_t>(std::min(forced, 8), max_by_len);
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) !=
-                                                hipSuccess || cus <= 0)
-      cus = 256;
-  }
-  const int64_t wgs = B * H * ((max_k + kFusedKB - 1) / kFusedKB);
-  const int64_t want = (6 * (int64_t)cus + wgs - 1) / std::max<int64_t>(1, wgs);   // ~2 rounds of 3 per CU
-  return (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(want, 4), max_by_len));
-}
-
-// floats of dQ partials the fused backward needs: one (Tq, H*hd) slab per key block when a sequence may
-// span more than one block
-static int64_t fused_part_elems(int64_t H, int64_t hd, int64_t max_q, int64_t max_k, int64_t Tq, const AttnPolicy& pol) {
-  if (!fused_plan(hd, max_q, max_k, pol)) return 0;
-  const int64_t nkb = (max_k + kFusedKB - 1) / kFusedKB;
-  return nkb > 1 ? nkb * Tq * H * hd : 0;
-}
-// + B ints of LPT order (float slots, padded to 16 B) [+ the query splits' dK / dV partials, Tk >= 0]
-static int64_t fused_ws_elems(int64_t B, int64_t H, int64_t hd, int64_t max_q, int64_t max_k, int64_t Tq,
-                              const AttnPolicy& pol, int64_t Tk = -1) {
-  if (!fused_plan(hd, max_q, max_k, pol)) return 0;
-  const int64_t base =
-      fused_part_elems(H, hd, max_q, max_k, Tq, pol) + (lpt_plan(B, max_q) ? ((B + 3) & ~(int64_t)3) : 0);
-  const int qs = Tk >= 0 ? fused_qsplit(B, H, max_q, max_k, pol) : 1;
-  return base + (qs > 1 ? 2 * qs * Tk * H * hd : 0);
-}
-
-// the one-pass short / few-query backwards in LPT order (scratch: B ints)
-static bool short_lpt_bwd(int64_t B, int64_t hd, int64_t max_q, int64_t max_k, const AttnPolicy& pol) {
-  return short_lpt_plan(B, pol) && !fused_plan(hd, max_q, max_k, pol) &&
-         (short_fused_plan(hd, max_q, max_k, pol) || (fewq_plan(hd, max_q, max_k, pol) && pol.fused));
-}
-
-template <int HD>
-static void launch_bwd_fused(int64_t B, int64_t H, int64_t max_q, int64_t max_k, hipStream_t st, const float* q,
-                             int64_t sq, const float* k, int64_t sk, const float* v, int64_t sv, const float* out,
-                             int64_t so, const float* dout, int64_t sdo, const float* lse, int64_t Tq, const int64_t* cq,
-                             const int64_t* ck, int causal, float scale, float* dq, int64_t sdq, float* dk, int64_t sdk,
-                             float* dv, int64_t sdv, int64_t Tk, float* delta, float* ws, int64_t ws_elems,
-                             const AttnPolicy& pol) {
-  if constexpr (HD == 64) {
-    constexpr int NW = kFusedNW, CH = kFusedCH, KB = 16 * NW;
-    const int* ord = nullptr;
-    if (lpt_plan(B, max_q)) {   // the order lives after the dQ partials in ws
-      int* o = reinterpret_cast<int*>(ws + fused_part_elems(H, HD, max_q, max_k, Tq, pol));
-      hipLaunchKernelGGL(attn_order_kernel, dim3(1), dim3(1024), 0, st, cq, (int)B, o);
-      ord = o;
-    }
-    constexpr int LPR = HD / 4 < 16 ? HD / 4 : 16;
-    const int64_t threads = Tq * H * LPR;
-    if (threads > 0)
-      hipLaunchKernelGGL((attn_delta_kernel<HD>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, out, so, dout,
-                         sdo, Tq, H, delta);
-    // query splits only when the caller sized the workspace for them (varlen_attn_bwd_ws_elems with Tk)
-    int qs = fused_qsplit(B, H, max_q, max_k, pol);
-    if (qs > 1 && ws_elems < fused_ws_elems(B, H, HD, max_q, max_k, Tq, pol, Tk)) qs = 1;
-    float* kvpart = qs > 1 ? ws + fused_ws_elems(B, H, HD, max_q, max_k, Tq, pol) : nullptr;
-    const dim3 g((unsigned)(std::max<int64_t>(1, (max_k + KB - 1) / KB) * qs), (unsigned)H, (unsigned)B + 1);   // + tail
-    if (pol.x3 && NW == 4 && CH == 32)
-      hipLaunchKernelGGL((attn_bwd_fused_x3_kernel<NW, CH>), g, dim3(64 * NW), 0, st, q, sq, k, sk, v, sv, dout, sdo, lse,
-                         delta, Tq, cq, ck, causal, scale, dq, sdq, ws, dk, sdk, dv, sdv, Tk, ord, qs, kvpart);
-    else
-      hipLaunchKernelGGL((attn_bwd_fused_kernel<HD, NW, CH>), g, dim3(64 * NW), 0, st, q, sq, k, sk, v, sv, dout, sdo,
-                         lse, delta, Tq, cq, ck, causal, scale, dq, sdq, ws, dk, sdk, dv, sdv, Tk, ord, qs, kvpart);
-    if (qs > 1 && Tk > 0) {
-      const int64_t n = Tk * H * (HD / 4);
-      hipLaunchKernelGGL((attn_kv_reduce_kernel<HD>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, kvpart, qs, Tk,
-                         H, ck, (int)B, scale, dk, sdk, dv, sdv);
-    }
-    if ((max_k + KB - 1) / KB > 1 && max_q > 0) {
-      constexpr int RPB = 256 / (HD / 4);
-      const dim3 gr((unsigned)((max_q + RPB - 1) / RPB), (unsigned)H, (unsigned)B);
-      hipLaunchKernelGGL((attn_dq_reduce_kernel<HD, KB>), gr, dim3(256), 0, st, ws, Tq, cq, ck, causal, scale, dq, sdq);
-    }
-  }
+  return ok;
 }
 
 static bool attn_args_ok(int64_t B, int64_t H, int64_t hd, int64_t max_q, int64_t max_k) {
@@ -3526,12 +3230,20 @@ using namespace rqhip;
 
 extern "C" {
 
+int varlen_attn_plan(int backward, int64_t B, int64_t H, int64_t hd, int64_t max_q, int64_t max_k, int64_t Tq,
+                     int64_t Tk, int causal, int flags, int64_t ws_elems, rq_attn_plan* plan) {
+  RQ_CHECK_ARG(plan, "varlen_attn_plan: null pointer");
+  RQ_CHECK_ARG(attn_args_ok(B, H, hd, max_q, max_k) && Tq >= 0, "varlen_attn_plan: bad shape");
+  const AttnShape s{B, H, hd, max_q, max_k, Tq, Tk, causal, flags, ws_elems};
+  *plan = backward ? attn_plan_bwd(s, attn_cus()) : attn_plan_fwd(s);
+  return 0;
+}
+
 int varlen_attn_fwd_ws_elems(int64_t B, int64_t H, int64_t hd, int64_t max_q, int64_t max_k, int64_t Tq, int causal,
                              int flags, int64_t* elems) {
   RQ_CHECK_ARG(elems, "varlen_attn_fwd_ws_elems: null pointer");
   RQ_CHECK_ARG(attn_args_ok(B, H, hd, max_q, max_k) && Tq >= 0, "varlen_attn_fwd_ws_elems: bad shape");
-  // order (B ints, 16-B padded) + split-key partials
-  *elems = ((B + 3) & ~(int64_t)3) + split_ws_elems(B, H, hd, max_q, max_k, Tq, causal, attn_policy(flags));
+  *elems = attn_plan_fwd(AttnShape{B, H, hd, max_q, max_k, Tq, -1, causal, flags, -1}).ws_total;
   return 0;
 }
 
@@ -3542,24 +3254,14 @@ int varlen_attn_fwd(const float* q, int64_t sq, const float* k, int64_t sk, cons
   RQ_CHECK_ARG(q && k && v && cu_q && cu_k && out && lse, "varlen_attn_fwd: null pointer");
   RQ_CHECK_ARG(attn_args_ok(B, H, hd, max_q, max_k), "varlen_attn_fwd: bad shape (hd must be 16/32/64/128, B<65535)");
   RQ_CHECK_ARG(sq % 4 == 0 && sk % 4 == 0 && sv % 4 == 0 && so % 4 == 0, "varlen_attn_fwd: row strides must be x4");
-  const AttnPolicy pol = attn_policy(flags);
-  int* order = nullptr;
-  float* split_ws = nullptr;
-  if (ws != nullptr) {   // no scratch (ws NULL): natural sequence order, no split-key / key-split forms
-    const int64_t ob = (B + 3) & ~(int64_t)3, sp = split_ws_elems(B, H, hd, max_q, max_k, Tq, causal, pol);
-    RQ_CHECK_ARG(ws_elems >= ob + sp, "varlen_attn_fwd: workspace %lld < varlen_attn_fwd_ws_elems %lld floats",
-                 (long long)ws_elems, (long long)(ob + sp));
-    order = reinterpret_cast<int*>(ws);
-    split_ws = sp ? ws + ob : nullptr;
-  }
+  // no scratch (ws NULL): natural sequence order, no split-key / key-split forms
+  const int64_t have = ws ? std::max<int64_t>(ws_elems, 0) : -1;
+  const rq_attn_plan p = attn_plan_fwd(AttnShape{B, H, hd, max_q, max_k, Tq, -1, causal, flags, have});
+  RQ_CHECK_ARG(ws == nullptr || ws_elems >= p.ws_need, "varlen_attn_fwd: workspace %lld < varlen_attn_fwd_ws_elems %lld floats",
+               (long long)ws_elems, (long long)p.ws_need);
   if (B == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  switch (hd) {
-    case 16: launch_fwd<16>(B, H, max_q, max_k, st, q, sq, k, sk, v, sv, cu_q, cu_k, causal, scale, out, so, lse, Tq, order, split_ws, pol); break;
-    case 32: launch_fwd<32>(B, H, max_q, max_k, st, q, sq, k, sk, v, sv, cu_q, cu_k, causal, scale, out, so, lse, Tq, order, split_ws, pol); break;
-    case 64: launch_fwd<64>(B, H, max_q, max_k, st, q, sq, k, sk, v, sv, cu_q, cu_k, causal, scale, out, so, lse, Tq, order, split_ws, pol); break;
-    case 128: launch_fwd<128>(B, H, max_q, max_k, st, q, sq, k, sk, v, sv, cu_q, cu_k, causal, scale, out, so, lse, Tq, order, split_ws, pol); break;
-  }
+  const AttnFwdArgs a{q, k, v, sq, sk, sv, cu_q, cu_k, B, H, Tq, max_k, causal, scale, out, so, lse, ws, (hipStream_t)stream};
+  RQ_CHECK_ARG(attn_run_fwd(p, a), "varlen_attn_fwd: the plan names a kernel instantiation that is not built");
   RQ_LAUNCH_CHECK("varlen_attn_fwd");
   return 0;
 }
@@ -3568,9 +3270,7 @@ int varlen_attn_bwd_ws_elems(int64_t B, int64_t H, int64_t hd, int64_t max_q, in
                              int flags, int64_t* elems) {
   RQ_CHECK_ARG(elems, "varlen_attn_bwd_ws_elems: null pointer");
   RQ_CHECK_ARG(attn_args_ok(B, H, hd, max_q, max_k) && Tq >= 0, "varlen_attn_bwd_ws_elems: bad shape");
-  const AttnPolicy pol = attn_policy(flags);
-  *elems = fused_ws_elems(B, H, hd, max_q, max_k, Tq, pol, Tk);
-  if (*elems == 0 && short_lpt_bwd(B, hd, max_q, max_k, pol)) *elems = (B + 3) & ~(int64_t)3;   // the LPT order
+  *elems = attn_plan_bwd(AttnShape{B, H, hd, max_q, max_k, Tq, Tk, 0, flags, -1}, attn_cus()).ws_total;
   return 0;
 }
 
@@ -3585,33 +3285,15 @@ int varlen_attn_bwd(const float* q, int64_t sq, const float* k, int64_t sk, cons
   RQ_CHECK_ARG(sq % 4 == 0 && sk % 4 == 0 && sv % 4 == 0 && so % 4 == 0 && sdo % 4 == 0 && sdq % 4 == 0 &&
                    sdk % 4 == 0 && sdv % 4 == 0,
                "varlen_attn_bwd: row strides must be x4");
-  const AttnPolicy pol = attn_policy(flags);
   // the fused long-range form needs its scratch; a call without one (ws NULL) runs the two-pass form there
-  const bool fused = fused_plan(hd, max_q, max_k, pol) && ws != nullptr;
-  if (fused) {
-    const int64_t need = fused_ws_elems(B, H, hd, max_q, max_k, Tq, pol);
-    RQ_CHECK_ARG(ws_elems >= need, "varlen_attn_bwd: workspace %lld < varlen_attn_bwd_ws_elems %lld floats",
-                 (long long)ws_elems, (long long)need);
-  }
+  const int64_t have = ws ? std::max<int64_t>(ws_elems, 0) : -1;
+  const rq_attn_plan p = attn_plan_bwd(AttnShape{B, H, hd, max_q, max_k, Tq, Tk, causal, flags, have}, attn_cus());
+  RQ_CHECK_ARG(ws == nullptr || have >= p.ws_need, "varlen_attn_bwd: workspace %lld < varlen_attn_bwd_ws_elems %lld floats",
+               (long long)ws_elems, (long long)p.ws_need);
   if (B == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  int* sord = nullptr;
-  if (!fused && ws != nullptr && ws_elems >= B && short_lpt_bwd(B, hd, max_q, max_k, pol)) {
-    sord = reinterpret_cast<int*>(ws);
-    if (!pol.order_given) hipLaunchKernelGGL(attn_order_kernel, dim3(1), dim3(1024), 0, st, cu_k, (int)B, sord);
-  }
-  if (fused) {
-    launch_bwd_fused<64>(B, H, max_q, max_k, st, q, sq, k, sk, v, sv, out, so, dout, sdo, lse, Tq, cu_q, cu_k, causal,
-                         scale, dq, sdq, dk, sdk, dv, sdv, Tk, delta, ws, ws_elems, pol);
-    RQ_LAUNCH_CHECK("varlen_attn_bwd");
-    return 0;
-  }
-  switch (hd) {
-    case 16: launch_bwd<16>(B, H, max_q, max_k, st, q, sq, k, sk, v, sv, out, so, dout, sdo, lse, Tq, cu_q, cu_k, causal, scale, dq, sdq, dk, sdk, dv, sdv, Tk, delta, pol); break;
-    case 32: launch_bwd<32>(B, H, max_q, max_k, st, q, sq, k, sk, v, sv, out, so, dout, sdo, lse, Tq, cu_q, cu_k, causal, scale, dq, sdq, dk, sdk, dv, sdv, Tk, delta, pol); break;
-    case 64: launch_bwd<64>(B, H, max_q, max_k, st, q, sq, k, sk, v, sv, out, so, dout, sdo, lse, Tq, cu_q, cu_k, causal, scale, dq, sdq, dk, sdk, dv, sdv, Tk, delta, pol, sord); break;
-    case 128: launch_bwd<128>(B, H, max_q, max_k, st, q, sq, k, sk, v, sv, out, so, dout, sdo, lse, Tq, cu_q, cu_k, causal, scale, dq, sdq, dk, sdk, dv, sdv, Tk, delta, pol); break;
-  }
+  const AttnBwdArgs a{q,  k,  v,     out,   dout, lse, sq, sk, sv,  so,  sdo, cu_q,  cu_k, B,
+                      H,  Tq, Tk,    causal, scale, dq,  dk, dv, sdq, sdk, sdv, delta, ws,   (hipStream_t)stream};
+  RQ_CHECK_ARG(attn_run_bwd(p, a), "varlen_attn_bwd: the plan names a kernel instantiation that is not built");
   RQ_LAUNCH_CHECK("varlen_attn_bwd");
   return 0;
 }

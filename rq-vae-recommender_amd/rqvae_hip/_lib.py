@@ -88,6 +88,7 @@ _SIGS = {
     "varlen_attn_bwd_ws_elems": ([_I64, _I64, _I64, _I64, _I64, _I64, _I64, _I, _P], _I),
     "varlen_attn_bwd": ([_P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _I64,
                          _I64, _I, _F, _P, _I64, _P, _I64, _P, _I64, _I64, _P, _P, _I64, _I, _P], _I),
+    "varlen_attn_plan": ([_I, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I, _I, _I64, _P], _I),
     "rq_seed_epoch_advance": ([_P], _I),
     "rq_seed_epoch_set": ([_U64, _P], _I),
     "rq_beam_candidates": ([_P, _P, _I64, _I64, _I64, _F, _P, _P, _P], _I),
@@ -114,6 +115,19 @@ _SIGS = {
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
+
+
+class AttnLaunch(ctypes.Structure):
+    """rq_attn_launch (include/rqvae_hip.h): one launch of a varlen_attn_plan."""
+    _fields_ = [("family", _I), ("hd", _I), ("nw", _I), ("r", _I), ("x3", _I), ("block", _I),
+                ("grid", ctypes.c_uint * 3)]
+
+
+class AttnPlan(ctypes.Structure):
+    """rq_attn_plan (include/rqvae_hip.h): pass ctypes.byref(AttnPlan()) to varlen_attn_plan."""
+    _fields_ = [("n_launches", _I), ("qsplit", _I), ("order_src", _I), ("reserved", _I), ("ws_total", _I64),
+                ("ws_need", _I64), ("order_off", _I64), ("part_off", _I64), ("kvpart_off", _I64),
+                ("launch", AttnLaunch * 6)]
 
 _lib = None
 

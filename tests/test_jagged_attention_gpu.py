@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import attn_plan_support as S
 import gen_inputs as gi
 from oracle import attention as A
 from oracle import jagged as J
@@ -74,12 +75,14 @@ def _varlen_case(g, B, max_q, max_k, H, hd, same):
     (2, 1281, 1281, 8, 64, False, True), # C5 longest context (256 items x 5 + 1)
     (3, 6, 1281, 8, 64, False, False),   # C5 cross-attention: L+2 future queries x 1281 keys
     (2, 6, 6, 8, 64, True, True),        # C5 decoder causal self-attention
-    (5, 128, 128, 8, 64, True, True),    # short forms: longest staged range (128 rows), causal
-    (4, 64, 100, 8, 64, False, False),   # short forms: 64 queries x 100 keys (dQ stages 112 keys)
-    (3, 17, 17, 8, 64, True, True),      # short forms: two query tiles per sequence, causal diagonal
-    (5, 16, 128, 8, 64, False, False),   # few-query fused backward: a full query tile, 2 key tiles per wave
+    (5, 128, 128, 8, 64, True, True),    # LDS-DMA short forms, 128 staged rows, causal (RQ_ATTN_NO_DMA: chunked kernels)
+    (4, 64, 100, 8, 64, False, False),   # LDS-DMA short forms, 64 staged rows (drawn lengths <= 45); RQ_ATTN_NO_DMA: the
+                                         # chunked kernels (the register-staged short forms stop at 32 staged rows)
+    (3, 17, 17, 8, 64, True, True),      # drawn lengths <= 14: one-wave few-query forms, causal diagonal (RQ_ATTN_NO_DMA:
+                                         # register-staged short forms)
+    (5, 16, 128, 8, 64, False, False),   # few-query forms, 2 key tiles per wave: one-pass backward as the persistent walk
     (4, 16, 16, 8, 64, True, True),      # few-query fused backward: one wave, causal
-    (3, 12, 40, 8, 64, False, False),    # few-query fused backward: two waves
+    (3, 12, 40, 8, 64, False, False),    # few-query forms over 39 keys: 4 waves, persistent walk at 64 staged keys
     (4, 70, 70, 4, 32, True, True),
     (2, 40, 90, 2, 128, False, False),
     (5, 30, 30, 4, 16, True, True),      # small head dim (decoder fixtures: A=64, H=4)
@@ -121,6 +124,28 @@ def _attention_vs_oracle(device, B, max_q, max_k, H, hd, causal, same):
     chk(qb.grad, dq, 1e-4, 1e-3, "dq")
     chk(kt.grad, dk, 1e-4, 1e-3, "dk")
     chk(vt.grad, dv, 1e-4, 1e-3, "dv")
+
+
+@pytest.mark.parametrize("hd,max_q,max_k,causal,same,flags,high,forms", S.FORM_CASES)
+def test_every_launch_form_vs_oracle(device, hd, max_q, max_k, causal, same, flags, high, forms):
+    """Every kernel instantiation the attention launcher builds runs at least once against the fp64 oracle
+    (tests/attn_plan_support.FORM_CASES: B = 3, H = 2, the smallest shape that reaches each). The case first asks
+    varlen_attn_plan that its call dispatches the forms it names, with the lengths _attention_vs_oracle will draw.
+    Exact-fp32 forms at 'highest', split-bf16 forms at 'high': the oracle tolerances of test_varlen_attention_vs_oracle
+    and test_varlen_attention_split_bf16_vs_oracle (the same)."""
+    from rqvae_hip import ops
+    B, H = 3, 2
+    _, _, _, _, cq, ck = _varlen_case(gi.rng(B * 131 + max_q + hd), B, max_q, max_k, H, hd, same)
+    eff = flags | (ops.ATTN_SPLIT_BF16 if high else 0)
+    fwd, bwd = S.call_plans(B, H, hd, int(np.diff(cq).max()), int(np.diff(ck).max()), int(cq[-1]), int(ck[-1]), causal, eff)
+    assert set(forms) <= set(fwd.forms + bwd.forms), (forms, fwd.forms, bwd.forms)
+    prev = torch.get_float32_matmul_precision()
+    try:
+        torch.set_float32_matmul_precision("high" if high else "highest")
+        with ops.attn_policy(flags):
+            _attention_vs_oracle(device, B, max_q, max_k, H, hd, causal, same)
+    finally:
+        torch.set_float32_matmul_precision(prev)
 
 
 @pytest.mark.parametrize("n", [81, 400])
@@ -361,6 +386,9 @@ def test_fused_backward_query_splits(device, qsplit):
             ls = [801, 0, 333, 64, 517]
             cq = np.concatenate([[0], np.cumsum(ls)]).astype(np.int64)
             T = int(cq[-1]) + 9
+            bwd = S.call_plans(len(ls), H, hd, max(ls), max(ls), T, T, causal, ops.ATTN_QSPLIT(qsplit))[1]
+            assert bwd.qsplit == qsplit and S.Form("bwd_fused", 64, 4, 32, 0) in bwd.forms
+            assert (S.Form("kv_reduce", 64) in bwd.forms) == (qsplit > 1)
             q = g.standard_normal((T, H, hd), dtype=np.float32)
             k = g.standard_normal((T, H, hd), dtype=np.float32)
             v = g.standard_normal((T, H, hd), dtype=np.float32)
@@ -387,7 +415,7 @@ def test_fused_backward_query_splits(device, qsplit):
 
 @pytest.mark.parametrize("B,max_q,max_k,H,hd,causal,same", [
     (3, 200, 200, 6, 64, True, True),     # chunked forward, causal
-    (4, 150, 260, 6, 64, False, False),   # ragged q x k (key-split forward at few workgroups)
+    (4, 150, 260, 6, 64, False, False),   # ragged q x k (251 keys: chunked split-bf16 forward, fused backward)
     (2, 801, 801, 6, 64, False, True),    # ML-32M context length (fused backward with query splits)
     (2, 700, 700, 4, 64, True, True),     # causal, several key blocks (dQ partials)
     (8, 81, 81, 8, 64, False, True),      # Amazon encoder contexts: short fused backward, 96 staged rows
@@ -482,6 +510,20 @@ def test_varlen_attention_lpt_order_bitwise(device, lq, lk, causal):
     Tq = int(cu_np[-1]) + 2
     q0, k0, v0, do = (torch.from_numpy(g.standard_normal((Tq, A_), dtype=np.float32)).to(device) for _ in range(4))
     order_np = sorted(range(len(lq)), key=lambda b: (-lq[b], b))
+    # the plan: every mode runs the same kernels; over short ranges they are the LDS-DMA short / few-query forms, "lpt"
+    # adds the order launches (of cu_k) and "given" reads the attached order without one; long ranges rank by themselves
+    plans = {mode: S.ops_call_plans(len(lq), H, hd, max(lq), max(lq), Tq, Tq, causal, ops.ATTN_LPT_SHORT if mode == "lpt" else 0,
+                                    order_attached=mode == "given") for mode in ("default", "lpt", "given")}
+    kernels = {mode: [f for p in fb for f in p.forms if f.family != "order"] for mode, fb in plans.items()}
+    assert kernels["lpt"] == kernels["default"] == kernels["given"]
+    if max(lq) <= 128:
+        assert {f.family for f in kernels["default"]} <= {"fwd_dma", "fwd_fewq", "bwd_short_fused", "bwd_fewq_fused"}
+        for mode, src, launched in (("default", "none", False), ("lpt", "cu_k", True), ("given", "given", False)):
+            for p in plans[mode]:
+                assert p.order_src == src and (S.Form("order") in p.forms) == launched, (mode, p)
+    else:
+        assert plans["lpt"] == plans["default"] == plans["given"]
+        assert [p.order_src for p in plans["default"]] == ["none", "cu_q"]   # key-split forward; the fused backward's own order
     res = {}
     for mode in ("default", "lpt", "given"):
         cu = torch.from_numpy(cu_np).to(device)
@@ -528,6 +570,9 @@ def test_varlen_attention_fewq_stream_bitwise(device, B, max_k, lpt):
     res = {}
     for mode in ("stream", "wg", "stream2"):
         flags = (ops.ATTN_FEWQ_WG if mode == "wg" else 0) | (ops.ATTN_LPT_SHORT if lpt else 0)
+        main = S.Form("bwd_fewq_fused", 0, 4) if mode == "wg" else S.Form("bwd_fewq_stream", 0, 0, 64 if max_k <= 64 else
+                                                                       96 if max_k <= 96 else 128)
+        assert S.call_plans(B, H, hd, 16, max_k, Tq, Tk, False, flags)[1].forms == [S.Form("order")] * lpt + [main]
         with ops.attn_policy(flags):
             qt, kt, vt = (t.clone().requires_grad_(True) for t in (q0, k0, v0))
             out = ops.varlen_attention(qt, kt, vt, cq, ck, H, False, 16, max_k)
