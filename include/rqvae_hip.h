@@ -741,6 +741,28 @@ int rq_codebook_revive(float* const* codebooks, float* const* exp_avg, float* co
                        int64_t D, const int64_t* counts, int64_t min_count, const float* res, int64_t B, uint64_t seed,
                        uint8_t* revived, int64_t* n_revived, void* workspace, size_t ws_bytes, void* stream);
 
+/* Beam-searched residual quantization (extension). The reference encodes greedily: its level loop
+ * (modules/rqvae.py:114-138) keeps one residual per item and takes one argmin per level. This call generalises
+ * that loop to the W best code paths per item, the beam encoder of Faiss's ResidualQuantizer (max_beam_size).
+ * Arguments are rq_quantize_fwd's plus W: x (B, D) fp32; codebooks (L, K, D); cb_sqnorm (L, K) from
+ * rq_codebook_sqnorm. Outputs: paths (B, W, L) int64; err (B, W); residual (B, W, D) or NULL.
+ * The rule: level 0 starts from one beam with residual x. At level l, beam w (residual r_w) and code k have the
+ *   key e(w, k) = (|r_w|^2 + |c_k|^2) - 2 r_w.c_k in fp32 (rq_quantize_fwd's distance expression; |r_w|^2 an
+ *   fp32 sum over the residual, |c_k|^2 from cb_sqnorm, the dot product's summation order free). The W candidates
+ *   with the smallest (e, w, k) in lexicographic order survive, stored in that order (beams are sorted, ties fall
+ *   to the lower beam, then the lower code: deterministic). A survivor's residual is r_w - c_k elementwise in
+ *   fp32 and its path is its parent's extended by k. err[b][w] is the last level's key, residual the last
+ *   level's residual. W = 1 is the greedy rule.
+ * Requires D a power of two in [8, 64] (wider rows are refused, not routed elsewhere), 1 <= K <= 4096,
+ * 1 <= L <= 16, 1 <= W <= min(K, 32), B <= 2^25; x, codebooks and residual 16-byte aligned. One launch, no
+ * allocation, no host sync, graph-capturable, the same bits on every run. workspace: at least
+ * rq_quantize_beam_workspace(B, D, K, L, W) bytes; the present kernel keeps paths and candidate lists in LDS and
+ * recomputes residuals from the paths, so the size is 0 and workspace may then be NULL. */
+size_t rq_quantize_beam_workspace(int64_t B, int64_t D, int64_t K, int64_t L, int64_t W);
+int rq_quantize_beam(const float* x, int64_t B, int64_t D, const float* codebooks, const float* cb_sqnorm, int64_t K,
+                     int64_t L, int64_t W, int64_t* paths, float* err, float* residual, void* workspace, size_t ws_bytes,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,12 @@ class RqVaeOutput(NamedTuple):
     quantize_loss: Tensor   # (B,)
 
 
+class RqVaeBeamOutput(NamedTuple):
+    sem_ids: Tensor         # (B, W, L) int64, beams ascending by error
+    errors: Tensor          # (B, W)
+    residuals: Tensor       # (B, W, D)
+
+
 class RqVaeComputedLosses(NamedTuple):
     loss: Tensor
     reconstruction_loss: Tensor
@@ -147,6 +153,30 @@ class RqVae(nn.Module):
         emb, res, ids, qloss, _ = self.quantize_levels(self.encode(x), gumbel_t)
         return RqVaeOutput(embeddings=emb.permute(1, 2, 0), residuals=res.permute(1, 2, 0), sem_ids=ids,
                            quantize_loss=qloss)
+
+    @torch.no_grad()
+    def get_semantic_id_beams(self, x: Tensor, width: int) -> RqVaeBeamOutput:
+        """The `width` best code paths of every item instead of the greedy one (an extension: beam-searched residual
+        quantization, modules.beam_quantize) -> RqVaeBeamOutput, beams sorted by reconstruction error in the code
+        space; width = 1 is get_semantic_ids' rule. Device tensors run one HIP launch (rqvae_hip.ops.rq_quantize_beam),
+        CPU tensors the torch restatement. Codebooks are used as in eval mode: L2-distance levels whose k-means init
+        is done, and not a training-mode model whose forward mode differs from its eval forward. No gradient."""
+        for layer in self.layers:
+            if layer.distance_mode != QuantizeDistance.L2:
+                raise ValueError("get_semantic_id_beams: needs L2-distance levels")
+            if layer.needs_init():
+                raise ValueError("get_semantic_id_beams: the k-means init of the codebooks is still pending")
+        if any(fused_mode(layer.forward_mode, self.training) != hip_ops.MODE_EVAL for layer in self.layers):
+            raise ValueError("get_semantic_id_beams: the model is in training mode with a non-eval forward mode; "
+                             "call eval() first")
+        codebooks = torch.stack([layer.codebook() for layer in self.layers])
+        res0 = self.encode(x)
+        if res0.is_cuda:
+            paths, err, res = hip_ops.rq_quantize_beam(res0, codebooks, width, with_residuals=True)
+        else:
+            from modules.beam_quantize import beam_quantize_torch
+            paths, err, res = beam_quantize_torch(res0, codebooks, width)
+        return RqVaeBeamOutput(sem_ids=paths, errors=err, residuals=res)
 
     def forward(self, batch: SeqBatch, gumbel_t: float) -> RqVaeComputedLosses:
         # every encoder / decoder GEMM weight split once for the step, in one launch (the fused chains take

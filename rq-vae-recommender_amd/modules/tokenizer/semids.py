@@ -9,6 +9,9 @@ MI355X path:
   * dedup column (`semids.py:84-99`: for each item, the number of EARLIER items with the same
     L-tuple): one stable device sort of packed tuple keys + a segmented rank, O(N log N) instead
     of the reference's O(N^2) all-pairs comparison — identical values;
+  * `precompute_corpus_ids(beam=, resolve_collisions=)` (this build's addition, off by default): ids from the beam
+    encoder (an item's best of `beam` code paths) and, asked to, a colliding item moved to its next-best path
+    (modules/tokenizer/collisions.py) before the dedup column is computed;
   * `exists_prefix`: sorted packed-prefix keys + binary search (torch.searchsorted) instead of
     the O(P x N) broadcast compare. `reference_batching=True` (default) reproduces the reference's
     batching quirk (`math.ceil(n // 16)` skips the last partial batch of 16 prefixes, which then
@@ -127,9 +130,17 @@ class SemanticIdTokenizer(nn.Module):
 
     @torch.no_grad()
     @eval_mode
-    def precompute_corpus_ids(self, movie_dataset, shard: bool = False) -> Tensor:
+    def precompute_corpus_ids(self, movie_dataset, shard: bool = False, beam: int = 1,
+                              resolve_collisions: bool = False) -> Tensor:
         """(N, L+1) corpus ids (semids.py:74-101). `shard=True` (a collective: every rank must call
-        it) splits the quantization over the data-parallel ranks and all-gathers the ids."""
+        it) splits the quantization over the data-parallel ranks and all-gathers the ids.
+        `beam` > 1 (this build's extension) encodes with the beam encoder (RqVae.get_semantic_id_beams): an item's
+        id is its best of `beam` paths instead of the greedy one. `resolve_collisions=True` (needs beam >= 2)
+        moves an item whose path another item already owns to its next-best path
+        (modules.tokenizer.collisions.resolve, on the gathered paths: identical on every rank); the dedup column
+        is computed afterwards as always. The defaults take the greedy code path unchanged."""
+        if beam < 1 or (resolve_collisions and beam < 2):
+            raise ValueError(f"precompute_corpus_ids: need beam >= 1, and beam >= 2 to resolve collisions (beam={beam})")
         dev = self.rq_vae.device
         n = len(movie_dataset)
         lo, hi = dp.shard_range(n, dp.rank(), dp.world()) if shard else (0, n)
@@ -137,10 +148,21 @@ class SemanticIdTokenizer(nn.Module):
         for a in range(lo, hi, CORPUS_BATCH):
             batch = movie_dataset[list(range(a, min(hi, a + CORPUS_BATCH)))]
             x = batch.x.to(dev, non_blocking=True)
-            chunks.append(self.rq_vae.get_semantic_ids(x).sem_ids)
-        ids = torch.cat(chunks, 0) if chunks else torch.zeros((0, self.n_layers), dtype=torch.int64, device=dev)
+            if beam == 1:
+                chunks.append(self.rq_vae.get_semantic_ids(x).sem_ids)
+            else:
+                chunks.append(self.rq_vae.get_semantic_id_beams(x, beam).sem_ids.reshape(x.shape[0], -1))
+        ids = (torch.cat(chunks, 0) if chunks
+               else torch.zeros((0, self.n_layers * beam), dtype=torch.int64, device=dev))
         if shard:
             ids = dp.all_gather_rows(ids, n)
+        if beam > 1:
+            paths = ids.view(n, beam, self.n_layers)
+            if resolve_collisions:
+                from modules.tokenizer import collisions
+                ids = collisions.resolve(paths, self.codebook_size)[0]
+            else:
+                ids = paths[:, 0].contiguous()
         self.cached_ids = torch.cat([ids, dedup_rank(ids).unsqueeze(1)], 1)
         self._prefix_index = {}
         self._trie = None

@@ -112,6 +112,8 @@ _SIGS = {
     "rq_code_usage": ([_P, _I64, _I64, _I64, _P, _P], _I),
     "rq_codebook_revive_workspace": ([_I64, _I64], _SZ),
     "rq_codebook_revive": ([_P, _P, _P, _I64, _I64, _I64, _P, _I64, _P, _I64, _U64, _P, _P, _P, _SZ, _P], _I),
+    "rq_quantize_beam_workspace": ([_I64, _I64, _I64, _I64, _I64], _SZ),
+    "rq_quantize_beam": ([_P, _I64, _I64, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _SZ, _P], _I),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -16,6 +16,7 @@
                                              that lead to an allowed item (beam_expand's allowed=), two launches
   code_usage / codebook_revive               tokenizer health: per-level code histogram added into device counters, one launch;
                                              dead codewords re-seated on data residuals (bit copies, moments zeroed), two launches
+  rq_quantize_beam                           beam-searched residual quantization: the W best code paths per item, one launch
 
 All kernels run on torch's current HIP stream; tensors must be on the GPU (no CPU path).
 """
@@ -2932,3 +2933,51 @@ def codebook_revive(weights, counts: torch.Tensor, res: torch.Tensor, min_count:
     call("rq_codebook_revive", tabs[0], tabs[1], tabs[2], L, K, D, ptr(counts), min_count, ptr(res), B,
          int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(revived), ptr(n_revived), ptr(ws), nbytes, stream_handle(dev))
     return revived.view(torch.bool), n_revived
+
+
+# ------------------------------------------------------------------ beam-searched residual quantization
+BEAM_Q_DIMS, BEAM_Q_MAX_K, BEAM_Q_MAX_L, BEAM_Q_MAX_W = (8, 16, 32, 64), 4096, 16, 32   # rq_quantize_beam's limits
+
+
+def beam_quantize_check_args(D: int, K: int, L: int, width: int, what: str = "rq_quantize_beam") -> None:
+    """The argument limits of rq_quantize_beam (ValueError outside them), shared with
+    modules.beam_quantize.beam_quantize_torch."""
+    if D not in BEAM_Q_DIMS:
+        raise ValueError(f"{what}: D must be a power of two in [8, 64], got {D} (wider rows are not supported)")
+    if not 1 <= K <= BEAM_Q_MAX_K:
+        raise ValueError(f"{what}: need 1 <= K <= {BEAM_Q_MAX_K}, got {K}")
+    if not 1 <= L <= BEAM_Q_MAX_L:
+        raise ValueError(f"{what}: need 1 <= L <= {BEAM_Q_MAX_L}, got {L}")
+    if not 1 <= width <= min(K, BEAM_Q_MAX_W):
+        raise ValueError(f"{what}: need 1 <= width <= min(K, {BEAM_Q_MAX_W}), got width={width}, K={K}")
+
+
+@torch.no_grad()
+def rq_quantize_beam(x: torch.Tensor, codebooks: torch.Tensor, width: int, with_residuals: bool = False):
+    """The `width` best code paths of every row of x (B, D) under codebooks (L, K, D) -> (paths (B, W, L) int64,
+    err (B, W) fp32[, residual (B, W, D) fp32]), beams sorted by err (rq_quantize_beam: one launch for all levels;
+    the rule is stated in include/rqvae_hip.h and restated by modules.beam_quantize.beam_quantize_torch).
+    width = 1 is the greedy rule of rq_quantize in eval mode. No gradient."""
+    what = "rq_quantize_beam"
+    require_gpu(x, codebooks, what=what)
+    if x.dim() != 2 or codebooks.dim() != 3 or x.shape[1] != codebooks.shape[2]:
+        raise ValueError(f"{what}: need x (B, D) and codebooks (L, K, D), got {tuple(x.shape)}, {tuple(codebooks.shape)}")
+    if x.dtype != torch.float32 or codebooks.dtype != torch.float32:
+        raise ValueError(f"{what}: fp32 only, got {x.dtype}, {codebooks.dtype}")
+    if codebooks.device != x.device:
+        raise RqHipError(f"{what}: x and codebooks must be on one device, got {x.device}, {codebooks.device}")
+    x, cbs = x.detach().contiguous(), codebooks.detach().contiguous()
+    (B, D), (L, K, _), W = x.shape, cbs.shape, int(width)
+    beam_quantize_check_args(D, K, L, W, what)
+    dev = x.device
+    s = stream_handle(dev)
+    csq = torch.empty((L, K), device=dev, dtype=torch.float32)
+    call("rq_codebook_sqnorm", ptr(cbs), L * K, D, ptr(csq), s)
+    paths = torch.empty((B, W, L), device=dev, dtype=torch.int64)
+    err = torch.empty((B, W), device=dev, dtype=torch.float32)
+    res = torch.empty((B, W, D), device=dev, dtype=torch.float32) if with_residuals else None
+    nbytes = _lib.load().rq_quantize_beam_workspace(B, D, K, L, W)
+    ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8) if nbytes else None
+    TIMER.around("rq_quantize_beam", call, "rq_quantize_beam", ptr(x), B, D, ptr(cbs), ptr(csq), K, L, W, ptr(paths),
+                 ptr(err), ptr(res), ptr(ws), nbytes, s)
+    return (paths, err, res) if with_residuals else (paths, err)

@@ -135,6 +135,11 @@ EVAL_EXCLUDE_SEEN = False
 # same negatives every pass, torch's global generators untouched) plus the next item with model.score_items and adds
 # neg{N}_recall@k / neg{N}_ndcg@k / neg{N}_mrr@k of the next item's rank among the N + 1. 0: off. Opt-in.
 EVAL_SAMPLED_NEGATIVES = 0
+# Corpus ids from the beam encoder (SemanticIdTokenizer.precompute_corpus_ids(beam=, resolve_collisions=)):
+# an item's id is the best of TOKENIZER_BEAM code paths, and with TOKENIZER_RESOLVE_COLLISIONS (needs a beam >= 2) an
+# item whose path is taken moves to its next-best one. The defaults are the reference's greedy ids. Opt-in.
+TOKENIZER_BEAM = 1
+TOKENIZER_RESOLVE_COLLISIONS = False
 
 
 class _Evaluator:
@@ -296,7 +301,9 @@ def train(iterations=500000, batch_size=64, learning_rate=0.001, weight_decay=0.
                                     codebook_size=vae_codebook_size, n_layers=vae_n_layers, n_cat_feats=vae_n_cat_feats,
                                     rqvae_weights_path=pretrained_rqvae_path,
                                     rqvae_codebook_normalize=vae_codebook_normalize, rqvae_sim_vq=vae_sim_vq).to(device)
-    corpus_ids = tokenizer.precompute_corpus_ids(item_ds, shard=True)   # not DDP-wrapped (reference A-7)
+    # not DDP-wrapped (reference A-7)
+    corpus_ids = tokenizer.precompute_corpus_ids(item_ds, shard=True, beam=TOKENIZER_BEAM,
+                                                 resolve_collisions=TOKENIZER_RESOLVE_COLLISIONS)
     top = int(corpus_ids.max())
     if top >= vae_codebook_size:   # would index past the SemIdEmbedder table on the device
         raise ValueError(f"semantic id / dedup value {top} >= codebook size {vae_codebook_size}: the tokenizer's "
