@@ -65,13 +65,52 @@ int rq_quantize_fwd(const float* x, int64_t B, int64_t D, const float* codebooks
  * (g_emb_sum, (B,D) or NULL), of residuals (g_res, (L,B,D) or NULL) and of qloss (g_qloss,
  * (B,) or NULL). Writes grad_x (B,D) and grad_codebooks (L,K,D) (every element written).
  * The codebook gradient is reduced in ascending row order per codeword (stable counting
- * sort + segmented sum): bitwise deterministic. K <= 4096.
+ * sort + segmented sum): bitwise deterministic. K <= 4096. An empty batch (B == 0) may come with NULL
+ * residuals / ids / grad_x, as rq_quantize_fwd's may: grad_codebooks is zeroed.
  * workspace: device scratch of at least rq_quantize_bwd_workspace(B,D,K,L) bytes. */
 size_t rq_quantize_bwd_workspace(int64_t B, int64_t D, int64_t K, int64_t L);
 int rq_quantize_bwd(const float* residuals, const int64_t* ids, const float* codebooks, int64_t B, int64_t D, int64_t K,
                     int64_t L, int mode, float beta, const float* g_emb, const float* g_emb_sum, const float* g_res,
                     const float* g_qloss, float* grad_x, float* grad_codebooks, void* workspace, size_t ws_bytes,
                     void* stream);
+
+/* The kernel form rq_quantize_fwd / rq_quantize_bwd launch for a shape: the same decision function the
+ * launches go through, on the host, without a launch, an allocation or a device access. Tests use it to
+ * ask which instantiation a shape reaches instead of restating the thresholds.
+ * Forward: impl as rq_quantize_fwd's (0 = auto); with_norms != 0 stands for a non-NULL emb_norms. The
+ * refusals are rq_quantize_fwd's shape refusals (D, K, L, B, mode, impl against D and K). B == 0: no launch,
+ * every field 0. */
+typedef struct rq_quantize_fwd_form {
+  int impl;        /* the resolved kernel family: 1 tiled, 2 register, 3 split, 4 register 16x16; 0 = no launch */
+  int d;           /* the family's D instantiation (16x16: 64) */
+  int resident;    /* register: 1 = a level's codebook is one LDS image, 0 = streamed in images of nb rows */
+  int wpi;         /* register: waves per 32-item tile (4, 2 or 1); 0 elsewhere */
+  int nb;          /* register: codewords per LDS image; 0 elsewhere */
+  int norms_pass;  /* 1 = emb_norms come from one rq_row_norms pass after the kernel (every family but 16x16) */
+  int items;       /* items per workgroup of the (first) launch */
+  unsigned grid;   /* its workgroups */
+  int64_t lds_bytes;  /* its dynamic LDS */
+} rq_quantize_fwd_form;
+int rq_quantize_fwd_plan(int64_t B, int64_t D, int64_t K, int64_t L, int mode, int impl, int with_norms,
+                         rq_quantize_fwd_form* form);
+/* Backward: has_g_qloss != 0 stands for a non-NULL g_qloss. rq_bwd_rows_kernel<lpi, epl>, then the codebook
+ * gradient by the chunk route (rq_cb_chunk_kernel<vpl> over chunks row chunks) or the sort route
+ * (rq_cb_segsum_kernel: contrib = 1 sums the rows kernel's contributions (eval), 0 rebuilds 2 gl (e - x)
+ * from the residuals; whether a codeword's segment is reduced directly or in partials depends on the ids). */
+#define RQ_QUANTIZE_CB_NONE 0   /* B == 0: grad_codebooks zeroed, no kernel */
+#define RQ_QUANTIZE_CB_CHUNK 1
+#define RQ_QUANTIZE_CB_SORT 2
+typedef struct rq_quantize_bwd_form {
+  int lpi, epl;    /* rq_bwd_rows_kernel's lanes per item and elements per lane (0 when B == 0) */
+  int route;       /* RQ_QUANTIZE_CB_* */
+  int vpl;         /* chunk route: D / 64; 0 otherwise */
+  int chunks;      /* chunk route: row chunks per level; 0 otherwise */
+  int contrib;     /* sort route: 1 = contrib form, 0 = recompute form */
+  int seg_direct;  /* sort route: the longest segment reduced by one workgroup */
+  int seg_split;   /* sort route: partials of a longer one */
+} rq_quantize_bwd_form;
+int rq_quantize_bwd_plan(int64_t B, int64_t D, int64_t K, int64_t L, int mode, int has_g_qloss,
+                         rq_quantize_bwd_form* form);
 
 /* Deterministic segmented sum: out[k] = sum of rows[b] (B, D) over b with keys[b] == k (int64, in
  * [0, K)), reduced in a fixed order; counts[k] = #rows (or NULL). Used by the k-means codebook

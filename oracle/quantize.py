@@ -126,9 +126,10 @@ def rq_fwd(res0, codebooks, mode, beta=0.25):
     return dict(ids=np.stack(ids, 1), emb=np.stack(embs), res=np.stack(ress), qloss=qloss, auxs=auxs)
 
 
-def rq_bwd(fwd, codebooks, mode, g_emb_sum=None, g_emb=None, g_qloss=None, beta=0.25):
+def rq_bwd(fwd, codebooks, mode, g_emb_sum=None, g_emb=None, g_qloss=None, beta=0.25, g_res=None):
     """VJP of rq_fwd wrt (res0, codebooks). g_emb_sum: grad of sum_l emb_out_l (B,D);
-    g_emb: per-level grads (L,B,D); g_qloss: grad of the summed quantize loss (B,)."""
+    g_emb: per-level grads (L,B,D); g_qloss: grad of the summed quantize loss (B,);
+    g_res: grads of the residuals output (L,B,D), res_l being the input of level l."""
     L, B, D = fwd["res"].shape
     K = codebooks.shape[1]
     g_next = np.zeros((B, D), F32)
@@ -144,6 +145,8 @@ def rq_bwd(fwd, codebooks, mode, g_emb_sum=None, g_emb=None, g_qloss=None, beta=
         gx, gc = level_bwd(fwd["res"][l], fwd["ids"][:, l], K, mode, fwd["auxs"][l], g_out, gl, beta)
         gcb[l] = gc
         g_next = (g_next + gx).astype(F32)
+        if g_res is not None:
+            g_next = (g_next + g_res[l].astype(F32)).astype(F32)
     return g_next, gcb
 
 

@@ -697,8 +697,8 @@ __global__ void __launch_bounds__(256) rq_cb_chunk_reduce_kernel(const float* __
   *reinterpret_cast<float4*>(grad_cb + (int64_t)l * KD + j) = r;
 }
 
-static bool cb_chunk_path(int64_t B, int64_t D, int64_t K, int mode, const float* g_qloss) {
-  return mode != kEval && g_qloss && (D == 64 || D == 128 || D == 256) && K * D <= 16384 && B >= 4 * kCbRows;
+static bool cb_chunk_path(int64_t B, int64_t D, int64_t K, int mode, bool has_g_qloss) {
+  return mode != kEval && has_g_qloss && (D == 64 || D == 128 || D == 256) && K * D <= 16384 && B >= 4 * kCbRows;
 }
 static int64_t cb_chunks(int64_t B) { return (B + kCbRows - 1) / kCbRows; }
 
@@ -1192,29 +1192,47 @@ rq_fwd_r16_kernel(const float* __restrict__ x, int B, const float* __restrict__ 
   }
 }
 
-static int launch_fwd_r16(int B, hipStream_t s, const float* x, const float* cbs, const float* csq, int K, int L,
-                          int mode, float beta, int64_t* ids, float* eo, float* res, float* ql, float* es,
-                          float* enorm) {
+static void r16_form(int B, int K, rq_quantize_fwd_form& f) {
   const int KP = (K + 31) & ~31;
-  const size_t lds = (size_t)KP * (64 + 1) * sizeof(float);
-  hipLaunchKernelGGL(rq_fwd_r16_kernel, dim3((B + kR16Items - 1) / kR16Items), dim3(512), lds, s, x, B, cbs, csq, K, L,
+  f.lds_bytes = (int64_t)KP * (64 + 1) * sizeof(float);
+  f.items = kR16Items;
+  f.grid = (unsigned)((B + kR16Items - 1) / kR16Items);
+}
+
+static int launch_fwd_r16(const rq_quantize_fwd_form& f, int B, hipStream_t s, const float* x, const float* cbs,
+                          const float* csq, int K, int L, int mode, float beta, int64_t* ids, float* eo, float* res,
+                          float* ql, float* es, float* enorm) {
+  hipLaunchKernelGGL(rq_fwd_r16_kernel, dim3(f.grid), dim3(512), (size_t)f.lds_bytes, s, x, B, cbs, csq, K, L,
                      mode, beta, ids, eo, res, ql, es, enorm);
   return 0;
 }
 
-template <int D, int WPI>
-static void launch_fwd_reg_w(int B, hipStream_t s, const float* x, const float* cbs, const float* csq, int K, int L,
-                             int mode, float beta, int64_t* ids, float* eo, float* res, float* ql, float* es) {
-  constexpr int LD = D + 4;
+// The register kernel's form for (B, D, K): resident or streamed image, its rows and bytes, waves per item tile.
+static void reg_form(int B, int D, int K, rq_quantize_fwd_form& f) {
+  const int LD = D + 4;
   constexpr int kMaxLds = 75 * 1024;              // two workgroups per CU
   const int fit = (kMaxLds - 1024) / ((LD + 1) * 4);
   const bool resident = (K + 31) / 32 * 32 <= fit;
   const int NB = resident ? K : (fit / 32) * 32;
   const int LDk = (resident && D == 64) ? D : LD;   // swizzled unpadded image (kernel's SWZ)
+  f.resident = resident ? 1 : 0;
+  f.nb = NB;
   // rows / |c|^2 entries up to the next multiple of 32 are read (|c|^2 = +inf) by the last tile
-  const size_t lds = (size_t)((NB + 31) / 32 * 32) * (LDk + 1) * sizeof(float) + 1024;
-  dim3 g((B + 128 / WPI - 1) / (128 / WPI));
-  if (resident)
+  f.lds_bytes = (int64_t)((NB + 31) / 32 * 32) * (LDk + 1) * sizeof(float) + 1024;
+  // fewer 128-item workgroups than CUs: let 2 or 4 waves split each 32-item tile's codewords
+  f.wpi = B <= 256 * 32 ? 4 : B <= 256 * 128 ? 2 : 1;
+  f.items = 128 / f.wpi;
+  f.grid = (unsigned)((B + f.items - 1) / f.items);
+}
+
+template <int D, int WPI>
+static void launch_fwd_reg_w(const rq_quantize_fwd_form& f, int B, hipStream_t s, const float* x, const float* cbs,
+                             const float* csq, int K, int L, int mode, float beta, int64_t* ids, float* eo, float* res,
+                             float* ql, float* es) {
+  const int NB = f.nb;
+  const size_t lds = (size_t)f.lds_bytes;
+  dim3 g(f.grid);
+  if (f.resident)
     hipLaunchKernelGGL((rq_fwd_reg_kernel<D, true, WPI>), g, dim3(256), lds, s, x, B, cbs, csq, K, L, mode, beta, NB,
                        ids, eo, res, ql, es);
   else
@@ -1223,15 +1241,15 @@ static void launch_fwd_reg_w(int B, hipStream_t s, const float* x, const float* 
 }
 
 template <int D>
-static void launch_fwd_reg(int B, hipStream_t s, const float* x, const float* cbs, const float* csq, int K, int L,
-                           int mode, float beta, int64_t* ids, float* eo, float* res, float* ql, float* es) {
-  // fewer 128-item workgroups than CUs: let 2 or 4 waves split each 32-item tile's codewords
-  if (B <= 256 * 32)
-    launch_fwd_reg_w<D, 4>(B, s, x, cbs, csq, K, L, mode, beta, ids, eo, res, ql, es);
-  else if (B <= 256 * 128)
-    launch_fwd_reg_w<D, 2>(B, s, x, cbs, csq, K, L, mode, beta, ids, eo, res, ql, es);
+static void launch_fwd_reg(const rq_quantize_fwd_form& f, int B, hipStream_t s, const float* x, const float* cbs,
+                           const float* csq, int K, int L, int mode, float beta, int64_t* ids, float* eo, float* res,
+                           float* ql, float* es) {
+  if (f.wpi == 4)
+    launch_fwd_reg_w<D, 4>(f, B, s, x, cbs, csq, K, L, mode, beta, ids, eo, res, ql, es);
+  else if (f.wpi == 2)
+    launch_fwd_reg_w<D, 2>(f, B, s, x, cbs, csq, K, L, mode, beta, ids, eo, res, ql, es);
   else
-    launch_fwd_reg_w<D, 1>(B, s, x, cbs, csq, K, L, mode, beta, ids, eo, res, ql, es);
+    launch_fwd_reg_w<D, 1>(f, B, s, x, cbs, csq, K, L, mode, beta, ids, eo, res, ql, es);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1580,50 +1598,72 @@ int rq_codebook_sqnorm(const float* rows, int64_t n, int64_t D, float* out, void
   return 0;
 }
 
-static int quantize_fwd(const float* x, int64_t B, int64_t D, const float* codebooks, const float* cb_sqnorm,
-                        int64_t K, int64_t L, int mode, float beta, int64_t* ids, float* emb_out, float* residuals,
-                        float* qloss, float* emb_sum, int impl, float* emb_norms, void* stream);
-
-int rq_quantize_fwd(const float* x, int64_t B, int64_t D, const float* codebooks, const float* cb_sqnorm, int64_t K,
-                    int64_t L, int mode, float beta, int64_t* ids, float* emb_out, float* residuals, float* qloss,
-                    float* emb_sum, float* emb_norms, int impl, void* stream) {
-  return quantize_fwd(x, B, D, codebooks, cb_sqnorm, K, L, mode, beta, ids, emb_out, residuals, qloss, emb_sum, impl,
-                      emb_norms, stream);
-}
-
-static int quantize_fwd(const float* x, int64_t B, int64_t D, const float* codebooks, const float* cb_sqnorm,
-                        int64_t K, int64_t L, int mode, float beta, int64_t* ids, float* emb_out, float* residuals,
-                        float* qloss, float* emb_sum, int impl, float* emb_norms, void* stream) {
+// The forward's form for a shape: every shape refusal of rq_quantize_fwd and the choice of kernel family and
+// instantiation. rq_quantize_fwd launches from it; rq_quantize_fwd_plan returns it.
+static int quantize_fwd_form(int64_t B, int64_t D, int64_t K, int64_t L, int mode, int impl, bool with_norms,
+                             rq_quantize_fwd_form& f) {
   int lpi, epl;
-  RQ_CHECK_ARG(codebooks && cb_sqnorm && (B == 0 || (x && ids && emb_out && residuals && qloss)),
-               "rq_quantize_fwd: null pointer");   // an empty batch may come as NULL buffers
+  f = rq_quantize_fwd_form{};
   RQ_CHECK_ARG(row_split((int)D, lpi, epl), "rq_quantize_fwd: D=%lld must be a power of two in [8, 1024]", (long long)D);
   RQ_CHECK_ARG(K >= 1 && K <= (1 << 20) && L >= 1 && L <= 64, "rq_quantize_fwd: bad K=%lld / L=%lld", (long long)K,
                (long long)L);
   RQ_CHECK_ARG(B >= 0 && B < (1ll << 31) && B * D < (1ll << 40), "rq_quantize_fwd: bad B=%lld", (long long)B);
   RQ_CHECK_ARG(mode == kEval || mode == kSte || mode == kRotation, "rq_quantize_fwd: mode %d has no fused kernel", mode);
   if (B == 0) return 0;
-  hipStream_t s = (hipStream_t)stream;
-  dim3 g((unsigned)((B + kTB - 1) / kTB));
-  const int b = (int)B, d = (int)D, k = (int)K, l = (int)L;
   RQ_CHECK_ARG(impl >= 0 && impl <= 4,
                "rq_quantize_fwd: impl must be 0 (auto), 1 (tiled), 2 (register), 3 (split) or 4 (register 16x16)");
   const bool split_ok = D >= 128 && 2 * ((K + kSN - 1) / kSN) + 1 <= D;
   const bool r16_ok = D == 64 && K <= 288;   // two 65 * K * 4-byte images per CU
   if (impl == 0) impl = (r16_ok && B >= 32768) ? 4 : D <= 64 ? 2 : (split_ok ? 3 : 1);
   RQ_CHECK_ARG(impl != 4 || r16_ok, "rq_quantize_fwd: 16x16 register kernel needs D == 64 and K <= 288");
-  if (emb_norms != nullptr && impl != 4) {   // only the 16x16 kernel fuses the norms: one extra row pass otherwise
-    const int rc = quantize_fwd(x, B, D, codebooks, cb_sqnorm, K, L, mode, beta, ids, emb_out, residuals, qloss,
-                                emb_sum, impl, nullptr, stream);
-    return rc != 0 ? rc : rq_row_norms(emb_out, L * B, D, emb_norms, stream);
+  RQ_CHECK_ARG(impl != 2 || D <= 64, "rq_quantize_fwd_impl: register kernel needs D <= 64");
+  RQ_CHECK_ARG(impl != 3 || split_ok, "rq_quantize_fwd_impl: split path needs D >= 128 and 2*ceil(K/128)+1 <= D");
+  f.impl = impl;
+  f.d = (int)D;
+  f.norms_pass = (with_norms && impl != 4) ? 1 : 0;   // only the 16x16 kernel fuses the norms: one extra row pass otherwise
+  if (impl == 4) {
+    r16_form((int)B, (int)K, f);
+  } else if (impl == 2) {
+    reg_form((int)B, (int)D, (int)K, f);
+  } else if (impl == 3) {
+    f.items = 4 * (64 / lpi);   // rq_split_prep_kernel / rq_level_epi_kernel; the distance GEMM runs 128 x 128 tiles
+    f.grid = (unsigned)((B + f.items - 1) / f.items);
+  } else {
+    f.items = kTB;
+    f.grid = (unsigned)((B + kTB - 1) / kTB);
+  }
+  return 0;
+}
+
+int rq_quantize_fwd_plan(int64_t B, int64_t D, int64_t K, int64_t L, int mode, int impl, int with_norms,
+                         rq_quantize_fwd_form* form) {
+  RQ_CHECK_ARG(form != nullptr, "rq_quantize_fwd_plan: null form");
+  return quantize_fwd_form(B, D, K, L, mode, impl, with_norms != 0, *form);
+}
+
+int rq_quantize_fwd(const float* x, int64_t B, int64_t D, const float* codebooks, const float* cb_sqnorm, int64_t K,
+                    int64_t L, int mode, float beta, int64_t* ids, float* emb_out, float* residuals, float* qloss,
+                    float* emb_sum, float* emb_norms, int impl, void* stream) {
+  RQ_CHECK_ARG(codebooks && cb_sqnorm && (B == 0 || (x && ids && emb_out && residuals && qloss)),
+               "rq_quantize_fwd: null pointer");   // an empty batch may come as NULL buffers
+  rq_quantize_fwd_form f;
+  const int rc = quantize_fwd_form(B, D, K, L, mode, impl, emb_norms != nullptr, f);
+  if (rc != 0) return rc;
+  if (B == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  dim3 g(f.grid);
+  const int b = (int)B, d = (int)D, k = (int)K, l = (int)L;
+  impl = f.impl;
+  if (f.norms_pass) {
+    const int rf = rq_quantize_fwd(x, B, D, codebooks, cb_sqnorm, K, L, mode, beta, ids, emb_out, residuals, qloss,
+                                   emb_sum, nullptr, impl, stream);
+    return rf != 0 ? rf : rq_row_norms(emb_out, L * B, D, emb_norms, stream);
   }
   if (impl == 4) {
-    launch_fwd_r16(b, s, x, codebooks, cb_sqnorm, k, l, mode, beta, ids, emb_out, residuals, qloss, emb_sum, emb_norms);
+    launch_fwd_r16(f, b, s, x, codebooks, cb_sqnorm, k, l, mode, beta, ids, emb_out, residuals, qloss, emb_sum, emb_norms);
     RQ_LAUNCH_CHECK("rq_quantize_fwd(register 16x16)");
     return 0;
   }
-  RQ_CHECK_ARG(impl != 2 || D <= 64, "rq_quantize_fwd_impl: register kernel needs D <= 64");
-  RQ_CHECK_ARG(impl != 3 || split_ok, "rq_quantize_fwd_impl: split path needs D >= 128 and 2*ceil(K/128)+1 <= D");
   if (impl == 3) {
     switch (D) {
 #define RQ_SPLIT_CASE(DD, LPI, EPL) \
@@ -1639,10 +1679,10 @@ static int quantize_fwd(const float* x, int64_t B, int64_t D, const float* codeb
   }
   if (impl == 2) {
     switch (D) {
-      case 8: launch_fwd_reg<8>(b, s, x, codebooks, cb_sqnorm, k, l, mode, beta, ids, emb_out, residuals, qloss, emb_sum); break;
-      case 16: launch_fwd_reg<16>(b, s, x, codebooks, cb_sqnorm, k, l, mode, beta, ids, emb_out, residuals, qloss, emb_sum); break;
-      case 32: launch_fwd_reg<32>(b, s, x, codebooks, cb_sqnorm, k, l, mode, beta, ids, emb_out, residuals, qloss, emb_sum); break;
-      case 64: launch_fwd_reg<64>(b, s, x, codebooks, cb_sqnorm, k, l, mode, beta, ids, emb_out, residuals, qloss, emb_sum); break;
+      case 8: launch_fwd_reg<8>(f, b, s, x, codebooks, cb_sqnorm, k, l, mode, beta, ids, emb_out, residuals, qloss, emb_sum); break;
+      case 16: launch_fwd_reg<16>(f, b, s, x, codebooks, cb_sqnorm, k, l, mode, beta, ids, emb_out, residuals, qloss, emb_sum); break;
+      case 32: launch_fwd_reg<32>(f, b, s, x, codebooks, cb_sqnorm, k, l, mode, beta, ids, emb_out, residuals, qloss, emb_sum); break;
+      case 64: launch_fwd_reg<64>(f, b, s, x, codebooks, cb_sqnorm, k, l, mode, beta, ids, emb_out, residuals, qloss, emb_sum); break;
     }
     RQ_LAUNCH_CHECK("rq_quantize_fwd(register)");
     return 0;
@@ -1678,16 +1718,47 @@ size_t rq_quantize_bwd_workspace(int64_t B, int64_t D, int64_t K, int64_t L) {
   return std::max(bytes + 256, chunk_bytes);
 }
 
-int rq_quantize_bwd(const float* residuals, const int64_t* ids, const float* codebooks, int64_t B, int64_t D, int64_t K,
-                    int64_t L, int mode, float beta, const float* g_emb, const float* g_emb_sum, const float* g_res,
-                    const float* g_qloss, float* grad_x, float* grad_codebooks, void* workspace, size_t ws_bytes,
-                    void* stream) {
+// The backward's form for a shape: rq_quantize_bwd's shape refusals, the rows kernel's split of a row over lanes and
+// the codebook gradient's route. rq_quantize_bwd launches from it; rq_quantize_bwd_plan returns it.
+static int quantize_bwd_form(int64_t B, int64_t D, int64_t K, int64_t L, int mode, bool has_g_qloss,
+                             rq_quantize_bwd_form& f) {
   int lpi, epl;
-  RQ_CHECK_ARG(residuals && ids && codebooks && grad_x && grad_codebooks, "rq_quantize_bwd: null pointer");
+  f = rq_quantize_bwd_form{};
   RQ_CHECK_ARG(row_split((int)D, lpi, epl), "rq_quantize_bwd: D=%lld must be a power of two in [8, 1024]", (long long)D);
   RQ_CHECK_ARG(K >= 1 && K <= 4096 && L >= 1 && L <= 64, "rq_quantize_bwd: bad K/L");
   RQ_CHECK_ARG(mode == kEval || mode == kSte || mode == kRotation, "rq_quantize_bwd: bad mode %d", mode);
   RQ_CHECK_ARG(B >= 0 && B < (1ll << 31), "rq_quantize_bwd: bad B");
+  if (B == 0) return 0;
+  f.lpi = lpi;
+  f.epl = epl;
+  if (cb_chunk_path(B, D, K, mode, has_g_qloss)) {
+    f.route = RQ_QUANTIZE_CB_CHUNK;
+    f.vpl = (int)(D / 64);
+    f.chunks = (int)cb_chunks(B);
+  } else {
+    f.route = RQ_QUANTIZE_CB_SORT;
+    f.contrib = mode == kEval ? 1 : 0;
+    f.seg_direct = kSegDirect;
+    f.seg_split = kSegSplit;
+  }
+  return 0;
+}
+
+int rq_quantize_bwd_plan(int64_t B, int64_t D, int64_t K, int64_t L, int mode, int has_g_qloss,
+                         rq_quantize_bwd_form* form) {
+  RQ_CHECK_ARG(form != nullptr, "rq_quantize_bwd_plan: null form");
+  return quantize_bwd_form(B, D, K, L, mode, has_g_qloss != 0, *form);
+}
+
+int rq_quantize_bwd(const float* residuals, const int64_t* ids, const float* codebooks, int64_t B, int64_t D, int64_t K,
+                    int64_t L, int mode, float beta, const float* g_emb, const float* g_emb_sum, const float* g_res,
+                    const float* g_qloss, float* grad_x, float* grad_codebooks, void* workspace, size_t ws_bytes,
+                    void* stream) {
+  RQ_CHECK_ARG(codebooks && grad_codebooks && (B == 0 || (residuals && ids && grad_x)),
+               "rq_quantize_bwd: null pointer");   // an empty batch may come as NULL buffers
+  rq_quantize_bwd_form f;
+  const int rc = quantize_bwd_form(B, D, K, L, mode, g_qloss != nullptr, f);
+  if (rc != 0) return rc;
   RQ_CHECK_ARG(workspace && ws_bytes >= rq_quantize_bwd_workspace(B, D, K, L), "rq_quantize_bwd: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   const int b = (int)B, d = (int)D, k = (int)K, l = (int)L;
@@ -1704,7 +1775,7 @@ int rq_quantize_bwd(const float* residuals, const int64_t* ids, const float* cod
   }
   switch (D) {
 #define RQ_BWD_CASE(DD, LPI, EPL) \
-  case DD: launch_bwd<LPI, EPL>(b, s, residuals, ids, codebooks, d, k, l, mode, beta, g_emb, g_emb_sum, g_res, g_qloss, grad_x, mode == kEval ? contrib : nullptr); break;
+  case DD: launch_bwd<LPI, EPL>(b, s, residuals, ids, codebooks, d, k, l, mode, beta, g_emb, g_emb_sum, g_res, g_qloss, grad_x, f.contrib ? contrib : nullptr); break;
     RQ_BWD_CASE(8, 2, 4)
     RQ_BWD_CASE(16, 4, 4)
     RQ_BWD_CASE(32, 8, 4)
@@ -1717,13 +1788,13 @@ int rq_quantize_bwd(const float* residuals, const int64_t* ids, const float* cod
     default: RQ_CHECK_ARG(false, "rq_quantize_bwd: unsupported D");
   }
   RQ_LAUNCH_CHECK("rq_bwd_rows");
-  if (cb_chunk_path(B, D, K, mode, g_qloss)) {
+  if (f.route == RQ_QUANTIZE_CB_CHUNK) {
     float* partial = (float*)(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
-    const int nchunk = (int)cb_chunks(B);
+    const int nchunk = f.chunks;
     const size_t lds = (size_t)K * D * sizeof(float) + kCbRows * sizeof(int) + kCbWaves * kCbList * sizeof(unsigned short);
-    switch (D) {
-      case 64: hipLaunchKernelGGL(rq_cb_chunk_kernel<1>, dim3(nchunk, l), dim3(64 * kCbWaves), lds, s, residuals, codebooks, g_qloss, ids, b, k, l, partial); break;
-      case 128: hipLaunchKernelGGL(rq_cb_chunk_kernel<2>, dim3(nchunk, l), dim3(64 * kCbWaves), lds, s, residuals, codebooks, g_qloss, ids, b, k, l, partial); break;
+    switch (f.vpl) {
+      case 1: hipLaunchKernelGGL(rq_cb_chunk_kernel<1>, dim3(nchunk, l), dim3(64 * kCbWaves), lds, s, residuals, codebooks, g_qloss, ids, b, k, l, partial); break;
+      case 2: hipLaunchKernelGGL(rq_cb_chunk_kernel<2>, dim3(nchunk, l), dim3(64 * kCbWaves), lds, s, residuals, codebooks, g_qloss, ids, b, k, l, partial); break;
       default: hipLaunchKernelGGL(rq_cb_chunk_kernel<4>, dim3(nchunk, l), dim3(64 * kCbWaves), lds, s, residuals, codebooks, g_qloss, ids, b, k, l, partial); break;
     }
     const int64_t KD = K * D;
@@ -1738,7 +1809,7 @@ int rq_quantize_bwd(const float* residuals, const int64_t* ids, const float* cod
   hipLaunchKernelGGL(sort_scatter_kernel, dim3(nblk, l), dim3(256), (2 * k + kSortRows) * sizeof(int), s, ids, b, l, k,
                      nblk, hist, key_off, perm);
   hipLaunchKernelGGL(rq_cb_segsum_kernel, dim3(k, kSegSplit, l), dim3(256), 0, s, residuals, codebooks, g_qloss,
-                     mode == kEval ? contrib : nullptr, perm, key_off, b, d, k, grad_codebooks, segs);
+                     f.contrib ? contrib : nullptr, perm, key_off, b, d, k, grad_codebooks, segs);
   hipLaunchKernelGGL(rq_segsum_finalize_kernel, dim3(k, l), dim3(256), 0, s, key_off, d, k, segs, grad_codebooks);
   RQ_LAUNCH_CHECK("rq_codebook_grad");
   return 0;

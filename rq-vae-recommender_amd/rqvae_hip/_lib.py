@@ -29,6 +29,8 @@ _SIGS = {
     "rq_quantize_fwd": ([_P, _I64, _I64, _P, _P, _I64, _I64, _I, _F, _P, _P, _P, _P, _P, _P, _I, _P], _I),
     "rq_quantize_bwd_workspace": ([_I64, _I64, _I64, _I64], _SZ),
     "rq_quantize_bwd": ([_P, _P, _P, _I64, _I64, _I64, _I64, _I, _F, _P, _P, _P, _P, _P, _P, _P, _SZ, _P], _I),
+    "rq_quantize_fwd_plan": ([_I64, _I64, _I64, _I64, _I, _I, _I, _P], _I),
+    "rq_quantize_bwd_plan": ([_I64, _I64, _I64, _I64, _I, _I, _P], _I),
     "rq_segment_sum_workspace": ([_I64, _I64], _SZ),
     "rq_segment_sum": ([_P, _P, _I64, _I64, _I64, _P, _P, _P, _SZ, _P], _I),
     "rq_rmsnorm_fwd": ([_P, _P, _I64, _I64, _F, _P, _P, _P], _I),
@@ -130,6 +132,19 @@ class AttnPlan(ctypes.Structure):
     _fields_ = [("n_launches", _I), ("qsplit", _I), ("order_src", _I), ("reserved", _I), ("ws_total", _I64),
                 ("ws_need", _I64), ("order_off", _I64), ("part_off", _I64), ("kvpart_off", _I64),
                 ("launch", AttnLaunch * 6)]
+
+
+class QuantizeFwdForm(ctypes.Structure):
+    """rq_quantize_fwd_form (include/rqvae_hip.h): pass ctypes.byref(QuantizeFwdForm()) to rq_quantize_fwd_plan."""
+    _fields_ = [("impl", _I), ("d", _I), ("resident", _I), ("wpi", _I), ("nb", _I), ("norms_pass", _I), ("items", _I),
+                ("grid", ctypes.c_uint), ("lds_bytes", _I64)]
+
+
+class QuantizeBwdForm(ctypes.Structure):
+    """rq_quantize_bwd_form (include/rqvae_hip.h): pass ctypes.byref(QuantizeBwdForm()) to rq_quantize_bwd_plan."""
+    _fields_ = [("lpi", _I), ("epl", _I), ("route", _I), ("vpl", _I), ("chunks", _I), ("contrib", _I),
+                ("seg_direct", _I), ("seg_split", _I)]
+
 
 _lib = None
 
