@@ -289,6 +289,12 @@ int rq_gemm_bf16x3_pair(const rq_gemm_desc* d, int* splits, void* stream);
 int rq_gemm_bf16x3_plan(const rq_gemm_desc* d, int* splits);
 /* 1 when rq_gemm_bf16x3_pair would run d[0], d[1] in one launch (host-only planning), else 0. */
 int rq_gemm_bf16x3_pair_plan(const rq_gemm_desc* d);
+/* Host-only planning for a Linear's backward pair, d[0] its data gradient and d[1] its weight gradient: the
+ * split-K count that balances the weight gradient's workgroups with the data gradient's in the paired launch
+ * (k chunks as long as the data gradient's K), which the caller adopts as RQ_GEMM_SPLIT(count) on d[1]; 0 = keep
+ * the weight gradient's own plan. rq_gemm_bf16x3_pair never applies it itself: its results stay those of two
+ * rq_gemm_bf16x3_run calls. */
+int rq_gemm_bf16x3_pair_resplit(const rq_gemm_desc* d);
 /* `count` (1..8) independent calls, the weight gradients dW = g^T x of one MLP chain (modules/encoder.py:7-36:
  * autograd's grad_weight of each nn.Linear). Members that carry an explicit split count (RQ_GEMM_SPLIT(S),
  * S >= 2) and have split m/n-contiguous operands, the plain epilogue, ldc == N, K % 32 == 0 and no other kernel

@@ -18,11 +18,10 @@
 // Workgroups that share a row chunk are placed on the same XCD (blockIdx % 8 selects the XCD)
 // so the tiles re-reading the same g / x rows hit one L2.
 #include "common.h"
+#include "gemm_plan.h"   // the tile constants (kWT, kWBK, kXT, kXK, kWT2, ...), the epilogue codes and every plan
 
 namespace rqhip {
 
-constexpr int kWT = 128;    // output tile (o and i)
-constexpr int kWBK = 32;    // rows per LDS stage
 constexpr int kWLD = 128;   // LDS row stride in floats (float2 operand reads: 32 lanes x 8 B = all 64 banks)
 
 // Operand mapping: a wave owns a 64 (o) x 64 (i) block as 2 x 2 MFMA tiles, interleaved so that
@@ -171,40 +170,17 @@ __global__ void __launch_bounds__(256) wgrad_reduce_kernel(const float* __restri
   }
 }
 
-struct WgradPlan {
-  int tiles_i, tiles, S, per;
-  int64_t chunk;
-};
-
-static int resident_slots() {   // 2 workgroups per CU (launch bounds), queried once
-  static int slots = 0;
-  if (slots == 0) {
-    int dev = 0, cus = 0;
+// CUs of the current device, queried once: the one machine fact every plan of gemm_plan.h takes as an argument.
+// 256 (an MI355X) when no device answers, so planning works on a machine without a GPU.
+static int x3_cus() {
+  static int cus = 0;
+  if (cus == 0) {
+    int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) !=
                                                  hipSuccess || cus <= 0)
       cus = 256;
-    slots = 2 * cus;
   }
-  return slots;
-}
-
-static WgradPlan wgrad_plan(int64_t Bn, int64_t O, int64_t I) {
-  WgradPlan p;
-  p.tiles_i = (int)((I + kWT - 1) / kWT);
-  p.tiles = (int)((O + kWT - 1) / kWT) * p.tiles_i;
-  // one full round of resident workgroups: a partial second round would double the time
-  int64_t S = resident_slots() / p.tiles;
-  const int64_t max_s = (Bn + 4 * kWBK - 1) / (4 * kWBK);   // at least 4 stages per workgroup
-  if (S > max_s) S = max_s;
-  if (S < 1) S = 1;
-  int64_t chunk = (Bn + S - 1) / S;
-  chunk = (chunk + kWBK - 1) / kWBK * kWBK;
-  if (chunk < kWBK) chunk = kWBK;
-  p.chunk = chunk;
-  p.S = (int)((Bn + chunk - 1) / chunk);
-  if (p.S < 1) p.S = 1;
-  p.per = (p.tiles * p.S + 7) / 8;
-  return p;
+  return cus;
 }
 
 
@@ -237,18 +213,16 @@ static WgradPlan wgrad_plan(int64_t Bn, int64_t O, int64_t I) {
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef short s16x4_t __attribute__((ext_vector_type(4)));
 
-constexpr int kXT = 128;                       // output tile (m and n)
-constexpr int kXK = 32;                        // k per LDS stage
 constexpr int kXCPR = kXK / 8;                 // 16-byte bf16 chunks per row of the row image
-constexpr int kXWG = 2;                        // resident workgroups per CU
 constexpr int kXPlane = kXT * kXK * 2;         // bytes of one bf16 plane (8 KiB)
 constexpr int kXOp = 2 * kXPlane;              // hi + lo planes of one operand
 constexpr int kXBuf = 2 * kXOp;                // A + B
 constexpr int kXLds = 2 * kXBuf;               // double buffer: 64 KiB (the 64-tile form: half)
 static_assert(kXLds == 65536, "LDS of the 128-tile form");
+static_assert(kXT == 128 && kXK == 32 && kXLds / 2 == 32768,
+              "gemm_plan.h: x3s_pad_lds pads a 64-tile launch by that form's own 32 KiB, to two workgroups per CU");
 
 __device__ __forceinline__ int col_swz(int k) { return ((k & 3) << 2) | ((k >> 2) & 3); }
-constexpr int kXWG64 = 4;   // resident workgroups per CU of the 64-tile form (128-B column-image rows, 32 KiB of LDS)
 // Byte offset of 16-B chunk `c` of k-row kr in a column image of TR columns: 256-B rows with col_swz
 // for TR = 128 (and the wide kernel); for TR = 64 128-B rows with a swizzle over the 8 chunks,
 // s = 2 ((kr >> 1) & 1) + 4 ((kr >> 3) & 1): a ds_read_b64_tr_b16 half-wave touches k-rows {4u..4u+3,
@@ -431,16 +405,7 @@ __device__ __forceinline__ bf16x8_t xfrag16(const char* plane, int rb, int lane)
   }
 }
 
-// Epilogues: what the accumulator tile becomes (all fp32 math; dropout mask = keep1(seed, m N + n),
-// the convention of the standalone dropout kernels, dropout.hip).
-enum X3Epi : int {
-  kEpiStore = 0,     // C = A B^T (fp32; split-K slabs when S > 1)
-  kEpiSiluFwd = 1,   // C = z = A B^T (fp32, kept for the backward); H = split(Dropout(SiLU(z)))
-  kEpiSiluBwd = 2,   // H = split(SiLU'(Z) * Dropout(A B^T)): the pre-activation grad of a hidden layer
-  kEpiAdd = 3,       // C = A B^T + Z (fp32; the residual add after an attention projection); with dropout
-                     // C = Z + Dropout(A B^T) (the block output h + Dropout(MLP(.)))
-};
-
+// The epilogue codes (X3Epi: kEpiStore, kEpiSiluFwd, kEpiSiluBwd, kEpiAdd) are gemm_plan.h's.
 struct X3Epilogue {
   const float* Z;    // kEpiSiluBwd: pre-activations (ld = ldc)
   uint16_t* Hh;      // split output planes (ld = ldh)
@@ -779,8 +744,8 @@ __global__ void __launch_bounds__(256, P1::kTS == 64 ? kXWG64 : kXWG) gemm_x3_pa
 // The accumulation order over k equals gemm_bf16x3_kernel's (same 32-deep steps, same product
 // order), so for the same split the two kernels agree bitwise.
 // ---------------------------------------------------------------------------------------------
-constexpr int kWT2 = 256;          // output tile (m and n)
 constexpr int kWH = 8192;          // one half-plane: 128 rows x 32 k bf16
+static_assert(kWH == (kWT2 / 2) * kWK * 2, "gemm_plan.h: the wide kernel's tile (kWT2) and k step (kWK)");
 constexpr int kWStep = 4 * kWH;    // one operand's k step: 2 halves x 2 planes
 constexpr int kWB0 = 3 * kWStep;   // B's slots follow A's three
 constexpr int kWLds = 5 * kWStep;  // 160 KiB
@@ -1036,7 +1001,6 @@ gemm_x3w_kernel(const uint16_t* __restrict__ Ah, const uint16_t* __restrict__ Al
 // grid: problem p owns work items first[p] .. first[p + 1) of the XCD-remapped grid, tiles[p] x S[p] of
 // them, each the single-problem kernel's work item (k chunk, tile) of that problem with that problem's own
 // chunk, so every member runs the wide tile over a long k loop on its proportional share of the chip.
-constexpr int kX3GroupMax = 8;
 struct X3WProb {
   const uint16_t* Ah;
   const uint16_t* Al;
@@ -1159,200 +1123,6 @@ __global__ void __launch_bounds__(256) split_bf16x3_multi_kernel(SplitMulti sm) 
   }
 }
 
-struct X3Plan {
-  int tiles_n, tiles, S, per;
-  int64_t chunk;
-  int ts;   // output tile of the 128-tile kernel family: 128 or 64 (the wide kernel: 256)
-};
-
-static int x3_slots() { return resident_slots() / 2 * kXWG; }
-
-// ---------------------------------------------------------------------------------------------
-// The planner's constants: split-K limits and the time model's measured rates.
-// ---------------------------------------------------------------------------------------------
-constexpr int kX3MaxSplit = 64;      // split-K: at most this many k chunks
-constexpr int kX3MinStages = 2;      // split-K: k-stages per workgroup at least (fewer slabs to reduce)
-constexpr int kX3SlabMB = 64;        // split-K: slab bytes (S x M x N fp32) allowed beyond kX3MaxSplit slabs
-constexpr int kX3WMinSteps = 8;      // split-K of the wide kernel: k steps per workgroup at least
-// Per-CU rates of the time model (x3_plan_time), M fp32-MAC / us:
-constexpr double kX3Rate2 = 0.53;    // 128-tile kernel, its two workgroups per CU
-constexpr double kX3Rate1 = 0.4;     // 128-tile kernel, a lone workgroup
-constexpr double kX3WSpeed = 1.3;    // wide kernel: this multiple of kX3Rate2
-constexpr double kX3SRate1 = 0.3;    // 64-tile kernel, one workgroup per CU
-constexpr double kX3SRate2 = 0.35;   // 64-tile kernel, kXWG64 workgroups per CU
-// Modelled cost (us) of the separate slab-reduction launch of a split-K call: the reduction kernel plus the
-// gap it adds between launches in a replayed step (4 us measured best of 4 / 8 / 16 at both decoder
-// configs in round 3 with whole rounds, profiles/r03/reduce_us_ab.txt; 3 with the fractional rounds, fitted
-// on the round-5 plan sweeps: a back-to-back tiny launch costs ~2.7 us in a replayed graph).
-constexpr double kX3ReduceUs = 3.0;
-constexpr double kX3SlabBpus = 3.0e6;   // slab bytes per us (written + read back)
-
-// Split-K count cap: kX3MaxSplit slabs, or more while the slabs stay within kX3SlabMB MiB — the
-// small weight grads (e.g. 128 x 64 over 65,536 rows: one output tile) need hundreds of k chunks to
-// cover the chip, and their slabs are tiny.
-static int64_t x3_split_cap(int64_t M, int64_t N) {
-  const int64_t by_bytes = ((int64_t)kX3SlabMB << 20) / (4 * M * N);
-  return by_bytes > kX3MaxSplit ? by_bytes : kX3MaxSplit;
-}
-
-// The 64-tile form's compact LDS (32 KiB) lets 4 workgroups share a CU. A launch that fits in 2 per CU
-// gets 32 KiB of padding LDS instead (dynamic, unused), so the dispatcher spreads it over every CU rather
-// than packing them 4 per CU onto fewer CUs (measured: 1280 x 1536 x 512, 480 workgroups: 14.5 us spread,
-// 24.8 us packed; 26,880 x 384 x 1152, 2,520 workgroups: 122.6 -> 109.1 us at 4 per CU).
-static int x3s_resident(int64_t wgs) {
-  return wgs > (int64_t)resident_slots() ? kXWG64 : kXWG;
-}
-template <typename P>
-static unsigned x3s_pad_lds(const P& pl) {
-  return x3s_resident((int64_t)pl.tiles * pl.S) == kXWG ? 32768u : 0u;
-}
-
-// Modelled time (us) of a plan, to choose the split-K factor and between the two kernels:
-//  * MMA: rounds of resident workgroups (fractional: a partly filled last round costs its share — fitted
-//    on measured plan sweeps, tools/plan_model_fit.py over profiles/r05/plan_sweep/; the whole-round count
-//    it replaced mispriced the 64-tile form at 4 per CU, e.g. C4's 4,608 x 1,024 x 384 SiLU launches) x the
-//    MACs a CU does per round, at the measured per-CU rates (128-tile kernel ~0.53 M fp32-MAC/us per
-//    CU with its two workgroups, ~0.4 for a lone workgroup; wide kernel 1.3x) — the wide kernel's
-//    256 x 256 tiles quantise into 4x coarser rounds (decoder context rows: a 1,536-wide projection is
-//    270 wide tiles, two rounds, the second nearly empty);
-//  * split-K: the slabs written by the GEMM and read back by the reduction, 2 S M N fp32 at ~3 TB/s (the
-//    rate the batched deferred reductions reach), plus the reduce launch (kX3ReduceUs). Round 4 priced (S + 1) M N at
-//    5 TB/s, which chose 256 x 256-tile plans with S = 21..30 for the decoder's 11k-row weight gradients:
-//    ~64 MB of slabs per weight, 444 MB (C4) / 800 MB (Amazon) a step. Same-process A/B on MI355X: C4
-//    2.766 -> 2.678 ms, Amazon 5.415 -> 5.355, RQ-VAE 1.957 -> 1.924 (half the rate, 1.5 TB/s, loses).
-// Checked against tools/gemm_ab.py on MI355X (RQ-VAE and decoder shapes, both kernels forced).
-static double x3_plan_time(const X3Plan& p, int64_t M, int64_t N, bool wide) {
-  const int64_t cus = resident_slots() / 2;
-  const int64_t wgs = (int64_t)p.tiles * p.S;
-  const bool small = p.ts == 64;
-  const double tile = wide ? (double)kWT2 * kWT2 : (double)p.ts * p.ts;
-  const double rate = small ? kX3SRate2 : kX3Rate2 * (wide ? kX3WSpeed : 1.0);   // M MAC / us per CU
-  double t;
-  if (wgs <= cus) {   // at most one workgroup per CU
-    t = tile * (double)p.chunk / ((wide ? rate : (small ? kX3SRate1 : kX3Rate1)) * 1e6);
-  } else {
-    const int per_cu = wide ? 1 : (small ? x3s_resident(wgs) : kXWG);
-    const int64_t slots = cus * per_cu;
-    // a partly filled last round costs its share; one round at least
-    const double rounds = wgs > slots ? (double)wgs / (double)slots : 1.0;
-    t = rounds * per_cu * tile * (double)p.chunk / (rate * 1e6);
-  }
-  if (p.S > 1) t += (double)(2 * p.S) * (double)(M * N) * 4.0 / kX3SlabBpus + kX3ReduceUs;
-  return t;
-}
-
-static X3Plan x3_plan_s(int64_t M, int64_t N, int64_t K, int64_t S, bool wide, int ts = kXT) {
-  X3Plan p;
-  const int T = wide ? kWT2 : ts, KS = wide ? 32 : kXK;
-  p.ts = T;
-  p.tiles_n = (int)((N + T - 1) / T);
-  p.tiles = (int)((M + T - 1) / T) * p.tiles_n;
-  int64_t chunk = (K + S - 1) / S;
-  chunk = (chunk + KS - 1) / KS * KS;
-  p.chunk = chunk;
-  p.S = (int)((K + chunk - 1) / chunk);
-  if (p.S < 1) p.S = 1;
-  p.per = wide ? 0 : (p.tiles * p.S + 7) / 8;
-  return p;
-}
-
-// Best split-K plan of one tile size: split K when the output tiles cannot fill the chip (weight
-// gradients, the decoder's future rows) and the model says the slabs pay for themselves.
-static X3Plan x3_plan_t(int64_t M, int64_t N, int64_t K, bool allow_split, int ts) {
-  X3Plan p = x3_plan_s(M, N, K, 1, false, ts);
-  const int64_t slots_t = (int64_t)(resident_slots() / 2) * kXWG;   // split-K fills the 2-per-CU slots
-  if (allow_split && p.tiles < slots_t / 2 && (M * N) % 4 == 0) {   // slab reduction reads float4
-    int64_t S = slots_t / p.tiles;
-    const int64_t max_s = (K + kX3MinStages * kXK - 1) / (kX3MinStages * kXK);   // min stages per workgroup
-    if (S > max_s) S = max_s;
-    if (S > x3_split_cap(M, N)) S = x3_split_cap(M, N);   // slab traffic of the reduction grows with S
-    if (ts == 64) {   // small tiles: the best of S = 2, 4, ... up to the one-round heuristic
-      for (int64_t s2 = 2; s2 < S; s2 *= 2) {
-        const X3Plan q = x3_plan_s(M, N, K, s2, false, ts);
-        if (x3_plan_time(q, M, N, false) < x3_plan_time(p, M, N, false)) p = q;
-      }
-    }
-    if (S > 1) {
-      const X3Plan q = x3_plan_s(M, N, K, S, false, ts);
-      if (x3_plan_time(q, M, N, false) < x3_plan_time(p, M, N, false)) p = q;
-    }
-  }
-  return p;
-}
-
-// 128-tile kernel, or its 64-tile form where the time model prefers it (the 128-tiles of a
-// 1,280-row operand are 40 workgroups: split-K slabs and their reduction cost more than the GEMM).
-// flags (the call's rq_gemm_desc.flags): RQ_GEMM_ONLY_128 / RQ_GEMM_ONLY_64 pin one tile size.
-
-static X3Plan x3_plan(int64_t M, int64_t N, int64_t K, int flags, bool allow_split = true, int epilogue = 0) {
-  // One row of 64-tiles (the C4 decoder's 40 future-token rows) over K <= 384 with a plain or residual
-  // epilogue: unsplit. Measured per call (profiles/r05/plan_sweep2/sweep_c4.jsonl, hipGraph of 10 calls with
-  // their reductions): 6.7-7.2 us unsplit vs 7.1-7.3 at the model's S = 6 plus a reduction launch per call
-  // — the model underprices the short-K workgroups' fixed latency; the SiLU epilogues keep the model's split.
-  if (!(flags & (RQ_GEMM_ONLY_128 | RQ_GEMM_ONLY_64)) && M <= 64 && K <= 384 &&
-      (epilogue == kEpiStore || epilogue == kEpiAdd))
-    allow_split = false;
-  const X3Plan p = x3_plan_t(M, N, K, allow_split, kXT);
-  if (flags & RQ_GEMM_ONLY_128) return p;
-  const X3Plan q = x3_plan_t(M, N, K, allow_split, 64);
-  if (flags & RQ_GEMM_ONLY_64) return q;
-  // K <= 128 (at most four 32-deep stages): the 64-tile form, whose 4 resident workgroups per CU hide the
-  // per-workgroup prologue / epilogue latency that such short k loops cannot — measured faster than the
-  // 128-tile kernel for every short-K call of the three bench steps (plan_sweep2: RQ-VAE 65,536 x 128 x 64
-  // SiLU' epilogue 27.6 -> 20.6 us, SiLU 23.4 -> 22.0; Amazon 11,520 x 512 x 128 14.6 -> 13.8)
-  if (K <= 128) return q;
-  return x3_plan_time(q, M, N, false) < x3_plan_time(p, M, N, false) ? q : p;
-}
-
-// Plan of the wide kernel, or false when the 128-tile kernel serves the shape better: k steps
-// must be whole (K % 32), padding of a partial 256-row tile must stay small (R % 256 == 0 or
-// R >= 2048), and the launch must cover at least a quarter of the CUs (split-K when allowed).
-static bool x3w_plan(int64_t M, int64_t N, int64_t K, bool allow_split, X3Plan* p) {
-  if (K % 32 != 0 || K <= 0) return false;
-  auto fits = [](int64_t R) { return R % kWT2 == 0 || R >= 2048; };
-  if (!fits(M) || !fits(N)) return false;
-  const int cus = resident_slots() / 2;
-  *p = x3_plan_s(M, N, K, 1, true);
-  if (allow_split && p->tiles < cus / 2 && (M * N) % 4 == 0) {
-    int64_t S = cus / p->tiles;
-    const int64_t max_s = K / (32 * kX3WMinSteps);
-    if (S > max_s) S = max_s;
-    if (S > x3_split_cap(M, N)) S = x3_split_cap(M, N);
-    if (S > 1) {
-      const X3Plan q = x3_plan_s(M, N, K, S, true);
-      if (x3_plan_time(q, M, N, true) < x3_plan_time(*p, M, N, true)) *p = q;
-    }
-  }
-  return (int64_t)p->tiles * p->S >= cus / 4;
-}
-
-// Elements one wide workgroup's operand DMA spans from its descriptor base (32-bit byte offsets):
-// 256 rows of a k-contiguous operand (+ K), or one k chunk of rows of an m/n-contiguous one (+ its rows).
-static int64_t x3w_span(int64_t R, int64_t K, int64_t ld, bool kc, int64_t chunk) {
-  return kc ? (int64_t)kWT2 * ld + K : (chunk + 32) * ld + R;
-}
-// Both operands of a wide problem within the DMA's 32-bit byte offsets (the span at the largest chunk, K:
-// a split only shortens it): what x3_prepare and the group planner (x3_group_plan) both require.
-static bool x3w_spans_ok(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, bool a_kc, bool b_kc) {
-  return x3w_span(M, K, lda, a_kc, K) < (1ll << 30) && x3w_span(N, K, ldb, b_kc, K) < (1ll << 30);
-}
-
-// The wide kernel runs when both operands are split planes, the (layout, epilogue) pair is
-// instantiated (every layout for the plain store; the fused MLP chain's layouts otherwise), the shape
-// plans (x3w_plan) and the time model prefers it — or wherever it can run under RQ_GEMM_FORCE_WIDE;
-// never under RQ_GEMM_NO_WIDE / RQ_GEMM_ONLY_128 / RQ_GEMM_ONLY_64.
-static bool x3w_choose(int64_t M, int64_t N, int64_t K, bool asp, bool bsp, bool a_kc, bool b_kc, int epilogue,
-                       int flags, X3Plan* p) {
-  if (flags & (RQ_GEMM_NO_WIDE | RQ_GEMM_ONLY_128 | RQ_GEMM_ONLY_64)) return false;
-  const bool combo = epilogue == kEpiStore || (epilogue == kEpiSiluFwd && a_kc && b_kc) ||
-                     (epilogue == kEpiSiluBwd && a_kc && !b_kc) || (epilogue == kEpiAdd && a_kc && b_kc);
-  if (!(asp && bsp && combo && x3w_plan(M, N, K, true, p))) return false;
-  // priced against the 128-/64-tile plan this call would really get (same epilogue: the skinny-unsplit rule
-  // applies to the store / add epilogues only)
-  return (flags & RQ_GEMM_FORCE_WIDE) ||
-         x3_plan_time(*p, M, N, true) < x3_plan_time(x3_plan(M, N, K, flags, true, epilogue), M, N, false);
-}
-
 }  // namespace rqhip
 
 using namespace rqhip;
@@ -1361,8 +1131,7 @@ extern "C" {
 
 size_t rq_linear_wgrad_workspace(int64_t Bn, int64_t O, int64_t I) {
   if (Bn <= 0 || O <= 0 || I <= 0) return 0;
-  const WgradPlan p = wgrad_plan(Bn, O, I);
-  return (size_t)p.S * (size_t)(O * I + O) * sizeof(float);
+  return wgrad_plan(Bn, O, I, x3_cus()).ws_bytes;
 }
 
 int rq_linear_wgrad(const float* g, int64_t ldg, const float* x, int64_t ldx, int64_t Bn, int64_t O, int64_t I,
@@ -1379,12 +1148,12 @@ int rq_linear_wgrad(const float* g, int64_t ldg, const float* x, int64_t ldx, in
     if (db) RQ_HIP(zero_async(db, (size_t)O * sizeof(float), s));
     return 0;
   }
-  const WgradPlan p = wgrad_plan(Bn, O, I);
-  const size_t need = (size_t)p.S * (size_t)(O * I + O) * sizeof(float);
-  RQ_CHECK_ARG(workspace != nullptr && ws_bytes >= need, "rq_linear_wgrad: workspace %zu < %zu bytes", ws_bytes, need);
+  const WgradPlan p = wgrad_plan(Bn, O, I, x3_cus());
+  RQ_CHECK_ARG(workspace != nullptr && ws_bytes >= p.ws_bytes, "rq_linear_wgrad: workspace %zu < %zu bytes", ws_bytes,
+               p.ws_bytes);
   float* P = static_cast<float*>(workspace);
   float* Pb = db ? P + (int64_t)p.S * O * I : nullptr;
-  hipLaunchKernelGGL(wgrad_partial_kernel, dim3((unsigned)(p.per * 8)), dim3(256), 0, s, g, ldg, x, ldx, Bn, (int)O,
+  hipLaunchKernelGGL(wgrad_partial_kernel, dim3(p.grid), dim3(256), 0, s, g, ldg, x, ldx, Bn, (int)O,
                      (int)I, p.tiles_i, p.tiles, p.S, p.chunk, p.per, P, Pb);
   RQ_LAUNCH_CHECK("wgrad_partial_kernel");
   const int64_t n = O * I;
@@ -1398,19 +1167,7 @@ int rq_linear_wgrad(const float* g, int64_t ldg, const float* x, int64_t ldx, in
 }
 
 
-// Slab bytes of a call: split-K slabs (S > 1) of whichever kernel may run for the shape (the largest of
-// the 128-tile, 64-tile and wide plans, so one workspace serves every rq_gemm_desc.flags policy). An
-// unsplit accumulating call adds in the GEMM's own epilogue: no slab.
-static size_t x3_workspace_bytes(int64_t M, int64_t N, int64_t K) {
-  if (M <= 0 || N <= 0 || K <= 0) return 0;
-  const X3Plan p = x3_plan_t(M, N, K, true, kXT), q = x3_plan_t(M, N, K, true, 64);
-  X3Plan pw;
-  int S = p.S > q.S ? p.S : q.S;
-  if (x3w_plan(M, N, K, true, &pw) && pw.S > S) S = pw.S;
-  return S > 1 ? (size_t)S * (size_t)(M * N) * sizeof(float) : 0;
-}
-
-size_t rq_gemm_bf16x3_workspace(int64_t M, int64_t N, int64_t K) { return x3_workspace_bytes(M, N, K); }
+size_t rq_gemm_bf16x3_workspace(int64_t M, int64_t N, int64_t K) { return x3_workspace_bytes(M, N, K, x3_cus()); }
 
 }  // extern "C"
 
@@ -1418,15 +1175,13 @@ namespace rqhip {
 
 // One validated and planned rq_gemm_bf16x3 call (x3_prepare), its kernel launch (x3_launch) and its slab
 // reduction or deferral (x3_post): rq_gemm_bf16x3_run runs the three in a row, rq_gemm_bf16x3_pair prepares
-// two calls and, where an instantiation exists, launches both problems in one gemm_x3_pair_kernel.
+// two calls and, where gemm_plan.h pairs them (x3_pair_plan), launches both problems in one gemm_x3_pair_kernel.
 struct X3Call {
-  X3Plan pl;
-  bool wide, slab, asp, bsp, trivial;
-  int a_kc, b_kc, epilogue, epi_k, code, accumulate, defer, flags;
-  int64_t M, N, K;
-  float* C;
-  float* out;
-  X3Args xa;
+  X3Plan pl;      // gemm_plan.h: the kernel, its grid, split-K and slabs
+  X3Args xa;      // the kernel's argument block; xa.C = where the kernel stores (C, or the slabs)
+  bool trivial;   // K == 0: nothing to launch
+  int epilogue, accumulate, defer;   // what x3_post applies to the slabs, and to ...
+  float* C;                          // ... the call's real output
 };
 
 // Validate and plan one call. dry = planning only (rq_gemm_bf16x3_plan): no stream work, no workspace check.
@@ -1436,6 +1191,7 @@ static int x3_prepare(const rq_gemm_desc& d, hipStream_t s, X3Call* c, bool dry 
   const int a_kcontig = d.a_kcontig, b_kcontig = d.b_kcontig, epilogue = d.epilogue, accumulate = d.accumulate;
   float* C = d.C;
   const bool asp = A_lo != nullptr, bsp = B_lo != nullptr;
+  *c = X3Call{};
   RQ_CHECK_ARG(dry || (((A && B) || K == 0) && M > 0 && N > 0), "rq_gemm_bf16x3: bad arguments");
   RQ_CHECK_ARG(K >= 0 && M > 0 && N > 0 && M < (1 << 30) && N < (1 << 30) && epilogue >= 0 && epilogue <= 3,
                "rq_gemm_bf16x3: bad arguments");
@@ -1468,161 +1224,99 @@ static int x3_prepare(const rq_gemm_desc& d, hipStream_t s, X3Call* c, bool dry 
       RQ_HIP(hipMemset2DAsync(C, (size_t)ldc * sizeof(float), 0, (size_t)N * sizeof(float), (size_t)M, s));
     return 0;
   }
-  const int flags = d.flags;
-  X3Plan pl = x3_plan(M, N, K, flags, true, epilogue);
-  X3Plan pw;
-  const bool wide = x3w_choose(M, N, K, asp, bsp, a_kcontig, b_kcontig, epilogue, flags, &pw) &&
-                    x3w_spans_ok(M, N, K, lda, ldb, a_kcontig, b_kcontig);
-  if (wide) pl = pw;
-  // a tuned plan: RQ_GEMM_SPLIT(S) forces the split-K count on the kernel the policy picked
-  const int forced_s = (flags >> RQ_GEMM_SPLIT_SHIFT) & RQ_GEMM_SPLIT_MASK;
-  if (forced_s > 0) pl = x3_plan_s(M, N, K, forced_s, wide, wide ? kWT2 : pl.ts);
-  // slab path: split-K partials go to the workspace with the plain store, and x3_reduce_kernel applies
-  // the real epilogue (and the accumulation); an unsplit accumulating call adds in the GEMM's epilogue
-  const bool slab = pl.S > 1;
-  ep.acc = accumulate && !slab;
+  const X3Plan pl = x3_call_plan(x3_shape(d, ep.thr != 0), x3_cus());
+  // slab path: x3_reduce_kernel applies the real epilogue (and the accumulation); an unsplit accumulating call
+  // adds in the GEMM's epilogue
+  ep.acc = accumulate && !pl.slab;
   float* out = C;
-  if (slab && !dry) {
-    const size_t need = (size_t)pl.S * (size_t)(M * N) * sizeof(float);
-    RQ_CHECK_ARG(d.workspace != nullptr && d.ws_bytes >= need && ldc == N,
-                 "rq_gemm_bf16x3: split-K / accumulate needs ldc == N and workspace %zu >= %zu bytes", d.ws_bytes, need);
+  if (pl.slab && !dry) {
+    RQ_CHECK_ARG(d.workspace != nullptr && d.ws_bytes >= pl.slab_bytes && ldc == N,
+                 "rq_gemm_bf16x3: split-K / accumulate needs ldc == N and workspace %zu >= %zu bytes", d.ws_bytes,
+                 pl.slab_bytes);
     out = static_cast<float*>(d.workspace);
   }
-  c->pl = pl;
-  c->wide = wide;
-  c->slab = slab;
-  c->asp = asp;
-  c->bsp = bsp;
-  c->a_kc = a_kcontig;
-  c->b_kc = b_kcontig;
-  c->epilogue = epilogue;
-  c->epi_k = slab ? (int)kEpiStore : epilogue;   // the epilogue the GEMM kernel itself runs
-  c->code = (a_kcontig ? 16 : 0) | (asp ? 8 : 0) | (b_kcontig ? 4 : 0) | (bsp ? 2 : 0);
-  c->accumulate = accumulate;
-  c->defer = d.defer;
-  c->flags = flags;
-  c->M = M;
-  c->N = N;
-  c->K = K;
-  c->C = C;
-  c->out = out;
-  const int64_t ldo = pl.S > 1 ? N : ldc;
-  // whole 32-deep stages: unmasked staging (bitwise the masked path; RQ_GEMM_MASKED keeps the masked one)
-  const int kfull = !(flags & RQ_GEMM_MASKED) && K % kXK == 0 && pl.chunk % kXK == 0;
-  c->xa = X3Args{A, A_lo, lda, B, B_lo, ldb, (int)M, (int)N, K, pl.tiles_n, pl.tiles, pl.S, pl.chunk, pl.per, out, ldo, ep,
-                 kfull};
+  const X3Args xa{A, A_lo, lda, B, B_lo, ldb, (int)M, (int)N, K, pl.tiles_n, pl.tiles, pl.S, pl.chunk, pl.per, out,
+                  pl.slab ? N : ldc, ep, pl.kfull};
+  *c = X3Call{pl, xa, false, epilogue, accumulate, d.defer, C};
   return 0;
 }
+
+// The launchers' switch arms are the only place that names template arguments, one arm per entry of gemm_plan.h's
+// built-form table (kX3Built): the operand flags come from the layout code, the key is (kernel epilogue, code).
+#define RQ_X3_OPS(CODE) ((CODE) & kCodeAK) != 0, ((CODE) & kCodeAS) != 0, ((CODE) & kCodeBK) != 0, ((CODE) & kCodeBS) != 0
+#define RQ_X3_KEY(EP, CODE) ((EP) << 5 | (CODE))
 
 static int x3_launch(const X3Call& c, hipStream_t s) {
   const X3Plan& pl = c.pl;
   const X3Args& xa = c.xa;
-  const X3Epilogue& ep = xa.ep;
-  const int64_t M = c.M, N = c.N, K = c.K, lda = xa.lda, ldb = xa.ldb, ldo = xa.ldc;
-  const int epi_k = c.epi_k, code = c.code, a_kcontig = c.a_kc, b_kcontig = c.b_kc;
-  const void *A = xa.A, *A_lo = xa.Al, *B = xa.B, *B_lo = xa.Bl;
-  float* out = c.out;
-  const dim3 grid((unsigned)(pl.per * 8)), block(256);
-#define RQ_X3D(AK, AS, BK, BS, EP, DR)                                                                               \
-  do {                                                                                                               \
-    if (pl.ts == 64)                                                                                                 \
-      hipLaunchKernelGGL((gemm_bf16x3_kernel<AK, AS, BK, BS, EP, DR, 64>), grid, block, x3s_pad_lds(pl), s, xa);     \
-    else                                                                                                             \
-      hipLaunchKernelGGL((gemm_bf16x3_kernel<AK, AS, BK, BS, EP, DR>), grid, block, 0, s, xa);                       \
-  } while (0)
-#define RQ_X3(AK, AS, BK, BS, EP)                                                                                    \
-  do {                                                                                                               \
-    if (ep.thr != 0)                                                                                                 \
-      RQ_X3D(AK, AS, BK, BS, EP, (EP != kEpiStore));                                                                 \
-    else                                                                                                             \
-      RQ_X3D(AK, AS, BK, BS, EP, false);                                                                             \
-  } while (0)
-  bool launched = true;
-  if (c.wide) {
-    const uint16_t *ah = static_cast<const uint16_t*>(A), *al = static_cast<const uint16_t*>(A_lo);
-    const uint16_t *bh = static_cast<const uint16_t*>(B), *bl = static_cast<const uint16_t*>(B_lo);
-    const dim3 wgrid((unsigned)(pl.tiles * pl.S)), wblock(512);
-#define RQ_X3W(AK, BK, EP, DR)                                                                                        \
-  hipLaunchKernelGGL((gemm_x3w_kernel<AK, BK, EP, DR>), wgrid, wblock, 0, s, ah, al, lda, bh, bl, ldb, (int)M, (int)N, \
-                     K, pl.tiles_n, pl.tiles, pl.chunk, out, ldo, ep)
-    const bool drop = ep.thr != 0;
-    const int kc = (a_kcontig ? 2 : 0) | (b_kcontig ? 1 : 0);
-    if (epi_k == kEpiStore) {
-      switch (kc) {
-        case 3: RQ_X3W(true, true, kEpiStore, false); break;
-        case 2: RQ_X3W(true, false, kEpiStore, false); break;
-        case 1: RQ_X3W(false, true, kEpiStore, false); break;
-        default: RQ_X3W(false, false, kEpiStore, false); break;
-      }
-    } else if (epi_k == kEpiSiluFwd && kc == 3) {
-      if (drop) RQ_X3W(true, true, kEpiSiluFwd, true); else RQ_X3W(true, true, kEpiSiluFwd, false);
-    } else if (epi_k == kEpiSiluBwd && kc == 2) {
-      if (drop) RQ_X3W(true, false, kEpiSiluBwd, true); else RQ_X3W(true, false, kEpiSiluBwd, false);
-    } else if (epi_k == kEpiAdd && kc == 3) {
-      if (drop) RQ_X3W(true, true, kEpiAdd, true); else RQ_X3W(true, true, kEpiAdd, false);
-    } else {
-      launched = false;
+  RQ_CHECK_ARG(x3_form_built(pl.kind, pl.code, pl.epi_k),
+               "rq_gemm_bf16x3: operand combination (a_kcontig %d, a_split %d, b_kcontig %d, b_split %d) "
+               "not built for epilogue %d", (pl.code & kCodeAK) != 0, (pl.code & kCodeAS) != 0, (pl.code & kCodeBK) != 0,
+               (pl.code & kCodeBS) != 0, c.epilogue);
+  const dim3 grid(pl.grid), block(pl.block);
+  if (pl.kind == kX3Wide) {
+    const uint16_t *ah = static_cast<const uint16_t*>(xa.A), *al = static_cast<const uint16_t*>(xa.Al);
+    const uint16_t *bh = static_cast<const uint16_t*>(xa.B), *bl = static_cast<const uint16_t*>(xa.Bl);
+#define RQ_X3WD(CODE, EP, DR)                                                                                       \
+  hipLaunchKernelGGL((gemm_x3w_kernel<((CODE) & kCodeAK) != 0, ((CODE) & kCodeBK) != 0, EP, DR>), grid, block, 0, s, \
+                     ah, al, xa.lda, bh, bl, xa.ldb, xa.M, xa.N, xa.K, xa.tiles_n, xa.tiles, xa.chunk, xa.C, xa.ldc, xa.ep)
+#define RQ_X3W(EP, CODE)                                                                                            \
+  case RQ_X3_KEY(EP, CODE):                                                                                         \
+    if (pl.drop) RQ_X3WD(CODE, EP, (EP != kEpiStore)); else RQ_X3WD(CODE, EP, false);                               \
+    break
+    switch (RQ_X3_KEY(pl.epi_k, pl.code)) {
+      RQ_X3W(kEpiStore, 30); RQ_X3W(kEpiStore, 26); RQ_X3W(kEpiStore, 14); RQ_X3W(kEpiStore, 10);
+      RQ_X3W(kEpiSiluFwd, 30);
+      RQ_X3W(kEpiSiluBwd, 26);
+      RQ_X3W(kEpiAdd, 30);
+      default: break;   // unreachable: x3_form_built
     }
 #undef RQ_X3W
-  } else if (epi_k == kEpiStore) {
-    switch (code) {
-      // every layout with fp32 operands (the generic entry point)
-      case 16 | 4: RQ_X3(true, false, true, false, kEpiStore); break;
-      case 16: RQ_X3(true, false, false, false, kEpiStore); break;
-      case 4: RQ_X3(false, false, true, false, kEpiStore); break;
-      case 0: RQ_X3(false, false, false, false, kEpiStore); break;
-      // fused MLP chain: forward of the last layer, data grads with split weights, weight grads
-      case 16 | 8 | 4 | 2: RQ_X3(true, true, true, true, kEpiStore); break;
-      case 16 | 4 | 2: RQ_X3(true, false, true, true, kEpiStore); break;
-      case 16 | 8 | 2: RQ_X3(true, true, false, true, kEpiStore); break;
-      case 16 | 2: RQ_X3(true, false, false, true, kEpiStore); break;
-      case 8 | 2: RQ_X3(false, true, false, true, kEpiStore); break;
-      case 8: RQ_X3(false, true, false, false, kEpiStore); break;
-      case 2: RQ_X3(false, false, false, true, kEpiStore); break;
-      default: launched = false;
-    }
-  } else if (epi_k == kEpiSiluFwd) {
-    switch (code) {
-      case 16 | 4 | 2: RQ_X3(true, false, true, true, kEpiSiluFwd); break;
-      case 16 | 8 | 4 | 2: RQ_X3(true, true, true, true, kEpiSiluFwd); break;
-      default: launched = false;
-    }
-  } else if (epi_k == kEpiSiluBwd) {
-    switch (code) {
-      case 16 | 2: RQ_X3(true, false, false, true, kEpiSiluBwd); break;
-      case 16 | 8 | 2: RQ_X3(true, true, false, true, kEpiSiluBwd); break;
-      default: launched = false;
-    }
+#undef RQ_X3WD
   } else {
-    switch (code) {
-      case 16 | 4 | 2: RQ_X3(true, false, true, true, kEpiAdd); break;   // Linear (split weight) + residual
-      case 16 | 8 | 4 | 2: RQ_X3(true, true, true, true, kEpiAdd); break;  // MLP chain's last layer + residual
-      default: launched = false;
+#define RQ_X3D(CODE, EP, DR)                                                                                        \
+  do {                                                                                                              \
+    if (pl.kind == kX3Tile64)                                                                                       \
+      hipLaunchKernelGGL((gemm_bf16x3_kernel<RQ_X3_OPS(CODE), EP, DR, 64>), grid, block, pl.lds_pad, s, xa);        \
+    else                                                                                                            \
+      hipLaunchKernelGGL((gemm_bf16x3_kernel<RQ_X3_OPS(CODE), EP, DR>), grid, block, 0, s, xa);                     \
+  } while (0)
+#define RQ_X3(EP, CODE)                                                                                             \
+  case RQ_X3_KEY(EP, CODE):                                                                                         \
+    if (pl.drop) RQ_X3D(CODE, EP, (EP != kEpiStore)); else RQ_X3D(CODE, EP, false);                                 \
+    break
+    switch (RQ_X3_KEY(pl.epi_k, pl.code)) {
+      // every layout with fp32 operands (the generic entry point)
+      RQ_X3(kEpiStore, 20); RQ_X3(kEpiStore, 16); RQ_X3(kEpiStore, 4); RQ_X3(kEpiStore, 0);
+      // fused MLP chain: forward of the last layer, data grads with split weights, weight grads
+      RQ_X3(kEpiStore, 30); RQ_X3(kEpiStore, 22); RQ_X3(kEpiStore, 26); RQ_X3(kEpiStore, 18);
+      RQ_X3(kEpiStore, 10); RQ_X3(kEpiStore, 8); RQ_X3(kEpiStore, 2);
+      RQ_X3(kEpiSiluFwd, 22); RQ_X3(kEpiSiluFwd, 30);
+      RQ_X3(kEpiSiluBwd, 18); RQ_X3(kEpiSiluBwd, 26);
+      RQ_X3(kEpiAdd, 22);   // Linear (split weight) + residual
+      RQ_X3(kEpiAdd, 30);   // MLP chain's last layer + residual
+      default: break;       // unreachable: x3_form_built
     }
-  }
 #undef RQ_X3
 #undef RQ_X3D
-  RQ_CHECK_ARG(launched, "rq_gemm_bf16x3: operand combination (a_kcontig %d, a_split %d, b_kcontig %d, b_split %d) "
-                         "not built for epilogue %d", a_kcontig, (int)c.asp, b_kcontig, (int)c.bsp, c.epilogue);
+  }
   RQ_LAUNCH_CHECK("gemm_bf16x3_kernel");
   return 0;
 }
 
 static int x3_post(const X3Call& c, int* splits, hipStream_t s) {
-  if (!c.slab) return 0;
+  if (!c.pl.slab) return 0;
+  const int S = c.pl.S;
   if (c.defer && c.accumulate && c.epilogue == kEpiStore && splits) {   // the caller reduces later
-    *splits = c.pl.S;                                                  // (rq_reduce_partials, layout 0)
+    *splits = S;                                                        // (rq_reduce_partials, layout 0)
     return 0;
   }
-  const int64_t n = c.M * c.N;
-  const int N = (int)c.N;
+  const int N = c.xa.N;
+  const int64_t n = (int64_t)c.xa.M * N;
   const dim3 rg((unsigned)((n / 4 + kRedColsPerWg - 1) / kRedColsPerWg)), rb(256);
   const X3Epilogue& ep = c.xa.ep;
   const bool drop = ep.thr != 0 && c.epilogue != kEpiStore;
-  float* out = c.out;
-  float* C = c.C;
-  const int S = c.pl.S;
-#define RQ_X3R(EP, DR, AC) hipLaunchKernelGGL((x3_reduce_kernel<EP, DR, AC>), rg, rb, 0, s, out, S, n, N, C, ep)
+#define RQ_X3R(EP, DR, AC) hipLaunchKernelGGL((x3_reduce_kernel<EP, DR, AC>), rg, rb, 0, s, c.xa.C, S, n, N, c.C, ep)
   switch (c.epilogue) {
     case kEpiStore: if (c.accumulate) RQ_X3R(kEpiStore, false, true); else RQ_X3R(kEpiStore, false, false); break;
     case kEpiSiluFwd: if (drop) RQ_X3R(kEpiSiluFwd, true, false); else RQ_X3R(kEpiSiluFwd, false, false); break;
@@ -1634,260 +1328,95 @@ static int x3_post(const X3Call& c, int* splits, hipStream_t s) {
   return 0;
 }
 
+// The paired launch of two problems on the 128- or 64-tile kernel (TS), as x3_pair_plan paired them.
 template <class P1, class P2>
-static void x3_pair_go(const X3Call& c1, const X3Call& c2, dim3 grid, unsigned pad, hipStream_t s, int n1) {
-  hipLaunchKernelGGL((gemm_x3_pair_kernel<P1, P2>), grid, dim3(256), pad, s, c1.xa, c2.xa, n1);
+static void x3_pair_go(const X3Call& c1, const X3Call& c2, const X3PairPlan& pp, hipStream_t s) {
+  hipLaunchKernelGGL((gemm_x3_pair_kernel<P1, P2>), dim3(pp.grid), dim3(256), pp.lds_pad, s, c1.xa, c2.xa, (int)pp.n1);
 }
+// c2 of a (data gradient, weight gradient) pair: m-contiguous A (fp32 / split) x n-contiguous B (fp32 / split), plain store
 template <class P1, int TS>
-static void x3_pair_p2(const X3Call& c1, const X3Call& c2, dim3 grid, unsigned pad, hipStream_t s, int n1) {
-  switch (c2.code) {   // c2: m-contiguous A (fp32 / split) x n-contiguous B (fp32 / split), plain store
-    case 0: x3_pair_go<P1, X3Body<false, false, false, false, kEpiStore, false, TS>>(c1, c2, grid, pad, s, n1); break;
-    case 2: x3_pair_go<P1, X3Body<false, false, false, true, kEpiStore, false, TS>>(c1, c2, grid, pad, s, n1); break;
-    case 8: x3_pair_go<P1, X3Body<false, true, false, false, kEpiStore, false, TS>>(c1, c2, grid, pad, s, n1); break;
-    default: x3_pair_go<P1, X3Body<false, true, false, true, kEpiStore, false, TS>>(c1, c2, grid, pad, s, n1); break;
+static void x3_pair_p2(const X3Call& c1, const X3Call& c2, const X3PairPlan& pp, hipStream_t s) {
+#define RQ_X3P2(CODE) \
+  case CODE: x3_pair_go<P1, X3Body<RQ_X3_OPS(CODE), kEpiStore, false, TS>>(c1, c2, pp, s); break
+  switch (c2.pl.code) {
+    RQ_X3P2(0); RQ_X3P2(2); RQ_X3P2(8); RQ_X3P2(10);
+    default: break;   // unreachable: x3_form_built(kX3PairWgrad)
   }
+#undef RQ_X3P2
 }
+// c1 of that pair: k-contiguous A (fp32 / split) x n-contiguous split B; plain or SiLU' (+ dropout)
 template <int TS>
-static bool x3_pair_ts(int k1, const X3Call& c1, const X3Call& c2, dim3 grid, unsigned pad, hipStream_t s, int n1) {
-  switch (k1) {   // c1: k-contiguous A (fp32 / split) x n-contiguous split B; plain or SiLU' (+ dropout)
-    case 16 | 2: x3_pair_p2<X3Body<true, false, false, true, kEpiStore, false, TS>, TS>(c1, c2, grid, pad, s, n1); return true;
-    case 16 | 8 | 2: x3_pair_p2<X3Body<true, true, false, true, kEpiStore, false, TS>, TS>(c1, c2, grid, pad, s, n1); return true;
-    case 16 | 2 | 32: x3_pair_p2<X3Body<true, false, false, true, kEpiSiluBwd, false, TS>, TS>(c1, c2, grid, pad, s, n1); return true;
-    case 16 | 2 | 64: x3_pair_p2<X3Body<true, false, false, true, kEpiSiluBwd, true, TS>, TS>(c1, c2, grid, pad, s, n1); return true;
-    default: return false;
+static void x3_pair_grad(const X3Call& c1, const X3Call& c2, const X3PairPlan& pp, hipStream_t s) {
+#define RQ_X3P1(EP, CODE, DR) x3_pair_p2<X3Body<RQ_X3_OPS(CODE), EP, DR, TS>, TS>(c1, c2, pp, s)
+  switch (RQ_X3_KEY(c1.pl.epi_k, c1.pl.code)) {
+    case RQ_X3_KEY(kEpiStore, 18): RQ_X3P1(kEpiStore, 18, false); break;
+    case RQ_X3_KEY(kEpiStore, 26): RQ_X3P1(kEpiStore, 26, false); break;
+    case RQ_X3_KEY(kEpiSiluBwd, 18):
+      if (c1.pl.drop) RQ_X3P1(kEpiSiluBwd, 18, true); else RQ_X3P1(kEpiSiluBwd, 18, false);
+      break;
+    default: break;   // unreachable: x3_form_built(kX3PairDgrad)
   }
+#undef RQ_X3P1
 }
-
+// two forward projections: k-contiguous A (fp32 / split) x k-contiguous split B, plain store
 template <int TS>
-static bool x3_pair_fwd_ts(const X3Call& c1, const X3Call& c2, dim3 grid, unsigned pad, hipStream_t s, int n1) {
-  using F32 = X3Body<true, false, true, true, kEpiStore, false, TS>;   // fp32 A
-  using SPL = X3Body<true, true, true, true, kEpiStore, false, TS>;    // split A
-  const bool a1 = c1.asp, a2 = c2.asp;
-  if (!a1 && !a2) x3_pair_go<F32, F32>(c1, c2, grid, pad, s, n1);
-  else if (!a1) x3_pair_go<F32, SPL>(c1, c2, grid, pad, s, n1);
-  else if (!a2) x3_pair_go<SPL, F32>(c1, c2, grid, pad, s, n1);
-  else x3_pair_go<SPL, SPL>(c1, c2, grid, pad, s, n1);
-  return true;
+static void x3_pair_fwd(const X3Call& c1, const X3Call& c2, const X3PairPlan& pp, hipStream_t s) {
+  using F32 = X3Body<RQ_X3_OPS(22), kEpiStore, false, TS>;   // fp32 A
+  using SPL = X3Body<RQ_X3_OPS(30), kEpiStore, false, TS>;   // split A
+  const bool a1 = c1.pl.code == 30, a2 = c2.pl.code == 30;
+  if (!a1 && !a2) x3_pair_go<F32, F32>(c1, c2, pp, s);
+  else if (!a1) x3_pair_go<F32, SPL>(c1, c2, pp, s);
+  else if (!a2) x3_pair_go<SPL, F32>(c1, c2, pp, s);
+  else x3_pair_go<SPL, SPL>(c1, c2, pp, s);
 }
 
-// The paired launch of a data-gradient problem c1 and a weight-gradient problem c2 (both on the 128- or
-// 64-tile kernel with the same tile size), for the operand forms of the decoder's backward: c1 = g W
-// (A fp32 or split k-contiguous, B split n-contiguous; plain or SiLU'-with-dropout epilogue), c2 = g^T x
-// (A fp32 or split m-contiguous, B fp32 or split n-contiguous, plain). false: no instantiation.
-static int x3_pair_k1(const X3Call& c1) {
-  const bool drop1 = c1.xa.ep.thr != 0 && c1.epi_k != kEpiStore;
-  return c1.code | (c1.epi_k == kEpiSiluBwd ? (drop1 ? 64 : 32) : (c1.epi_k == kEpiStore ? 0 : 128));
+static void x3_pair_launch(const X3Call& c1, const X3Call& c2, const X3PairPlan& pp, hipStream_t s) {
+  const bool t64 = c1.pl.kind == kX3Tile64;
+  if (pp.kind == kX3PairFwd)
+    t64 ? x3_pair_fwd<64>(c1, c2, pp, s) : x3_pair_fwd<128>(c1, c2, pp, s);
+  else
+    t64 ? x3_pair_grad<64>(c1, c2, pp, s) : x3_pair_grad<128>(c1, c2, pp, s);
 }
+#undef RQ_X3_OPS
+#undef RQ_X3_KEY
 
-// The two problems can share a launch: both on the 128- / 64-tile kernel with one tile size, an instantiated
-// form pair, and at least one of them leaving resident slots idle alone (the decoder's 40..11,332-row
-// launches; two launches that each fill the chip already — the RQ-VAE's 65,536-row 64-tile layers — gain
-// nothing and measured 4 us slower paired).
-// Two forward projections of different inputs (the decoder block's self-attention qkv of attn_norm(x) and
-// cross-attention q of cross_attn_norm(x)): k-contiguous A (fp32 / split) x k-contiguous split B, plain store.
-static bool x3_fwd_form(const X3Call& c) {
-  return c.epi_k == kEpiStore && (c.code == (16 | 4 | 2) || c.code == (16 | 8 | 4 | 2));
-}
-
-static bool x3_pairable(const X3Call& c1, const X3Call& c2) {
-  if (c1.wide || c2.wide || c1.pl.ts != c2.pl.ts) return false;
-  const bool fwd = x3_fwd_form(c1) && x3_fwd_form(c2);
-  if (!fwd) {
-    if (c2.epi_k != kEpiStore || c2.code != (c2.code & (8 | 2))) return false;   // c2: m-contig A, n-contig B
-    const int k1 = x3_pair_k1(c1);
-    if (k1 != (16 | 2) && k1 != (16 | 8 | 2) && k1 != (16 | 2 | 32) && k1 != (16 | 2 | 64)) return false;
-  }
-  const int64_t w1 = (int64_t)c1.pl.tiles * c1.pl.S, w2 = (int64_t)c2.pl.tiles * c2.pl.S;
-  const int64_t slots = c1.pl.ts == 64 ? (int64_t)x3s_resident(w1 + w2) * (resident_slots() / 2) : x3_slots();
-  return !(w1 >= slots && w2 >= slots);
-}
-
-static bool x3_pair_launch(const X3Call& c1, const X3Call& c2, hipStream_t s) {
-  if (!x3_pairable(c1, c2)) return false;
-  const int64_t w1 = (int64_t)c1.pl.tiles * c1.pl.S, w2 = (int64_t)c2.pl.tiles * c2.pl.S;
-  const int n1 = c1.pl.per * 8, n2 = c2.pl.per * 8;
-  const dim3 grid((unsigned)(n1 + n2));
-  const bool t64 = c1.pl.ts == 64;
-  unsigned pad = 0;
-  if (t64 && x3s_resident(w1 + w2) == kXWG) pad = 32768u;   // few workgroups: 2 per CU (x3s_pad_lds)
-  if (x3_fwd_form(c1) && x3_fwd_form(c2))
-    return t64 ? x3_pair_fwd_ts<64>(c1, c2, grid, pad, s, n1) : x3_pair_fwd_ts<128>(c1, c2, grid, 0u, s, n1);
-  const int k1 = x3_pair_k1(c1);
-  return t64 ? x3_pair_ts<64>(k1, c1, c2, grid, pad, s, n1) : x3_pair_ts<128>(k1, c1, c2, grid, 0u, s, n1);
-}
-
-// ---------------------------------------------------------------------------------------------
-// Grouped weight gradients (gemm_x3w_group_kernel): the dW = g^T x problems of one MLP chain share the batch
-// as K and nothing in the backward waits for them, so they can share one launch in which each member takes
-// its proportional share of the chip on the wide tile, instead of each filling 256 CUs alone (the big layer
-// in many short chunks, the small ones on the 128- / 64-tile kernels at 2-4x the LDS fill per MFMA).
-// The plan: one step budget T (k steps of 32 per workgroup) for every member, S_p = ceil(K / 32 T) chunks
-// each, the whole group in one round of workgroups.
-// ---------------------------------------------------------------------------------------------
-// k steps per grouped workgroup at least: the wide loop's prologue and epilogue cost about 20 steps' worth
-// (profiles/r06/gemm_diag/wgrad_policy.jsonl: 512 x 256 x 65,536 at S = 128, 16 steps per workgroup, 65.9 us
-// against 62.4 us on the 128-tile kernel; at 49 steps the wide tile wins), so a budget under 32 steps is
-// mostly ramp. Never below the wide kernel's own kX3WMinSteps.
-constexpr int kX3GMinSteps = 32;
-static_assert(kX3GMinSteps >= kX3WMinSteps, "the group's step budget respects the wide kernel's minimum");
-// Rows (K) from which the model may group. Measured at the RQ-VAE's 65,536 rows only (profiles/r07/group_wgrad);
-// the decoder's 40..11,332-row chains pair each weight gradient with its data gradient (gemm_x3_pair_kernel),
-// which a grouped member gives up and the model does not price: they stay ungrouped until measured.
-constexpr int64_t kX3GMinK = 32768;
-
-struct X3GroupPlan {
-  int n;                       // members sharing the launch (0: no group)
-  bool in[kX3GroupMax];
-  X3Plan pl[kX3GroupMax];      // a member's wide plan (tiles, S, chunk)
-};
-
-// A problem the group kernel can run: split m/n-contiguous operands, plain store, whole k steps, no kernel
-// policy of its own, and the wide kernel's operand conditions (dims % 8 by x3_prepare; x3w_spans_ok).
-static bool x3_group_member(const rq_gemm_desc& d, const X3Call& c) {
-  return !c.trivial && c.asp && c.bsp && !c.a_kc && !c.b_kc && c.epilogue == kEpiStore && (c.flags & 0xFFFF) == 0 &&
-         c.K % 32 == 0 && c.M % 8 == 0 && c.N % 8 == 0 && d.ldc == c.N &&
-         x3w_spans_ok(c.M, c.N, c.K, c.xa.lda, c.xa.ldb, false, false);
-}
-
-// Modelled time (us) of the members `in` at step budget T, with x3_plan_time's constants: one round of wide
-// workgroups of at most T steps each, every member's slabs written and read back, one reduction launch.
-// < 0: the group does not fit one round.
-static double x3_group_time(const X3Call* c, int count, const bool* in, int64_t T, X3Plan* pl) {
-  const int64_t cus = resident_slots() / 2;
-  int64_t wgs = 0, steps = 0;
-  double slab = 0;
-  for (int i = 0; i < count; ++i) {
-    if (!in[i]) continue;
-    const int64_t nk = c[i].K / 32;
-    pl[i] = x3_plan_s(c[i].M, c[i].N, c[i].K, (nk + T - 1) / T, true);
-    wgs += (int64_t)pl[i].tiles * pl[i].S;
-    steps = std::max(steps, pl[i].chunk / 32);
-    slab += (double)(2 * pl[i].S) * (double)(c[i].M * c[i].N) * 4.0;
-  }
-  if (wgs > cus) return -1.0;
-  return (double)kWT2 * kWT2 * 32.0 * (double)steps / (kX3Rate2 * kX3WSpeed * 1e6) + slab / kX3SlabBpus + kX3ReduceUs;
-}
-
-// Best budget for the members `in`: the modelled saving (us) against their separate plans, <= 0 when
-// grouping them does not pay or cannot run in one round.
-static double x3_group_gain(const X3Call* c, int count, const bool* in, X3Plan* best) {
-  int n = 0;
-  int64_t K = -1;
-  double apart = 0;
-  for (int i = 0; i < count; ++i) {
-    if (!in[i]) continue;
-    if (K >= 0 && c[i].K != K) return 0;
-    K = c[i].K;
-    apart += x3_plan_time(c[i].pl, c[i].M, c[i].N, c[i].wide);
-    ++n;
-  }
-  if (n < 2 || K < kX3GMinK) return 0;
-  double tbest = -1;
-  X3Plan pl[kX3GroupMax] = {};
-  for (int64_t T = kX3GMinSteps; T <= K / 32; ++T) {
-    const double t = x3_group_time(c, count, in, T, pl);
-    if (t >= 0 && (tbest < 0 || t < tbest)) {
-      tbest = t;
-      for (int i = 0; i < count; ++i)
-        if (in[i]) best[i] = pl[i];
-    }
-  }
-  return tbest < 0 ? 0 : apart - tbest;
-}
-
-// Which of the problems share one grouped launch. Members that carry an explicit split count (RQ_GEMM_SPLIT)
-// are grouped as told: the only way rq_gemm_bf16x3_group itself groups (model = false). The model's common
-// step budget gives the members other split counts than their separate plans, which changes the fp32
-// summation order of their results (RQ-VAE step: 5.7 % faster, loss after 25 steps 1.1e-4 off the ungrouped
-// run's, profiles/r07/group_wgrad), so taking its plan is the caller's decision: rq_gemm_bf16x3_group_plan
-// reports it (model = true) and the caller passes the counts back as explicit ones. The model drops one
-// member at a time while that raises the modelled saving (a mostly empty tile, 128 x 64, costs the group a
-// whole tile's steps and stays in its own launch), and groups only when the rest beats its separate plans.
-static X3GroupPlan x3_group_plan(const rq_gemm_desc* d, const X3Call* c, int count, bool model) {
-  X3GroupPlan g{};
-  if (count < 2 || count > kX3GroupMax) return g;
-  bool el[kX3GroupMax] = {}, forced = false;
-  for (int i = 0; i < count; ++i) {
-    if (d[i].flags & RQ_GEMM_NO_GROUP) return g;
-    el[i] = x3_group_member(d[i], c[i]);
-    forced = forced || ((d[i].flags >> RQ_GEMM_SPLIT_SHIFT) & RQ_GEMM_SPLIT_MASK) > 0;
-  }
-  if (forced) {
-    for (int i = 0; i < count; ++i) {
-      const int fs = (d[i].flags >> RQ_GEMM_SPLIT_SHIFT) & RQ_GEMM_SPLIT_MASK;
-      if (!el[i] || fs < 2) continue;
-      const X3Plan p = x3_plan_s(c[i].M, c[i].N, c[i].K, fs, true);
-      if (p.S < 2) continue;
-      g.in[i] = true;
-      g.pl[i] = p;
-      ++g.n;
-    }
-  } else if (model) {
-    double gain = x3_group_gain(c, count, el, g.pl);
-    for (;;) {
-      int drop = -1;
-      X3Plan pl[kX3GroupMax] = {};
-      for (int j = 0; j < count; ++j) {
-        if (!el[j]) continue;
-        el[j] = false;
-        const double gj = x3_group_gain(c, count, el, pl);
-        el[j] = true;
-        if (gj > gain) {
-          gain = gj;
-          drop = j;
-        }
-      }
-      if (drop < 0) break;
-      el[drop] = false;
-      gain = x3_group_gain(c, count, el, g.pl);
-    }
-    if (gain > 0)
-      for (int i = 0; i < count; ++i) {
-        g.in[i] = el[i] && g.pl[i].S >= 2;
-        g.n += g.in[i];
-      }
-    if (g.n != (int)std::count(el, el + count, true)) g.n = 0;   // an unsplit member: the plan does not hold
-  }
-  if (g.n < 2) {
-    g.n = 0;
-    for (int i = 0; i < count; ++i) g.in[i] = false;
-  }
-  return g;
-}
-
+// The grouped launch of the members of g (gemm_plan.h: x3_group_plan), each to split-K slabs in its own workspace.
 static int x3_group_launch(const rq_gemm_desc* d, const X3Call* c, int count, const X3GroupPlan& g, hipStream_t s) {
   X3WGroup w{};
-  int n = 0, first = 0;
+  int n = 0;
   for (int i = 0; i < count; ++i) {
     if (!g.in[i]) continue;
     const X3Plan& pl = g.pl[i];
-    const size_t need = (size_t)pl.S * (size_t)(c[i].M * c[i].N) * sizeof(float);
-    RQ_CHECK_ARG(d[i].workspace != nullptr && d[i].ws_bytes >= need && ((uintptr_t)d[i].workspace) % 16 == 0,
-                 "rq_gemm_bf16x3_group: member %d needs workspace %zu >= %zu bytes", i, d[i].ws_bytes, need);
-    RQ_CHECK_ARG(pl.chunk % 32 == 0 && (int64_t)(pl.S - 1) * pl.chunk < c[i].K, "rq_gemm_bf16x3_group: bad plan");
-    X3WProb& q = w.p[n];
-    q.Ah = static_cast<const uint16_t*>(c[i].xa.A);
-    q.Al = static_cast<const uint16_t*>(c[i].xa.Al);
-    q.lda = c[i].xa.lda;
-    q.Bh = static_cast<const uint16_t*>(c[i].xa.B);
-    q.Bl = static_cast<const uint16_t*>(c[i].xa.Bl);
-    q.ldb = c[i].xa.ldb;
-    q.K = c[i].K;
-    q.chunk = pl.chunk;
-    q.slabs = static_cast<float*>(d[i].workspace);
-    q.M = (int)c[i].M;
-    q.N = (int)c[i].N;
-    q.tiles_n = pl.tiles_n;
-    q.tiles = pl.tiles;
-    q.S = pl.S;
-    w.first[n++] = first;
-    first += pl.tiles * pl.S;
+    const X3Args& xa = c[i].xa;
+    RQ_CHECK_ARG(d[i].workspace != nullptr && d[i].ws_bytes >= pl.slab_bytes && ((uintptr_t)d[i].workspace) % 16 == 0,
+                 "rq_gemm_bf16x3_group: member %d needs workspace %zu >= %zu bytes", i, d[i].ws_bytes, pl.slab_bytes);
+    w.p[n] = X3WProb{static_cast<const uint16_t*>(xa.A), static_cast<const uint16_t*>(xa.Al), xa.lda,
+                     static_cast<const uint16_t*>(xa.B), static_cast<const uint16_t*>(xa.Bl), xa.ldb, xa.K, pl.chunk,
+                     static_cast<float*>(d[i].workspace), xa.M, xa.N, pl.tiles_n, pl.tiles, pl.S, 0};
+    w.first[n + 1] = w.first[n] + (int)pl.grid;   // the members' work items, in order: one round when the model grouped
+    ++n;
   }
-  w.first[n] = first;
   w.count = n;
-  hipLaunchKernelGGL(gemm_x3w_group_kernel, dim3((unsigned)first), dim3(512), 0, s, w);
+  hipLaunchKernelGGL(gemm_x3w_group_kernel, dim3((unsigned)w.first[n]), dim3(512), 0, s, w);
   RQ_LAUNCH_CHECK("gemm_x3w_group_kernel");
   return 0;
+}
+
+// Plan `count` descriptors without a stream (the host-only *_plan entry points). false: one is empty or invalid.
+static bool x3_plan_only(const rq_gemm_desc* d, int count, X3Call* c) {
+  for (int i = 0; i < count; ++i)
+    if (d[i].M <= 0 || d[i].N <= 0 || d[i].K <= 0 || x3_prepare(d[i], nullptr, &c[i], true) != 0) return false;
+  return true;
+}
+
+static X3GroupPlan x3_group_of(const rq_gemm_desc* d, const X3Call* c, int count, bool model) {
+  X3Shape sh[kX3GroupMax];
+  X3Plan own[kX3GroupMax];
+  for (int i = 0; i < count; ++i) {
+    sh[i] = x3_shape(d[i]);
+    own[i] = c[i].pl;
+  }
+  return x3_group_plan(sh, own, count, model, x3_cus());
 }
 
 }  // namespace rqhip
@@ -1917,23 +1446,26 @@ int rq_gemm_bf16x3_pair(const rq_gemm_desc* d, int* splits, void* stream) {
     const int rc = x3_prepare(d[i], s, &c[i]);
     if (rc) return rc;
   }
-  const bool no_pair = ((d[0].flags | d[1].flags) & RQ_GEMM_NO_PAIR) != 0;
-  if (c[0].trivial || c[1].trivial || no_pair || !x3_pair_launch(c[0], c[1], s)) {
+  X3PairPlan pp{};
+  if (!c[0].trivial && !c[1].trivial && !((d[0].flags | d[1].flags) & RQ_GEMM_NO_PAIR))
+    pp = x3_pair_plan(c[0].pl, c[1].pl, x3_cus());
+  if (pp.kind) {
+    x3_pair_launch(c[0], c[1], pp, s);
+    RQ_LAUNCH_CHECK("gemm_x3_pair_kernel");
+  } else {
     for (int i = 0; i < 2; ++i) {
       if (c[i].trivial) continue;
       const int rl = x3_launch(c[i], s);
       if (rl) return rl;
     }
-  } else {
-    RQ_LAUNCH_CHECK("gemm_x3_pair_kernel");
   }
   // two plain-store slab outputs: one batched reduction (rq_reduce_partials layout 0 = x3_reduce_kernel's
   // order, bitwise) instead of two launches
-  auto plain_slab = [](const X3Call& x) { return !x.trivial && x.slab && x.epilogue == kEpiStore && !x.accumulate; };
+  auto plain_slab = [](const X3Call& x) { return x.pl.slab && x.epilogue == kEpiStore && !x.accumulate; };
   if (plain_slab(c[0]) && plain_slab(c[1])) {
-    const float* P[2] = {c[0].out, c[1].out};
+    const float* P[2] = {c[0].xa.C, c[1].xa.C};
     float* out[2] = {c[0].C, c[1].C};
-    const int64_t n[2] = {c[0].M * c[0].N, c[1].M * c[1].N};
+    const int64_t n[2] = {(int64_t)c[0].xa.M * c[0].xa.N, (int64_t)c[1].xa.M * c[1].xa.N};
     const int S[2] = {c[0].pl.S, c[1].pl.S}, layout[2] = {0, 0}, acc[2] = {0, 0};
     return rq_reduce_partials(2, P, out, n, S, layout, acc, stream);
   }
@@ -1947,21 +1479,22 @@ int rq_gemm_bf16x3_pair(const rq_gemm_desc* d, int* splits, void* stream) {
 
 int rq_gemm_bf16x3_plan(const rq_gemm_desc* d, int* splits) {
   if (splits) *splits = 0;
-  if (!d || d->M <= 0 || d->N <= 0 || d->K <= 0) return -1;
   X3Call c;
-  if (x3_prepare(*d, nullptr, &c, true) != 0) return -1;
+  if (!d || !x3_plan_only(d, 1, &c)) return -1;
   if (splits) *splits = c.pl.S;
-  return c.wide ? 1 : (c.pl.ts == 64 ? 2 : 0);
+  return c.pl.kind;
 }
 
 int rq_gemm_bf16x3_pair_plan(const rq_gemm_desc* d) {
-  if (!d || ((d[0].flags | d[1].flags) & RQ_GEMM_NO_PAIR)) return 0;
   X3Call c[2];
-  for (int i = 0; i < 2; ++i) {
-    if (d[i].M <= 0 || d[i].N <= 0 || d[i].K <= 0) return 0;
-    if (x3_prepare(d[i], nullptr, &c[i], true) != 0) return 0;
-  }
-  return x3_pairable(c[0], c[1]) ? 1 : 0;
+  if (!d || ((d[0].flags | d[1].flags) & RQ_GEMM_NO_PAIR) || !x3_plan_only(d, 2, c)) return 0;
+  return x3_pair_plan(c[0].pl, c[1].pl, x3_cus()).kind ? 1 : 0;
+}
+
+int rq_gemm_bf16x3_pair_resplit(const rq_gemm_desc* d) {
+  X3Call c[2];
+  if (!d || !x3_plan_only(d, 2, c)) return 0;
+  return x3_pair_resplit(c[0].pl, c[1].pl, d[0].K, d[1].K, x3_cus());
 }
 
 // Up to kX3GroupMax independent calls, the weight gradients of one MLP chain: the members that carry explicit
@@ -1980,7 +1513,7 @@ int rq_gemm_bf16x3_group(const rq_gemm_desc* d, int count, int* splits, void* st
     const int rc = x3_prepare(d[i], s, &c[i]);
     if (rc) return rc;
   }
-  const X3GroupPlan g = x3_group_plan(d, c, count, false);
+  const X3GroupPlan g = x3_group_of(d, c, count, false);
   if (g.n) {
     const int rl = x3_group_launch(d, c, count, g, s);
     if (rl) return rl;
@@ -2001,7 +1534,7 @@ int rq_gemm_bf16x3_group(const rq_gemm_desc* d, int count, int* splits, void* st
     } else {
       P[nr] = static_cast<const float*>(d[i].workspace);
       out[nr] = c[i].C;
-      n[nr] = c[i].M * c[i].N;
+      n[nr] = (int64_t)c[i].xa.M * c[i].xa.N;
       S[nr] = g.pl[i].S;
       layout[nr] = 0;
       acc[nr++] = c[i].accumulate != 0;
@@ -2013,13 +1546,9 @@ int rq_gemm_bf16x3_group(const rq_gemm_desc* d, int count, int* splits, void* st
 int rq_gemm_bf16x3_group_plan(const rq_gemm_desc* d, int count, int* splits) {
   if (splits)
     for (int i = 0; i < count && i < kX3GroupMax; ++i) splits[i] = 0;
-  if (!d || count < 2 || count > kX3GroupMax) return 0;
   X3Call c[kX3GroupMax];
-  for (int i = 0; i < count; ++i) {
-    if (d[i].M <= 0 || d[i].N <= 0 || d[i].K <= 0) return 0;
-    if (x3_prepare(d[i], nullptr, &c[i], true) != 0) return 0;
-  }
-  const X3GroupPlan g = x3_group_plan(d, c, count, true);
+  if (!d || count < 2 || count > kX3GroupMax || !x3_plan_only(d, count, c)) return 0;
+  const X3GroupPlan g = x3_group_of(d, c, count, true);
   if (splits)
     for (int i = 0; i < count; ++i) splits[i] = g.in[i] ? g.pl[i].S : 0;
   return g.n;

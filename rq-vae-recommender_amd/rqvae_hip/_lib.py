@@ -57,6 +57,7 @@ _SIGS = {
     "rq_ce_loss_bwd": ([_P, _I64, _I64, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P], _I),
     "rq_gemm_bf16x3_pair": ([_P, _P, _P], _I),
     "rq_gemm_bf16x3_pair_plan": ([_P], _I),
+    "rq_gemm_bf16x3_pair_resplit": ([_P], _I),
     "rq_gemm_bf16x3_group": ([_P, _I, _P, _P], _I),
     "rq_gemm_bf16x3_group_plan": ([_P, _I, _P], _I),
     "rq_segment_sum_multi_workspace": ([_I, _P, _P, _I64], _SZ),

@@ -525,8 +525,8 @@ def _x3_setup(a, a_kcontig: bool, b, b_kcontig: bool, M: int, N: int, K: int, ep
     flags = _GEMM_POLICY["flags"] if flags is None else int(flags)   # per-call override (probes)
     nbytes = _x3_workspace(M, N, K)
     forced = (flags >> GEMM_SPLIT_SHIFT) & GEMM_SPLIT_MASK
-    if forced > 1:   # a forced split count: its slabs (the library sizes only the planner's)
-        nbytes = max(nbytes, forced * M * N * 4)
+    if forced > 1:   # a forced split count: its slabs (the library sizes only the planner's), at most forced of
+        nbytes = max(nbytes, forced * M * N * 4)   # them: X3Plan.slab_bytes of csrc/gemm_plan.h, S x M x N fp32
     ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8) if nbytes else None
     defer = bool(defer and accumulate and nbytes)
     if defer and C.data_ptr() in _DEFER["outs"]:
@@ -682,28 +682,17 @@ def _spec_key(sp: dict):
 
 def _bwd_pair(dspec: dict, wspec: dict):
     """gemm_x3_pair of a Linear's data gradient (dspec) and weight gradient (wspec) with the weight gradient's
-    split count chosen for the PAIR: where the data gradient alone leaves resident slots idle (128-tile
-    kernel, unsplit), the weight gradient's k chunks are sized like the data gradient's K (S = ceil(rows / K_d))
-    when that is fewer slabs than its own plan and the pair still spans more than one round of workgroups —
-    equal-length workgroups instead of a tail of short ones, and fewer slabs (measured on the paired launches of
-    the decoder's 11k-row qkv / MLP-up layers: 152 -> 127 and 93 -> 85 us, tools/pair_split_probe.py)."""
+    split count chosen for the PAIR (rq_gemm_bf16x3_pair_resplit; the rule is csrc/gemm_plan.h's x3_pair_resplit):
+    k chunks as long as the data gradient's K where that balances the paired launch."""
     if _PAIR_RESPLIT and (_GEMM_POLICY["flags"] & ~GEMM_NO_GROUP) == 0 and wspec.get("flags") is None and \
             int(wspec.get("epilogue", EPI_STORE)) == EPI_STORE:
         key = (_spec_key(dspec), _spec_key(wspec))
         S = _RESPLIT_CACHE.get(key)
         if S is None:
-            S = 0
-            kd, sd = gemm_x3_choice(*key[0][:3], key[0][5], key[0][6], key[0][3], key[0][4], key[0][7])
-            kw, sw = gemm_x3_choice(*key[1][:3], key[1][5], key[1][6], key[1][3], key[1][4], EPI_STORE)
-            if kd == "x3" and kw == "x3" and sd == 1 and sw > 1:
-                slots = 2 * torch.cuda.get_device_properties(dspec["a"].hi.device if isinstance(dspec["a"], Split)
-                                                             else dspec["a"].device).multi_processor_count
-                w1 = -(-int(dspec["M"]) // 128) * -(-int(dspec["N"]) // 128)
-                t2 = -(-int(wspec["M"]) // 128) * -(-int(wspec["N"]) // 128)
-                s_bal = -(-int(wspec["K"]) // int(dspec["K"]))
-                if w1 < slots and 1 < s_bal < sw and w1 + t2 * s_bal > slots:
-                    S = s_bal
-            _RESPLIT_CACHE[key] = S
+            D = _desc_type()
+            pair = (D * 2)(_plan_desc(*key[0][:3], key[0][5], key[0][6], key[0][3], key[0][4], key[0][7]),
+                           _plan_desc(*key[1][:3], key[1][5], key[1][6], key[1][3], key[1][4], EPI_STORE))
+            S = _RESPLIT_CACHE[key] = int(_lib.load().rq_gemm_bf16x3_pair_resplit(pair))
         if S:
             wspec = dict(wspec, flags=gemm_split(S))
     return gemm_x3_pair(dspec, wspec)
@@ -840,15 +829,20 @@ def pending_reductions() -> int:
     return len(_DEFER["pending"]) + len(_EMB["pending"])
 
 
+def _plan_desc(M, N, K, a_split, b_split, a_kcontig, b_kcontig, epilogue):
+    """A descriptor for the host-only planning entry points: no real pointers, dense operands, the current policy."""
+    return _desc_type()(A_lo=16 if a_split else None, lda=K if a_kcontig else M, a_kcontig=int(a_kcontig),
+                        B_lo=16 if b_split else None, ldb=K if b_kcontig else N, b_kcontig=int(b_kcontig), M=M, N=N, K=K,
+                        ldc=N, epilogue=int(epilogue), ldh=N, flags=_GEMM_POLICY["flags"])
+
+
 def gemm_x3_choice(M: int, N: int, K: int, a_split: bool, b_split: bool, a_kcontig: bool, b_kcontig: bool,
                    epilogue: int = EPI_STORE):
     """(kernel, splits) rq_gemm_bf16x3_run picks for a call under the current gemm_policy: kernel 'wide'
     (256 x 256 tiles, LDS-DMA, both operands split), 'x3' (128 x 128 tiles) or 'x3s' (its 64 x 64-tile
     form); 'none' for an empty or invalid shape. Host-only (rq_gemm_bf16x3_plan)."""
     import ctypes
-    d = _desc_type()(A_lo=16 if a_split else None, lda=K if a_kcontig else M, a_kcontig=int(a_kcontig),
-                     B_lo=16 if b_split else None, ldb=K if b_kcontig else N, b_kcontig=int(b_kcontig), M=M, N=N, K=K,
-                     ldc=N, epilogue=int(epilogue), ldh=N, flags=_GEMM_POLICY["flags"])
+    d = _plan_desc(M, N, K, a_split, b_split, a_kcontig, b_kcontig, epilogue)
     s_ = ctypes.c_int(0)
     k = _lib.load().rq_gemm_bf16x3_plan(ctypes.byref(d), ctypes.byref(s_))
     return {1: "wide", 2: "x3s", 0: "x3"}.get(k, "none"), int(s_.value)

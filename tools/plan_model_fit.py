@@ -1,6 +1,6 @@
 """Offline check of the split-bf16 GEMM planner's time model against measured plan sweeps
-(tools/x3_plan_sweep.py output): re-implements x3_plan / x3w_choose (csrc/linear.hip) with adjustable
-constants, lets the model pick (kernel, S) for every recorded call, and prices the pick with the measured
+(tools/x3_plan_sweep.py output): re-implements x3_plan / x3w_choose (csrc/gemm_plan.h) with adjustable
+constants — on purpose a second copy, the header's constants are fixed — lets the model pick (kernel, S) for every recorded call, and prices the pick with the measured
 time of that plan (nearest measured S of the same kernel). Prints, per constant set, the step total of the
 model's picks against the per-call measured optimum.
 
