@@ -686,6 +686,40 @@ int varlen_attn_plan(int backward, int64_t B, int64_t H, int64_t hd, int64_t max
  *   under the lowest allowed one). ALL outputs must arrive ZEROED. The reductions are bit OR and index MIN: the result
  *   does not depend on the order, two runs give the same bits. A leaf outside [0, n_leaves) or an ancestor outside
  *   [0, n_nodes) is skipped. D <= RQ_BEAM_MAX_T, else -22; G == 0 or n_leaves == 0 returns 0 without a launch.
+ * rq_trie_bias_nodes: the tables of a per-item score bias, in TWO launches and no host read (capturable in a graph).
+ *   bias (G, n_items) fp32: bias[g][i] is what group g adds to corpus item i's score; it is read CLEANED: NaN and +inf
+ *   as -inf (a bad value can only hide an item; -inf means "never show"), -0.0 as +0.0. item_leaf, leaf_anc, n_nodes
+ *   as rq_trie_allowed_nodes takes them (leaf_anc, n_nodes and out_upper are HOST arrays of D entries copied into the
+ *   kernel arguments). out_upper[q - 1]: (G, n_nodes[q - 1]) fp32, per group every level-q node's BOUND: the largest
+ *   cleaned bias of an item below it, -inf if it has none — no completion of that prefix can gain more, and at the
+ *   leaves it is the chosen item's own bias. out_leaf_item (G, n_leaves) int64: the lowest corpus index among the
+ *   items on that leaf that attain the leaf's bound, -1 if the bound is -inf (ItemFilter.leaf_item's rule: a row that
+ *   several items share is reported under one definite item). ALL outputs must arrive ZEROED; no workspace is needed
+ *   (the reduction runs in the outputs: an integer max over the order-preserving image of the float per node, one
+ *   64-bit max of (that image << 32 | ~item) per leaf, turned into floats / items in place by the second launch). No
+ *   float atomic: the result does not depend on the order, two runs give the same bits. A leaf outside [0, n_leaves)
+ *   or an ancestor outside [0, n_nodes) is skipped. n_items < 2^31; D <= RQ_BEAM_MAX_T, else -22; G == 0 or
+ *   n_leaves == 0 returns 0 without a launch.
+ * rq_beam_expand_biased: rq_beam_expand's step ranked by "log p + a bound on what the items below can still gain"
+ *   (per-item score bias: promotions, de-biasing, priors, a second ranker's score), one launch. The arguments are
+ *   rq_beam_expand's with out_score (B, k) fp32 after out_lp and, in place of allowed / n_words / G / group,
+ *   bias (G, n_bias) fp32 — the level-(P + 1) slice of rq_trie_bias_nodes' out_upper — n_bias, G and group (B) int32:
+ *   batch element b reads row group[b]; a group outside [0, G) (-1 is the documented spelling), or group == NULL,
+ *   leaves it UNBIASED. blocked / n_blocked are rq_beam_expand's and compose. For child c (token v) of live beam j:
+ *   it is a candidate iff rq_beam_expand would score it and, for a biased user, U = clean(bias[g][c]) > -inf (the
+ *   cleaning of rq_trie_bias_nodes, applied again on the read: NaN and +inf are -inf); lp_c = rq_beam_expand's score,
+ *   the same operations and bits; s_c = lp_c + U, one fp32 add (an unbiased user: s_c = lp_c). The k best by s_c
+ *   descending, ties to the lower beam then the lower token: out_ids, out_parent, out_node as rq_beam_expand;
+ *   out_score = s_c, the ranking key; out_lp = the winner's UNBIASED lp_c — what the next step takes as parent_lp, so
+ *   no bound is ever accumulated: after the last level the bound is the item's own bias and out_score =
+ *   log p(item) + bias[g][item]. Dead rows as rq_beam_expand, out_score -inf. With every group outside [0, G) or an
+ *   all-zero table the first four outputs are rq_beam_expand's bit for bit and out_score == out_lp. Limits are
+ *   rq_beam_expand's and kprev <= 1024 (the beams' softmax statistics stay in LDS for out_lp, three floats per beam);
+ *   n_bias != n_children, n_bias or G negative, bias == NULL with G n_bias > 0: -22 before any launch; the kernel
+ *   never indexes bias outside [0, n_bias). There is no catalogue bitmap here: write a filter into the bias as -inf.
+ * rq_beam_expand_wide_biased: rq_beam_expand_biased in rq_beam_expand_wide's envelope (kprev, k <= 1024, any kprev V),
+ *   the same arguments; where both accept a shape all five outputs are bit for bit the same. There is no biased form
+ *   of rq_beam_expand_sampled: a draw in proportion to p e^bias needs a log-sum over every subtree, not a maximum.
  * rq_rank_hist: actual (B, D) int64 targets, topk (B, k, D) int64 beams; hist (k + 1) int64 is ACCUMULATED into:
  *   hist[r] += #rows whose first beam equal to the target in all D columns has rank r, hist[k] += #rows without one.
  *   Rows with actual[b][0] < 0 are skipped entirely. D <= 64, k <= 1024. D == 1 serves item ids.
@@ -742,6 +776,21 @@ int rq_trie_blocked_nodes(const int64_t* items, int64_t B, int64_t H, const int3
 int rq_trie_allowed_nodes(const bool* mask, int64_t G, int64_t n_items, const int32_t* item_leaf, int64_t n_leaves,
                           const int32_t* const* leaf_anc, const int64_t* n_nodes, int64_t D, int32_t* const* out_bits,
                           int64_t* out_leaf_item, void* stream);
+int rq_trie_bias_nodes(const float* bias, int64_t G, int64_t n_items, const int32_t* item_leaf, int64_t n_leaves,
+                       const int32_t* const* leaf_anc, const int64_t* n_nodes, int64_t D, float* const* out_upper,
+                       int64_t* out_leaf_item, void* stream);
+int rq_beam_expand_biased(const float* logits, float temperature, const int32_t* node, const int32_t* child_off,
+                          int64_t n_nodes, const int32_t* tok, int64_t n_children, const int64_t* parents,
+                          const float* parent_lp, int64_t B, int64_t kprev, int64_t V, int64_t P, int64_t k,
+                          int64_t* out_ids, float* out_lp, float* out_score, int32_t* out_parent, int32_t* out_node,
+                          const int32_t* blocked, int64_t n_blocked, const float* bias, int64_t n_bias, int64_t G,
+                          const int32_t* group, void* stream);
+int rq_beam_expand_wide_biased(const float* logits, float temperature, const int32_t* node, const int32_t* child_off,
+                               int64_t n_nodes, const int32_t* tok, int64_t n_children, const int64_t* parents,
+                               const float* parent_lp, int64_t B, int64_t kprev, int64_t V, int64_t P, int64_t k,
+                               int64_t* out_ids, float* out_lp, float* out_score, int32_t* out_parent,
+                               int32_t* out_node, const int32_t* blocked, int64_t n_blocked, const float* bias,
+                               int64_t n_bias, int64_t G, const int32_t* group, void* stream);
 int rq_rank_hist(const int64_t* actual, const int64_t* topk, int64_t B, int64_t k, int64_t D, int64_t* hist,
                  void* stream);
 int rq_score_paths(const float* logits, float temperature, const int64_t* tokens, int64_t tok_stride_b,

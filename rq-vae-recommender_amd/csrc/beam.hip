@@ -12,7 +12,9 @@
 //                           best in stable order, the parent gather and each winner's trie node. A second
 //                           instantiation (BLOCKED) skips the children found in a per-user sorted row of blocked
 //                           nodes (seen-item exclusion); FILTERED keeps only the children whose bit is set in the
-//                           user's row of a per-group node bitmap (catalogue filters), read from global memory.
+//                           user's row of a per-group node bitmap (catalogue filters), read from global memory;
+//                           BIASED ranks by log p + the user's row of per-group subtree bounds (per-item score bias)
+//                           and writes the unbiased log p beside the ranking score.
 //   beam_expand_wide_kernel the same step for up to 1,024 beams in and out, any kprev * V: the candidates are enumerated
 //                           from the trie instead of kept as a dense key array, the k best come from an exact radix
 //                           select and one LDS sort; bit for bit beam_expand_kernel's outputs where both take the shape.
@@ -26,6 +28,8 @@
 //                           user's exclusion list, sorted / deduplicated / counted in LDS.
 //   trie_allowed_kernel     catalogue filters: per group of an item mask the bitmap of every level's nodes with an
 //                           allowed item below them (bit OR) and every leaf's lowest allowed item (index MIN).
+//   trie_bias_kernel        per-item score bias: per group of a bias table every level's per-node maximum of the items
+//                           below (the bound the biased expand adds) and every leaf's item that attains it.
 //   beam_self_attn_kernel   incremental decoding: the newest token's causal self-attention over its beam's
 //                           ancestors, read in place from every step's packed qkv output through an
 //                           ancestor row table (no per-beam cache is gathered or appended).
@@ -343,6 +347,20 @@ struct AllowedBits {   // FILTERED's arguments; never read otherwise
   const int32_t* group;   // (B)
   int n_words, G;
 };
+struct BiasArgs {   // BIASED's arguments, in AllowedBits' place
+  const float* rows;      // (G, n_bias): the level-(P + 1) subtree bounds
+  const int32_t* group;   // (B), or NULL: nobody is biased
+  int n_bias, G;
+  float* out_score;       // (B, k): the ranking key; out_lp then carries the unbiased log p
+};
+template <bool BIASED>
+using ChildRows = std::conditional_t<BIASED, BiasArgs, AllowedBits>;
+
+// A bias value as every kernel reads it: NaN and +inf are -inf (a bad value can only hide an item), -0.0 is +0.0
+__device__ __forceinline__ float clean_bias(float u) {
+  if (u != u || u == INFINITY) return -INFINITY;
+  return u == 0.0f ? 0.0f : u;
+}
 
 // One level of the trie: the nodes' child offsets and the next level's tokens, as the caller passed them.
 struct TrieLevel {
@@ -359,12 +377,15 @@ struct TrieLevel {
   }
 };
 
-// One user's filters on a level's children: which of them are candidates is stated here and nowhere else.
+// One user's filters on a level's children: which of them are candidates, and what is added to a candidate's score,
+// is stated here and nowhere else.
 struct ChildFilter {
   const int* blk;        // BLOCKED: the user's blocked row, staged in LDS
   int n_blocked;
   const int32_t* arow;   // FILTERED: the user's bitmap row (global memory)
   int n_words;           // < 0: the user is not filtered
+  const float* brow;     // BIASED: the user's row of subtree bounds (global memory)
+  int n_bias;            // < 0: the user is not biased
   // c >= 0, a child index: it has an allowed item below it
   template <bool BLOCKED, bool FILTERED>
   __device__ __forceinline__ bool allowed(int c) const {
@@ -386,11 +407,33 @@ struct ChildFilter {
     }
     return allowed<BLOCKED, FILTERED>(c);
   }
+  // BIASED: the above, and for a biased user a bound above -inf (some item below c may still be shown); add = the
+  // bound, read once (an index outside [0, n_bias) reads as -inf and is never read)
+  template <bool BLOCKED, bool FILTERED, bool BIASED>
+  __device__ __forceinline__ bool candidate(int c, int v, int V, float& add) const {
+    static_assert(!(FILTERED && BIASED), "a filter is written into the bias as -inf");
+    add = 0.0f;
+    if (!candidate<BLOCKED, FILTERED>(c, v, V)) return false;
+    if constexpr (BIASED) {
+      if (n_bias < 0) return true;
+      add = c < n_bias ? clean_bias(brow[c]) : -INFINITY;
+      return add > -INFINITY;
+    }
+    return true;
+  }
+  // the ranking score of a candidate with log-probability lp: one add for a biased user, lp itself otherwise
+  template <bool BIASED>
+  __device__ __forceinline__ float score(float lp, float add) const {
+    if constexpr (BIASED) {
+      if (n_bias >= 0) return lp + add;
+    }
+    return lp;
+  }
 };
-// batch element b's filters over the staged row blk; a group outside [0, G) leaves b unfiltered
+// batch element b's filters over the staged row blk; a group outside [0, G) leaves b unfiltered / unbiased
 template <bool FILTERED>
 __device__ __forceinline__ ChildFilter child_filter(const int* blk, int n_blocked, const AllowedBits& a, int64_t b) {
-  ChildFilter f = {blk, n_blocked, nullptr, -1};
+  ChildFilter f = {blk, n_blocked, nullptr, -1, nullptr, -1};
   if constexpr (FILTERED) {
     const int g = a.group[b];
     if (g >= 0 && g < a.G) {
@@ -400,13 +443,24 @@ __device__ __forceinline__ ChildFilter child_filter(const int* blk, int n_blocke
   }
   return f;
 }
+template <bool FILTERED>
+__device__ __forceinline__ ChildFilter child_filter(const int* blk, int n_blocked, const BiasArgs& a, int64_t b) {
+  ChildFilter f = {blk, n_blocked, nullptr, -1, nullptr, -1};
+  const int g = a.group ? a.group[b] : -1;
+  if (g >= 0 && g < a.G) {
+    f.brow = a.rows + (int64_t)g * a.n_bias;
+    f.n_bias = a.n_bias;
+  }
+  return f;
+}
 
 // The dense kernels' LDS: key[N rounded up to 4], select_rounds' exchange, then (BLOCKED)
-// blk[n_blocked <= kBlockedMax]. Zeroes key[], stages batch element b's blocked row and ends on a barrier.
-template <bool BLOCKED, bool FILTERED>
+// blk[n_blocked <= kBlockedMax], then (BIASED) the beams' row statistics m[kprev], sum[kprev], log_norm[kprev]. Zeroes
+// key[], stages batch element b's blocked row and ends on a barrier. Rows: AllowedBits or BiasArgs.
+template <bool BLOCKED, bool FILTERED, typename Rows>
 __device__ __forceinline__ ChildFilter expand_prologue(char* smem, int N, int64_t b,
                                                        const int32_t* __restrict__ blocked, int n_blocked,
-                                                       const AllowedBits& allowed, uint32_t*& key) {
+                                                       const Rows& allowed, uint32_t*& key) {
   const int tid = threadIdx.x, nthr = blockDim.x;
   key = reinterpret_cast<uint32_t*>(smem);
   int* blk = reinterpret_cast<int*>(key + (N + 3) / 4 * 4 + 2 * kExpMaxWaves);
@@ -422,7 +476,8 @@ __device__ __forceinline__ ChildFilter expand_prologue(char* smem, int N, int64_
 struct ExpandRows {
   int64_t* ids;      // (k, P + 1)
   float* score;      // the selection's score: key_score of the winner's key
-  float* later;      // sampled: out_phi, -inf in a dead row and written after the rounds in a live one; else NULL
+  float* later;      // sampled: out_phi, biased: out_lp — -inf in a dead row and written after the rounds in a live
+                     // one; else NULL
   int32_t* parent;
   int32_t* node;
 };
@@ -452,8 +507,10 @@ __device__ __forceinline__ void expand_write_row(const ExpandRows& o, int r, uin
 }
 // After the rounds, a thread per row: the winner's node, the child of its parent's node (nd0[parent], the root without
 // nd0) that carries its token — the first entry >= v of the node's ascending range; -1: an unsorted (bad) table.
+// live(r, v): whatever else the same thread owes a live row r with token v.
+template <typename Live>
 __device__ __forceinline__ void expand_nodes(const ExpandRows& o, int k, int P, const int32_t* __restrict__ nd0,
-                                             const TrieLevel& lvl) {
+                                             const TrieLevel& lvl, Live live) {
   __syncthreads();   // thread 0's rows (global) are visible to the workgroup
   for (int r = threadIdx.x; r < k; r += blockDim.x) {
     const int v = (int)o.ids[(int64_t)r * (P + 1) + P];
@@ -464,15 +521,25 @@ __device__ __forceinline__ void expand_nodes(const ExpandRows& o, int k, int P, 
       if (!(at < hi && lvl.tok[at] == v)) at = -1;
     }
     o.node[r] = at;
+    live(r, v);
   }
 }
+__device__ __forceinline__ void expand_nodes(const ExpandRows& o, int k, int P, const int32_t* __restrict__ nd0,
+                                             const TrieLevel& lvl) {
+  expand_nodes(o, k, P, nd0, lvl, [](int, int) {});
+}
 
-template <bool BLOCKED, bool FILTERED>
+// BIASED: the ranking key of a candidate is s = lp + the bound of its subtree (ChildFilter::score), so the k best are
+// the k best by what a completion of the prefix can still score; rows.score is then out_score and out_lp, the unbiased
+// lp that the next step adds to, is formed again after the rounds by expand_nodes' thread from the parent beam's
+// statistics, which phase 1 leaves in LDS (three floats per beam behind the blocked row): the operations of phase 1,
+// the same bits. Only this form grows the LDS layout and takes kprev <= kWideMax (the host refuses more).
+template <bool BLOCKED, bool FILTERED, bool BIASED = false>
 __global__ void __launch_bounds__(64 * kExpMaxWaves) beam_expand_kernel(
     const float* __restrict__ logits, float temperature, const int32_t* __restrict__ node, TrieLevel lvl,
     const int64_t* __restrict__ parents, const float* __restrict__ parent_lp, int kprev, int V, int P, int k,
     int64_t* __restrict__ out_ids, float* __restrict__ out_lp, int32_t* __restrict__ out_parent,
-    int32_t* __restrict__ out_node, const int32_t* __restrict__ blocked, int n_blocked, AllowedBits allowed) {
+    int32_t* __restrict__ out_node, const int32_t* __restrict__ blocked, int n_blocked, ChildRows<BIASED> allowed) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nthr = blockDim.x, nwave = nthr >> 6;   // 4 or kExpMaxWaves waves (the host picks by kprev)
@@ -481,6 +548,8 @@ __global__ void __launch_bounds__(64 * kExpMaxWaves) beam_expand_kernel(
   const int32_t* nd0 = node ? node + b * kprev : nullptr;
   uint32_t* key;
   const ChildFilter flt = expand_prologue<BLOCKED, FILTERED>(smem, N, b, blocked, n_blocked, allowed, key);
+  // BIASED: m[kprev], sum[kprev], log_norm[kprev] behind the blocked row
+  float* stat = reinterpret_cast<float*>(key + (N + 3) / 4 * 4 + 2 * kExpMaxWaves) + (BLOCKED ? n_blocked : 0);
 
   for (int j = wave; j < kprev; j += nwave) {
     int lo, hi;
@@ -490,19 +559,43 @@ __global__ void __launch_bounds__(64 * kExpMaxWaves) beam_expand_kernel(
         V, lane, [&](int, int v) { return x[v] / temperature; },
         [&](int, int v, float m) { return x[v] / temperature - m; });
     const float plp = parent_lp ? parent_lp[b * kprev + j] : 0.0f;
-    for (int c = lo + lane; c < hi; c += 64) {
-      const int v = lvl.tok[c];
-      if (!flt.candidate<BLOCKED, FILTERED>(c, v, V)) continue;
-      key[j * V + v] = score_key(log_prob(x[v] / temperature - st.m, st) + plp);
+    if constexpr (BIASED) {
+      if (lane == 0) { stat[j] = st.m; stat[kprev + j] = st.sum; stat[2 * kprev + j] = st.log_norm; }
+      for (int c = lo + lane; c < hi; c += 64) {
+        const int v = lvl.tok[c];
+        float add;
+        if (!flt.candidate<BLOCKED, FILTERED, BIASED>(c, v, V, add)) continue;
+        key[j * V + v] = score_key(flt.score<BIASED>(log_prob(x[v] / temperature - st.m, st) + plp, add));
+      }
+    } else {
+      for (int c = lo + lane; c < hi; c += 64) {
+        const int v = lvl.tok[c];
+        if (!flt.candidate<BLOCKED, FILTERED>(c, v, V)) continue;
+        key[j * V + v] = score_key(log_prob(x[v] / temperature - st.m, st) + plp);
+      }
     }
   }
   __syncthreads();
 
-  const ExpandRows rows = {out_ids + b * k * (P + 1), out_lp + b * k, nullptr, out_parent + b * k, out_node + b * k};
-  select_rounds<kExpMaxWaves>(key, N, k, nthr, [&](int r, uint32_t wk, int wi) {
-    expand_write_row(rows, r, wk, wi, parents + b * kprev * P, V, P);
-  });
-  expand_nodes(rows, k, P, nd0, lvl);
+  if constexpr (BIASED) {
+    const ExpandRows rows = {out_ids + b * k * (P + 1), allowed.out_score + b * k, out_lp + b * k, out_parent + b * k,
+                             out_node + b * k};
+    select_rounds<kExpMaxWaves>(key, N, k, nthr, [&](int r, uint32_t wk, int wi) {
+      expand_write_row(rows, r, wk, wi, parents + b * kprev * P, V, P);
+    });
+    expand_nodes(rows, k, P, nd0, lvl, [&](int r, int v) {
+      const int j = rows.parent[r];   // a live row: a beam that phase 1 scored
+      const RowStats st = {stat[j], stat[kprev + j], stat[2 * kprev + j]};
+      const float plp = parent_lp ? parent_lp[b * kprev + j] : 0.0f;
+      rows.later[r] = log_prob(logits[(b * kprev + j) * V + v] / temperature - st.m, st) + plp;
+    });
+  } else {
+    const ExpandRows rows = {out_ids + b * k * (P + 1), out_lp + b * k, nullptr, out_parent + b * k, out_node + b * k};
+    select_rounds<kExpMaxWaves>(key, N, k, nthr, [&](int r, uint32_t wk, int wi) {
+      expand_write_row(rows, r, wk, wi, parents + b * kprev * P, V, P);
+    });
+    expand_nodes(rows, k, P, nd0, lvl);
+  }
 }
 
 // ------------------------------------------------------------------------------------- expand, sampled
@@ -725,8 +818,17 @@ struct WideBeams {   // LDS, per beam
   int lo[kWideMax], off[kWideMax + 1];   // first child; candidates before this beam (off[kprev] = M)
 };
 
-// f(key, c) for every candidate of the user that thread tid owns: c its level-(P + 1) node
-template <bool BLOCKED, bool FILTERED, typename F>
+// the log-probability of token v on beam j (x the user's logits rows), the parent's added: beam_expand_kernel's
+// operations, from the stored statistics
+__device__ __forceinline__ float wide_lp(const WideBeams& s, const float* __restrict__ x, float temperature, int V,
+                                         int j, int v) {
+  const RowStats st = {s.m[j], s.sum[j], s.log_norm[j]};
+  return log_prob(x[(int64_t)j * V + v] / temperature - st.m, st) + s.plp[j];
+}
+
+// f(key, c) for every candidate of the user that thread tid owns: c its level-(P + 1) node. BIASED: the key is formed
+// from the biased score (ChildFilter::score), in every pass.
+template <bool BLOCKED, bool FILTERED, bool BIASED = false, typename F>
 __device__ __forceinline__ void wide_for_candidates(const WideBeams& s, const ChildFilter& flt,
                                                     const float* __restrict__ x, float temperature,
                                                     const int32_t* __restrict__ tok, int kprev, int V, F f) {
@@ -735,19 +837,27 @@ __device__ __forceinline__ void wide_for_candidates(const WideBeams& s, const Ch
     const int j = upper_bound(s.off, 0, kprev, e) - 1;
     const int c = s.lo[j] + (e - s.off[j]);
     const int v = tok[c];
-    if (!flt.candidate<BLOCKED, FILTERED>(c, v, V)) continue;
-    const RowStats st = {s.m[j], s.sum[j], s.log_norm[j]};
-    const uint32_t sk = score_key(log_prob(x[(int64_t)j * V + v] / temperature - st.m, st) + s.plp[j]);
+    uint32_t sk;
+    if constexpr (BIASED) {
+      float add;
+      if (!flt.candidate<BLOCKED, FILTERED, BIASED>(c, v, V, add)) continue;
+      sk = score_key(flt.score<BIASED>(wide_lp(s, x, temperature, V, j, v), add));
+    } else {
+      if (!flt.candidate<BLOCKED, FILTERED>(c, v, V)) continue;
+      sk = score_key(wide_lp(s, x, temperature, V, j, v));
+    }
     f(((uint64_t)sk << 32) | (uint32_t)~(uint32_t)(j * V + v), c);
   }
 }
 
-template <bool BLOCKED, bool FILTERED>
+// BIASED: the score written from the winner's key is out_score; out_lp is wide_lp of the winner's (beam, token), both
+// known when the rows are written.
+template <bool BLOCKED, bool FILTERED, bool BIASED = false>
 __global__ void __launch_bounds__(kWideThreads) beam_expand_wide_kernel(
     const float* __restrict__ logits, float temperature, const int32_t* __restrict__ node, TrieLevel lvl,
     const int64_t* __restrict__ parents, const float* __restrict__ parent_lp, int kprev, int V, int P, int k,
     int64_t* __restrict__ out_ids, float* __restrict__ out_lp, int32_t* __restrict__ out_parent,
-    int32_t* __restrict__ out_node, const int32_t* __restrict__ blocked, int n_blocked, AllowedBits allowed) {
+    int32_t* __restrict__ out_node, const int32_t* __restrict__ blocked, int n_blocked, ChildRows<BIASED> allowed) {
   __shared__ WideBeams s;
   __shared__ int hist[256];
   __shared__ uint64_t wkey[kWideMax];
@@ -805,7 +915,7 @@ __global__ void __launch_bounds__(kWideThreads) beam_expand_wide_kernel(
     if (tid < 256) hist[tid] = 0;
     __syncthreads();   // also: the statistics are written
     const uint64_t above = shift == 56 ? 0 : ~0ull << (shift + 8);   // the digits already fixed
-    wide_for_candidates<BLOCKED, FILTERED>(s, flt, x, temperature, lvl.tok, kprev, V, [&](uint64_t key, int) {
+    wide_for_candidates<BLOCKED, FILTERED, BIASED>(s, flt, x, temperature, lvl.tok, kprev, V, [&](uint64_t key, int) {
       if ((key & above) == cut) atomicAdd(&hist[(int)(key >> shift) & 255], 1);
     });
     __syncthreads();
@@ -842,7 +952,7 @@ __global__ void __launch_bounds__(kWideThreads) beam_expand_wide_kernel(
   }
 
   // 3. collect, sort, write
-  wide_for_candidates<BLOCKED, FILTERED>(s, flt, x, temperature, lvl.tok, kprev, V, [&](uint64_t key, int c) {
+  wide_for_candidates<BLOCKED, FILTERED, BIASED>(s, flt, x, temperature, lvl.tok, kprev, V, [&](uint64_t key, int c) {
     if (key >= cut) {
       const int at = atomicAdd(&n_won, 1);
       if (at < kWideMax) { wkey[at] = key; wnode[at] = c; }
@@ -872,7 +982,13 @@ __global__ void __launch_bounds__(kWideThreads) beam_expand_wide_kernel(
   if (tid < k) {
     const bool dead = tid >= live;
     const uint64_t key = dead ? 0 : wkey[tid];
-    out_lp[b * k + tid] = dead ? -INFINITY : key_score((uint32_t)(key >> 32));
+    if constexpr (BIASED) {
+      const int at = (int)~(uint32_t)key, par = at / V;
+      allowed.out_score[b * k + tid] = dead ? -INFINITY : key_score((uint32_t)(key >> 32));
+      out_lp[b * k + tid] = dead ? -INFINITY : wide_lp(s, x, temperature, V, par, at - par * V);
+    } else {
+      out_lp[b * k + tid] = dead ? -INFINITY : key_score((uint32_t)(key >> 32));
+    }
     out_parent[b * k + tid] = dead ? 0 : (int)(~(uint32_t)key) / V;
     out_node[b * k + tid] = dead ? -1 : wnode[tid];
   }
@@ -1289,6 +1405,74 @@ __global__ void __launch_bounds__(kAllowThreads) trie_allowed_finish_kernel(unsi
   for (int64_t i = (int64_t)blockIdx.x * kAllowThreads + threadIdx.x; i < n; i += stride) lowest[i] = ~lowest[i];
 }
 
+// ------------------------------------------------------------------------------------- bias bounds of trie nodes
+// Per-item score bias: bias (G, N) fp32 says what group g adds to item i's score. Per group, level q = 1..D gets every
+// node's bound — the largest cleaned bias (clean_bias) of an item below it, -inf with none: what a completion of that
+// prefix can still gain — and every leaf the item that attains its bound, the lowest index among equals (-1 at -inf).
+// Both are integer maxima, which do not depend on the order, so two runs give the same bits; no float atomic is used.
+// The outputs arrive zeroed.
+//   trie_bias_kernel  a thread per (group, item), grid stride. An item whose cleaned bias is -inf is skipped: it can
+//                     raise no bound. Else, with k = score_key(bias) (monotone, never 0) and leaf l: atomicMax of
+//                     (k << 32 | ~i) into best[g][l] (the largest key, then the lowest i), and atomicMax of k into the
+//                     bound of l's ancestor at every level — each tested with a plain load first, the atomic only
+//                     where it would still raise the value (the upper levels have a handful of nodes per group).
+//   trie_bias_finish_kernel  in place: a bound's key back to its float (0, never raised: -inf), best[g][l] to the
+//                     item (0: -1).
+// Table values are never trusted for addressing: a leaf outside [0, n_leaves) or an ancestor outside [0, n_nodes) is
+// skipped.
+struct BiasLevels {
+  const int32_t* anc[RQ_BEAM_MAX_T];   // (n_leaves): each leaf's level-q ancestor
+  uint32_t* upper[RQ_BEAM_MAX_T];      // (G, n_nodes[q - 1]), zeroed: keys while reducing, floats after the finish
+  int n_nodes[RQ_BEAM_MAX_T];
+};
+
+__global__ void __launch_bounds__(kAllowThreads) trie_bias_kernel(const float* __restrict__ bias, int64_t G,
+                                                                 int64_t n_items,
+                                                                 const int32_t* __restrict__ item_leaf, int n_leaves,
+                                                                 BiasLevels lv, int D,
+                                                                 unsigned long long* __restrict__ best) {
+  const int64_t total = G * n_items;
+  const int64_t stride = (int64_t)gridDim.x * kAllowThreads;
+  for (int64_t e = (int64_t)blockIdx.x * kAllowThreads + threadIdx.x; e < total; e += stride) {
+    const float u = clean_bias(bias[e]);
+    if (u == -INFINITY) continue;
+    const uint32_t key = score_key(u);
+    const int64_t g = e / n_items, item = e - g * n_items;
+    const int leaf = item_leaf[item];
+    if (leaf < 0 || leaf >= n_leaves) continue;
+    unsigned long long* bw = best + g * n_leaves + leaf;
+    const unsigned long long enc = ((unsigned long long)key << 32) | (uint32_t)~(uint32_t)item;
+    if (__atomic_load_n(bw, __ATOMIC_RELAXED) < enc) atomicMax(bw, enc);
+#pragma unroll 1
+    for (int q = 0; q < D; ++q) {
+      const int a = lv.anc[q][leaf];
+      if (a < 0 || a >= lv.n_nodes[q]) continue;
+      uint32_t* w = lv.upper[q] + g * lv.n_nodes[q] + a;
+      if (__atomic_load_n(w, __ATOMIC_RELAXED) < key) atomicMax(w, key);
+    }
+  }
+}
+
+__global__ void __launch_bounds__(kAllowThreads) trie_bias_finish_kernel(BiasLevels lv, int D, int64_t G,
+                                                                        unsigned long long* __restrict__ best,
+                                                                        int64_t n_best) {
+  const int64_t stride = (int64_t)gridDim.x * kAllowThreads;
+  const int64_t first = (int64_t)blockIdx.x * kAllowThreads + threadIdx.x;
+#pragma unroll 1
+  for (int q = 0; q < D; ++q) {
+    uint32_t* up = lv.upper[q];
+    const int64_t n = G * lv.n_nodes[q];
+    for (int64_t i = first; i < n; i += stride) {
+      const uint32_t key = up[i];
+      up[i] = __builtin_bit_cast(uint32_t, key == 0 ? -INFINITY : key_score(key));
+    }
+  }
+  for (int64_t i = first; i < n_best; i += stride) {
+    const unsigned long long v = best[i];
+    best[i] = v == 0 ? ~0ull : (unsigned long long)(uint32_t)~(uint32_t)v;
+  }
+}
+
 // Host side of the expand kernels: f(BLOCKED, FILTERED), the two as std::bool_constant values — the instantiation that
 // the filters given ask for
 template <typename F>
@@ -1401,42 +1585,82 @@ static int beam_expand_check(const char* fn, ExpandForm form, float temperature,
   return 0;
 }
 
-static size_t beam_expand_lds(int64_t kprev, int64_t V, int64_t n_blocked) {   // expand_prologue's layout
+static size_t beam_expand_lds(int64_t kprev, int64_t V, int64_t n_blocked, bool biased = false) {   // expand_prologue's layout
   return (size_t)((kprev * V + 3) / 4 * 4 + 2 * rqhip::kExpMaxWaves) * sizeof(uint32_t) +
-         (size_t)n_blocked * sizeof(int32_t);
+         (size_t)n_blocked * sizeof(int32_t) + (biased ? (size_t)kprev * 3 * sizeof(float) : 0);
 }
 
+// bias / out_score: the biased entry points' (`biased`), whose n_words is n_bias and whose `allowed` is NULL
 static int beam_expand_launch(const char* fn, bool wide, const float* logits, float temperature, const int32_t* node,
                               const int32_t* child_off, int64_t n_nodes, const int32_t* tok, int64_t n_children,
                               const int64_t* parents, const float* parent_lp, int64_t B, int64_t kprev, int64_t V,
                               int64_t P, int64_t k, int64_t* out_ids, float* out_lp, int32_t* out_parent,
                               int32_t* out_node, const int32_t* blocked, int64_t n_blocked, const int32_t* allowed,
-                              int64_t n_words, int64_t G, const int32_t* group, void* stream) {
+                              int64_t n_words, int64_t G, const int32_t* group, void* stream, bool biased = false,
+                              const float* bias = nullptr, float* out_score = nullptr) {
+  if (biased) {
+    RQ_CHECK_ARG(n_words >= 0 && G >= 0 && G <= 0x7fffffff && n_words == n_children,
+                 "%s: need G >= 0 and n_bias == n_children (n_bias=%lld, n_children=%lld, G=%lld)", fn,
+                 (long long)n_words, (long long)n_children, (long long)G);
+    RQ_CHECK_ARG(bias || G == 0 || n_words == 0, "%s: null bias", fn);
+    RQ_CHECK_ARG(wide || kprev <= rqhip::kWideMax, "%s: the biased step takes kprev <= %d (kprev=%lld)", fn,
+                 rqhip::kWideMax, (long long)kprev);
+  }
   const int rc = beam_expand_check(
       fn, wide ? ExpandForm::kWide : ExpandForm::kDense, temperature, n_nodes, tok, n_children,
       (P == 0) ? (!node && !parents && !parent_lp) : (node && parents && parent_lp), "node, parents and parent_lp", B,
-      kprev, V, P, k, logits && child_off && out_ids && out_lp && out_parent && out_node, blocked, n_blocked, allowed,
-      n_words, G, group);
+      kprev, V, P, k, logits && child_off && out_ids && out_lp && out_parent && out_node && (out_score || !biased),
+      blocked, n_blocked, allowed, biased ? 0 : n_words, biased ? 0 : G, biased ? nullptr : group);
   if (rc != 0 || B == 0) return rc;
   const rqhip::TrieLevel lvl = {child_off, (int)n_nodes, tok, (int)n_children};
-  const rqhip::AllowedBits ab = {allowed, group, (int)n_words, (int)G};
   if (n_blocked == 0) blocked = nullptr;
-  rqhip::with_filters(n_blocked > 0, group != nullptr, [&](auto blk, auto flt) {
-    constexpr bool kBlk = decltype(blk)::value, kFlt = decltype(flt)::value;
+  auto run = [&](auto blk, auto flt, auto bia, const auto& rows) {
+    constexpr bool kBlk = decltype(blk)::value, kFlt = decltype(flt)::value, kBia = decltype(bia)::value;
     auto launch = [&](auto kernel, int threads, size_t lds) {
       hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(threads), lds, (hipStream_t)stream, logits, temperature, node,
                          lvl, parents, parent_lp, (int)kprev, (int)V, (int)P, (int)k, out_ids, out_lp, out_parent,
-                         out_node, blocked, (int)n_blocked, ab);
+                         out_node, blocked, (int)n_blocked, rows);
     };
     if (wide) {   // static LDS, one shape of workgroup
-      launch(rqhip::beam_expand_wide_kernel<kBlk, kFlt>, rqhip::kWideThreads, 0);
+      launch(rqhip::beam_expand_wide_kernel<kBlk, kFlt, kBia>, rqhip::kWideThreads, 0);
     } else {
-      launch(rqhip::beam_expand_kernel<kBlk, kFlt>, kprev > 4 ? 64 * rqhip::kExpMaxWaves : 64 * 4,
-             beam_expand_lds(kprev, V, n_blocked));
+      launch(rqhip::beam_expand_kernel<kBlk, kFlt, kBia>, kprev > 4 ? 64 * rqhip::kExpMaxWaves : 64 * 4,
+             beam_expand_lds(kprev, V, n_blocked, kBia));
     }
-  });
+  };
+  if (biased) {
+    const rqhip::BiasArgs ba = {bias, group, (int)n_words, (int)G, out_score};
+    if (n_blocked > 0) run(std::true_type{}, std::false_type{}, std::true_type{}, ba);
+    else run(std::false_type{}, std::false_type{}, std::true_type{}, ba);
+  } else {
+    const rqhip::AllowedBits ab = {allowed, group, (int)n_words, (int)G};
+    rqhip::with_filters(n_blocked > 0, group != nullptr,
+                        [&](auto blk, auto flt) { run(blk, flt, std::false_type{}, ab); });
+  }
   RQ_LAUNCH_CHECK(fn);
   return 0;
+}
+
+int rq_beam_expand_biased(const float* logits, float temperature, const int32_t* node, const int32_t* child_off,
+                          int64_t n_nodes, const int32_t* tok, int64_t n_children, const int64_t* parents,
+                          const float* parent_lp, int64_t B, int64_t kprev, int64_t V, int64_t P, int64_t k,
+                          int64_t* out_ids, float* out_lp, float* out_score, int32_t* out_parent, int32_t* out_node,
+                          const int32_t* blocked, int64_t n_blocked, const float* bias, int64_t n_bias, int64_t G,
+                          const int32_t* group, void* stream) {
+  return beam_expand_launch("rq_beam_expand_biased", false, logits, temperature, node, child_off, n_nodes, tok,
+                            n_children, parents, parent_lp, B, kprev, V, P, k, out_ids, out_lp, out_parent, out_node,
+                            blocked, n_blocked, nullptr, n_bias, G, group, stream, true, bias, out_score);
+}
+
+int rq_beam_expand_wide_biased(const float* logits, float temperature, const int32_t* node, const int32_t* child_off,
+                               int64_t n_nodes, const int32_t* tok, int64_t n_children, const int64_t* parents,
+                               const float* parent_lp, int64_t B, int64_t kprev, int64_t V, int64_t P, int64_t k,
+                               int64_t* out_ids, float* out_lp, float* out_score, int32_t* out_parent,
+                               int32_t* out_node, const int32_t* blocked, int64_t n_blocked, const float* bias,
+                               int64_t n_bias, int64_t G, const int32_t* group, void* stream) {
+  return beam_expand_launch("rq_beam_expand_wide_biased", true, logits, temperature, node, child_off, n_nodes, tok,
+                            n_children, parents, parent_lp, B, kprev, V, P, k, out_ids, out_lp, out_parent, out_node,
+                            blocked, n_blocked, nullptr, n_bias, G, group, stream, true, bias, out_score);
 }
 
 int rq_beam_expand(const float* logits, float temperature, const int32_t* node, const int32_t* child_off,
@@ -1578,6 +1802,44 @@ int rq_trie_allowed_nodes(const bool* mask, int64_t G, int64_t n_items, const in
   hipLaunchKernelGGL(rqhip::trie_allowed_finish_kernel, dim3(blocks(G * n_leaves)), dim3(rqhip::kAllowThreads), 0, hs,
                      lowest, G * n_leaves);
   RQ_LAUNCH_CHECK("rq_trie_allowed_nodes");
+  return 0;
+}
+
+int rq_trie_bias_nodes(const float* bias, int64_t G, int64_t n_items, const int32_t* item_leaf, int64_t n_leaves,
+                       const int32_t* const* leaf_anc, const int64_t* n_nodes, int64_t D, float* const* out_upper,
+                       int64_t* out_leaf_item, void* stream) {
+  RQ_CHECK_ARG(G >= 0 && D >= 1 && D <= RQ_BEAM_MAX_T, "rq_trie_bias_nodes: need G >= 0, 1 <= D <= %d (G=%lld, D=%lld)",
+               RQ_BEAM_MAX_T, (long long)G, (long long)D);
+  RQ_CHECK_ARG(n_items >= 0 && n_items <= 0x7fffffff && n_leaves >= 0 && n_leaves < 0x7fffffff,
+               "rq_trie_bias_nodes: bad corpus size");
+  RQ_CHECK_ARG(n_items == 0 || G <= INT64_MAX / 8 / n_items, "rq_trie_bias_nodes: bias too large");
+  RQ_CHECK_ARG(n_leaves == 0 || G <= INT64_MAX / 8 / n_leaves, "rq_trie_bias_nodes: too many (group, leaf) pairs");
+  RQ_CHECK_ARG(leaf_anc && n_nodes && out_upper, "rq_trie_bias_nodes: null level array");
+  rqhip::BiasLevels lv = {};
+  for (int64_t q = 0; q < D; ++q) {
+    RQ_CHECK_ARG(n_nodes[q] >= 0 && n_nodes[q] < 0x7fffffff, "rq_trie_bias_nodes: level %lld has %lld nodes",
+                 (long long)(q + 1), (long long)n_nodes[q]);
+    RQ_CHECK_ARG((leaf_anc[q] || n_leaves == 0) && (out_upper[q] || n_nodes[q] == 0 || G == 0),
+                 "rq_trie_bias_nodes: null table at level %lld", (long long)(q + 1));
+    lv.anc[q] = leaf_anc[q];
+    lv.upper[q] = reinterpret_cast<uint32_t*>(out_upper[q]);
+    lv.n_nodes[q] = (int)n_nodes[q];
+  }
+  if (G == 0 || n_leaves == 0) return 0;
+  RQ_CHECK_ARG(out_leaf_item && (n_items == 0 || (bias && item_leaf)), "rq_trie_bias_nodes: null pointer");
+  hipStream_t hs = (hipStream_t)stream;
+  auto blocks = [](int64_t threads) {
+    return (unsigned)std::min<int64_t>((threads + rqhip::kAllowThreads - 1) / rqhip::kAllowThreads,
+                                       rqhip::kAllowMaxBlocks);
+  };
+  unsigned long long* best = reinterpret_cast<unsigned long long*>(out_leaf_item);
+  if (n_items > 0) {
+    hipLaunchKernelGGL(rqhip::trie_bias_kernel, dim3(blocks(G * n_items)), dim3(rqhip::kAllowThreads), 0, hs, bias, G,
+                       n_items, item_leaf, (int)n_leaves, lv, (int)D, best);
+  }
+  hipLaunchKernelGGL(rqhip::trie_bias_finish_kernel, dim3(blocks(G * n_leaves)), dim3(rqhip::kAllowThreads), 0, hs, lv,
+                     (int)D, G, best, G * n_leaves);
+  RQ_LAUNCH_CHECK("rq_trie_bias_nodes");
   return 0;
 }
 

@@ -56,6 +56,14 @@ class Recommendation(NamedTuple):
     log_probas: Tensor   # (B, k)
 
 
+class RankedItems(NamedTuple):
+    """recommend(item_bias=...): the rows are ordered by `scores`, descending."""
+    item_ids: Tensor     # (B, k) int64 corpus indices, -1 for dead beams
+    sem_ids: Tensor      # (B, k, D)
+    log_probas: Tensor   # (B, k) fp32: the raw model score log p(item | user), what score_items reproduces
+    scores: Tensor       # (B, k) fp32: log_probas + bias[group][item] (one fp32 add); log_probas for an unbiased user
+
+
 class SampledItems(NamedTuple):
     item_ids: Tensor     # (B, k) int64 corpus indices, -1 for dead rows
     sem_ids: Tensor      # (B, k, D)
@@ -74,12 +82,17 @@ class _TrieSearch(NamedTuple):
     blocked: Tensor       # (D, B, H) int32 blocked nodes of every level, or None
     item_filter: object   # ItemFilter or None
     group: Tensor         # (B,) int32 with item_filter, else None
+    item_bias: object = None    # ItemBias or None; never together with item_filter
+    bias_group: Tensor = None   # (B,) int32 with item_bias, else None
 
     def level(self, i: int) -> dict:
-        """Step i's trie and filter arguments of hip_ops.beam_expand / beam_expand_sampled."""
-        return dict(child_off=self.trie.child_off[i], tok=self.trie.tok[i + 1],
-                    blocked=None if self.blocked is None else self.blocked[i],
-                    allowed=None if self.item_filter is None else self.item_filter.bits[i], group=self.group)
+        """Step i's trie and filter arguments of hip_ops.beam_expand / beam_expand_sampled — with item_bias, of
+        hip_ops.beam_expand_biased."""
+        lvl = dict(child_off=self.trie.child_off[i], tok=self.trie.tok[i + 1],
+                   blocked=None if self.blocked is None else self.blocked[i])
+        if self.item_bias is not None:
+            return dict(lvl, bias=self.item_bias.upper[i], bias_group=self.bias_group)
+        return dict(lvl, allowed=None if self.item_filter is None else self.item_filter.bits[i], group=self.group)
 
 
 class EncoderDecoderRetrievalModel(nn.Module):
@@ -295,9 +308,9 @@ class EncoderDecoderRetrievalModel(nn.Module):
             self._constrained_trie("generate_next_sem_id")
         assert self.enable_generation, "Model generation is not enabled"
         if constrained:
-            generated, log_probas, _ = self._generate_constrained(batch, temperature, beams if top_k else 1,
-                                                                  incremental, exclude_items, item_filter,
-                                                                  filter_group)
+            generated, log_probas, _, _ = self._generate_constrained(batch, temperature, beams if top_k else 1,
+                                                                     incremental, exclude_items, item_filter,
+                                                                     filter_group)
             return GenerationOutput(sem_ids=generated.squeeze(), log_probas=log_probas.squeeze())
         if fused:
             return self._generate_sampled(batch, temperature, top_k, sample, incremental)
@@ -343,20 +356,47 @@ class EncoderDecoderRetrievalModel(nn.Module):
                              "tokens; items are the leaves of the full depth")
         return trie
 
-    def _trie_search(self, what: str, batch: TokenizedSeqBatch, exclude_items, item_filter, filter_group):
+    def _trie_search(self, what: str, batch: TokenizedSeqBatch, exclude_items, item_filter, filter_group,
+                     item_bias=None, bias_group=None):
         """The per-call tables of a search over the trie, errors under the caller's name `what`: the trie, the users'
         blocked nodes of every level (exclude_items (B, H); the tokenizer's blocked_nodes, one launch for the whole
-        call) and the catalogue filter (_item_filter's arguments). _TrieSearch.level(i) hands step i its slices."""
+        call), the catalogue filter (_item_filter's arguments) and the score bias (_item_bias's). _TrieSearch.level(i)
+        hands step i its slices."""
         trie = self._constrained_trie(what)
         B = batch.sem_ids.shape[0]
         item_filter, group = self._item_filter(what, item_filter, filter_group, B, batch.sem_ids.device)
+        item_bias, bias_group = self._item_bias(what, item_bias, bias_group, B, batch.sem_ids.device)
+        if item_filter is not None and item_bias is not None:
+            raise ValueError(f"{what}: item_filter and item_bias cannot be combined; write the filter into the bias "
+                             "as -inf (a {0, -inf} table is a hard filter)")
         blocked = None
         if exclude_items is not None:
             if exclude_items.dim() != 2 or exclude_items.shape[0] != B:
                 raise ValueError(f"{what}: exclude_items must be (B, H) with B = {B} rows, got "
                                  f"{tuple(exclude_items.shape)}")
             blocked = self.inference_prefix_index.blocked_nodes(exclude_items)
-        return _TrieSearch(trie, blocked, item_filter, group)
+        return _TrieSearch(trie, blocked, item_filter, group, item_bias, bias_group)
+
+    def _item_bias(self, what: str, item_bias, bias_group, B: int, device):
+        """(ItemBias, group (B,) int32 on the device) of a call's item_bias / bias_group arguments, or (None, None)
+        without a bias: _item_filter's rules. A raw fp32 tensor becomes an ItemBias through the tokenizer (built per
+        call); the groups are converted on the device, nothing is read back."""
+        if item_bias is None:
+            if bias_group is not None:
+                raise ValueError(f"{what}: bias_group without item_bias")
+            return None, None
+        if isinstance(item_bias, Tensor):
+            item_bias = self.inference_prefix_index.item_bias(item_bias)
+        if bias_group is None:
+            if item_bias.groups != 1:
+                raise ValueError(f"{what}: item_bias has {item_bias.groups} groups; bias_group (B,) must say which "
+                                 "one every user reads (-1: unbiased)")
+            return item_bias, torch.zeros(B, dtype=torch.int32, device=device)
+        if bias_group.dim() != 1 or bias_group.shape[0] != B or bias_group.dtype.is_floating_point or \
+                bias_group.dtype == torch.bool:
+            raise ValueError(f"{what}: bias_group must be (B,) integer with B = {B}, got {bias_group.dtype} "
+                             f"{tuple(bias_group.shape)}")
+        return item_bias, bias_group.to(device=device, dtype=torch.int32).contiguous()
 
     def _item_filter(self, what: str, item_filter, filter_group, B: int, device):
         """(ItemFilter, group (B,) int32 on the device) of a call's item_filter / filter_group arguments, or (None,
@@ -382,7 +422,8 @@ class EncoderDecoderRetrievalModel(nn.Module):
     @staticmethod
     def _leaf_items(trie, item_filter, group, node: Tensor) -> Tensor:
         """The corpus index of every leaf node (B, k), -1 for dead rows: the trie's lowest index for an unfiltered user,
-        the filter's lowest ALLOWED index for a filtered one."""
+        the filter's lowest ALLOWED index for a filtered one. An ItemBias in item_filter's place (with its groups): the
+        item that attains the leaf's bound for a biased user."""
         node = node.long()
         at = node.clamp_min(0)
         items = trie.leaf_item[at]
@@ -398,7 +439,7 @@ class EncoderDecoderRetrievalModel(nn.Module):
     @torch.no_grad()
     def recommend(self, batch: TokenizedSeqBatch, k: int = 10, temperature: int = 1,
                   incremental: bool = True, exclude_items: Tensor = None, beams: int = 32, item_filter=None,
-                  filter_group: Tensor = None) -> Recommendation:
+                  filter_group: Tensor = None, item_bias=None, bias_group: Tensor = None):
         """The k <= beams most probable corpus items for every user: the constrained beam search (`beams` wide, 32
         by default and up to 1024; sample=False; generate_next_sem_id(constrained=True, beams=beams)) with each kept
         beam mapped back to its corpus index through the trie's leaves. A user with fewer than k valid beams gets
@@ -406,15 +447,37 @@ class EncoderDecoderRetrievalModel(nn.Module):
         the items sharing their sem-ID rows) that are never returned — the k best of the REMAINING corpus, see
         generate_next_sem_id. item_filter / filter_group: a catalogue filter, see generate_next_sem_id — the k best of the
         ALLOWED items of each user's group; every returned id is an allowed item (a row that several items share is
-        reported under its lowest allowed index), never a disallowed one."""
+        reported under its lowest allowed index), never a disallowed one.
+        item_bias / bias_group: rank by the model's score PLUS a per-item adjustment (promotion boosts, popularity
+        de-biasing, recency or price priors, another ranker's score) — an ItemBias (the tokenizer's item_bias(bias),
+        built once and reused) or a raw fp32 tensor (N,) / (G, N) over corpus indices, turned into one per call; -inf
+        never shows an item. bias_group (B,) integer: each user's row; -1 leaves a user unbiased; None is row 0 for
+        everyone, which needs a one-group bias. The search itself is biased (hip_ops.beam_expand_biased): every prefix
+        is ranked by its log-probability plus the largest adjustment of an item below its node, an optimistic estimate
+        of the best final score there, so the beams go where the adjusted score can still be high — an item whose boost
+        puts it first is found although its first token is unlikely, which over-fetching and re-ranking cannot promise;
+        with `beams` at the width of the trie the result is exhaustive and exact. The result is then a RankedItems:
+        rows ordered by `scores` = log p(item | user) + bias[group][item] descending, `log_probas` the raw model score
+        (score_items' value), item ids from the ItemBias' leaves for biased users (a row several items share is
+        reported under its highest-bias item). Composes with beams, incremental and exclude_items; together with
+        item_filter it raises (write the filter into the bias as -inf). Without item_bias the call and its
+        Recommendation are what they were."""
         if not 1 <= k <= beams <= hip_ops.BEAM_WIDE_MAX:
             raise ValueError(f"recommend: need 1 <= k <= {beams} beams <= {hip_ops.BEAM_WIDE_MAX}, got k = {k}")
         trie = self._constrained_trie("recommend", items=True)
         assert self.enable_generation, "Model generation is not enabled"
         B, dev = batch.sem_ids.shape[0], batch.sem_ids.device
+        if item_filter is not None and item_bias is not None:
+            raise ValueError("recommend: item_filter and item_bias cannot be combined; write the filter into the bias "
+                             "as -inf (a {0, -inf} table is a hard filter)")
         item_filter, group = self._item_filter("recommend", item_filter, filter_group, B, dev)
-        generated, log_probas, node = self._generate_constrained(batch, temperature, beams, incremental, exclude_items,
-                                                                 item_filter, group)
+        item_bias, bias_group = self._item_bias("recommend", item_bias, bias_group, B, dev)
+        generated, log_probas, node, scores = self._generate_constrained(
+            batch, temperature, beams, incremental, exclude_items, item_filter, group, item_bias, bias_group)
+        if item_bias is not None:
+            items = self._leaf_items(trie, item_bias, bias_group, node[:, :k])
+            return RankedItems(item_ids=items, sem_ids=generated[:, :k], log_probas=log_probas[:, :k],
+                               scores=scores[:, :k])
         items = self._leaf_items(trie, item_filter, group, node[:, :k])
         return Recommendation(item_ids=items, sem_ids=generated[:, :k], log_probas=log_probas[:, :k])
 
@@ -537,26 +600,32 @@ class EncoderDecoderRetrievalModel(nn.Module):
         return Scores(log_probas=lp, rank=rank)
 
     def _generate_constrained(self, batch: TokenizedSeqBatch, temperature, k: int, incremental: bool,
-                              exclude_items: Tensor = None, item_filter=None, filter_group: Tensor = None):
+                              exclude_items: Tensor = None, item_filter=None, filter_group: Tensor = None,
+                              item_bias=None, bias_group: Tensor = None):
         """_generate_sampled's loop with beam_candidates + _beam_verify + beam_select replaced by one
         hip_ops.beam_expand per step: a beam carries its trie node, the node's children are the
-        only candidates. Returns (sem_ids (B, k, L+1), log_probas (B, k), the beams' leaf nodes (B, k) int32), dead
-        beams as beam_expand marks them. Tokens handed back to the model for dead beams are clamped to 0 (row
+        only candidates. Returns (sem_ids (B, k, L+1), log_probas (B, k), the beams' leaf nodes (B, k) int32, the
+        biased scores (B, k) or None), dead beams as beam_expand marks them. Tokens handed back to the model for dead beams are clamped to 0 (row
         counts stay B * k: static shapes, no negative index reaches an embedding kernel); whatever they compute is
         never read, a dead beam has no children. exclude_items (B, H): step i's beam_expand skips the user's blocked
         level-(i + 1) nodes (the tokenizer's blocked_nodes, one launch for the whole call). item_filter / filter_group
         (_item_filter's arguments): step i's beam_expand keeps only the children set in item_filter.bits[i], row
-        filter_group[b]. Runs under the caller's decorators."""
+        filter_group[b]. item_bias / bias_group (_item_bias's arguments): the steps are hip_ops.beam_expand_biased's,
+        ranked by log-probability + item_bias.upper[i], row bias_group[b]; the UNBIASED log-probability is what is
+        carried to the next step as parent_lp (no bound is ever accumulated) and the last step's ranking score is
+        kept. Runs under the caller's decorators."""
         B = batch.sem_ids.shape[0]
-        search = self._trie_search("generate_next_sem_id", batch, exclude_items, item_filter, filter_group)
-        generated, log_probas, parent, node = None, None, None, None
+        search = self._trie_search("generate_next_sem_id", batch, exclude_items, item_filter, filter_group, item_bias,
+                                   bias_group)
+        expand = hip_ops.beam_expand if search.item_bias is None else hip_ops.beam_expand_biased
+        generated, log_probas, score, parent, node = None, None, (), None, None
         with self._step_logits(batch, incremental) as step:
             for i in range(self.sem_id_dim):
                 logits = step() if generated is None else step(generated.clamp_min(0), parent)
-                generated, log_probas, parent, node = hip_ops.beam_expand(
+                generated, log_probas, *score, parent, node = expand(
                     logits.contiguous(), k, batch=B, node=node, parents=generated, parent_lp=log_probas,
                     temperature=temperature, wide=None, **search.level(i))
-        return generated, log_probas, node
+        return generated, log_probas, node, (score[0] if score else None)
 
     def _beams_batch(self, cur: TokenizedSeqBatch, generated: Tensor, first: bool, k: int) -> TokenizedSeqBatch:
         """The next full forward's batch for the beams `generated` (B, k, i + 1) of _ForwardSteps: after the first

@@ -22,7 +22,11 @@ MI355X path:
     (seen-item exclusion) — one HIP launch on the device, plain torch on the CPU;
   * `item_filter` (this build's addition): per group of a bool item mask the ItemFilter tables — every level's bitmap
     of nodes that still lead to an allowed item, and every leaf's lowest allowed item (catalogue filters: "only what
-    is in stock") — two HIP launches on the device, plain torch on the CPU.
+    is in stock") — two HIP launches on the device, plain torch on the CPU;
+  * `item_bias` (this build's addition): per group of an fp32 per-item score adjustment the ItemBias tables — every
+    level's per-node bound (the largest adjustment of an item below the node) and every leaf's item that attains it
+    (promotions, de-biasing, priors: "rank by the model's score plus an adjustment") — two HIP launches on the device,
+    plain torch on the CPU.
 """
 import math
 from typing import List, NamedTuple, Optional
@@ -90,6 +94,16 @@ class ItemFilter(NamedTuple):
     bits: tuple         # bits[q - 1], q = 1..depth: int32 (G, ceil(n_q / 32)); bit c & 31 of word c >> 5 in row g is
                         # set iff the level-q node c has at least one allowed item below it in group g
     leaf_item: Tensor   # int64 (G, n_depth): the lowest ALLOWED corpus index whose row is that leaf, -1 if none
+    groups: int         # G
+
+
+class ItemBias(NamedTuple):
+    """A per-item score bias over the PrefixTrie (SemanticIdTokenizer.item_bias): per group of a bias table, the most
+    any item below each node of every level adds to its score. Built once, reused across calls."""
+    upper: tuple        # upper[q - 1], q = 1..depth: fp32 (G, n_q); row g holds every level-q node's bound, the largest
+                        # (cleaned) bias[g][i] of an item i below it, -inf if it has none
+    leaf_item: Tensor   # int64 (G, n_depth): the lowest corpus index among the items on that leaf that attain its
+                        # bound, -1 where the bound is -inf
     groups: int         # G
 
 
@@ -313,6 +327,46 @@ class SemanticIdTokenizer(nn.Module):
             words = ((below > 0).view(G, W, 32).long() << shifts).sum(-1)                       # in [0, 2^32)
             bits.append(torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32))
         return ItemFilter(bits=tuple(bits), leaf_item=torch.where(leaf_ok, lowest, -1), groups=G)
+
+    @torch.no_grad()
+    def item_bias(self, bias: Tensor) -> ItemBias:
+        """The ItemBias of `bias`, fp32 (N,) or (G, N) over corpus indices: bias[g][i] is what group g (a region, a
+        campaign, a user) adds to item i's log-probability — a promotion boost, -alpha log popularity, a price prior,
+        another ranker's score; -inf means "never show". Values are read cleaned: NaN and +inf as -inf (a bad value can
+        only hide an item), -0.0 as +0.0. A constrained search that ranks every prefix by its log-probability plus its
+        node's bound (rqvae_hip.ops.beam_expand_biased) spends its beams where the biased score can still be high, and
+        ends on log p(item) + bias[g][item]. A row that several items share is reported under the item that attains the
+        leaf's bound, the lowest index among equals. Device tensors: two HIP launches for all levels
+        (rqvae_hip.ops.trie_bias_nodes), no host read; CPU tensors: the same tables, bit for bit, with plain torch.
+        Nothing is cached: build once, reuse across calls."""
+        idx = self.trie_index()
+        N = idx.item_leaf.numel()
+        if bias.dtype != torch.float32 or bias.dim() not in (1, 2) or bias.shape[-1] != N:
+            raise ValueError(f"item_bias: bias must be float32 (N,) or (G, N) with N = {N} corpus items, got "
+                             f"{bias.dtype} {tuple(bias.shape)}")
+        if bias.device != idx.item_leaf.device:
+            raise ValueError(f"item_bias: bias must live on the corpus ids' device {idx.item_leaf.device}, got "
+                             f"{bias.device}")
+        if bias.dim() == 1:
+            bias = bias.unsqueeze(0)
+        G, n_leaves = bias.shape[0], idx.leaf_anc[0].numel()
+        n_nodes = [c.numel() for c in idx.leaf_count]
+        if bias.is_cuda:
+            from rqvae_hip import ops as hip_ops
+            upper, leaf_item = hip_ops.trie_bias_nodes(bias.contiguous(), idx.item_leaf, idx.leaf_anc, n_nodes)
+            return ItemBias(upper=upper, leaf_item=leaf_item, groups=G)
+        ninf = float("-inf")
+        clean = torch.where(bias.isnan() | (bias == float("inf")), ninf, bias)
+        clean = torch.where(clean == 0, 0.0, clean)                       # -0.0 -> +0.0
+        leaf = idx.item_leaf.long().expand(G, N)
+        best = torch.full((G, n_leaves), ninf).scatter_reduce_(1, leaf, clean, "amax")
+        none = torch.iinfo(torch.int64).max
+        attains = (clean == best.gather(1, leaf)) & (clean > ninf)
+        lowest = torch.full((G, n_leaves), none, dtype=torch.int64)
+        lowest.scatter_reduce_(1, leaf, torch.where(attains, torch.arange(N), none), "amin")
+        upper = tuple(torch.full((G, n_q), ninf).scatter_reduce_(1, idx.leaf_anc[q].long().expand(G, n_leaves), best, "amax")
+                      for q, n_q in enumerate(n_nodes))
+        return ItemBias(upper=upper, leaf_item=torch.where(lowest != none, lowest, -1), groups=G)
 
     @torch.no_grad()
     @eval_mode

@@ -108,6 +108,11 @@ _SIGS = {
                                 _P, _P, _P, _I64, _P, _I64, _I64, _P, _P], _I),
     "rq_trie_blocked_nodes": ([_P, _I64, _I64, _P, _I64, _I64, _P, _P, _P, _I64, _P, _P], _I),
     "rq_trie_allowed_nodes": ([_P, _I64, _I64, _P, _I64, _P, _P, _I64, _P, _P, _P], _I),
+    "rq_trie_bias_nodes": ([_P, _I64, _I64, _P, _I64, _P, _P, _I64, _P, _P, _P], _I),
+    "rq_beam_expand_biased": ([_P, _F, _P, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P,
+                               _P, _I64, _P, _I64, _I64, _P, _P], _I),
+    "rq_beam_expand_wide_biased": ([_P, _F, _P, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P,
+                                    _P, _P, _I64, _P, _I64, _I64, _P, _P], _I),
     "rq_rank_hist": ([_P, _P, _I64, _I64, _I64, _P, _P], _I),
     "rq_score_paths": ([_P, _F, _P, _I64, _I64, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _P], _I),
     "rq_adamw_step": ([_P, _I64, _F, _F, _F, _F, _F, _F, _F, _P], _I),

@@ -2586,6 +2586,47 @@ def beam_expand(logits: torch.Tensor, k: int, *, batch: int, child_off: torch.Te
     return c.out_ids, out_lp, c.out_parent, c.out_node
 
 
+def beam_expand_biased(logits: torch.Tensor, k: int, *, batch: int, child_off: torch.Tensor, tok: torch.Tensor,
+                       bias: torch.Tensor, bias_group: torch.Tensor, node: torch.Tensor = None,
+                       parents: torch.Tensor = None, parent_lp: torch.Tensor = None, temperature: float = 1.0,
+                       blocked: torch.Tensor = None, wide: bool = False):
+    """(out_ids, out_lp, out_score, out_parent, out_node): beam_expand's step ranked by log p + a per-item score bias
+    (rq_beam_expand_biased / rq_beam_expand_wide_biased). bias (G, n_children) fp32: slice P of trie_bias_nodes' upper
+    tables (ItemBias.upper[P]) — per group the most any item below each level-(P + 1) node adds to its score;
+    bias_group (B) int32: each batch element's row, one outside [0, G) (-1) leaves it unbiased. A child whose bound is
+    -inf (read cleaned: NaN and +inf are -inf) is no candidate of a biased user; the k best are taken by
+    out_score = lp + bound (lp itself for an unbiased user), ties as beam_expand. out_lp (B, k) fp32 is the winner's
+    UNBIASED log-probability — the next call's parent_lp, so no bound is ever accumulated; after the last level the
+    bound is the item's own bias and out_score = log p(item) + bias. Dead rows as beam_expand, out_score -inf. The
+    other arguments, `wide` and the envelopes are beam_expand's (the narrow form also needs kprev <= 1024); a catalogue
+    bitmap is not taken: write the filter into the bias as -inf. One launch, no host read."""
+    what = "beam_expand_biased"
+    if bias is None or bias_group is None:
+        raise RqHipError(f"{what}: bias and bias_group are required")
+    c = _beam_expand_setup(what, logits, k, batch, child_off, tok, node, parents, parent_lp, blocked, None, None, bias,
+                           bias_group)
+    B, kprev, V = c.shape[:3]
+    if bias.dim() != 2 or bias.shape[1] != tok.numel():
+        raise RqHipError(f"{what}: bias must be (G, n_children = {tok.numel()}), got {tuple(bias.shape)}")
+    _beam_arg(bias, torch.float32, what, "bias")
+    _beam_arg(bias_group, torch.int32, what, "bias_group", (B,))
+    if wide is None:
+        wide = kprev * V > BEAM_MAX_N
+    if wide:
+        if V < 1 or V > BEAM_MAX_V or kprev > BEAM_WIDE_MAX or not 1 <= int(k) <= BEAM_WIDE_MAX:
+            raise RqHipError(f"{what}: outside the wide kernel's envelope V <= {BEAM_MAX_V}, kprev <= {BEAM_WIDE_MAX}, "
+                             f"1 <= k <= {BEAM_WIDE_MAX} (kprev={kprev}, V={V}, k={k})")
+    elif V < 1 or V > BEAM_MAX_V or kprev * V > BEAM_MAX_N or kprev > BEAM_WIDE_MAX or not 1 <= int(k) <= BEAM_MAX_N:
+        raise RqHipError(f"{what}: outside the supported envelope V <= {BEAM_MAX_V}, kprev * V <= {BEAM_MAX_N}, "
+                         f"kprev <= {BEAM_WIDE_MAX}, 1 <= k <= {BEAM_MAX_N} (kprev={kprev}, V={V}, k={k})")
+    out_lp, out_score = c.scores(), c.scores()
+    G, n_bias = bias.shape
+    call("rq_beam_expand_wide_biased" if wide else "rq_beam_expand_biased", ptr(logits), float(temperature), *c.trie,
+         ptr(parents), ptr(parent_lp), *c.shape, ptr(c.out_ids), ptr(out_lp), ptr(out_score), ptr(c.out_parent),
+         ptr(c.out_node), *c.tail[:2], ptr(bias) if G * n_bias else None, n_bias, G, ptr(bias_group), c.tail[-1])
+    return c.out_ids, out_lp, out_score, c.out_parent, c.out_node
+
+
 def beam_expand_sampled(logits: torch.Tensor, k: int, *, batch: int, child_off: torch.Tensor, tok: torch.Tensor,
                         noise: torch.Tensor, node: torch.Tensor = None, parents: torch.Tensor = None,
                         parent_phi: torch.Tensor = None, parent_g: torch.Tensor = None, temperature: float = 1.0,
@@ -2694,6 +2735,41 @@ def trie_allowed_nodes(mask: torch.Tensor, item_leaf: torch.Tensor, leaf_anc, n_
     call("rq_trie_allowed_nodes", ptr(mask), G, N, ptr(item_leaf), n_leaves, P(*[t.data_ptr() for t in leaf_anc]),
          (ctypes.c_int64 * D)(*n_nodes), D, P(*[t.data_ptr() for t in bits]), ptr(leaf_item), stream_handle(dev))
     return bits, leaf_item
+
+
+def trie_bias_nodes(bias: torch.Tensor, item_leaf: torch.Tensor, leaf_anc, n_nodes):
+    """(upper, leaf_item) of a per-item score bias (rq_trie_bias_nodes): upper, a tuple of D fp32 tensors, upper[q - 1]
+    (G, n_q) with row g holding every level-q trie node's bound — the largest bias[g][i] of an item i below it, -inf
+    with none — beam_expand_biased's `bias` of step q - 1; leaf_item (G, n_leaves) int64, the lowest corpus index among
+    the items on that leaf that attain its bound, -1 at -inf. bias (G, N) fp32, read cleaned: NaN and +inf as -inf,
+    -0.0 as +0.0. item_leaf (N) int32 and leaf_anc, D int32 tensors (n_leaves) — SemanticIdTokenizer.trie_index();
+    n_nodes: the D level sizes n_q. Two launches, no host read; the reductions are integer maxima (no float atomic), so
+    two runs give the same bits."""
+    import ctypes
+    what = "trie_bias_nodes"
+    leaf_anc, n_nodes = list(leaf_anc), [int(n) for n in n_nodes]
+    require_gpu(bias, item_leaf, *leaf_anc, what=what)
+    D = len(leaf_anc)
+    if bias.dim() != 2:
+        raise RqHipError(f"{what}: bias must be (G, N), got {tuple(bias.shape)}")
+    G, N = bias.shape
+    if not 1 <= D <= BEAM_MAX_T or len(n_nodes) != D:
+        raise RqHipError(f"{what}: outside the supported envelope 1 <= D <= {BEAM_MAX_T} with D level sizes (D={D}, "
+                         f"{len(n_nodes)} sizes)")
+    _beam_arg(bias, torch.float32, what, "bias")
+    _beam_arg(item_leaf, torch.int32, what, "item_leaf", (N,))
+    n_leaves = leaf_anc[0].numel()
+    for q in range(D):
+        _beam_arg(leaf_anc[q], torch.int32, what, f"leaf_anc[{q}]", (n_leaves,))
+        if n_nodes[q] < 0:
+            raise RqHipError(f"{what}: n_nodes[{q}] = {n_nodes[q]}")
+    dev = bias.device
+    upper = tuple(torch.zeros((G, n), device=dev, dtype=torch.float32) for n in n_nodes)
+    leaf_item = torch.zeros((G, n_leaves), device=dev, dtype=torch.int64)
+    P = ctypes.c_void_p * D
+    call("rq_trie_bias_nodes", ptr(bias), G, N, ptr(item_leaf), n_leaves, P(*[t.data_ptr() for t in leaf_anc]),
+         (ctypes.c_int64 * D)(*n_nodes), D, P(*[t.data_ptr() for t in upper]), ptr(leaf_item), stream_handle(dev))
+    return upper, leaf_item
 
 
 def beam_self_attention(q: torch.Tensor, kv_steps, anc: torch.Tensor, num_heads: int, scale: float = None):

@@ -95,7 +95,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     names = ["unfused", "fused", "incremental", "constrained", "excluded", "model", "acc_device", "acc_reference",
              "recommend", "score", "score_full", "wide", "wide_excluded", "recommend_forced", "sampled_items",
-             "filtered_shared", "filtered_groups", "filter_build", "filter_build_groups"]
+             "filtered_shared", "filtered_groups", "filter_build", "filter_build_groups", "biased", "bias_build",
+             "bias_build_groups"]
     ap.add_argument("--score-candidates", type=int, default=100)
     ap.add_argument("--score-full-candidates", type=int, default=None)
     ap.add_argument("--beams", type=int, default=128, help="width of the `wide` / `wide_excluded` search")
@@ -174,6 +175,10 @@ def main():
     user_masks = (torch.rand(args.batch, n_corpus, generator=gm) < 0.5).to(device)
     shared_filter, user_filter = tok.item_filter(shared_mask), tok.item_filter(user_masks)
     own_group = torch.arange(args.batch, device=device)
+    # score bias: 2 randn per item — one table for everyone, and one per user for the builder's time
+    shared_table = (2.0 * torch.randn(n_corpus, generator=gm)).to(device)
+    user_tables = (2.0 * torch.randn(args.batch, n_corpus, generator=gm)).to(device)
+    shared_bias = tok.item_bias(shared_table)
 
     top = gen(True).sem_ids.contiguous()
     actual = batch.sem_ids_fut.contiguous()
@@ -199,7 +204,10 @@ def main():
              "filtered_shared": lambda: model.recommend(batch, k=10, item_filter=shared_filter),
              "filtered_groups": lambda: model.recommend(batch, k=10, item_filter=user_filter, filter_group=own_group),
              "filter_build": lambda: tok.item_filter(shared_mask),
-             "filter_build_groups": lambda: tok.item_filter(user_masks)}
+             "filter_build_groups": lambda: tok.item_filter(user_masks),
+             "biased": lambda: model.recommend(batch, k=10, item_bias=shared_bias),
+             "bias_build": lambda: tok.item_bias(shared_table),
+             "bias_build_groups": lambda: tok.item_bias(user_tables)}
     if args.only:
         forms = {args.only: forms[args.only]}
     elif args.forms:
@@ -219,7 +227,8 @@ def main():
            "min_max_ms": {n: [round(min(v), 4), round(max(v), 4)] for n, v in times.items() if v}}
     peak = {}
     for name in ("unfused", "fused", "incremental", "constrained", "excluded", "recommend", "score", "score_full",
-                 "wide", "wide_excluded", "recommend_forced", "sampled_items", "filtered_shared", "filtered_groups"):
+                 "wide", "wide_excluded", "recommend_forced", "sampled_items", "filtered_shared", "filtered_groups",
+                 "biased"):
         if name in forms and not args.only:   # one more call of each generation form, alone after a peak reset
             torch.cuda.synchronize()
             torch.cuda.reset_peak_memory_stats(device)
@@ -249,6 +258,15 @@ def main():
             ratio={n: round(med[n] / med["recommend"], 4) for n in ("filtered_shared", "filtered_groups") if n in med},
             recommend_min_max_over_median=[round(lo / med["recommend"], 4), round(hi / med["recommend"], 4)],
             groups=dict(filtered_shared=1, filtered_groups=args.batch), allowed_fraction=0.5)
+    if {"constrained", "biased"} <= set(med):
+        # the yardstick is the unbiased constrained search of the same run: the ratio, next to that form's own spread
+        lo, hi = min(times["constrained"]), max(times["constrained"])
+        out["biased_vs_constrained"] = dict(
+            ratio=round(med["biased"] / med["constrained"], 4), delta_ms=round(med["biased"] - med["constrained"], 4),
+            constrained_min_max_over_median=[round(lo / med["constrained"], 4), round(hi / med["constrained"], 4)],
+            groups=1)
+    if {"bias_build", "bias_build_groups"} & set(med):
+        out["bias_build"] = dict(items=n_corpus, groups=dict(bias_build=1, bias_build_groups=args.batch))
     if {"wide", "wide_excluded"} & set(med):
         out["wide"] = dict(beams=args.beams, k=min(100, args.beams))
     if {"score", "score_full"} & set(med):
