@@ -329,9 +329,9 @@ int rq_segment_sum_multi(int count, const float* const* rows, const int64_t* con
                          void* stream);
 /* Decoder loss head (modules/model.py:137-143): X = out_proj output rows (B * npos_x, K), row stride ldx;
  * logits row r = b * npos + j is X row b * npos_x + j (the reference drops the last position);
- * u[r] = cross_entropy(logits[r], tgt[r], ignore_index=-1) (NaN for a target >= K), lse[r] saved for the
- * backward, logits = the contiguous (B * npos, K) copy, loss = sum(u) / B, loss_d[j] = sum_b u[b][j] / B
- * (fixed-order sums). K <= 1024. */
+ * u[r] = cross_entropy(logits[r], tgt[r], ignore_index=-1) (NaN for a target >= K), lse[r] = log sum_k
+ * exp(x_k - max_k x_k) saved for the backward (which takes the row maximum again), logits = the contiguous
+ * (B * npos, K) copy, loss = sum(u) / B, loss_d[j] = sum_b u[b][j] / B (fixed-order sums). K <= 1024. */
 int rq_ce_loss_fwd(const float* X, int64_t ldx, int64_t K, const int64_t* tgt, int64_t B, int64_t npos, int64_t npos_x,
                    float* u, float* lse, float* logits, float* loss, float* loss_d, void* stream);
 /* Its backward: dX (B * npos_x, K, contiguous) from g_loss (scalar), g_loss_d (npos) and g_logits

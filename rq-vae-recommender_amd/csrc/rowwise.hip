@@ -604,9 +604,12 @@ __global__ void __launch_bounds__(256) ce_rows_kernel(const float* __restrict__ 
   for (int k = lane; k < K; k += 64) s += expf(x[k] - m);
   s = wave_sum(s);
   if (lane == 0) {
-    const float L = m + logf(s);
+    const float ls = logf(s);
+    const float L = m + ls;
     const int64_t t = tgt[r];
-    lse[r] = L;
+    // saved for the backward: log sum_k exp(x_k - m) alone. m + ls rounds at an ulp of |L| (1.5e-5 at logits near
+    // 150), and that rounding would enter every probability exp(x - L); the backward takes the maximum again.
+    lse[r] = ls;
     u[r] = t < 0 ? 0.f : (t < K ? L - x[t] : __builtin_nanf(""));   // out-of-range target: NaN, loudly
   }
 }
@@ -651,6 +654,7 @@ __global__ void __launch_bounds__(256) ce_means_kernel(const float* __restrict__
 
 // dX row R = b * npos_x + j: (g_loss + g_loss_d[j]) / B * (softmax(x) - onehot(t)) (+ g_logits row) for
 // j < npos and t >= 0; g_logits only for j < npos and t < 0; zeros otherwise.
+constexpr int kCeMaxK = 1024, kCeVals = kCeMaxK / 64;
 __global__ void __launch_bounds__(256) ce_bwd_kernel(const float* __restrict__ X, int64_t ldx, int K,
                                                      const int64_t* __restrict__ tgt, const float* __restrict__ lse,
                                                      int B, int npos, int npos_x, const float* __restrict__ g_loss,
@@ -672,10 +676,24 @@ __global__ void __launch_bounds__(256) ce_bwd_kernel(const float* __restrict__ X
     return;
   }
   const float g = ((g_loss ? g_loss[0] : 0.f) + (g_loss_d ? g_loss_d[j] : 0.f)) / (float)B;
-  const float L = lse[r];
+  const float ls = lse[r];
   const float* x = X + ((int64_t)b * npos_x + j) * ldx;
-  for (int k = lane; k < K; k += 64) {
-    const float p = expf(x[k] - L);
+  // the row once into registers (K <= 1024: 16 values a lane), its maximum as the forward took it, then
+  // p = exp((x - m) - log sum exp(x - m)): the shifted form keeps p to an ulp whatever the size of the logits
+  float xv[kCeVals];
+  float m = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < kCeVals; ++i) {
+    const int k = lane + 64 * i;
+    xv[i] = k < K ? x[k] : -INFINITY;
+    m = fmaxf(m, xv[i]);
+  }
+  m = wave_max(m);
+#pragma unroll
+  for (int i = 0; i < kCeVals; ++i) {
+    const int k = lane + 64 * i;
+    if (k >= K) continue;
+    const float p = expf((xv[i] - m) - ls);
     const float v = g * (p - (k == t ? 1.f : 0.f));
     dx[k] = gl ? v + gl[k] : v;
   }
@@ -804,7 +822,7 @@ extern "C" {
 
 int rq_ce_loss_fwd(const float* X, int64_t ldx, int64_t K, const int64_t* tgt, int64_t B, int64_t npos, int64_t npos_x,
                    float* u, float* lse, float* logits, float* loss, float* loss_d, void* stream) {
-  RQ_CHECK_ARG(B > 0 && K > 0 && K <= 1024 && npos > 0 && npos_x >= npos && ldx >= K && B * npos_x < (1LL << 31),
+  RQ_CHECK_ARG(B > 0 && K > 0 && K <= kCeMaxK && npos > 0 && npos_x >= npos && ldx >= K && B * npos_x < (1LL << 31),
                "rq_ce_loss_fwd: bad shape");
   RQ_CHECK_ARG(X && tgt && u && lse && logits && loss && loss_d, "rq_ce_loss_fwd: null pointer");
   hipStream_t s = (hipStream_t)stream;
@@ -819,7 +837,7 @@ int rq_ce_loss_fwd(const float* X, int64_t ldx, int64_t K, const int64_t* tgt, i
 int rq_ce_loss_bwd(const float* X, int64_t ldx, int64_t K, const int64_t* tgt, const float* lse, int64_t B, int64_t npos,
                    int64_t npos_x, const float* g_loss, const float* g_loss_d, const float* g_logits, float* dX,
                    void* stream) {
-  RQ_CHECK_ARG(B > 0 && K > 0 && K <= 1024 && npos > 0 && npos_x >= npos && ldx >= K && B * npos_x < (1LL << 31),
+  RQ_CHECK_ARG(B > 0 && K > 0 && K <= kCeMaxK && npos > 0 && npos_x >= npos && ldx >= K && B * npos_x < (1LL << 31),
                "rq_ce_loss_bwd: bad shape");
   RQ_CHECK_ARG(X && tgt && lse && dX, "rq_ce_loss_bwd: null pointer");
   const int rows = (int)(B * npos_x);

@@ -9,22 +9,9 @@ against the reference itself."""
 import pytest
 import torch
 
+from rowwise_support import gumbel_ref64 as _ref64
+
 pytestmark = pytest.mark.gpu
-
-
-def _ref64(x0, cb0, proj, noise, T, g_emb, beta=0.25):
-    """Reference Quantize.forward (modules/quantize.py:105-129,146 with distributions/gumbel.py:14-18 and
-    modules/loss.py:34-42) in fp64: (ids, emb, loss, grad_x, grad_codebook, dist) of the same objective."""
-    x = x0.double().requires_grad_(True)
-    w = cb0.double().requires_grad_(True)
-    codebook = w @ proj.double().t() if proj is not None else w
-    dist = (x ** 2).sum(1, keepdim=True) + (codebook.t() ** 2).sum(0, keepdim=True) - 2 * x @ codebook.t()
-    ids = dist.detach().min(1).indices
-    weights = torch.softmax((-dist + noise.double()) / T, dim=-1)
-    emb = weights @ codebook
-    loss = ((x.detach() - emb) ** 2).sum(-1) + beta * ((x - emb.detach()) ** 2).sum(-1)
-    ((emb * g_emb.double()).sum() + loss.sum()).backward()
-    return ids, emb.detach(), loss.detach(), x.grad, w.grad, dist.detach()
 
 
 @pytest.mark.parametrize("B,D,K,T,sim", [(1000, 32, 256, 0.5, False), (777, 64, 256, 0.2, False),

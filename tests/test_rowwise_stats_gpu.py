@@ -7,7 +7,8 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("rows,D", [(196608, 64), (1000, 32), (7, 4), (513, 96), (300, 768), (5, 1028)])
+@pytest.mark.parametrize("rows,D", [(196608, 64), (1000, 32), (7, 4), (513, 96), (300, 768), (5, 1028), (37, 8),
+                                    (37, 16)])
 def test_row_norms(device, rows, D):
     from rqvae_hip import ops
     x = torch.randn(rows, D, device=device, generator=torch.Generator(device=device).manual_seed(rows + D))
