@@ -835,6 +835,51 @@ int rq_codebook_revive(float* const* codebooks, float* const* exp_avg, float* co
                        int64_t D, const int64_t* counts, int64_t min_count, const float* res, int64_t B, uint64_t seed,
                        uint8_t* revived, int64_t* n_revived, void* workspace, size_t ws_bytes, void* stream);
 
+/* EMA-maintained codebooks (csrc/codebook.hip). EXTENSIONS: the update rule of VQ-VAE / Sonnet's
+ * VectorQuantizerEMA; the reference trains its codebooks with AdamW on the codebook term of the loss only.
+ * The rule, per level l and code k, for residuals res (L, B, D) fp32 and ids (B, L) int64:
+ *   n[l][k]   += #{b : ids[b][l] == k}                       exact, int64
+ *   s[l][k][:] = s[l][k][:] + sum_{b : ids[b][l] == k} res[l][b][:]   fp32; the batch sum is formed first, in an
+ *                order that depends on the shapes only (no float atomics: the same bits on every run), and added once
+ *   ids outside [0, K) are skipped. Both are ACCUMULATED (micro-batches and data-parallel shards add up).
+ * and, with decay g and smoothing eps, the update from the accumulated n, s:
+ *   N'[l][k] = g N[l][k] + (1 - g) n[l][k];   S'[l][k] = g S[l][k] + (1 - g) s[l][k];   T[l] = sum_k N'[l][k]
+ *   N~[l][k] = (N'[l][k] + eps) / (T[l] + K eps) * T[l];   codebook_l[k][:] = S'[l][k][:] / N~[l][k]
+ * rq_codebook_ema_stats: 1 <= L <= 16, 1 <= K <= 4096, D % 4 == 0, 4 <= D <= 1024, B < 2^31 (-22 otherwise); B == 0
+ *   is a no-op. res and s 16-byte aligned. Two launches whatever the form, no allocation, no host sync,
+ *   graph-capturable; workspace >= rq_codebook_ema_stats_workspace(B, D, K, L) bytes. Launch 1: workgroups over
+ *   (row chunk, level, code tile) sum their rows into an LDS image of the tile's codes — each of 16 waves owns a
+ *   range of the codes and adds its matching rows in ascending row order — and write it as a partial; launch 2 adds
+ *   the chunks' partials in chunk order into s and n. RQ_EMA_STATS_LDS: a level's K D image is one tile
+ *   (K D <= RQ_EMA_STATS_LDS_ELEMS and K <= 2048, which holds for every D >= 8 under that bound);
+ *   RQ_EMA_STATS_TILED: the codes are split into tiles of codes_per_tile = min(RQ_EMA_STATS_LDS_ELEMS / D, 2048),
+ *   every tile's workgroups re-reading the chunk's ids. A chunk is rows_per_chunk rows (a multiple of 1024), chosen
+ *   so that a level has at most 64 chunks and at most 2^22 / (K D) of them (at least one).
+ * rq_codebook_ema_stats_plan: host-only; the form a shape takes (RQ_EMA_STATS_NONE for B == 0).
+ * rq_codebook_ema_apply: codebooks: HOST array of L device pointers to (K, D) fp32, 16-byte aligned, copied into the
+ *   kernel arguments. N (L, K), S (L, K, D) fp32 state, n (L, K) int64 and s (L, K, D) fp32 statistics; writes N, S
+ *   and the codebooks, zeroes n and s. decay and 1 - decay are rounded to fp32 once each, from the doubles.
+ *   0 <= decay < 1, eps > 0 (-22 otherwise). One launch, one workgroup per level (it rewrites N, which every code's
+ *   N~ reads through T); T is summed in a fixed order. */
+#define RQ_EMA_STATS_NONE 0
+#define RQ_EMA_STATS_LDS 1
+#define RQ_EMA_STATS_TILED 2
+#define RQ_EMA_STATS_LDS_ELEMS 16384   /* floats of a level's K D image that one workgroup keeps in LDS */
+typedef struct rq_codebook_ema_stats_form {
+  int form;                /* RQ_EMA_STATS_* */
+  int chunks;              /* row chunks per level */
+  int tiles;               /* code tiles per level (1: RQ_EMA_STATS_LDS) */
+  int codes_per_tile;
+  int64_t rows_per_chunk;
+  int64_t lds_bytes;       /* launch 1's dynamic LDS */
+} rq_codebook_ema_stats_form;
+int rq_codebook_ema_stats_plan(int64_t B, int64_t D, int64_t K, int64_t L, rq_codebook_ema_stats_form* form);
+size_t rq_codebook_ema_stats_workspace(int64_t B, int64_t D, int64_t K, int64_t L);
+int rq_codebook_ema_stats(const float* res, const int64_t* ids, int64_t B, int64_t D, int64_t K, int64_t L, int64_t* n,
+                          float* s, void* workspace, size_t ws_bytes, void* stream);
+int rq_codebook_ema_apply(float* const* codebooks, int64_t L, int64_t K, int64_t D, float* N, float* S, int64_t* n,
+                          float* s, double decay, double eps, void* stream);
+
 /* Beam-searched residual quantization (extension). The reference encodes greedily: its level loop
  * (modules/rqvae.py:114-138) keeps one residual per item and takes one argmin per level. This call generalises
  * that loop to the W best code paths per item, the beam encoder of Faiss's ResidualQuantizer (max_beam_size).

@@ -1,4 +1,5 @@
-// Codebook usage counters and dead-code revival for the RQ-VAE tokenizer.
+// Codebook usage counters, dead-code revival and EMA-maintained codebooks (statistics + update, below) for the
+// RQ-VAE tokenizer.
 //
 // Extensions: the reference only LOGS codebook usage at checkpoint time (train_rqvae.py:232-239,
 // `codebook_usage_{l}` = len(unique(corpus_ids[:, l])) / K) and has no countermeasure against codebook
@@ -177,6 +178,209 @@ __global__ void __launch_bounds__(kReviveChunk) revive_copy_kernel(const ReviveT
 
 static inline int64_t revive_chunks(int64_t K) { return (K + kReviveChunk - 1) / kReviveChunk; }
 
+// --------------------------------------------------------------------------------- EMA statistics
+// Per-code statistics of a batch for EMA-maintained codebooks (an extension; rule in include/rqvae_hip.h):
+// n[l][k] += #{b : ids[b][l] == k}, s[l][k] += sum of those rows of res[l], no float atomics.
+// Workgroup (c, l, t) owns the rows [c R, (c + 1) R) of level l and the codes [t KT, (t + 1) KT), whose sums it
+// keeps in an LDS image acc[KT][D]. It walks its rows in sub-blocks of kEmaRows ids held in LDS; wave w of 16 owns
+// the tile's codes k with 16 k / KT' == w (KT' = the tile's code count) and collects its matching rows in
+// ascending order (a ballot per 64 rows, as rq_cb_chunk_kernel). A row is G = D / 4 (rounded up to a power of
+// two, at most 64) lanes wide, so one wave load fetches 64 / G matches; they are then added into the image one
+// match at a time, lowest row first (LDS operations of one wave execute in program order), so every acc[k] is a
+// row-ordered sum whatever the other waves do. Counts are LDS integer adds by the owning wave. The image and the
+// counts go to partial[l][c]; ema_stats_reduce adds the chunks in c order (slab_sum_w4) into s and n.
+constexpr int kEmaRows = 1024;       // ids per sub-block
+constexpr int kEmaWaves = 16;
+constexpr int kEmaList = 256;        // match-list entries per wave
+constexpr int kEmaMaxChunks = 64;    // row chunks per level, at most
+constexpr int kEmaMaxTile = 2048;    // codes per tile, at most (their LDS counters)
+constexpr int64_t kEmaPartialElems = 1ll << 22;   // K D chunks <= this (or one chunk): bounds the workspace
+
+struct EmaPlan {
+  int form, chunks, tiles, kt;
+  int64_t rows;
+  size_t lds;
+};
+
+static EmaPlan ema_plan(int64_t B, int64_t D, int64_t K) {
+  EmaPlan p = {RQ_EMA_STATS_NONE, 0, 0, 0, 0, 0};
+  if (B == 0) return p;
+  p.kt = (int)std::min<int64_t>(std::min<int64_t>(K, RQ_EMA_STATS_LDS_ELEMS / D), kEmaMaxTile);
+  p.tiles = (int)((K + p.kt - 1) / p.kt);
+  p.form = p.tiles == 1 ? RQ_EMA_STATS_LDS : RQ_EMA_STATS_TILED;
+  const int64_t max_chunks = std::max<int64_t>(1, std::min<int64_t>(kEmaMaxChunks, kEmaPartialElems / (K * D)));
+  const int64_t blocks = (B + kEmaRows - 1) / kEmaRows;
+  const int64_t per = (blocks + max_chunks - 1) / max_chunks;   // sub-blocks per chunk
+  p.chunks = (int)((blocks + per - 1) / per);
+  p.rows = per * kEmaRows;
+  p.lds = (size_t)p.kt * D * sizeof(float) + (size_t)p.kt * sizeof(int) + kEmaRows * sizeof(int) +
+          kEmaWaves * kEmaList * sizeof(unsigned short);
+  return p;
+}
+
+__global__ void __launch_bounds__(64 * kEmaWaves) ema_stats_kernel(const float* __restrict__ res,
+                                                                   const int64_t* __restrict__ ids, int64_t B, int D, int K,
+                                                                   int L, int KT, int64_t rows, float* __restrict__ part_s,
+                                                                   int* __restrict__ part_n) {
+  extern __shared__ __attribute__((aligned(16))) float acc[];   // [KT][D], counts, the sub-block's ids, match lists
+  int* cnt = reinterpret_cast<int*>(acc + (int64_t)KT * D);
+  int* ids_s = cnt + KT;
+  const int c = blockIdx.x, l = blockIdx.y, t = blockIdx.z, nchunk = gridDim.x, tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63;
+  unsigned short* list = reinterpret_cast<unsigned short*>(ids_s + kEmaRows) + wave * kEmaList;
+  const int k0 = t * KT, kn = min(KT, K - k0), D4 = D / 4;
+  int G = 1;
+  while (G < D4 && G < 64) G <<= 1;
+  const int NR = 64 / G, g = lane / G, col0 = lane & (G - 1);
+  for (int i = tid; i < kn * D4; i += 64 * kEmaWaves) reinterpret_cast<float4*>(acc)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int i = tid; i < kn; i += 64 * kEmaWaves) cnt[i] = 0;
+  const int64_t rbeg = (int64_t)c * rows, rend = min(B, rbeg + rows);
+  const float* xl = res + (int64_t)l * B * D;
+  for (int64_t sb = rbeg; sb < rend; sb += kEmaRows) {   // uniform over the workgroup
+    __syncthreads();   // the image is zeroed / the previous sub-block's ids are consumed
+    for (int i = tid; i < kEmaRows; i += 64 * kEmaWaves) {
+      const int64_t r = sb + i;
+      const int64_t k = r < rend ? ids[r * L + l] : -1;
+      ids_s[i] = (k >= k0 && k < (int64_t)k0 + kn) ? (int)(k - k0) : -1;   // k0 >= 0, k0 + kn <= K
+    }
+    __syncthreads();
+    // this wave's matches (list entries i0 ..), 64 / G at a time: loads first, then the row-ordered adds
+    auto drain = [&](int n_list) {
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the list entries other lanes wrote
+      for (int i0 = 0; i0 < n_list; i0 += NR) {
+        // unconditional loads (lanes past the list repeat its last entry, columns past the row its last column;
+        // neither is added): a branch around a load makes the compiler wait for it at the merge
+        const int row = list[min(i0 + g, n_list - 1)];
+        const int kc = ids_s[row];
+        const float4* __restrict__ src = reinterpret_cast<const float4*>(xl + (sb + row) * D);
+        float4 v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = src[min(col0 + 64 * j, D4 - 1)];
+        float4* a = reinterpret_cast<float4*>(acc + (int64_t)kc * D);
+        const int nb = min(NR, n_list - i0);
+        for (int u = 0; u < nb; ++u) {
+          if (g == u) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const int col = col0 + 64 * j;
+              if (col < D4) {
+                float4 o = a[col];
+                o.x += v[j].x; o.y += v[j].y; o.z += v[j].z; o.w += v[j].w;
+                a[col] = o;
+              }
+            }
+          }
+        }
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the list is rewritten after this
+    };
+    const int nrows = (int)min((int64_t)kEmaRows, rend - sb);
+    int n_list = 0;
+    for (int g0 = 0; g0 < nrows; g0 += 64) {
+      const int kk = ids_s[g0 + lane];
+      const bool mine = kk >= 0 && (kEmaWaves * kk) / kn == wave;
+      const unsigned long long m = __ballot(mine);
+      const int n_mine = __popcll(m);
+      if (n_list + n_mine > kEmaList) {
+        drain(n_list);
+        n_list = 0;
+      }
+      const int before = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+      if (mine) {
+        list[n_list + before] = (unsigned short)(g0 + lane);
+        atomicAdd(&cnt[kk], 1);   // only this wave touches cnt[kk]; lanes may share kk
+      }
+      n_list += n_mine;
+    }
+    drain(n_list);
+  }
+  __syncthreads();
+  const int64_t slot = (int64_t)l * nchunk + c;
+  float4* dst = reinterpret_cast<float4*>(part_s + (slot * K + k0) * D);
+  for (int i = tid; i < kn * D4; i += 64 * kEmaWaves) dst[i] = reinterpret_cast<const float4*>(acc)[i];
+  for (int i = tid; i < kn; i += 64 * kEmaWaves) part_n[slot * K + k0 + i] = cnt[i];
+}
+
+// s[l][j] = s[l][j] + (sum over chunks c, in order, of part_s[l][c][j]); n[l][k] += sum over c of part_n[l][c][k].
+__global__ void __launch_bounds__(256) ema_stats_reduce_kernel(const float* __restrict__ part_s,
+                                                               const int* __restrict__ part_n, int nchunk, int64_t K,
+                                                               int64_t KD, float* __restrict__ s, int64_t* __restrict__ n) {
+  const int l = blockIdx.y;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x, j = 4 * i;
+  if (j < KD) {
+    const float4 r = slab_sum_w4(part_s + (int64_t)l * nchunk * KD, nchunk, KD, j);
+    float4* o = reinterpret_cast<float4*>(s + (int64_t)l * KD + j);
+    float4 v = *o;
+    v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
+    *o = v;
+  }
+  if (i < K) {   // K <= K D / 4: the grid covers every code
+    // eight loads in flight per round (indices past the end re-read the last chunk and are not added), as
+    // strided_slab_sum: one dependent load per chunk made this the longest thread of the launch
+    const int* __restrict__ p = part_n + (int64_t)l * nchunk * K + i;
+    int64_t total = 0;
+    for (int c = 0; c < nchunk; c += 8) {
+      int v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v[u] = p[(int64_t)min(c + u, nchunk - 1) * K];
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        if (c + u < nchunk) total += v[u];
+    }
+    n[(int64_t)l * K + i] += total;
+  }
+}
+
+// ------------------------------------------------------------------------------------- EMA update
+struct EmaTable {   // BY VALUE in the kernel arguments
+  float* cb[kReviveMaxL];
+};
+
+// One workgroup per level: another workgroup of the level would read N while this one rewrites it. Pass 1 writes
+// N' = g N + (1 - g) n, zeroes n and sums T = sum_k N' (per-thread strided sums, a butterfly per wave, the 16 wave
+// sums in wave order: a fixed order); pass 2 writes S', zeroes s and writes the codewords S' / N~.
+constexpr int kEmaApplyThreads = 1024;
+__global__ void __launch_bounds__(kEmaApplyThreads) ema_apply_kernel(const EmaTable tab, int K, int D, float* __restrict__ N,
+                                                                     float* __restrict__ S, int64_t* __restrict__ n,
+                                                                     float* __restrict__ s, float g, float omg, float eps,
+                                                                     float keps) {
+  __shared__ float s_wave[kEmaApplyThreads / 64];
+  const int l = blockIdx.x, tid = threadIdx.x;
+  float* __restrict__ Nl = N + (int64_t)l * K;
+  int64_t* __restrict__ nl = n + (int64_t)l * K;
+  float part = 0.f;
+  for (int k = tid; k < K; k += kEmaApplyThreads) {
+    const float np = g * Nl[k] + omg * (float)nl[k];
+    Nl[k] = np;
+    nl[k] = 0;
+    part += np;
+  }
+  part = group_sum<64>(part);
+  if ((tid & 63) == 0) s_wave[tid >> 6] = part;
+  __syncthreads();   // also: every N' of the level is written
+  float T = 0.f;
+#pragma unroll
+  for (int w = 0; w < kEmaApplyThreads / 64; ++w) T += s_wave[w];
+  const float den = T + keps;
+  const int D4 = D / 4;
+  float4* __restrict__ Sl = reinterpret_cast<float4*>(S + (int64_t)l * K * D);
+  float4* __restrict__ sl = reinterpret_cast<float4*>(s + (int64_t)l * K * D);
+  float4* __restrict__ W = reinterpret_cast<float4*>(tab.cb[l]);
+  for (int e = tid; e < K * D4; e += kEmaApplyThreads) {
+    const float nt = (Nl[e / D4] + eps) / den * T;
+    const float4 a = Sl[e], b = sl[e];
+    const float4 sp = make_float4(g * a.x + omg * b.x, g * a.y + omg * b.y, g * a.z + omg * b.z, g * a.w + omg * b.w);
+    Sl[e] = sp;
+    sl[e] = make_float4(0.f, 0.f, 0.f, 0.f);
+    W[e] = make_float4(sp.x / nt, sp.y / nt, sp.z / nt, sp.w / nt);
+  }
+}
+
+static bool ema_shape_ok(int64_t B, int64_t D, int64_t K, int64_t L) {
+  return L >= 1 && L <= kReviveMaxL && K >= 1 && K <= 4096 && D >= 4 && D % 4 == 0 && D <= 1024 && B >= 0 &&
+         B < (1ll << 31);
+}
+
 }  // namespace rqhip
 
 using namespace rqhip;
@@ -246,6 +450,72 @@ int rq_codebook_revive(float* const* codebooks, float* const* exp_avg, float* co
   hipLaunchKernelGGL(revive_copy_kernel, grid, dim3(kReviveChunk), 0, (hipStream_t)stream, tab, counts, K, D, min_count,
                      res, B, seed, chunk_tot, n_revived);
   RQ_LAUNCH_CHECK("rq_codebook_revive (copy)");
+  return 0;
+}
+
+int rq_codebook_ema_stats_plan(int64_t B, int64_t D, int64_t K, int64_t L, rq_codebook_ema_stats_form* form) {
+  RQ_CHECK_ARG(form != nullptr, "rq_codebook_ema_stats_plan: null form");
+  RQ_CHECK_ARG(ema_shape_ok(B, D, K, L),
+               "rq_codebook_ema_stats: need 1 <= L <= 16, 1 <= K <= 4096, D %% 4 == 0, 4 <= D <= 1024, 0 <= B < 2^31 "
+               "(B=%lld D=%lld K=%lld L=%lld)", (long long)B, (long long)D, (long long)K, (long long)L);
+  const EmaPlan p = ema_plan(B, D, K);
+  form->form = p.form;
+  form->chunks = p.chunks;
+  form->tiles = p.tiles;
+  form->codes_per_tile = p.kt;
+  form->rows_per_chunk = p.rows;
+  form->lds_bytes = (int64_t)p.lds;
+  return 0;
+}
+
+size_t rq_codebook_ema_stats_workspace(int64_t B, int64_t D, int64_t K, int64_t L) {
+  if (!ema_shape_ok(B, D, K, L) || B == 0) return 0;
+  const EmaPlan p = ema_plan(B, D, K);
+  return (size_t)(L * p.chunks * K) * (size_t)(D + 1) * sizeof(float) + 16;
+}
+
+int rq_codebook_ema_stats(const float* res, const int64_t* ids, int64_t B, int64_t D, int64_t K, int64_t L, int64_t* n,
+                          float* s, void* workspace, size_t ws_bytes, void* stream) {
+  rq_codebook_ema_stats_form f;
+  const int rc = rq_codebook_ema_stats_plan(B, D, K, L, &f);
+  if (rc != 0) return rc;
+  if (B == 0) return 0;
+  RQ_CHECK_ARG(res && ids && n && s && workspace, "rq_codebook_ema_stats: null pointer");
+  RQ_CHECK_ARG(((uintptr_t)res | (uintptr_t)s) % 16 == 0, "rq_codebook_ema_stats: res / s must be 16-byte aligned");
+  RQ_CHECK_ARG(ws_bytes >= rq_codebook_ema_stats_workspace(B, D, K, L), "rq_codebook_ema_stats: workspace too small");
+  float* part_s = reinterpret_cast<float*>(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
+  int* part_n = reinterpret_cast<int*>(part_s + L * f.chunks * K * D);
+  hipLaunchKernelGGL(ema_stats_kernel, dim3((unsigned)f.chunks, (unsigned)L, (unsigned)f.tiles), dim3(64 * kEmaWaves),
+                     (size_t)f.lds_bytes, (hipStream_t)stream, res, ids, B, (int)D, (int)K, (int)L, f.codes_per_tile,
+                     f.rows_per_chunk, part_s, part_n);
+  RQ_LAUNCH_CHECK("rq_codebook_ema_stats (chunks)");
+  const int64_t KD = K * D;
+  hipLaunchKernelGGL(ema_stats_reduce_kernel, dim3((unsigned)((KD / 4 + 255) / 256), (unsigned)L), dim3(256), 0,
+                     (hipStream_t)stream, part_s, part_n, f.chunks, K, KD, s, n);
+  RQ_LAUNCH_CHECK("rq_codebook_ema_stats (reduce)");
+  return 0;
+}
+
+int rq_codebook_ema_apply(float* const* codebooks, int64_t L, int64_t K, int64_t D, float* N, float* S, int64_t* n,
+                          float* s, double decay, double eps, void* stream) {
+  RQ_CHECK_ARG(ema_shape_ok(0, D, K, L),
+               "rq_codebook_ema_apply: need 1 <= L <= 16, 1 <= K <= 4096, D %% 4 == 0, 4 <= D <= 1024 (D=%lld K=%lld "
+               "L=%lld)", (long long)D, (long long)K, (long long)L);
+  RQ_CHECK_ARG(decay >= 0.0 && decay < 1.0 && eps > 0.0, "rq_codebook_ema_apply: need 0 <= decay < 1 and eps > 0");
+  RQ_CHECK_ARG(codebooks && N && S && n && s, "rq_codebook_ema_apply: null pointer");
+  RQ_CHECK_ARG(((uintptr_t)S | (uintptr_t)s) % 16 == 0, "rq_codebook_ema_apply: S / s must be 16-byte aligned");
+  EmaTable tab;
+  for (int l = 0; l < kReviveMaxL; ++l) {
+    tab.cb[l] = l < L ? codebooks[l] : nullptr;
+    if (l < L)
+      RQ_CHECK_ARG(tab.cb[l] != nullptr && (uintptr_t)tab.cb[l] % 16 == 0,
+                   "rq_codebook_ema_apply: codebook %d is null or not 16-byte aligned", l);
+  }
+  // decay and 1 - decay are each rounded to fp32 once, from the double (1.0f - (float)decay would carry the
+  // rounding of decay at 1 / (1 - decay) times its relative size)
+  hipLaunchKernelGGL(ema_apply_kernel, dim3((unsigned)L), dim3(kEmaApplyThreads), 0, (hipStream_t)stream, tab, (int)K,
+                     (int)D, N, S, n, s, (float)decay, (float)(1.0 - decay), (float)eps, (float)((double)K * eps));
+  RQ_LAUNCH_CHECK("rq_codebook_ema_apply");
   return 0;
 }
 

@@ -90,6 +90,7 @@ class RqVae(nn.Module):
         self.reconstruction_loss = (CategoricalReconstuctionLoss(n_cat_features) if n_cat_features != 0
                                     else ReconstructionLoss())
         self.code_usage = None   # (L, K) int64 usage counters while track_usage() is on; never a buffer
+        self.ema = None          # use_ema_codebooks(): dict(decay, eps, N, S, n, s); plain tensors, never buffers
 
     @property
     def config(self) -> dict:
@@ -189,7 +190,7 @@ class RqVae(nn.Module):
         x = batch.x
         # the level loop also returns embs_norm = |emb_l| (modules/rqvae.py:151 of the reference),
         # written from the fused kernel's level epilogue
-        emb, _, ids, qloss, emb_sum, emb_norms = self.quantize_levels(self.encode(x), gumbel_t, with_norms=True)
+        emb, res, ids, qloss, emb_sum, emb_norms = self.quantize_levels(self.encode(x), gumbel_t, with_norms=True)
         n = self.n_cat_feats
         head = self.decoder.mlp
         if n == 0 and isinstance(head[-1], L2NormalizationLayer) and x.dtype == torch.float32:
@@ -213,6 +214,9 @@ class RqVae(nn.Module):
             p_unique_ids = hip_ops.unique_fraction(ids, self.codebook_size)
             if self.code_usage is not None and self.training:
                 hip_ops.code_usage(ids, self.code_usage)
+            if self.ema is not None and self.training:
+                from modules.codebook_ema import ema_stats_
+                ema_stats_(res, ids, self.ema["n"], self.ema["s"])
         return RqVaeComputedLosses(loss=loss, reconstruction_loss=recon_mean, rqvae_loss=rq_mean,
                                    embs_norm=embs_norm, p_unique_ids=p_unique_ids)
 
@@ -237,7 +241,8 @@ class RqVae(nn.Module):
         ppl = torch.where(c.sum(1) > 0, torch.exp(ent), torch.zeros_like(ent))
         return (c > 0).to(torch.float64).mean(1).tolist(), ppl.tolist()
 
-    def revive_dead_codes(self, x: Tensor, *, min_count: int = 1, seed: int, optimizer=None) -> Tensor:
+    def revive_dead_codes(self, x: Tensor, *, min_count: int = 1, seed: int, optimizer=None,
+                          ema_min_count: float = None) -> Tensor:
         """Re-seat every codeword counted fewer than min_count times since the counters were last zeroed on the
         residual of a row of x (modules.codebook_revival.revive_: the rule, the data-parallel protocol) ->
         n_revived (L,) int64; zeroes the counters. x (B >= K, input_dim): data rows; their level inputs come from
@@ -245,9 +250,14 @@ class RqVae(nn.Module):
         levels are knowingly not recomputed after a shallower level is re-seated, so a deeper donor is a residual
         the old shallower codebook left. optimizer: when given, the exp_avg / exp_avg_sq rows of the re-seated
         codewords are zeroed too (if that state exists yet). Parameters and moments are written through their
-        existing storage, so captured graphs stay valid. L2-distance levels without out_proj only."""
+        existing storage, so captured graphs stay valid. L2-distance levels without out_proj only.
+        ema_min_count (EMA codebooks only): the dead set is {k : N[l][k] < ema_min_count}, the decayed usage of the
+        EMA state, instead of the window counters (track_usage() is then not needed; N is identical on every rank).
+        After any revival with EMA codebooks on, the re-seated rows restart at N = 1, S = W."""
         from modules.codebook_revival import revive_
-        if self.code_usage is None:
+        if ema_min_count is not None and self.ema is None:
+            raise ValueError("revive_dead_codes: ema_min_count needs use_ema_codebooks()")
+        if ema_min_count is None and self.code_usage is None:
             raise ValueError("revive_dead_codes: call track_usage() first")
         for layer in self.layers:
             if not all(isinstance(m, nn.Identity) for m in layer.out_proj):
@@ -271,5 +281,106 @@ class RqVae(nn.Module):
             states = [optimizer.state.get(w, {}) for w in weights]
             if all("exp_avg" in st and "exp_avg_sq" in st for st in states):
                 moments = ([st["exp_avg"] for st in states], [st["exp_avg_sq"] for st in states])
-        return revive_(weights, self.code_usage, res, min_count=min_count, seed=seed,
-                       exp_avg=moments and moments[0], exp_avg_sq=moments and moments[1])
+        import torch.distributed as dist
+        dead = None
+        if ema_min_count is None:
+            counts = self.code_usage
+            if self.ema is not None:   # the dead set revive_ will see: the counters summed over the ranks
+                total = counts.clone()
+                if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+                    dist.all_reduce(total, op=dist.ReduceOp.SUM)
+                dead = total < min_count
+        else:
+            # dead <=> N < ema_min_count, as counters for revive_'s `counts < min_count`; N is the same on every
+            # rank, so the ranks' sum (world x these) keeps the dead set: dead codes stay 0
+            counts, min_count = (self.ema["N"] >= float(ema_min_count)).to(torch.int64), 1
+            dead = counts < min_count
+        n_rev = revive_(weights, counts, res, min_count=min_count, seed=seed,
+                        exp_avg=moments and moments[0], exp_avg_sq=moments and moments[1])
+        if self.ema is not None:
+            N, S = self.ema["N"], self.ema["S"]
+            for l, w in enumerate(weights):
+                # copies and a constant: the ranks still agree bit for bit
+                N[l] = torch.where(dead[l], torch.ones_like(N[l]), N[l])
+                S[l] = torch.where(dead[l][:, None], w.detach(), S[l])
+        return n_rev
+
+    # ---------------------------------------------------------------- EMA-maintained codebooks (extension)
+    def use_ema_codebooks(self, decay: float = 0.99, eps: float = 1e-5) -> None:
+        """Maintain the codebooks as an exponential moving average of the residuals assigned to them
+        (modules.codebook_ema: the rule, the data-parallel protocol) instead of by the optimizer: every TRAINING
+        forward adds its per-code counts and residual sums into `self.ema["n"]`, `self.ema["s"]` (one
+        codebook_ema_stats call, captured with a graphed step; eval forwards do not), and `ema_update()` — once per
+        optimizer step, eagerly, after `opt.step()` — applies the update. The L codebook weights stop requiring a
+        gradient, so gradient buckets and AdamW (and its weight decay) leave them alone: call this BEFORE the
+        buckets and the optimizer are built and before the first captured step. With torch.distributed initialised
+        and more than one rank the codebooks are broadcast from rank 0 here (the buckets no longer do). The state
+        N (L, K), S (L, K, D) starts as N = 1, S = W; like `code_usage` it is a plain attribute, not a buffer:
+        state_dict() keeps the reference's keys (ema_state_dict() / load_ema_state_dict() for checkpoints). The loss
+        values and the encoder's commitment gradient are unchanged. L2-distance levels without out_proj whose
+        k-means init is done, forward mode STE or ROTATION_TRICK."""
+        import torch.distributed as dist
+        from modules.codebook_ema import initial_state
+        hip_ops.ema_check_args(self.n_layers, self.codebook_size, self.embed_dim, float(decay), float(eps),
+                               "use_ema_codebooks")
+        for layer in self.layers:
+            if not all(isinstance(m, nn.Identity) for m in layer.out_proj):
+                raise ValueError("use_ema_codebooks: codebooks with an out_proj (sim_vq / codebook_normalize) are not "
+                                 "supported")
+            if layer.distance_mode != QuantizeDistance.L2:
+                raise ValueError("use_ema_codebooks: needs L2-distance levels")
+            if layer.needs_init():
+                raise ValueError("use_ema_codebooks: the k-means init of the codebooks is still pending")
+            if layer.forward_mode not in (QuantizeForwardMode.STE, QuantizeForwardMode.ROTATION_TRICK):
+                raise ValueError("use_ema_codebooks: the forward mode must be STE or ROTATION_TRICK, got "
+                                 f"{layer.forward_mode}")
+        weights = [layer.embedding.weight for layer in self.layers]
+        for w in weights:
+            w.requires_grad_(False)
+            w.grad = None
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            for w in weights:
+                dist.broadcast(w.data, src=0)
+        N, S, n, s = initial_state(weights)
+        self.ema = dict(decay=float(decay), eps=float(eps), N=N, S=S, n=n, s=s)
+
+    def _ema(self, what: str) -> dict:
+        if self.ema is None:
+            raise ValueError(f"{what}: call use_ema_codebooks() first")
+        return self.ema
+
+    def ema_update(self, group=None) -> None:
+        """One EMA update of the codebooks from the statistics accumulated since the last one (summed over the
+        data-parallel ranks first); zeroes the statistics. Writes the weights through their existing storage, so
+        captured graphs stay valid."""
+        from modules.codebook_ema import ema_apply_
+        e = self._ema("ema_update")
+        ema_apply_([layer.embedding.weight for layer in self.layers], e["N"], e["S"], e["n"], e["s"],
+                   decay=e["decay"], eps=e["eps"], group=group)
+
+    def ema_discard_stats(self) -> None:
+        """Zero the accumulated statistics without an update (e.g. after the warm-up passes of a step capture,
+        which run training forwards on the step's batch)."""
+        e = self._ema("ema_discard_stats")
+        e["n"].zero_()
+        e["s"].zero_()
+
+    def ema_state_dict(self) -> dict:
+        """{"decay", "eps", "N", "S"}: what a checkpoint needs beside state_dict() (the statistics of an unfinished
+        step are not part of it)."""
+        e = self._ema("ema_state_dict")
+        return {"decay": e["decay"], "eps": e["eps"], "N": e["N"].clone(), "S": e["S"].clone()}
+
+    def load_ema_state_dict(self, state: dict) -> None:
+        """Restore ema_state_dict()'s result (after use_ema_codebooks(); decay and eps are taken from `state`)."""
+        e = self._ema("load_ema_state_dict")
+        if tuple(state["N"].shape) != tuple(e["N"].shape) or tuple(state["S"].shape) != tuple(e["S"].shape):
+            raise ValueError(f"load_ema_state_dict: N / S must be {tuple(e['N'].shape)} / {tuple(e['S'].shape)}, got "
+                             f"{tuple(state['N'].shape)} / {tuple(state['S'].shape)}")
+        hip_ops.ema_check_args(self.n_layers, self.codebook_size, self.embed_dim, float(state["decay"]),
+                               float(state["eps"]), "load_ema_state_dict")
+        e["decay"], e["eps"] = float(state["decay"]), float(state["eps"])
+        e["N"].copy_(state["N"])
+        e["S"].copy_(state["S"])
+        e["n"].zero_()
+        e["s"].zero_()

@@ -21,6 +21,7 @@ _I = ctypes.c_int
 _F = ctypes.c_float
 _SZ = ctypes.c_size_t
 _U64 = ctypes.c_uint64
+_D = ctypes.c_double
 
 _SIGS = {
     "rq_abi_version": ([], _I),
@@ -120,6 +121,10 @@ _SIGS = {
     "rq_code_usage": ([_P, _I64, _I64, _I64, _P, _P], _I),
     "rq_codebook_revive_workspace": ([_I64, _I64], _SZ),
     "rq_codebook_revive": ([_P, _P, _P, _I64, _I64, _I64, _P, _I64, _P, _I64, _U64, _P, _P, _P, _SZ, _P], _I),
+    "rq_codebook_ema_stats_plan": ([_I64, _I64, _I64, _I64, _P], _I),
+    "rq_codebook_ema_stats_workspace": ([_I64, _I64, _I64, _I64], _SZ),
+    "rq_codebook_ema_stats": ([_P, _P, _I64, _I64, _I64, _I64, _P, _P, _P, _SZ, _P], _I),
+    "rq_codebook_ema_apply": ([_P, _I64, _I64, _I64, _P, _P, _P, _P, _D, _D, _P], _I),
     "rq_quantize_beam_workspace": ([_I64, _I64, _I64, _I64, _I64], _SZ),
     "rq_quantize_beam": ([_P, _I64, _I64, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _SZ, _P], _I),
 }
@@ -150,6 +155,13 @@ class QuantizeBwdForm(ctypes.Structure):
     """rq_quantize_bwd_form (include/rqvae_hip.h): pass ctypes.byref(QuantizeBwdForm()) to rq_quantize_bwd_plan."""
     _fields_ = [("lpi", _I), ("epl", _I), ("route", _I), ("vpl", _I), ("chunks", _I), ("contrib", _I),
                 ("seg_direct", _I), ("seg_split", _I)]
+
+
+class EmaStatsForm(ctypes.Structure):
+    """rq_codebook_ema_stats_form (include/rqvae_hip.h): pass ctypes.byref(EmaStatsForm()) to
+    rq_codebook_ema_stats_plan."""
+    _fields_ = [("form", _I), ("chunks", _I), ("tiles", _I), ("codes_per_tile", _I), ("rows_per_chunk", _I64),
+                ("lds_bytes", _I64)]
 
 
 _lib = None

@@ -127,6 +127,9 @@ class GraphedSteps:
       static inputs before a capture. Beyond `max_graphs` distinct graphs, new (signature, key)
       pairs run eagerly (e.g. token-balanced shards whose sequence count changes every step).
     * All graphs share one memory pool (they never run concurrently).
+    * `after_warmup()` runs eagerly after a new key's warm-up passes and before its capture: a step that
+      accumulates into state outside the gradients (RqVae's EMA codebook statistics) discards there what the
+      warm-up passes, which run the body on the step's own batch, added.
     * `capture=False` runs the same bodies eagerly (the exchange inside the body, as captured): the
       CPU / gloo tests exercise the in-graph exchange logic this way.
     * A capture must not overlap a live eager autograd graph of the same parameters (e.g. a kept
@@ -134,8 +137,10 @@ class GraphedSteps:
       break the capture. Drop such references (or `.detach()` them) before a new key's first call."""
 
     def __init__(self, loss_fn, key_fn, buckets, prepare=None, warmup: int = 2, run_backward: bool = True,
-                 in_graph_exchange=None, capture: bool = True, max_graphs: int = 16, local_fallback=None):
+                 in_graph_exchange=None, capture: bool = True, max_graphs: int = 16, local_fallback=None,
+                 after_warmup=None):
         self.loss_fn, self.key_fn, self.buckets, self.prepare, self.warmup = loss_fn, key_fn, buckets, prepare, warmup
+        self.after_warmup = after_warmup
         self.run_backward = run_backward
         self.in_graph = _in_graph_default(buckets) if in_graph_exchange is None else bool(in_graph_exchange)
         self.local_fallback = _local_fallback_default() if local_fallback is None else bool(local_fallback)
@@ -272,6 +277,8 @@ class GraphedSteps:
         if self.prepare is not None:
             self.prepare(self.static, batch)
         self._warm()
+        if self.after_warmup is not None:
+            self.after_warmup()
         exchanged = self.in_graph
         agree = exchanged and not self._settled and self._agreed()   # the job's first capture, world > 1
         # thread_local capture mode everywhere: other threads of the process keep making HIP calls while

@@ -16,6 +16,8 @@
                                              that lead to an allowed item (beam_expand's allowed=), two launches
   code_usage / codebook_revive               tokenizer health: per-level code histogram added into device counters, one launch;
                                              dead codewords re-seated on data residuals (bit copies, moments zeroed), two launches
+  codebook_ema_stats / codebook_ema_apply    EMA-maintained codebooks: per-code counts and residual sums added into device
+                                             accumulators in a fixed order, two launches; the EMA update of every level, one launch
   rq_quantize_beam                           beam-searched residual quantization: the W best code paths per item, one launch
 
 All kernels run on torch's current HIP stream; tensors must be on the GPU (no CPU path).
@@ -3003,6 +3005,98 @@ def codebook_revive(weights, counts: torch.Tensor, res: torch.Tensor, min_count:
     call("rq_codebook_revive", tabs[0], tabs[1], tabs[2], L, K, D, ptr(counts), min_count, ptr(res), B,
          int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(revived), ptr(n_revived), ptr(ws), nbytes, stream_handle(dev))
     return revived.view(torch.bool), n_revived
+
+
+# ------------------------------------------------------------------ EMA-maintained codebooks
+EMA_MAX_L, EMA_MAX_K, EMA_MAX_D = 16, 4096, 1024   # the limits of rq_codebook_ema_stats / rq_codebook_ema_apply
+
+
+def ema_check_args(L: int, K: int, D: int, decay: float = 0.0, eps: float = 1.0, what: str = "codebook_ema") -> None:
+    """The argument limits of rq_codebook_ema_stats / rq_codebook_ema_apply (ValueError outside them), shared with
+    the CPU path of modules.codebook_ema."""
+    if not 1 <= L <= EMA_MAX_L:
+        raise ValueError(f"{what}: need 1 <= L <= {EMA_MAX_L} levels, got {L}")
+    if not 1 <= K <= EMA_MAX_K:
+        raise ValueError(f"{what}: need 1 <= K <= {EMA_MAX_K}, got {K}")
+    if D < 4 or D % 4 != 0 or D > EMA_MAX_D:
+        raise ValueError(f"{what}: need D % 4 == 0 and 4 <= D <= {EMA_MAX_D}, got {D}")
+    if not 0.0 <= decay < 1.0:
+        raise ValueError(f"{what}: need 0 <= decay < 1, got {decay}")
+    if not eps > 0.0:
+        raise ValueError(f"{what}: need eps > 0, got {eps}")
+
+
+def _ema_stat_args(what, n, s, dev):
+    if n.dim() != 2 or s.dim() != 3 or tuple(s.shape[:2]) != tuple(n.shape):
+        raise ValueError(f"{what}: need n (L, K) and s (L, K, D), got {tuple(n.shape)}, {tuple(s.shape)}")
+    _beam_arg(n, torch.int64, what, "n")
+    _beam_arg(s, torch.float32, what, "s")
+    if n.device != dev or s.device != dev:
+        raise RqHipError(f"{what}: every tensor must be on {dev}")
+
+
+def codebook_ema_stats_plan(B: int, D: int, K: int, L: int) -> "_lib.EmaStatsForm":
+    """The form rq_codebook_ema_stats takes for a shape (host only; rq_codebook_ema_stats_plan)."""
+    import ctypes
+    form = _lib.EmaStatsForm()
+    call("rq_codebook_ema_stats_plan", int(B), int(D), int(K), int(L), ctypes.byref(form))
+    return form
+
+
+def codebook_ema_stats(res: torch.Tensor, ids: torch.Tensor, n: torch.Tensor, s: torch.Tensor):
+    """n (L, K) int64 += the per-level histogram of ids (B, L) int64, s (L, K, D) fp32 += the per-code sums of the
+    rows of res (L, B, D) fp32 (rq_codebook_ema_stats); ids outside [0, K) are skipped. The batch sum is formed in a
+    fixed order (no float atomics: the same bits on every run) and added to s once. Two launches, no host read
+    (graph-capturable) -> (n, s)."""
+    what = "codebook_ema_stats"
+    require_gpu(res, ids, n, s, what=what)
+    if res.dim() != 3 or ids.dim() != 2 or tuple(ids.shape) != (res.shape[1], res.shape[0]):
+        raise ValueError(f"{what}: need res (L, B, D) and ids (B, L), got {tuple(res.shape)}, {tuple(ids.shape)}")
+    L, B, D = res.shape
+    _ema_stat_args(what, n, s, res.device)
+    K = n.shape[1]
+    if n.shape[0] != L or s.shape[2] != D:
+        raise ValueError(f"{what}: n / s do not match res (L={L}, D={D}): {tuple(n.shape)}, {tuple(s.shape)}")
+    ema_check_args(L, K, D, what=what)
+    if B >= 1 << 31:
+        raise ValueError(f"{what}: need B < 2^31, got {B}")
+    _beam_arg(res, torch.float32, what, "res")
+    _beam_arg(ids, torch.int64, what, "ids")
+    if ids.device != res.device:
+        raise RqHipError(f"{what}: every tensor must be on {res.device}")
+    nbytes = _lib.load().rq_codebook_ema_stats_workspace(B, D, K, L)
+    ws = torch.empty((max(nbytes, 1),), device=res.device, dtype=torch.uint8)
+    call("rq_codebook_ema_stats", ptr(res), ptr(ids), B, D, K, L, ptr(n), ptr(s), ptr(ws), nbytes,
+         stream_handle(res.device))
+    return n, s
+
+
+def codebook_ema_apply(weights, N: torch.Tensor, S: torch.Tensor, n: torch.Tensor, s: torch.Tensor, decay: float,
+                       eps: float) -> None:
+    """The EMA update of every level IN PLACE (rq_codebook_ema_apply): N' = decay N + (1 - decay) n, S' likewise,
+    weights[l][k] = S'[l][k] / N~[l][k] with N~ = (N' + eps) / (sum_k N' + K eps) * sum_k N'; n and s are zeroed.
+    weights: L fp32 (K, D) tensors; N (L, K), S (L, K, D) fp32; n (L, K) int64, s (L, K, D) fp32. One launch."""
+    import ctypes
+    what = "codebook_ema_apply"
+    weights = list(weights)
+    if not weights or weights[0].dim() != 2:
+        raise ValueError(f"{what}: weights must be a non-empty list of (K, D) tensors")
+    require_gpu(*weights, N, S, n, s, what=what)
+    L, (K, D) = len(weights), weights[0].shape
+    ema_check_args(L, K, D, float(decay), float(eps), what)
+    dev = weights[0].device
+    _ema_stat_args(what, n, s, dev)
+    for t in weights:
+        _beam_arg(t.detach(), torch.float32, what, "every weight", (K, D))
+    _beam_arg(N, torch.float32, what, "N", (L, K))
+    _beam_arg(S, torch.float32, what, "S", (L, K, D))
+    if tuple(n.shape) != (L, K) or tuple(s.shape) != (L, K, D):
+        raise ValueError(f"{what}: n / s must be ({L}, {K}) and ({L}, {K}, {D})")
+    if any(t.device != dev for t in weights + [N, S]):
+        raise RqHipError(f"{what}: every tensor must be on {dev}")
+    tab = (ctypes.c_void_p * L)(*[t.data_ptr() for t in weights])
+    call("rq_codebook_ema_apply", tab, L, K, D, ptr(N), ptr(S), ptr(n), ptr(s), float(decay), float(eps),
+         stream_handle(dev))
 
 
 # ------------------------------------------------------------------ beam-searched residual quantization

@@ -17,7 +17,9 @@ Differences from the reference loop (train_rqvae.py:24-250), all on the MI355X p
   * the loop runs `iterations + 1` times like the reference (SURVEY A-4);
   * opt-in extension (REVIVE_EVERY, off by default): per-level code usage counted inside the step and dead codewords
     re-seated on data residuals between steps (modules/codebook_revival.py); rank 0 prints one JSON line per revival,
-    {"iter", "revived", "codebook_used", "codebook_perplexity"} (the last two from its own counters).
+    {"iter", "revived", "codebook_used", "codebook_perplexity"} (the last two from its own counters);
+  * opt-in extension (CODEBOOK_EMA_DECAY, off by default): codebooks maintained as an exponential moving average of
+    the residuals assigned to them (modules/codebook_ema.py) instead of by AdamW.
 Data: `data.processed.ItemData` (seeded synthetic corpus unless `data_path` names a feature file).
 """
 import contextlib
@@ -58,6 +60,14 @@ def sample_batch_indices(gen: torch.Generator, n_items: int, global_batch: int, 
 # batch stream of a run is the same with the feature on or off). 0: off — no counter launch, no extra state.
 REVIVE_EVERY = 0
 REVIVE_MIN_COUNT = 1
+# EMA-maintained codebooks (modules/codebook_ema.py; an extension, off by default): CODEBOOK_EMA_DECAY > 0
+# keeps the codebooks as an exponential moving average of the residuals assigned to them instead of training them
+# with AdamW: per-code statistics inside the step, one update after the optimiser step, a "codebook_ema" checkpoint
+# key. 0: off — no extra launch, no extra state, no extra key. REVIVE_EMA_MIN_COUNT (with REVIVE_EVERY and EMA on):
+# revival re-seats the codes whose decayed usage N is below it instead of reading the window counters.
+CODEBOOK_EMA_DECAY = 0
+CODEBOOK_EMA_EPS = 1e-5
+REVIVE_EMA_MIN_COUNT = None
 
 
 # Last train() call: steady-state time per iteration (CUDA-synchronised once at the start and once at
@@ -106,13 +116,17 @@ def train(iterations=50000, batch_size=64, learning_rate=0.0001, weight_decay=0.
                   codebook_size=vae_codebook_size, codebook_kmeans_init=use_kmeans_init and pretrained_rqvae_path is None,
                   codebook_normalize=vae_codebook_normalize, codebook_sim_vq=vae_sim_vq, codebook_mode=vae_codebook_mode,
                   n_layers=vae_n_layers, n_cat_features=vae_n_cat_feats, commitment_weight=commitment_weight).to(device)
-    opt = hip_optim.AdamW(model.parameters(), lr=learning_rate, weight_decay=weight_decay)
+    ema_on = CODEBOOK_EMA_DECAY > 0
     start_iter = 0
+    state = None
     if pretrained_rqvae_path is not None:
         state = torch.load(pretrained_rqvae_path, map_location=device, weights_only=True)
         model.load_state_dict(state["model"])
-        opt.load_state_dict(state["optimizer"])
         start_iter = state["iter"] + 1
+    if not ema_on:
+        opt = hip_optim.AdamW(model.parameters(), lr=learning_rate, weight_decay=weight_decay)
+        if state is not None:
+            opt.load_state_dict(state["optimizer"])
 
     tokenizer = SemanticIdTokenizer(input_dim=vae_input_dim, hidden_dims=vae_hidden_dims, output_dim=vae_embed_dim,
                                     codebook_size=vae_codebook_size, n_layers=vae_n_layers, n_cat_feats=vae_n_cat_feats,
@@ -126,6 +140,15 @@ def train(iterations=50000, batch_size=64, learning_rate=0.0001, weight_decay=0.
                 model(SeqBatch(None, None, None, items[: min(20000, n_items)], None, None), 0.2)
         for layer in model.layers:
             layer.kmeans_initted = True
+    if ema_on:
+        # after the k-means block, before the buckets and the optimizer: both then leave the codebooks alone
+        model.use_ema_codebooks(decay=CODEBOOK_EMA_DECAY, eps=CODEBOOK_EMA_EPS)
+        opt = hip_optim.AdamW([p for p in model.parameters() if p.requires_grad], lr=learning_rate,
+                              weight_decay=weight_decay)
+        if state is not None:
+            opt.load_state_dict(state["optimizer"])
+            if "codebook_ema" in state:
+                model.load_ema_state_dict(state["codebook_ema"])
     # grads become ready decoder -> codebooks -> encoder: the first bucket's all-reduce overlaps the
     # encoder backward
     buckets = dp.GradBuckets([list(model.decoder.parameters()) + list(model.layers.parameters()),
@@ -147,10 +170,13 @@ def train(iterations=50000, batch_size=64, learning_rate=0.0001, weight_decay=0.
         return torch.stack([total, out.reconstruction_loss.detach(), out.rqvae_loss.detach(),
                             out.p_unique_ids.detach()])
 
+    ema_revive = ema_on and REVIVE_EMA_MIN_COUNT is not None
     if REVIVE_EVERY > 0:
-        model.track_usage()   # before the first step: the counter launch is captured with it
+        if not ema_revive:
+            model.track_usage()   # before the first step: the counter launch is captured with it
         revive_gen = torch.Generator(device=device).manual_seed(seed + 29)   # same stream on every rank
-    graphed = GraphedSteps(step_body, lambda idx: 0, buckets, run_backward=False) if cuda_graphs else None
+    graphed = GraphedSteps(step_body, lambda idx: 0, buckets, run_backward=False,
+                           after_warmup=model.ema_discard_stats if ema_on else None) if cuda_graphs else None
     gen = torch.Generator(device=device).manual_seed(seed + 17)   # same stream on every rank
     hist = []
     t0 = time.time()
@@ -170,15 +196,22 @@ def train(iterations=50000, batch_size=64, learning_rate=0.0001, weight_decay=0.
             stats = step_body(idx)
         buckets.synchronize()
         opt.step()
+        if ema_on:
+            model.ema_update()   # eager, between replays, like revival: the weights keep their storage
         if REVIVE_EVERY > 0 and (it + 1) % REVIVE_EVERY == 0:
             # eager, between replays: parameters and moments are written through their existing storage
             ridx = torch.randint(0, n_items, (max(vae_codebook_size, hi - lo),), generator=revive_gen, device=device)
-            used, ppl = model.usage_stats()
-            n_rev = model.revive_dead_codes(items[ridx], min_count=REVIVE_MIN_COUNT, seed=splitmix64(seed, it),
-                                            optimizer=opt)
+            if ema_revive:
+                n_rev = model.revive_dead_codes(items[ridx], seed=splitmix64(seed, it), optimizer=opt,
+                                                ema_min_count=REVIVE_EMA_MIN_COUNT)
+                line = {"iter": it, "revived": n_rev.tolist()}
+            else:
+                used, ppl = model.usage_stats()
+                n_rev = model.revive_dead_codes(items[ridx], min_count=REVIVE_MIN_COUNT, seed=splitmix64(seed, it),
+                                                optimizer=opt)
+                line = {"iter": it, "revived": n_rev.tolist(), "codebook_used": used, "codebook_perplexity": ppl}
             if rank == 0:
-                print(json.dumps({"iter": it, "revived": n_rev.tolist(), "codebook_used": used,
-                                  "codebook_perplexity": ppl}), flush=True)
+                print(json.dumps(line), flush=True)
         hist.append(stats)
         if it == last_it - 1 and t_mark is not None:
             torch.cuda.synchronize()
@@ -210,8 +243,10 @@ def train(iterations=50000, batch_size=64, learning_rate=0.0001, weight_decay=0.
         if rank == 0 and ((it + 1) % save_model_every == 0 or it + 1 == iterations):
             os.makedirs(save_dir_root, exist_ok=True)
             config = {k: (v.name if isinstance(v, Enum) else v) for k, v in model.config.items()}   # tensors/plain only
-            torch.save({"iter": it, "model": model.state_dict(), "model_config": config,
-                        "optimizer": opt.state_dict()}, os.path.join(save_dir_root, f"checkpoint_{it}.pt"))
+            ckpt = {"iter": it, "model": model.state_dict(), "model_config": config, "optimizer": opt.state_dict()}
+            if ema_on:
+                ckpt["codebook_ema"] = model.ema_state_dict()
+            torch.save(ckpt, os.path.join(save_dir_root, f"checkpoint_{it}.pt"))
             tokenizer.reset()
             model.eval()
             corpus_ids = tokenizer.precompute_corpus_ids(index_ds)
