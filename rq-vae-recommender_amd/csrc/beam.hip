@@ -1473,20 +1473,158 @@ __global__ void __launch_bounds__(kAllowThreads) trie_bias_finish_kernel(BiasLev
   }
 }
 
-// Host side of the expand kernels: f(BLOCKED, FILTERED), the two as std::bool_constant values — the instantiation that
-// the filters given ask for
-template <typename F>
-static void with_filters(bool blocked, bool filtered, F f) {
-  if (filtered) {
-    if (blocked) f(std::true_type{}, std::true_type{}); else f(std::false_type{}, std::true_type{});
+// Host side of the expand kernels: f(BLOCKED, FILTERED, BIASED), the three as std::bool_constant values — the one
+// instantiation the tables given ask for. BiasArgs: BIASED, never FILTERED; AllowedBits: FILTERED iff it has a group.
+template <typename Rows, typename F>
+static void with_tables(bool blocked, const Rows& rows, F f) {
+  constexpr bool kBia = std::is_same_v<Rows, BiasArgs>;
+  auto blk = [&](auto flt) {
+    if (blocked) f(std::true_type{}, flt, std::bool_constant<kBia>{});
+    else f(std::false_type{}, flt, std::bool_constant<kBia>{});
+  };
+  if constexpr (kBia) blk(std::false_type{});
+  else if (rows.group != nullptr) blk(std::true_type{});
+  else blk(std::false_type{});
+}
+
+// An int64 size of the C ABI as the int of a kernel argument struct; where it does not fit, -1, which every check refuses
+static int arg_int(int64_t v) { return v < 0 || v > 0x7fffffff ? -1 : (int)v; }
+
+// The argument checks of the three expand entry points, in one order; fn is the entry point's name for the message.
+// beams_ok / beam_names: the P == 0 rule over the entry point's own beam arrays; own_ptrs: its logits and outputs; ab:
+// its catalogue bitmap, NULL where it takes none. After a 0 the caller still returns at once when B == 0 (nothing is
+// dereferenced, NULL is fine then).
+enum class ExpandForm { kDense, kWide, kSampled };
+static int beam_expand_check(const char* fn, ExpandForm form, float temperature, int64_t n_nodes, const int32_t* tok,
+                             int64_t n_children, bool beams_ok, const char* beam_names, int64_t B, int64_t kprev,
+                             int64_t V, int64_t P, int64_t k, bool own_ptrs, const int32_t* blocked, int64_t n_blocked,
+                             const AllowedBits* ab) {
+  const bool filtered = ab && ab->group;
+  RQ_CHECK_ARG(B >= 0 && kprev >= 1 && V >= 1 && P >= 0 && P < 64, "%s: bad shape", fn);
+  if (form == ExpandForm::kWide) {
+    RQ_CHECK_ARG(V <= kBeamMaxV && kprev <= kWideMax && k >= 1 && k <= kWideMax,
+                 "%s: need V <= %d, kprev <= %d and 1 <= k <= %d (kprev=%lld, V=%lld, k=%lld)", fn, kBeamMaxV,
+                 kWideMax, kWideMax, (long long)kprev, (long long)V, (long long)k);
   } else {
-    if (blocked) f(std::true_type{}, std::false_type{}); else f(std::false_type{}, std::false_type{});
+    RQ_CHECK_ARG(V <= kBeamMaxV && kprev <= kBeamMaxN && kprev * V <= kBeamMaxN,
+                 "%s: need V <= %d and kprev * V <= %d (kprev=%lld, V=%lld)%s", fn, kBeamMaxV, kBeamMaxN,
+                 (long long)kprev, (long long)V,
+                 form == ExpandForm::kSampled
+                     ? "; the wide form (more than 32 beams at V = 256) is not built for the sampled step"
+                     : "");
+    RQ_CHECK_ARG(k >= 1 && k <= kBeamMaxN, "%s: need 1 <= k <= %d (k=%lld)", fn, kBeamMaxN, (long long)k);
   }
+  RQ_CHECK_ARG(temperature > 0.f && temperature <= 3.0e38f, "%s: temperature must be positive", fn);
+  RQ_CHECK_ARG(n_nodes >= 0 && n_nodes < 0x7fffffff && n_children >= 0 && n_children <= 0x7fffffff,
+               "%s: bad trie level (n_nodes=%lld, n_children=%lld)", fn, (long long)n_nodes, (long long)n_children);
+  RQ_CHECK_ARG(beams_ok, "%s: %s are all NULL when P == 0, all given otherwise", fn, beam_names);
+  RQ_CHECK_ARG(n_blocked >= 0 && n_blocked <= kBlockedMax, "%s: need 0 <= n_blocked <= %d (n_blocked=%lld)", fn,
+               kBlockedMax, (long long)n_blocked);
+  RQ_CHECK_ARG(!filtered || (ab->n_words >= 0 && ab->n_words <= 0x7fffffff / 32 && ab->G >= 0),
+               "%s: bad bitmap (n_words=%d, G=%d)", fn, filtered ? ab->n_words : 0, filtered ? ab->G : 0);
+  if (B == 0) return 0;
+  RQ_CHECK_ARG(B <= 0x7fffffff, "%s: too many batch elements", fn);
+  RQ_CHECK_ARG(own_ptrs && (tok || n_children == 0) && (blocked || n_blocked == 0) &&
+                   (!filtered || ab->bits || (int64_t)ab->n_words * ab->G == 0),
+               "%s: null pointer", fn);
+  return 0;
+}
+
+static size_t beam_expand_lds(int64_t kprev, int64_t V, int64_t n_blocked, bool biased) {   // expand_prologue's layout
+  return (size_t)((kprev * V + 3) / 4 * 4 + 2 * kExpMaxWaves) * sizeof(uint32_t) +
+         (size_t)n_blocked * sizeof(int32_t) + (biased ? (size_t)kprev * 3 * sizeof(float) : 0);
+}
+
+// The four deterministic entry points; rows: the form's own kernel argument, sizes through arg_int, checked here.
+template <typename Rows>
+static int beam_expand_launch(const char* fn, bool wide, const float* logits, float temperature, const int32_t* node,
+                              const int32_t* child_off, int64_t n_nodes, const int32_t* tok, int64_t n_children,
+                              const int64_t* parents, const float* parent_lp, int64_t B, int64_t kprev, int64_t V,
+                              int64_t P, int64_t k, int64_t* out_ids, float* out_lp, int32_t* out_parent,
+                              int32_t* out_node, const int32_t* blocked, int64_t n_blocked, const Rows& rows,
+                              void* stream) {
+  bool own_ptrs = logits && child_off && out_ids && out_lp && out_parent && out_node;
+  const AllowedBits* ab = nullptr;
+  if constexpr (std::is_same_v<Rows, BiasArgs>) {
+    RQ_CHECK_ARG(rows.n_bias >= 0 && rows.G >= 0 && rows.n_bias == n_children,
+                 "%s: need G >= 0 and n_bias == n_children (n_bias=%d, n_children=%lld, G=%d)", fn, rows.n_bias,
+                 (long long)n_children, rows.G);
+    RQ_CHECK_ARG(rows.rows || rows.G == 0 || rows.n_bias == 0, "%s: null bias", fn);
+    RQ_CHECK_ARG(wide || kprev <= kWideMax, "%s: the biased step takes kprev <= %d (kprev=%lld)", fn,
+                 kWideMax, (long long)kprev);
+    own_ptrs = own_ptrs && rows.out_score;
+  } else {
+    ab = &rows;
+  }
+  const int rc = beam_expand_check(
+      fn, wide ? ExpandForm::kWide : ExpandForm::kDense, temperature, n_nodes, tok, n_children,
+      (P == 0) ? (!node && !parents && !parent_lp) : (node && parents && parent_lp), "node, parents and parent_lp", B,
+      kprev, V, P, k, own_ptrs, blocked, n_blocked, ab);
+  if (rc != 0 || B == 0) return rc;
+  const TrieLevel lvl = {child_off, (int)n_nodes, tok, (int)n_children};
+  if (n_blocked == 0) blocked = nullptr;
+  with_tables(n_blocked > 0, rows, [&](auto blk, auto flt, auto bia) {
+    constexpr bool kBlk = decltype(blk)::value, kFlt = decltype(flt)::value, kBia = decltype(bia)::value;
+    auto launch = [&](auto kernel, int threads, size_t lds) {
+      hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(threads), lds, (hipStream_t)stream, logits, temperature, node,
+                         lvl, parents, parent_lp, (int)kprev, (int)V, (int)P, (int)k, out_ids, out_lp, out_parent,
+                         out_node, blocked, (int)n_blocked, rows);
+    };
+    if (wide) {   // static LDS, one shape of workgroup
+      launch(beam_expand_wide_kernel<kBlk, kFlt, kBia>, kWideThreads, 0);
+    } else {
+      launch(beam_expand_kernel<kBlk, kFlt, kBia>, kprev > 4 ? 64 * kExpMaxWaves : 64 * 4,
+             beam_expand_lds(kprev, V, n_blocked, kBia));
+    }
+  });
+  RQ_LAUNCH_CHECK(fn);
+  return 0;
+}
+
+// rq_trie_allowed_nodes and rq_trie_bias_nodes: a per-group table (G, n_items) reduced onto the trie's D levels. The
+// shared checks in one order and the levels struct filled (set_level: the entry point's own part), then the entry point's
+// two launches through launch(kernel, work items, arguments...): its scatter (no items: no launch) and its finish.
+static void set_level(AllowedLevels& lv, int64_t q, int32_t* bits, int64_t n_nodes) {
+  lv.bits[q] = bits;
+  lv.n_words[q] = (int)((n_nodes + 31) / 32);
+}
+static void set_level(BiasLevels& lv, int64_t q, float* upper, int64_t) { lv.upper[q] = reinterpret_cast<uint32_t*>(upper); }
+
+template <typename Levels, typename Out, typename Launches>
+static int trie_group_tables(const char* fn, const char* table_name, const void* table, int64_t G, int64_t n_items,
+                             const int32_t* item_leaf, int64_t n_leaves, const int32_t* const* leaf_anc,
+                             const int64_t* n_nodes, int64_t D, Out* const* out_levels, int64_t* out_leaf_item,
+                             void* stream, Levels& lv, Launches launches) {
+  RQ_CHECK_ARG(G >= 0 && D >= 1 && D <= RQ_BEAM_MAX_T, "%s: need G >= 0, 1 <= D <= %d (G=%lld, D=%lld)", fn,
+               RQ_BEAM_MAX_T, (long long)G, (long long)D);
+  RQ_CHECK_ARG(n_items >= 0 && n_leaves >= 0 && n_leaves < 0x7fffffff, "%s: bad corpus size", fn);
+  RQ_CHECK_ARG(n_items == 0 || G <= INT64_MAX / 8 / n_items, "%s: %s too large", fn, table_name);
+  RQ_CHECK_ARG(leaf_anc && n_nodes && out_levels, "%s: null level array", fn);
+  for (int64_t q = 0; q < D; ++q) {
+    RQ_CHECK_ARG(n_nodes[q] >= 0 && n_nodes[q] < 0x7fffffff, "%s: level %lld has %lld nodes", fn, (long long)(q + 1),
+                 (long long)n_nodes[q]);
+    RQ_CHECK_ARG((leaf_anc[q] || n_leaves == 0) && (out_levels[q] || n_nodes[q] == 0 || G == 0),
+                 "%s: null table at level %lld", fn, (long long)(q + 1));
+    lv.anc[q] = leaf_anc[q];
+    lv.n_nodes[q] = (int)n_nodes[q];
+    set_level(lv, q, out_levels[q], n_nodes[q]);
+  }
+  if (G == 0 || n_leaves == 0) return 0;
+  RQ_CHECK_ARG(out_leaf_item && (n_items == 0 || (table && item_leaf)), "%s: null pointer", fn);
+  launches([&](auto kernel, int64_t work, auto... args) {
+    const int64_t blocks = std::min<int64_t>((work + kAllowThreads - 1) / kAllowThreads, kAllowMaxBlocks);
+    if (blocks == 0) return;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kAllowThreads), 0, (hipStream_t)stream, args...);
+  });
+  RQ_LAUNCH_CHECK(fn);
+  return 0;
 }
 
 }  // namespace rqhip
 
 extern "C" {
+
+using rqhip::AllowedBits, rqhip::BiasArgs, rqhip::arg_int;
 
 int rq_beam_candidates(const float* logits, const float* noise, int64_t R, int64_t V, int64_t n_cand,
                        float temperature, int64_t* cand_ids, float* cand_lp, void* stream) {
@@ -1547,109 +1685,15 @@ int rq_beam_select(const int64_t* cand_ids, const float* cand_lp, const bool* va
                                n_cand, P, k, out_ids, out_lp, nullptr, stream);
 }
 
-// The argument checks of the three expand entry points, in one order; fn is the entry point's name for the message.
-// beams_ok / beam_names: the P == 0 rule over the entry point's own beam arrays; own_ptrs: its logits and outputs.
-// After a 0 the caller still returns at once when B == 0 (nothing is dereferenced, NULL is fine then).
-enum class ExpandForm { kDense, kWide, kSampled };
-static int beam_expand_check(const char* fn, ExpandForm form, float temperature, int64_t n_nodes, const int32_t* tok,
-                             int64_t n_children, bool beams_ok, const char* beam_names, int64_t B, int64_t kprev,
-                             int64_t V, int64_t P, int64_t k, bool own_ptrs, const int32_t* blocked, int64_t n_blocked,
-                             const int32_t* allowed, int64_t n_words, int64_t G, const int32_t* group) {
-  RQ_CHECK_ARG(B >= 0 && kprev >= 1 && V >= 1 && P >= 0 && P < 64, "%s: bad shape", fn);
-  if (form == ExpandForm::kWide) {
-    RQ_CHECK_ARG(V <= rqhip::kBeamMaxV && kprev <= rqhip::kWideMax && k >= 1 && k <= rqhip::kWideMax,
-                 "%s: need V <= %d, kprev <= %d and 1 <= k <= %d (kprev=%lld, V=%lld, k=%lld)", fn, rqhip::kBeamMaxV,
-                 rqhip::kWideMax, rqhip::kWideMax, (long long)kprev, (long long)V, (long long)k);
-  } else {
-    RQ_CHECK_ARG(V <= rqhip::kBeamMaxV && kprev <= rqhip::kBeamMaxN && kprev * V <= rqhip::kBeamMaxN,
-                 "%s: need V <= %d and kprev * V <= %d (kprev=%lld, V=%lld)%s", fn, rqhip::kBeamMaxV, rqhip::kBeamMaxN,
-                 (long long)kprev, (long long)V,
-                 form == ExpandForm::kSampled
-                     ? "; the wide form (more than 32 beams at V = 256) is not built for the sampled step"
-                     : "");
-    RQ_CHECK_ARG(k >= 1 && k <= rqhip::kBeamMaxN, "%s: need 1 <= k <= %d (k=%lld)", fn, rqhip::kBeamMaxN, (long long)k);
-  }
-  RQ_CHECK_ARG(temperature > 0.f && temperature <= 3.0e38f, "%s: temperature must be positive", fn);
-  RQ_CHECK_ARG(n_nodes >= 0 && n_nodes < 0x7fffffff && n_children >= 0 && n_children <= 0x7fffffff,
-               "%s: bad trie level (n_nodes=%lld, n_children=%lld)", fn, (long long)n_nodes, (long long)n_children);
-  RQ_CHECK_ARG(beams_ok, "%s: %s are all NULL when P == 0, all given otherwise", fn, beam_names);
-  RQ_CHECK_ARG(n_blocked >= 0 && n_blocked <= rqhip::kBlockedMax, "%s: need 0 <= n_blocked <= %d (n_blocked=%lld)", fn,
-               rqhip::kBlockedMax, (long long)n_blocked);
-  RQ_CHECK_ARG(!group || (n_words >= 0 && n_words <= 0x7fffffff / 32 && G >= 0 && G <= 0x7fffffff),
-               "%s: bad bitmap (n_words=%lld, G=%lld)", fn, (long long)n_words, (long long)G);
-  if (B == 0) return 0;
-  RQ_CHECK_ARG(B <= 0x7fffffff, "%s: too many batch elements", fn);
-  RQ_CHECK_ARG(own_ptrs && (tok || n_children == 0) && (blocked || n_blocked == 0) &&
-                   (!group || allowed || n_words * G == 0),
-               "%s: null pointer", fn);
-  return 0;
-}
-
-static size_t beam_expand_lds(int64_t kprev, int64_t V, int64_t n_blocked, bool biased = false) {   // expand_prologue's layout
-  return (size_t)((kprev * V + 3) / 4 * 4 + 2 * rqhip::kExpMaxWaves) * sizeof(uint32_t) +
-         (size_t)n_blocked * sizeof(int32_t) + (biased ? (size_t)kprev * 3 * sizeof(float) : 0);
-}
-
-// bias / out_score: the biased entry points' (`biased`), whose n_words is n_bias and whose `allowed` is NULL
-static int beam_expand_launch(const char* fn, bool wide, const float* logits, float temperature, const int32_t* node,
-                              const int32_t* child_off, int64_t n_nodes, const int32_t* tok, int64_t n_children,
-                              const int64_t* parents, const float* parent_lp, int64_t B, int64_t kprev, int64_t V,
-                              int64_t P, int64_t k, int64_t* out_ids, float* out_lp, int32_t* out_parent,
-                              int32_t* out_node, const int32_t* blocked, int64_t n_blocked, const int32_t* allowed,
-                              int64_t n_words, int64_t G, const int32_t* group, void* stream, bool biased = false,
-                              const float* bias = nullptr, float* out_score = nullptr) {
-  if (biased) {
-    RQ_CHECK_ARG(n_words >= 0 && G >= 0 && G <= 0x7fffffff && n_words == n_children,
-                 "%s: need G >= 0 and n_bias == n_children (n_bias=%lld, n_children=%lld, G=%lld)", fn,
-                 (long long)n_words, (long long)n_children, (long long)G);
-    RQ_CHECK_ARG(bias || G == 0 || n_words == 0, "%s: null bias", fn);
-    RQ_CHECK_ARG(wide || kprev <= rqhip::kWideMax, "%s: the biased step takes kprev <= %d (kprev=%lld)", fn,
-                 rqhip::kWideMax, (long long)kprev);
-  }
-  const int rc = beam_expand_check(
-      fn, wide ? ExpandForm::kWide : ExpandForm::kDense, temperature, n_nodes, tok, n_children,
-      (P == 0) ? (!node && !parents && !parent_lp) : (node && parents && parent_lp), "node, parents and parent_lp", B,
-      kprev, V, P, k, logits && child_off && out_ids && out_lp && out_parent && out_node && (out_score || !biased),
-      blocked, n_blocked, allowed, biased ? 0 : n_words, biased ? 0 : G, biased ? nullptr : group);
-  if (rc != 0 || B == 0) return rc;
-  const rqhip::TrieLevel lvl = {child_off, (int)n_nodes, tok, (int)n_children};
-  if (n_blocked == 0) blocked = nullptr;
-  auto run = [&](auto blk, auto flt, auto bia, const auto& rows) {
-    constexpr bool kBlk = decltype(blk)::value, kFlt = decltype(flt)::value, kBia = decltype(bia)::value;
-    auto launch = [&](auto kernel, int threads, size_t lds) {
-      hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(threads), lds, (hipStream_t)stream, logits, temperature, node,
-                         lvl, parents, parent_lp, (int)kprev, (int)V, (int)P, (int)k, out_ids, out_lp, out_parent,
-                         out_node, blocked, (int)n_blocked, rows);
-    };
-    if (wide) {   // static LDS, one shape of workgroup
-      launch(rqhip::beam_expand_wide_kernel<kBlk, kFlt, kBia>, rqhip::kWideThreads, 0);
-    } else {
-      launch(rqhip::beam_expand_kernel<kBlk, kFlt, kBia>, kprev > 4 ? 64 * rqhip::kExpMaxWaves : 64 * 4,
-             beam_expand_lds(kprev, V, n_blocked, kBia));
-    }
-  };
-  if (biased) {
-    const rqhip::BiasArgs ba = {bias, group, (int)n_words, (int)G, out_score};
-    if (n_blocked > 0) run(std::true_type{}, std::false_type{}, std::true_type{}, ba);
-    else run(std::false_type{}, std::false_type{}, std::true_type{}, ba);
-  } else {
-    const rqhip::AllowedBits ab = {allowed, group, (int)n_words, (int)G};
-    rqhip::with_filters(n_blocked > 0, group != nullptr,
-                        [&](auto blk, auto flt) { run(blk, flt, std::false_type{}, ab); });
-  }
-  RQ_LAUNCH_CHECK(fn);
-  return 0;
-}
-
 int rq_beam_expand_biased(const float* logits, float temperature, const int32_t* node, const int32_t* child_off,
                           int64_t n_nodes, const int32_t* tok, int64_t n_children, const int64_t* parents,
                           const float* parent_lp, int64_t B, int64_t kprev, int64_t V, int64_t P, int64_t k,
                           int64_t* out_ids, float* out_lp, float* out_score, int32_t* out_parent, int32_t* out_node,
                           const int32_t* blocked, int64_t n_blocked, const float* bias, int64_t n_bias, int64_t G,
                           const int32_t* group, void* stream) {
-  return beam_expand_launch("rq_beam_expand_biased", false, logits, temperature, node, child_off, n_nodes, tok,
+  return rqhip::beam_expand_launch("rq_beam_expand_biased", false, logits, temperature, node, child_off, n_nodes, tok,
                             n_children, parents, parent_lp, B, kprev, V, P, k, out_ids, out_lp, out_parent, out_node,
-                            blocked, n_blocked, nullptr, n_bias, G, group, stream, true, bias, out_score);
+                            blocked, n_blocked, BiasArgs{bias, group, arg_int(n_bias), arg_int(G), out_score}, stream);
 }
 
 int rq_beam_expand_wide_biased(const float* logits, float temperature, const int32_t* node, const int32_t* child_off,
@@ -1658,9 +1702,9 @@ int rq_beam_expand_wide_biased(const float* logits, float temperature, const int
                                int64_t* out_ids, float* out_lp, float* out_score, int32_t* out_parent,
                                int32_t* out_node, const int32_t* blocked, int64_t n_blocked, const float* bias,
                                int64_t n_bias, int64_t G, const int32_t* group, void* stream) {
-  return beam_expand_launch("rq_beam_expand_wide_biased", true, logits, temperature, node, child_off, n_nodes, tok,
+  return rqhip::beam_expand_launch("rq_beam_expand_wide_biased", true, logits, temperature, node, child_off, n_nodes, tok,
                             n_children, parents, parent_lp, B, kprev, V, P, k, out_ids, out_lp, out_parent, out_node,
-                            blocked, n_blocked, nullptr, n_bias, G, group, stream, true, bias, out_score);
+                            blocked, n_blocked, BiasArgs{bias, group, arg_int(n_bias), arg_int(G), out_score}, stream);
 }
 
 int rq_beam_expand(const float* logits, float temperature, const int32_t* node, const int32_t* child_off,
@@ -1668,9 +1712,9 @@ int rq_beam_expand(const float* logits, float temperature, const int32_t* node, 
                    const float* parent_lp, int64_t B, int64_t kprev, int64_t V, int64_t P, int64_t k, int64_t* out_ids,
                    float* out_lp, int32_t* out_parent, int32_t* out_node, const int32_t* blocked, int64_t n_blocked,
                    const int32_t* allowed, int64_t n_words, int64_t G, const int32_t* group, void* stream) {
-  return beam_expand_launch("rq_beam_expand", false, logits, temperature, node, child_off, n_nodes, tok, n_children,
+  return rqhip::beam_expand_launch("rq_beam_expand", false, logits, temperature, node, child_off, n_nodes, tok, n_children,
                             parents, parent_lp, B, kprev, V, P, k, out_ids, out_lp, out_parent, out_node, blocked,
-                            n_blocked, allowed, n_words, G, group, stream);
+                            n_blocked, AllowedBits{allowed, group, arg_int(n_words), arg_int(G)}, stream);
 }
 
 int rq_beam_expand_wide(const float* logits, float temperature, const int32_t* node, const int32_t* child_off,
@@ -1679,9 +1723,9 @@ int rq_beam_expand_wide(const float* logits, float temperature, const int32_t* n
                         int64_t* out_ids, float* out_lp, int32_t* out_parent, int32_t* out_node,
                         const int32_t* blocked, int64_t n_blocked, const int32_t* allowed, int64_t n_words, int64_t G,
                         const int32_t* group, void* stream) {
-  return beam_expand_launch("rq_beam_expand_wide", true, logits, temperature, node, child_off, n_nodes, tok, n_children,
+  return rqhip::beam_expand_launch("rq_beam_expand_wide", true, logits, temperature, node, child_off, n_nodes, tok, n_children,
                             parents, parent_lp, B, kprev, V, P, k, out_ids, out_lp, out_parent, out_node, blocked,
-                            n_blocked, allowed, n_words, G, group, stream);
+                            n_blocked, AllowedBits{allowed, group, arg_int(n_words), arg_int(G)}, stream);
 }
 
 int rq_beam_expand_sampled(const float* logits, const float* noise, float temperature, const int32_t* node,
@@ -1692,20 +1736,19 @@ int rq_beam_expand_sampled(const float* logits, const float* noise, float temper
                            int64_t n_blocked, const int32_t* allowed, int64_t n_words, int64_t G, const int32_t* group,
                            void* stream) {
   const char* fn = "rq_beam_expand_sampled";
-  const int rc = beam_expand_check(
-      fn, ExpandForm::kSampled, temperature, n_nodes, tok, n_children,
+  const AllowedBits ab = {allowed, group, arg_int(n_words), arg_int(G)};
+  const int rc = rqhip::beam_expand_check(
+      fn, rqhip::ExpandForm::kSampled, temperature, n_nodes, tok, n_children,
       (P == 0) ? (!node && !parents && !parent_phi && !parent_g) : (node && parents && parent_phi && parent_g),
       "node, parents, parent_phi and parent_g", B, kprev, V, P, k,
-      logits && noise && child_off && out_ids && out_phi && out_g && out_parent && out_node, blocked, n_blocked,
-      allowed, n_words, G, group);
+      logits && noise && child_off && out_ids && out_phi && out_g && out_parent && out_node, blocked, n_blocked, &ab);
   if (rc != 0 || B == 0) return rc;
   const rqhip::TrieLevel lvl = {child_off, (int)n_nodes, tok, (int)n_children};
-  const rqhip::AllowedBits ab = {allowed, group, (int)n_words, (int)G};
   if (n_blocked == 0) blocked = nullptr;
-  rqhip::with_filters(n_blocked > 0, group != nullptr, [&](auto blk, auto flt) {
+  rqhip::with_tables(n_blocked > 0, ab, [&](auto blk, auto flt, auto) {
     hipLaunchKernelGGL((rqhip::beam_expand_sampled_kernel<decltype(blk)::value, decltype(flt)::value>),
                        dim3((unsigned)B), dim3(kprev > 4 ? 64 * rqhip::kExpMaxWaves : 64 * 4),
-                       beam_expand_lds(kprev, V, n_blocked), (hipStream_t)stream, logits, noise, temperature, node, lvl,
+                       rqhip::beam_expand_lds(kprev, V, n_blocked, false), (hipStream_t)stream, logits, noise, temperature, node, lvl,
                        parents, parent_phi, parent_g, (int)kprev, (int)V, (int)P, (int)k, out_ids, out_phi, out_g,
                        out_parent, out_node, blocked, (int)n_blocked, ab);
   });
@@ -1771,76 +1814,31 @@ int rq_trie_blocked_nodes(const int64_t* items, int64_t B, int64_t H, const int3
 int rq_trie_allowed_nodes(const bool* mask, int64_t G, int64_t n_items, const int32_t* item_leaf, int64_t n_leaves,
                           const int32_t* const* leaf_anc, const int64_t* n_nodes, int64_t D, int32_t* const* out_bits,
                           int64_t* out_leaf_item, void* stream) {
-  RQ_CHECK_ARG(G >= 0 && D >= 1 && D <= RQ_BEAM_MAX_T, "rq_trie_allowed_nodes: need G >= 0, 1 <= D <= %d (G=%lld, D=%lld)",
-               RQ_BEAM_MAX_T, (long long)G, (long long)D);
-  RQ_CHECK_ARG(n_items >= 0 && n_leaves >= 0 && n_leaves < 0x7fffffff, "rq_trie_allowed_nodes: bad corpus size");
-  RQ_CHECK_ARG(n_items == 0 || G <= INT64_MAX / 8 / n_items, "rq_trie_allowed_nodes: mask too large");
-  RQ_CHECK_ARG(leaf_anc && n_nodes && out_bits, "rq_trie_allowed_nodes: null level array");
   rqhip::AllowedLevels lv = {};
-  for (int64_t q = 0; q < D; ++q) {
-    RQ_CHECK_ARG(n_nodes[q] >= 0 && n_nodes[q] < 0x7fffffff, "rq_trie_allowed_nodes: level %lld has %lld nodes",
-                 (long long)(q + 1), (long long)n_nodes[q]);
-    RQ_CHECK_ARG((leaf_anc[q] || n_leaves == 0) && (out_bits[q] || n_nodes[q] == 0 || G == 0),
-                 "rq_trie_allowed_nodes: null table at level %lld", (long long)(q + 1));
-    lv.anc[q] = leaf_anc[q];
-    lv.bits[q] = out_bits[q];
-    lv.n_nodes[q] = (int)n_nodes[q];
-    lv.n_words[q] = (int)((n_nodes[q] + 31) / 32);
-  }
-  if (G == 0 || n_leaves == 0) return 0;
-  RQ_CHECK_ARG(out_leaf_item && (n_items == 0 || (mask && item_leaf)), "rq_trie_allowed_nodes: null pointer");
-  hipStream_t hs = (hipStream_t)stream;
-  auto blocks = [](int64_t threads) {
-    return (unsigned)std::min<int64_t>((threads + rqhip::kAllowThreads - 1) / rqhip::kAllowThreads,
-                                       rqhip::kAllowMaxBlocks);
-  };
   unsigned long long* lowest = reinterpret_cast<unsigned long long*>(out_leaf_item);
-  if (n_items > 0) {
-    hipLaunchKernelGGL(rqhip::trie_allowed_kernel, dim3(blocks((G * n_items + 3) / 4)), dim3(rqhip::kAllowThreads), 0, hs,
-                       reinterpret_cast<const uint8_t*>(mask), G, n_items, item_leaf, (int)n_leaves, lv, (int)D, lowest);
-  }
-  hipLaunchKernelGGL(rqhip::trie_allowed_finish_kernel, dim3(blocks(G * n_leaves)), dim3(rqhip::kAllowThreads), 0, hs,
-                     lowest, G * n_leaves);
-  RQ_LAUNCH_CHECK("rq_trie_allowed_nodes");
-  return 0;
+  return rqhip::trie_group_tables(
+      "rq_trie_allowed_nodes", "mask", mask, G, n_items, item_leaf, n_leaves, leaf_anc, n_nodes, D, out_bits,
+      out_leaf_item, stream, lv, [&](auto launch) {
+        launch(rqhip::trie_allowed_kernel, (G * n_items + 3) / 4, reinterpret_cast<const uint8_t*>(mask), G, n_items,
+               item_leaf, (int)n_leaves, lv, (int)D, lowest);
+        launch(rqhip::trie_allowed_finish_kernel, G * n_leaves, lowest, G * n_leaves);
+      });
 }
 
 int rq_trie_bias_nodes(const float* bias, int64_t G, int64_t n_items, const int32_t* item_leaf, int64_t n_leaves,
                        const int32_t* const* leaf_anc, const int64_t* n_nodes, int64_t D, float* const* out_upper,
                        int64_t* out_leaf_item, void* stream) {
-  RQ_CHECK_ARG(G >= 0 && D >= 1 && D <= RQ_BEAM_MAX_T, "rq_trie_bias_nodes: need G >= 0, 1 <= D <= %d (G=%lld, D=%lld)",
-               RQ_BEAM_MAX_T, (long long)G, (long long)D);
-  RQ_CHECK_ARG(n_items >= 0 && n_items <= 0x7fffffff && n_leaves >= 0 && n_leaves < 0x7fffffff,
-               "rq_trie_bias_nodes: bad corpus size");
-  RQ_CHECK_ARG(n_items == 0 || G <= INT64_MAX / 8 / n_items, "rq_trie_bias_nodes: bias too large");
-  RQ_CHECK_ARG(n_leaves == 0 || G <= INT64_MAX / 8 / n_leaves, "rq_trie_bias_nodes: too many (group, leaf) pairs");
-  RQ_CHECK_ARG(leaf_anc && n_nodes && out_upper, "rq_trie_bias_nodes: null level array");
+  // its own two: the scatter packs an item index into 32 bits of a key, the finish indexes the (group, leaf) pairs
+  RQ_CHECK_ARG(n_items <= 0x7fffffff, "rq_trie_bias_nodes: bad corpus size");
+  RQ_CHECK_ARG(n_leaves <= 0 || G <= INT64_MAX / 8 / n_leaves, "rq_trie_bias_nodes: too many (group, leaf) pairs");
   rqhip::BiasLevels lv = {};
-  for (int64_t q = 0; q < D; ++q) {
-    RQ_CHECK_ARG(n_nodes[q] >= 0 && n_nodes[q] < 0x7fffffff, "rq_trie_bias_nodes: level %lld has %lld nodes",
-                 (long long)(q + 1), (long long)n_nodes[q]);
-    RQ_CHECK_ARG((leaf_anc[q] || n_leaves == 0) && (out_upper[q] || n_nodes[q] == 0 || G == 0),
-                 "rq_trie_bias_nodes: null table at level %lld", (long long)(q + 1));
-    lv.anc[q] = leaf_anc[q];
-    lv.upper[q] = reinterpret_cast<uint32_t*>(out_upper[q]);
-    lv.n_nodes[q] = (int)n_nodes[q];
-  }
-  if (G == 0 || n_leaves == 0) return 0;
-  RQ_CHECK_ARG(out_leaf_item && (n_items == 0 || (bias && item_leaf)), "rq_trie_bias_nodes: null pointer");
-  hipStream_t hs = (hipStream_t)stream;
-  auto blocks = [](int64_t threads) {
-    return (unsigned)std::min<int64_t>((threads + rqhip::kAllowThreads - 1) / rqhip::kAllowThreads,
-                                       rqhip::kAllowMaxBlocks);
-  };
   unsigned long long* best = reinterpret_cast<unsigned long long*>(out_leaf_item);
-  if (n_items > 0) {
-    hipLaunchKernelGGL(rqhip::trie_bias_kernel, dim3(blocks(G * n_items)), dim3(rqhip::kAllowThreads), 0, hs, bias, G,
-                       n_items, item_leaf, (int)n_leaves, lv, (int)D, best);
-  }
-  hipLaunchKernelGGL(rqhip::trie_bias_finish_kernel, dim3(blocks(G * n_leaves)), dim3(rqhip::kAllowThreads), 0, hs, lv,
-                     (int)D, G, best, G * n_leaves);
-  RQ_LAUNCH_CHECK("rq_trie_bias_nodes");
-  return 0;
+  return rqhip::trie_group_tables(
+      "rq_trie_bias_nodes", "bias", bias, G, n_items, item_leaf, n_leaves, leaf_anc, n_nodes, D, out_upper,
+      out_leaf_item, stream, lv, [&](auto launch) {
+        launch(rqhip::trie_bias_kernel, G * n_items, bias, G, n_items, item_leaf, (int)n_leaves, lv, (int)D, best);
+        launch(rqhip::trie_bias_finish_kernel, G * n_leaves, lv, (int)D, G, best, G * n_leaves);
+      });
 }
 
 int rq_beam_self_attn(const float* q, int64_t sq, const float* const* k_steps, const float* const* v_steps,

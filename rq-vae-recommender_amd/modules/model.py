@@ -22,6 +22,7 @@ from data.schemas import TokenizedSeqBatch
 from modules.linear import Linear
 from modules.embedding.id_embedder import Embedding, SemIdEmbedder, UserIdEmbedder
 from modules.normalize import RMSNorm
+from modules.tokenizer.semids import ItemBias
 from modules.transformer.model import TransformerEncoderDecoder
 from modules.utils import eval_mode, maybe_repeat_interleave, reset_encoder_cache
 from ops.jagged import Jagged, jagged_to_flattened_tensor, jagged_to_padded_tensor, padded_to_jagged, row_counts
@@ -79,20 +80,27 @@ class Scores(NamedTuple):
 class _TrieSearch(NamedTuple):
     """A trie search's per-call tables (EncoderDecoderRetrievalModel._trie_search)."""
     trie: object
-    blocked: Tensor       # (D, B, H) int32 blocked nodes of every level, or None
-    item_filter: object   # ItemFilter or None
-    group: Tensor         # (B,) int32 with item_filter, else None
-    item_bias: object = None    # ItemBias or None; never together with item_filter
-    bias_group: Tensor = None   # (B,) int32 with item_bias, else None
+    blocked: Tensor   # (D, B, H) int32 blocked nodes of every level, or None
+    table: object     # the call's group table: an ItemFilter, an ItemBias or None
+    group: Tensor     # (B,) int32 with a table: every user's row of it; else None
+
+    @property
+    def biased(self) -> bool:
+        return isinstance(self.table, ItemBias)
+
+    @property
+    def expand(self):
+        """The deterministic step's op: hip_ops.beam_expand_biased under an ItemBias, else hip_ops.beam_expand (the
+        sampled step, hip_ops.beam_expand_sampled, takes beam_expand's keywords and no bias)."""
+        return hip_ops.beam_expand_biased if self.biased else hip_ops.beam_expand
 
     def level(self, i: int) -> dict:
-        """Step i's trie and filter arguments of hip_ops.beam_expand / beam_expand_sampled — with item_bias, of
-        hip_ops.beam_expand_biased."""
+        """Step i's trie and table keywords of `expand`."""
         lvl = dict(child_off=self.trie.child_off[i], tok=self.trie.tok[i + 1],
                    blocked=None if self.blocked is None else self.blocked[i])
-        if self.item_bias is not None:
-            return dict(lvl, bias=self.item_bias.upper[i], bias_group=self.bias_group)
-        return dict(lvl, allowed=None if self.item_filter is None else self.item_filter.bits[i], group=self.group)
+        if self.biased:
+            return dict(lvl, bias=self.table.upper[i], bias_group=self.group)
+        return dict(lvl, allowed=None if self.table is None else self.table.bits[i], group=self.group)
 
 
 class EncoderDecoderRetrievalModel(nn.Module):
@@ -308,9 +316,9 @@ class EncoderDecoderRetrievalModel(nn.Module):
             self._constrained_trie("generate_next_sem_id")
         assert self.enable_generation, "Model generation is not enabled"
         if constrained:
+            search = self._trie_search("generate_next_sem_id", batch, exclude_items, item_filter, filter_group)
             generated, log_probas, _, _ = self._generate_constrained(batch, temperature, beams if top_k else 1,
-                                                                     incremental, exclude_items, item_filter,
-                                                                     filter_group)
+                                                                     incremental, search)
             return GenerationOutput(sem_ids=generated.squeeze(), log_probas=log_probas.squeeze())
         if fused:
             return self._generate_sampled(batch, temperature, top_k, sample, incremental)
@@ -357,81 +365,65 @@ class EncoderDecoderRetrievalModel(nn.Module):
         return trie
 
     def _trie_search(self, what: str, batch: TokenizedSeqBatch, exclude_items, item_filter, filter_group,
-                     item_bias=None, bias_group=None):
-        """The per-call tables of a search over the trie, errors under the caller's name `what`: the trie, the users'
-        blocked nodes of every level (exclude_items (B, H); the tokenizer's blocked_nodes, one launch for the whole
-        call), the catalogue filter (_item_filter's arguments) and the score bias (_item_bias's). _TrieSearch.level(i)
-        hands step i its slices."""
+                     item_bias=None, bias_group=None) -> _TrieSearch:
+        """The per-call tables of a search over the trie, and the one place a public call's exclude_items, item_filter /
+        filter_group and item_bias / bias_group are validated, errors under the caller's name `what`: the trie, the
+        users' blocked nodes of every level (exclude_items (B, H); the tokenizer's blocked_nodes, one launch for the
+        whole call) and the call's group table — the catalogue filter or the score bias, never both (_group_table).
+        _TrieSearch.level(i) hands step i its slices."""
         trie = self._constrained_trie(what)
-        B = batch.sem_ids.shape[0]
-        item_filter, group = self._item_filter(what, item_filter, filter_group, B, batch.sem_ids.device)
-        item_bias, bias_group = self._item_bias(what, item_bias, bias_group, B, batch.sem_ids.device)
+        index, B, dev = self.inference_prefix_index, batch.sem_ids.shape[0], batch.sem_ids.device
         if item_filter is not None and item_bias is not None:
             raise ValueError(f"{what}: item_filter and item_bias cannot be combined; write the filter into the bias "
                              "as -inf (a {0, -inf} table is a hard filter)")
+        table, group = self._group_table(what, "item_filter", "filter_group", "unfiltered", item_filter, filter_group,
+                                         B, dev)
+        bias = self._group_table(what, "item_bias", "bias_group", "unbiased", item_bias, bias_group, B, dev)
+        if bias[0] is not None:
+            table, group = bias
         blocked = None
         if exclude_items is not None:
             if exclude_items.dim() != 2 or exclude_items.shape[0] != B:
                 raise ValueError(f"{what}: exclude_items must be (B, H) with B = {B} rows, got "
                                  f"{tuple(exclude_items.shape)}")
-            blocked = self.inference_prefix_index.blocked_nodes(exclude_items)
-        return _TrieSearch(trie, blocked, item_filter, group, item_bias, bias_group)
+            blocked = index.blocked_nodes(exclude_items)
+        return _TrieSearch(trie, blocked, table, group)
 
-    def _item_bias(self, what: str, item_bias, bias_group, B: int, device):
-        """(ItemBias, group (B,) int32 on the device) of a call's item_bias / bias_group arguments, or (None, None)
-        without a bias: _item_filter's rules. A raw fp32 tensor becomes an ItemBias through the tokenizer (built per
-        call); the groups are converted on the device, nothing is read back."""
-        if item_bias is None:
-            if bias_group is not None:
-                raise ValueError(f"{what}: bias_group without item_bias")
+    def _group_table(self, what: str, arg: str, group_arg: str, off: str, table, group, B: int, device):
+        """(table, group (B,) int32 on the device) of a call's table argument `arg` and group argument `group_arg`, or
+        (None, None) without a table. A raw tensor becomes a table through the tokenizer's method of `arg`'s name
+        (item_filter / item_bias; built per call); group None is row 0 for everyone, which needs a one-group table (-1
+        leaves a user `off`); the groups are converted on the device, nothing is read back."""
+        if table is None:
+            if group is not None:
+                raise ValueError(f"{what}: {group_arg} without {arg}")
             return None, None
-        if isinstance(item_bias, Tensor):
-            item_bias = self.inference_prefix_index.item_bias(item_bias)
-        if bias_group is None:
-            if item_bias.groups != 1:
-                raise ValueError(f"{what}: item_bias has {item_bias.groups} groups; bias_group (B,) must say which "
-                                 "one every user reads (-1: unbiased)")
-            return item_bias, torch.zeros(B, dtype=torch.int32, device=device)
-        if bias_group.dim() != 1 or bias_group.shape[0] != B or bias_group.dtype.is_floating_point or \
-                bias_group.dtype == torch.bool:
-            raise ValueError(f"{what}: bias_group must be (B,) integer with B = {B}, got {bias_group.dtype} "
-                             f"{tuple(bias_group.shape)}")
-        return item_bias, bias_group.to(device=device, dtype=torch.int32).contiguous()
-
-    def _item_filter(self, what: str, item_filter, filter_group, B: int, device):
-        """(ItemFilter, group (B,) int32 on the device) of a call's item_filter / filter_group arguments, or (None,
-        None) without a filter. A bool mask becomes an ItemFilter through the tokenizer (built per call); the groups
-        are converted on the device, nothing is read back."""
-        if item_filter is None:
-            if filter_group is not None:
-                raise ValueError(f"{what}: filter_group without item_filter")
-            return None, None
-        if isinstance(item_filter, Tensor):
-            item_filter = self.inference_prefix_index.item_filter(item_filter)
-        if filter_group is None:
-            if item_filter.groups != 1:
-                raise ValueError(f"{what}: item_filter has {item_filter.groups} groups; filter_group (B,) must say "
-                                 "which one every user reads (-1: unfiltered)")
-            return item_filter, torch.zeros(B, dtype=torch.int32, device=device)
-        if filter_group.dim() != 1 or filter_group.shape[0] != B or filter_group.dtype.is_floating_point or \
-                filter_group.dtype == torch.bool:
-            raise ValueError(f"{what}: filter_group must be (B,) integer with B = {B}, got {filter_group.dtype} "
-                             f"{tuple(filter_group.shape)}")
-        return item_filter, filter_group.to(device=device, dtype=torch.int32).contiguous()
+        if isinstance(table, Tensor):
+            table = getattr(self.inference_prefix_index, arg)(table)
+        if group is None:
+            if table.groups != 1:
+                raise ValueError(f"{what}: {arg} has {table.groups} groups; {group_arg} (B,) must say which one every "
+                                 f"user reads (-1: {off})")
+            return table, torch.zeros(B, dtype=torch.int32, device=device)
+        if group.dim() != 1 or group.shape[0] != B or group.dtype.is_floating_point or group.dtype == torch.bool:
+            raise ValueError(f"{what}: {group_arg} must be (B,) integer with B = {B}, got {group.dtype} "
+                             f"{tuple(group.shape)}")
+        return table, group.to(device=device, dtype=torch.int32).contiguous()
 
     @staticmethod
-    def _leaf_items(trie, item_filter, group, node: Tensor) -> Tensor:
-        """The corpus index of every leaf node (B, k), -1 for dead rows: the trie's lowest index for an unfiltered user,
-        the filter's lowest ALLOWED index for a filtered one. An ItemBias in item_filter's place (with its groups): the
-        item that attains the leaf's bound for a biased user."""
+    def _leaf_items(search: _TrieSearch, node: Tensor) -> Tensor:
+        """The corpus index of every leaf node (B, k), -1 for dead rows: the trie's lowest index for a user outside
+        the search's table (no table, or a group outside it), else the table's own leaf item of the user's group — an
+        ItemFilter's lowest ALLOWED index, an ItemBias' item that attains the leaf's bound."""
         node = node.long()
         at = node.clamp_min(0)
-        items = trie.leaf_item[at]
-        if item_filter is not None:
-            g = group.long().unsqueeze(1)
-            filtered = (g >= 0) & (g < item_filter.groups)
-            if item_filter.groups > 0:
-                items = torch.where(filtered, item_filter.leaf_item[g.clamp(0, item_filter.groups - 1), at], items)
+        items = search.trie.leaf_item[at]
+        table = search.table
+        if table is not None:
+            g = search.group.long().unsqueeze(1)
+            inside = (g >= 0) & (g < table.groups)
+            if table.groups > 0:
+                items = torch.where(inside, table.leaf_item[g.clamp(0, table.groups - 1), at], items)
         return torch.where(node >= 0, items, -1)
 
     @eval_mode
@@ -464,21 +456,14 @@ class EncoderDecoderRetrievalModel(nn.Module):
         Recommendation are what they were."""
         if not 1 <= k <= beams <= hip_ops.BEAM_WIDE_MAX:
             raise ValueError(f"recommend: need 1 <= k <= {beams} beams <= {hip_ops.BEAM_WIDE_MAX}, got k = {k}")
-        trie = self._constrained_trie("recommend", items=True)
+        self._constrained_trie("recommend", items=True)
         assert self.enable_generation, "Model generation is not enabled"
-        B, dev = batch.sem_ids.shape[0], batch.sem_ids.device
-        if item_filter is not None and item_bias is not None:
-            raise ValueError("recommend: item_filter and item_bias cannot be combined; write the filter into the bias "
-                             "as -inf (a {0, -inf} table is a hard filter)")
-        item_filter, group = self._item_filter("recommend", item_filter, filter_group, B, dev)
-        item_bias, bias_group = self._item_bias("recommend", item_bias, bias_group, B, dev)
-        generated, log_probas, node, scores = self._generate_constrained(
-            batch, temperature, beams, incremental, exclude_items, item_filter, group, item_bias, bias_group)
-        if item_bias is not None:
-            items = self._leaf_items(trie, item_bias, bias_group, node[:, :k])
+        search = self._trie_search("recommend", batch, exclude_items, item_filter, filter_group, item_bias, bias_group)
+        generated, log_probas, node, scores = self._generate_constrained(batch, temperature, beams, incremental, search)
+        items = self._leaf_items(search, node[:, :k])
+        if search.biased:
             return RankedItems(item_ids=items, sem_ids=generated[:, :k], log_probas=log_probas[:, :k],
                                scores=scores[:, :k])
-        items = self._leaf_items(trie, item_filter, group, node[:, :k])
         return Recommendation(item_ids=items, sem_ids=generated[:, :k], log_probas=log_probas[:, :k])
 
     @eval_mode
@@ -518,7 +503,7 @@ class EncoderDecoderRetrievalModel(nn.Module):
                 generated, phi, g, parent, node = hip_ops.beam_expand_sampled(
                     logits, k, batch=B, noise=noise, node=node, parents=generated, parent_phi=phi, parent_g=g,
                     temperature=temperature, **search.level(i))
-        items = self._leaf_items(search.trie, search.item_filter, search.group, node)
+        items = self._leaf_items(search, node)
         return SampledItems(item_ids=items, sem_ids=generated, log_probas=phi, perturbed=g)
 
     @eval_mode
@@ -600,24 +585,20 @@ class EncoderDecoderRetrievalModel(nn.Module):
         return Scores(log_probas=lp, rank=rank)
 
     def _generate_constrained(self, batch: TokenizedSeqBatch, temperature, k: int, incremental: bool,
-                              exclude_items: Tensor = None, item_filter=None, filter_group: Tensor = None,
-                              item_bias=None, bias_group: Tensor = None):
+                              search: _TrieSearch):
         """_generate_sampled's loop with beam_candidates + _beam_verify + beam_select replaced by one
-        hip_ops.beam_expand per step: a beam carries its trie node, the node's children are the
+        `search.expand` launch per step: a beam carries its trie node, the node's children are the
         only candidates. Returns (sem_ids (B, k, L+1), log_probas (B, k), the beams' leaf nodes (B, k) int32, the
-        biased scores (B, k) or None), dead beams as beam_expand marks them. Tokens handed back to the model for dead beams are clamped to 0 (row
-        counts stay B * k: static shapes, no negative index reaches an embedding kernel); whatever they compute is
-        never read, a dead beam has no children. exclude_items (B, H): step i's beam_expand skips the user's blocked
-        level-(i + 1) nodes (the tokenizer's blocked_nodes, one launch for the whole call). item_filter / filter_group
-        (_item_filter's arguments): step i's beam_expand keeps only the children set in item_filter.bits[i], row
-        filter_group[b]. item_bias / bias_group (_item_bias's arguments): the steps are hip_ops.beam_expand_biased's,
-        ranked by log-probability + item_bias.upper[i], row bias_group[b]; the UNBIASED log-probability is what is
-        carried to the next step as parent_lp (no bound is ever accumulated) and the last step's ranking score is
-        kept. Runs under the caller's decorators."""
+        biased scores (B, k) or None), dead beams as beam_expand marks them. Tokens handed back to the model for dead
+        beams are clamped to 0 (row counts stay B * k: static shapes, no negative index reaches an embedding kernel);
+        whatever they compute is never read, a dead beam has no children. `search` (_trie_search, built by the public
+        call under its own name): step i skips the user's blocked level-(i + 1) nodes and, under an ItemFilter, keeps
+        only the children set in its bits[i], row group[b]; under an ItemBias the steps are hip_ops.beam_expand_biased's,
+        ranked by log-probability + its upper[i], row group[b] — the UNBIASED log-probability is what is carried to the
+        next step as parent_lp (no bound is ever accumulated) and the last step's ranking score is kept. Runs under the
+        caller's decorators."""
         B = batch.sem_ids.shape[0]
-        search = self._trie_search("generate_next_sem_id", batch, exclude_items, item_filter, filter_group, item_bias,
-                                   bias_group)
-        expand = hip_ops.beam_expand if search.item_bias is None else hip_ops.beam_expand_biased
+        expand = search.expand
         generated, log_probas, score, parent, node = None, None, (), None, None
         with self._step_logits(batch, incremental) as step:
             for i in range(self.sem_id_dim):

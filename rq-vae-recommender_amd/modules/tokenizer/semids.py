@@ -288,6 +288,22 @@ class SemanticIdTokenizer(nn.Module):
             out[q] = torch.where(full, a, _NO_NODE).sort(dim=1).values.to(torch.int32)
         return out
 
+    def _group_table(self, what: str, name: str, table: Tensor, dtype):
+        """The shared front of item_filter and item_bias: `table` checked — `dtype`, (N,) or (G, N) over the N corpus
+        items, on the corpus ids' device — and as (G, N), then the trie index, G, N, the leaf count and the level
+        sizes n_q."""
+        idx = self.trie_index()
+        N = idx.item_leaf.numel()
+        if table.dtype != dtype or table.dim() not in (1, 2) or table.shape[-1] != N:
+            raise ValueError(f"{what}: {name} must be {str(dtype)[6:]} (N,) or (G, N) with N = {N} corpus items, got "
+                             f"{table.dtype} {tuple(table.shape)}")
+        if table.device != idx.item_leaf.device:
+            raise ValueError(f"{what}: {name} must live on the corpus ids' device {idx.item_leaf.device}, got "
+                             f"{table.device}")
+        if table.dim() == 1:
+            table = table.unsqueeze(0)
+        return table, idx, table.shape[0], N, idx.leaf_anc[0].numel(), [c.numel() for c in idx.leaf_count]
+
     @torch.no_grad()
     def item_filter(self, mask: Tensor) -> ItemFilter:
         """The ItemFilter of `mask`, bool (N,) or (G, N) over corpus indices: mask[g][i] says whether group g (a
@@ -297,18 +313,7 @@ class SemanticIdTokenizer(nn.Module):
         several items share stays reachable while one of them is allowed and is reported under the lowest allowed
         index. Device tensors: two HIP launches for all levels (rqvae_hip.ops.trie_allowed_nodes), no host read; CPU
         tensors: the same tables with plain torch. Nothing is cached: build once, reuse across calls."""
-        idx = self.trie_index()
-        N = idx.item_leaf.numel()
-        if mask.dtype != torch.bool or mask.dim() not in (1, 2) or mask.shape[-1] != N:
-            raise ValueError(f"item_filter: mask must be bool (N,) or (G, N) with N = {N} corpus items, got "
-                             f"{mask.dtype} {tuple(mask.shape)}")
-        if mask.device != idx.item_leaf.device:
-            raise ValueError(f"item_filter: mask must live on the corpus ids' device {idx.item_leaf.device}, got "
-                             f"{mask.device}")
-        if mask.dim() == 1:
-            mask = mask.unsqueeze(0)
-        G, n_leaves = mask.shape[0], idx.leaf_anc[0].numel()
-        n_nodes = [c.numel() for c in idx.leaf_count]
+        mask, idx, G, N, n_leaves, n_nodes = self._group_table("item_filter", "mask", mask, torch.bool)
         if mask.is_cuda:
             from rqvae_hip import ops as hip_ops
             bits, leaf_item = hip_ops.trie_allowed_nodes(mask.contiguous(), idx.item_leaf, idx.leaf_anc, n_nodes)
@@ -339,18 +344,7 @@ class SemanticIdTokenizer(nn.Module):
         leaf's bound, the lowest index among equals. Device tensors: two HIP launches for all levels
         (rqvae_hip.ops.trie_bias_nodes), no host read; CPU tensors: the same tables, bit for bit, with plain torch.
         Nothing is cached: build once, reuse across calls."""
-        idx = self.trie_index()
-        N = idx.item_leaf.numel()
-        if bias.dtype != torch.float32 or bias.dim() not in (1, 2) or bias.shape[-1] != N:
-            raise ValueError(f"item_bias: bias must be float32 (N,) or (G, N) with N = {N} corpus items, got "
-                             f"{bias.dtype} {tuple(bias.shape)}")
-        if bias.device != idx.item_leaf.device:
-            raise ValueError(f"item_bias: bias must live on the corpus ids' device {idx.item_leaf.device}, got "
-                             f"{bias.device}")
-        if bias.dim() == 1:
-            bias = bias.unsqueeze(0)
-        G, n_leaves = bias.shape[0], idx.leaf_anc[0].numel()
-        n_nodes = [c.numel() for c in idx.leaf_count]
+        bias, idx, G, N, n_leaves, n_nodes = self._group_table("item_bias", "bias", bias, torch.float32)
         if bias.is_cuda:
             from rqvae_hip import ops as hip_ops
             upper, leaf_item = hip_ops.trie_bias_nodes(bias.contiguous(), idx.item_leaf, idx.leaf_anc, n_nodes)

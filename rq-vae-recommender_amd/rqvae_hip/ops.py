@@ -2484,42 +2484,62 @@ BEAM_MAX_V, BEAM_MAX_N = 4096, 8192   # kBeamMaxV, kBeamMaxN (csrc/beam.hip)
 BEAM_WIDE_MAX = 1024   # kWideMax (csrc/beam.hip): most beams in / out of the wide kernel
 
 
-def _beam_allowed(what, B, allowed, group) -> tuple:
-    """The (allowed, n_words, G, group) arguments of the expand entry points — allowed (G, n_words) int32 and group
-    (B) int32, given together — or the NULLs that say "no catalogue filter" with neither."""
-    if (allowed is None) != (group is None):
-        raise RqHipError(f"{what}: allowed and group go together")
-    if allowed is None:
+def _beam_group_table(what, B, table, group, dtype, name, group_name, cols, n=None) -> tuple:
+    """The (table, n, G, group) arguments of the expand entry points for a per-group table (G, n) of `dtype` and its
+    group (B) int32, given together — `allowed` (G, n_words) with `group`, `bias` (G, n_children) with `bias_group`; n:
+    the width the table must have — or the NULLs that say "no table" with neither."""
+    if (table is None) != (group is None):
+        raise RqHipError(f"{what}: {name} and {group_name} go together")
+    if table is None:
         return (None, 0, 0, None)
-    if allowed.dim() != 2:
-        raise RqHipError(f"{what}: allowed must be (G, n_words), got {tuple(allowed.shape)}")
-    _beam_arg(allowed, torch.int32, what, "allowed")
-    _beam_arg(group, torch.int32, what, "group", (B,))
-    G, n_words = allowed.shape
-    return (ptr(allowed) if G * n_words else None, n_words, G, ptr(group))
+    if table.dim() != 2 or (n is not None and table.shape[1] != n):
+        raise RqHipError(f"{what}: {name} must be (G, {cols}), got {tuple(table.shape)}")
+    _beam_arg(table, dtype, what, name)
+    _beam_arg(group, torch.int32, what, group_name, (B,))
+    G, n = table.shape
+    return (ptr(table) if G * n else None, n, G, ptr(group))
 
 
 class _ExpandCall(NamedTuple):
-    """What beam_expand and beam_expand_sampled share once their arguments are checked (_beam_expand_setup)."""
-    kprev: int
-    V: int
+    """What the three expand steps share once their arguments are checked (_beam_expand_setup)."""
     trie: tuple    # node, child_off, n_nodes, tok, n_children
     shape: tuple   # B, kprev, V, P, k
     out_ids: torch.Tensor      # (B, k, P + 1) int64
     out_parent: torch.Tensor   # (B, k) int32
     out_node: torch.Tensor     # (B, k) int32
-    tail: tuple    # blocked, n_blocked, allowed, n_words, G, group, stream
+    blocked: tuple   # blocked, n_blocked
+    rows: tuple      # the group table: allowed, n_words, G, group — or bias, n_bias, G, bias_group
+    stream: object
 
     def scores(self) -> torch.Tensor:
         """A (B, k) fp32 output: out_lp, out_phi or out_g."""
         return torch.empty(self.out_parent.shape, device=self.out_parent.device, dtype=torch.float32)
 
+    def wide(self, what, wide, narrow_kprev: bool = False, no_wide: str = "") -> bool:
+        """The form the step runs in — wide=None: the narrow kernel wherever its envelope holds — after refusing a
+        shape outside that form's envelope. narrow_kprev: the narrow form also needs kprev <= 1024 (the biased step);
+        no_wide: the step has no wide form, the refusal says so."""
+        _, kprev, V, _, k = self.shape
+        if wide is None:
+            wide = kprev * V > BEAM_MAX_N
+        if wide:
+            if V < 1 or V > BEAM_MAX_V or kprev > BEAM_WIDE_MAX or not 1 <= k <= BEAM_WIDE_MAX:
+                raise RqHipError(f"{what}: outside the wide kernel's envelope V <= {BEAM_MAX_V}, kprev <= "
+                                 f"{BEAM_WIDE_MAX}, 1 <= k <= {BEAM_WIDE_MAX} (kprev={kprev}, V={V}, k={k})")
+        elif V < 1 or V > BEAM_MAX_V or kprev * V > BEAM_MAX_N or (narrow_kprev and kprev > BEAM_WIDE_MAX) or \
+                not 1 <= k <= BEAM_MAX_N:
+            raise RqHipError(f"{what}: outside the supported envelope V <= {BEAM_MAX_V}, kprev * V <= {BEAM_MAX_N}, "
+                             f"{f'kprev <= {BEAM_WIDE_MAX}, ' if narrow_kprev else ''}1 <= k <= {BEAM_MAX_N} "
+                             f"(kprev={kprev}, V={V}, k={k}){no_wide}")
+        return wide
 
-def _beam_expand_setup(what, logits, k, batch, child_off, tok, node, parents, parent_lp, blocked, allowed, group, *more,
-                       lp_name="parent_lp", first_step="node, parents and parent_lp") -> _ExpandCall:
-    """The argument checks, the outputs and the trailing arguments common to the expand steps. more: the caller's own
-    tensors, checked for residence only; the envelope is the caller's to check (the wide form has its own)."""
-    require_gpu(logits, child_off, tok, node, parents, parent_lp, blocked, allowed, group, *more, what=what)
+
+def _beam_expand_setup(what, logits, k, batch, child_off, tok, node, parents, parent_lp, blocked, table, group, *more,
+                       bias=False, lp_name="parent_lp", first_step="node, parents and parent_lp") -> _ExpandCall:
+    """The argument checks, the outputs and the trailing arguments common to the expand steps. table / group: the
+    catalogue filter's allowed / group or, with `bias`, the score bias' bias / bias_group. more: the caller's own
+    tensors, checked for residence only; the envelope is checked by the caller, through _ExpandCall.wide."""
+    require_gpu(logits, child_off, tok, node, parents, parent_lp, blocked, table, group, *more, what=what)
     B = int(batch)
     if logits.dim() != 2 or B < 0 or (B and logits.shape[0] % B):
         raise RqHipError(f"{what}: logits must be (B * kprev, V)")
@@ -2539,14 +2559,18 @@ def _beam_expand_setup(what, logits, k, batch, child_off, tok, node, parents, pa
             raise RqHipError(f"{what}: blocked must be (B, n_blocked <= {BLOCKED_MAX}), got {tuple(blocked.shape)}")
         _beam_arg(blocked, torch.int32, what, "blocked")
         n_blocked = blocked.shape[1]
-    bitmap = _beam_allowed(what, B, allowed, group)
+    if bias:
+        rows = _beam_group_table(what, B, table, group, torch.float32, "bias", "bias_group",
+                                 f"n_children = {tok.numel()}", tok.numel())
+    else:
+        rows = _beam_group_table(what, B, table, group, torch.int32, "allowed", "group", "n_words")
     dev = logits.device
     return _ExpandCall(
-        kprev, V, (ptr(node), ptr(child_off), child_off.numel() - 1, ptr(tok), tok.numel()), (B, kprev, V, P, int(k)),
+        (ptr(node), ptr(child_off), child_off.numel() - 1, ptr(tok), tok.numel()), (B, kprev, V, P, int(k)),
         torch.empty((B, int(k), P + 1), device=dev, dtype=torch.int64),
         torch.empty((B, int(k)), device=dev, dtype=torch.int32),
         torch.empty((B, int(k)), device=dev, dtype=torch.int32),
-        (ptr(blocked) if n_blocked else None, n_blocked, *bitmap, stream_handle(dev)))
+        (ptr(blocked) if n_blocked else None, n_blocked), rows, stream_handle(dev))
 
 
 def beam_expand(logits: torch.Tensor, k: int, *, batch: int, child_off: torch.Tensor, tok: torch.Tensor,
@@ -2572,19 +2596,11 @@ def beam_expand(logits: torch.Tensor, k: int, *, batch: int, child_off: torch.Te
     [0, G) (-1) leaves that element unfiltered. Composes with blocked: a candidate passes both."""
     what = "beam_expand"
     c = _beam_expand_setup(what, logits, k, batch, child_off, tok, node, parents, parent_lp, blocked, allowed, group)
-    kprev, V = c.kprev, c.V
-    if wide is None:
-        wide = kprev * V > BEAM_MAX_N
-    if wide:
-        if V < 1 or V > BEAM_MAX_V or kprev > BEAM_WIDE_MAX or not 1 <= int(k) <= BEAM_WIDE_MAX:
-            raise RqHipError(f"{what}: outside the wide kernel's envelope V <= {BEAM_MAX_V}, kprev <= {BEAM_WIDE_MAX}, "
-                             f"1 <= k <= {BEAM_WIDE_MAX} (kprev={kprev}, V={V}, k={k})")
-    elif V < 1 or V > BEAM_MAX_V or kprev * V > BEAM_MAX_N or not 1 <= int(k) <= BEAM_MAX_N:
-        raise RqHipError(f"{what}: outside the supported envelope V <= {BEAM_MAX_V}, kprev * V <= {BEAM_MAX_N}, "
-                         f"1 <= k <= {BEAM_MAX_N} (kprev={kprev}, V={V}, k={k})")
+    wide = c.wide(what, wide)
     out_lp = c.scores()
     call("rq_beam_expand_wide" if wide else "rq_beam_expand", ptr(logits), float(temperature), *c.trie, ptr(parents),
-         ptr(parent_lp), *c.shape, ptr(c.out_ids), ptr(out_lp), ptr(c.out_parent), ptr(c.out_node), *c.tail)
+         ptr(parent_lp), *c.shape, ptr(c.out_ids), ptr(out_lp), ptr(c.out_parent), ptr(c.out_node), *c.blocked, *c.rows,
+         c.stream)
     return c.out_ids, out_lp, c.out_parent, c.out_node
 
 
@@ -2605,27 +2621,13 @@ def beam_expand_biased(logits: torch.Tensor, k: int, *, batch: int, child_off: t
     what = "beam_expand_biased"
     if bias is None or bias_group is None:
         raise RqHipError(f"{what}: bias and bias_group are required")
-    c = _beam_expand_setup(what, logits, k, batch, child_off, tok, node, parents, parent_lp, blocked, None, None, bias,
-                           bias_group)
-    B, kprev, V = c.shape[:3]
-    if bias.dim() != 2 or bias.shape[1] != tok.numel():
-        raise RqHipError(f"{what}: bias must be (G, n_children = {tok.numel()}), got {tuple(bias.shape)}")
-    _beam_arg(bias, torch.float32, what, "bias")
-    _beam_arg(bias_group, torch.int32, what, "bias_group", (B,))
-    if wide is None:
-        wide = kprev * V > BEAM_MAX_N
-    if wide:
-        if V < 1 or V > BEAM_MAX_V or kprev > BEAM_WIDE_MAX or not 1 <= int(k) <= BEAM_WIDE_MAX:
-            raise RqHipError(f"{what}: outside the wide kernel's envelope V <= {BEAM_MAX_V}, kprev <= {BEAM_WIDE_MAX}, "
-                             f"1 <= k <= {BEAM_WIDE_MAX} (kprev={kprev}, V={V}, k={k})")
-    elif V < 1 or V > BEAM_MAX_V or kprev * V > BEAM_MAX_N or kprev > BEAM_WIDE_MAX or not 1 <= int(k) <= BEAM_MAX_N:
-        raise RqHipError(f"{what}: outside the supported envelope V <= {BEAM_MAX_V}, kprev * V <= {BEAM_MAX_N}, "
-                         f"kprev <= {BEAM_WIDE_MAX}, 1 <= k <= {BEAM_MAX_N} (kprev={kprev}, V={V}, k={k})")
+    c = _beam_expand_setup(what, logits, k, batch, child_off, tok, node, parents, parent_lp, blocked, bias, bias_group,
+                           bias=True)
+    wide = c.wide(what, wide, narrow_kprev=True)
     out_lp, out_score = c.scores(), c.scores()
-    G, n_bias = bias.shape
     call("rq_beam_expand_wide_biased" if wide else "rq_beam_expand_biased", ptr(logits), float(temperature), *c.trie,
          ptr(parents), ptr(parent_lp), *c.shape, ptr(c.out_ids), ptr(out_lp), ptr(out_score), ptr(c.out_parent),
-         ptr(c.out_node), *c.tail[:2], ptr(bias) if G * n_bias else None, n_bias, G, ptr(bias_group), c.tail[-1])
+         ptr(c.out_node), *c.blocked, *c.rows, c.stream)
     return c.out_ids, out_lp, out_score, c.out_parent, c.out_node
 
 
@@ -2651,23 +2653,32 @@ def beam_expand_sampled(logits: torch.Tensor, k: int, *, batch: int, child_off: 
     c = _beam_expand_setup(what, logits, k, batch, child_off, tok, node, parents, parent_phi, blocked, allowed, group,
                            noise, parent_g, lp_name="parent_phi",
                            first_step="node, parents, parent_phi and parent_g")
-    B, kprev, V = c.shape[:3]
+    B, kprev = c.shape[:2]
     if noise is None:
         raise RqHipError(f"{what}: noise (Exponential(1) draws, the shape of logits) is required")
     _beam_arg(noise, torch.float32, what, "noise", tuple(logits.shape))
     if parent_g is not None:
         _beam_arg(parent_g, torch.float32, what, "parent_g", (B, kprev))
-    if V < 1 or V > BEAM_MAX_V or kprev * V > BEAM_MAX_N or not 1 <= int(k) <= BEAM_MAX_N:
-        raise RqHipError(f"{what}: outside the supported envelope V <= {BEAM_MAX_V}, kprev * V <= {BEAM_MAX_N}, "
-                         f"1 <= k <= {BEAM_MAX_N} (kprev={kprev}, V={V}, k={k}); the sampled step has no wide form")
+    c.wide(what, False, no_wide="; the sampled step has no wide form")
     out_phi, out_g = c.scores(), c.scores()
     call("rq_beam_expand_sampled", ptr(logits), ptr(noise), float(temperature), *c.trie, ptr(parents), ptr(parent_phi),
-         ptr(parent_g), *c.shape, ptr(c.out_ids), ptr(out_phi), ptr(out_g), ptr(c.out_parent), ptr(c.out_node), *c.tail)
+         ptr(parent_g), *c.shape, ptr(c.out_ids), ptr(out_phi), ptr(out_g), ptr(c.out_parent), ptr(c.out_node),
+         *c.blocked, *c.rows, c.stream)
     return c.out_ids, out_phi, out_g, c.out_parent, c.out_node
 
 
 BEAM_MAX_T = 8   # RQ_BEAM_MAX_T
 BLOCKED_MAX = 1024   # kBlockedMax (csrc/beam.hip): widest exclusion list / blocked row
+
+
+def _leaf_ancestors(what, leaf_anc) -> tuple:
+    """(n_leaves, the D-pointer array) of trie_index()'s leaf_anc: D int32 tensors (n_leaves) — what the three trie
+    builders take."""
+    import ctypes
+    n_leaves = leaf_anc[0].numel()
+    for q, anc in enumerate(leaf_anc):
+        _beam_arg(anc, torch.int32, what, f"leaf_anc[{q}]", (n_leaves,))
+    return n_leaves, (ctypes.c_void_p * len(leaf_anc))(*[t.data_ptr() for t in leaf_anc])
 
 
 def trie_blocked_nodes(items: torch.Tensor, item_leaf: torch.Tensor, leaf_anc, leaf_count) -> torch.Tensor:
@@ -2691,18 +2702,44 @@ def trie_blocked_nodes(items: torch.Tensor, item_leaf: torch.Tensor, leaf_anc, l
     if item_leaf.dim() != 1:
         raise RqHipError(f"{what}: item_leaf must be 1-D")
     _beam_arg(item_leaf, torch.int32, what, "item_leaf")
-    n_leaves = leaf_anc[0].numel()
+    n_leaves, anc = _leaf_ancestors(what, leaf_anc)
     for q in range(D):
-        _beam_arg(leaf_anc[q], torch.int32, what, f"leaf_anc[{q}]", (n_leaves,))
         if leaf_count[q].dim() != 1:
             raise RqHipError(f"{what}: leaf_count[{q}] must be 1-D")
         _beam_arg(leaf_count[q], torch.int32, what, f"leaf_count[{q}]")
     out = torch.empty((D, B, H), device=items.device, dtype=torch.int32)
-    P = ctypes.c_void_p * D
-    call("rq_trie_blocked_nodes", ptr(items), B, H, ptr(item_leaf), item_leaf.numel(), n_leaves,
-         P(*[t.data_ptr() for t in leaf_anc]), P(*[t.data_ptr() for t in leaf_count]),
+    call("rq_trie_blocked_nodes", ptr(items), B, H, ptr(item_leaf), item_leaf.numel(), n_leaves, anc,
+         (ctypes.c_void_p * D)(*[t.data_ptr() for t in leaf_count]),
          (ctypes.c_int64 * D)(*[t.numel() for t in leaf_count]), D, ptr(out), stream_handle(items.device))
     return out
+
+
+def _trie_group_tables(what, fn, table, dtype, name, item_leaf, leaf_anc, n_nodes, out_dtype, width) -> tuple:
+    """trie_allowed_nodes and trie_bias_nodes: a per-group table (G, N) of `dtype` over the corpus reduced onto the trie
+    by entry point `fn` — (levels, leaf_item): D zeroed `out_dtype` tensors (G, width(n_q)) that `fn` fills, and
+    (G, n_leaves) int64."""
+    import ctypes
+    leaf_anc, n_nodes = list(leaf_anc), [int(n) for n in n_nodes]
+    require_gpu(table, item_leaf, *leaf_anc, what=what)
+    D = len(leaf_anc)
+    if table.dim() != 2:
+        raise RqHipError(f"{what}: {name} must be (G, N), got {tuple(table.shape)}")
+    G, N = table.shape
+    if not 1 <= D <= BEAM_MAX_T or len(n_nodes) != D:
+        raise RqHipError(f"{what}: outside the supported envelope 1 <= D <= {BEAM_MAX_T} with D level sizes (D={D}, "
+                         f"{len(n_nodes)} sizes)")
+    _beam_arg(table, dtype, what, name)
+    _beam_arg(item_leaf, torch.int32, what, "item_leaf", (N,))
+    n_leaves, anc = _leaf_ancestors(what, leaf_anc)
+    for q in range(D):
+        if n_nodes[q] < 0:
+            raise RqHipError(f"{what}: n_nodes[{q}] = {n_nodes[q]}")
+    dev = table.device
+    levels = tuple(torch.zeros((G, width(n)), device=dev, dtype=out_dtype) for n in n_nodes)
+    leaf_item = torch.zeros((G, n_leaves), device=dev, dtype=torch.int64)
+    call(fn, ptr(table), G, N, ptr(item_leaf), n_leaves, anc, (ctypes.c_int64 * D)(*n_nodes), D,
+         (ctypes.c_void_p * D)(*[t.data_ptr() for t in levels]), ptr(leaf_item), stream_handle(dev))
+    return levels, leaf_item
 
 
 def trie_allowed_nodes(mask: torch.Tensor, item_leaf: torch.Tensor, leaf_anc, n_nodes):
@@ -2712,31 +2749,8 @@ def trie_allowed_nodes(mask: torch.Tensor, item_leaf: torch.Tensor, leaf_anc, n_
     corpus index whose row is that leaf, -1 if none. mask (G, N) bool; item_leaf (N) int32 and leaf_anc, D int32 tensors
     (n_leaves) — SemanticIdTokenizer.trie_index(); n_nodes: the D level sizes n_q. Two launches, no host read; the
     reductions are bit OR and index MIN, so the result does not depend on the order."""
-    import ctypes
-    what = "trie_allowed_nodes"
-    leaf_anc, n_nodes = list(leaf_anc), [int(n) for n in n_nodes]
-    require_gpu(mask, item_leaf, *leaf_anc, what=what)
-    D = len(leaf_anc)
-    if mask.dim() != 2:
-        raise RqHipError(f"{what}: mask must be (G, N), got {tuple(mask.shape)}")
-    G, N = mask.shape
-    if not 1 <= D <= BEAM_MAX_T or len(n_nodes) != D:
-        raise RqHipError(f"{what}: outside the supported envelope 1 <= D <= {BEAM_MAX_T} with D level sizes (D={D}, "
-                         f"{len(n_nodes)} sizes)")
-    _beam_arg(mask, torch.bool, what, "mask")
-    _beam_arg(item_leaf, torch.int32, what, "item_leaf", (N,))
-    n_leaves = leaf_anc[0].numel()
-    for q in range(D):
-        _beam_arg(leaf_anc[q], torch.int32, what, f"leaf_anc[{q}]", (n_leaves,))
-        if n_nodes[q] < 0:
-            raise RqHipError(f"{what}: n_nodes[{q}] = {n_nodes[q]}")
-    dev = mask.device
-    bits = tuple(torch.zeros((G, (n + 31) // 32), device=dev, dtype=torch.int32) for n in n_nodes)
-    leaf_item = torch.zeros((G, n_leaves), device=dev, dtype=torch.int64)
-    P = ctypes.c_void_p * D
-    call("rq_trie_allowed_nodes", ptr(mask), G, N, ptr(item_leaf), n_leaves, P(*[t.data_ptr() for t in leaf_anc]),
-         (ctypes.c_int64 * D)(*n_nodes), D, P(*[t.data_ptr() for t in bits]), ptr(leaf_item), stream_handle(dev))
-    return bits, leaf_item
+    return _trie_group_tables("trie_allowed_nodes", "rq_trie_allowed_nodes", mask, torch.bool, "mask", item_leaf,
+                              leaf_anc, n_nodes, torch.int32, lambda n: (n + 31) // 32)
 
 
 def trie_bias_nodes(bias: torch.Tensor, item_leaf: torch.Tensor, leaf_anc, n_nodes):
@@ -2747,31 +2761,8 @@ def trie_bias_nodes(bias: torch.Tensor, item_leaf: torch.Tensor, leaf_anc, n_nod
     -0.0 as +0.0. item_leaf (N) int32 and leaf_anc, D int32 tensors (n_leaves) — SemanticIdTokenizer.trie_index();
     n_nodes: the D level sizes n_q. Two launches, no host read; the reductions are integer maxima (no float atomic), so
     two runs give the same bits."""
-    import ctypes
-    what = "trie_bias_nodes"
-    leaf_anc, n_nodes = list(leaf_anc), [int(n) for n in n_nodes]
-    require_gpu(bias, item_leaf, *leaf_anc, what=what)
-    D = len(leaf_anc)
-    if bias.dim() != 2:
-        raise RqHipError(f"{what}: bias must be (G, N), got {tuple(bias.shape)}")
-    G, N = bias.shape
-    if not 1 <= D <= BEAM_MAX_T or len(n_nodes) != D:
-        raise RqHipError(f"{what}: outside the supported envelope 1 <= D <= {BEAM_MAX_T} with D level sizes (D={D}, "
-                         f"{len(n_nodes)} sizes)")
-    _beam_arg(bias, torch.float32, what, "bias")
-    _beam_arg(item_leaf, torch.int32, what, "item_leaf", (N,))
-    n_leaves = leaf_anc[0].numel()
-    for q in range(D):
-        _beam_arg(leaf_anc[q], torch.int32, what, f"leaf_anc[{q}]", (n_leaves,))
-        if n_nodes[q] < 0:
-            raise RqHipError(f"{what}: n_nodes[{q}] = {n_nodes[q]}")
-    dev = bias.device
-    upper = tuple(torch.zeros((G, n), device=dev, dtype=torch.float32) for n in n_nodes)
-    leaf_item = torch.zeros((G, n_leaves), device=dev, dtype=torch.int64)
-    P = ctypes.c_void_p * D
-    call("rq_trie_bias_nodes", ptr(bias), G, N, ptr(item_leaf), n_leaves, P(*[t.data_ptr() for t in leaf_anc]),
-         (ctypes.c_int64 * D)(*n_nodes), D, P(*[t.data_ptr() for t in upper]), ptr(leaf_item), stream_handle(dev))
-    return upper, leaf_item
+    return _trie_group_tables("trie_bias_nodes", "rq_trie_bias_nodes", bias, torch.float32, "bias", item_leaf,
+                              leaf_anc, n_nodes, torch.float32, lambda n: n)
 
 
 def beam_self_attention(q: torch.Tensor, kv_steps, anc: torch.Tensor, num_heads: int, scale: float = None):
