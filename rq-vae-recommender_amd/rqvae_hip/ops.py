@@ -399,41 +399,55 @@ def _operand_tensors(t):
     return [t.hi, t.lo] if isinstance(t, Split) else [t]
 
 
-def _wgrad_into(weight, g, g_kc: bool, inp, inp_kc: bool, O: int, I: int, rows: int):
-    """dW = g^T inp for `weight` (split-bf16 GEMM): added straight into weight's flat gradient bucket
-    when dp.GradBuckets owns one (returns None: autograd must not accumulate it again), else a new
-    (O, I) tensor for autograd. (A side stream for these was measured slower inside the captured steps:
-    Amazon 6.16 -> 6.38-6.43 ms, profiles/r03 — one stream it is.)"""
+def _wgrad_kw(weight, g, inp, rows: int, flags: int = None) -> dict:
+    """gemm_x3 keywords of dW = g^T inp for `weight` (g, inp: Split, or fp32 — flattened to 2-D and made
+    contiguous here, where the weight gradient's launch is about to be issued): added straight into weight's flat
+    gradient bucket when dp.GradBuckets owns one. The one place that asks dp.direct_grad, so once per weight per
+    backward; which launch carries the keywords is the caller's choice (_linear_bwd: alone or paired;
+    _mlp_backward: a grouped launch, with `flags` = its split count)."""
     from . import dp
+    O, I = weight.shape
+    kw = dict(a=g if isinstance(g, Split) else g.reshape(-1, O).contiguous(), a_kcontig=False,
+              b=inp if isinstance(inp, Split) else inp.reshape(-1, I).contiguous(), b_kcontig=False, M=O, N=I, K=rows)
+    if flags is not None:
+        kw["flags"] = flags
     sink = dp.direct_grad(weight)
-    if sink is None:
-        return gemm_x3(g, g_kc, inp, inp_kc, O, I, rows)
-    gemm_x3(g, g_kc, inp, inp_kc, O, I, rows, out=sink, accumulate=True, defer=dp.defer_ok(weight))
-    dp.direct_grad_done(weight)
-    return None
-
-
-def _wgrad_spec(weight, g, g_kc: bool, inp, inp_kc: bool, O: int, I: int, rows: int):
-    """gemm_x3 keywords of dW = g^T inp for a paired launch with the data gradient (gemm_x3_pair), added
-    straight into weight's flat gradient bucket when dp.GradBuckets owns one — or None when the GEMM
-    policy asks for separate launches (GEMM_NO_PAIR: _wgrad_into)."""
-    from . import dp
-    if not _pairing():
-        return None
-    sink = dp.direct_grad(weight)
-    spec = dict(a=g, a_kcontig=g_kc, b=inp, b_kcontig=inp_kc, M=O, N=I, K=rows)
     if sink is not None:
-        spec.update(out=sink, accumulate=True, defer=dp.defer_ok(weight))
-    return spec
+        kw.update(out=sink, accumulate=True, defer=dp.defer_ok(weight))
+    return kw
 
 
-def _wgrad_result(weight, spec, result):
-    """What autograd gets for weight after a paired launch: None when the gradient went into its bucket."""
-    if spec.get("accumulate"):
+def _wgrad_result(weight, kw: dict, result):
+    """What autograd gets for weight after the launch of _wgrad_kw's keywords: None when the gradient went into
+    its bucket (autograd must not accumulate it again)."""
+    if kw.get("accumulate"):
         from . import dp
         dp.direct_grad_done(weight)
         return None
     return result
+
+
+def _wgrad_into(weight, g, inp, rows: int):
+    """dW = g^T inp in a launch of its own. (A side stream for these was measured slower inside the captured
+    steps: Amazon 6.16 -> 6.38-6.43 ms, profiles/r03 — one stream it is.)"""
+    kw = _wgrad_kw(weight, g, inp, rows)
+    return _wgrad_result(weight, kw, gemm_x3(**kw))
+
+
+def _linear_bwd(weight, wsp, g, inp, rows: int, need_x: bool, need_w: bool, pair: bool = True, **dgrad):
+    """The backward of one bias-free layer y = inp W^T with W's split planes wsp, g and inp fp32 or Split:
+    (data-gradient result or None, dW or None — None too when it went into its bucket). `dgrad`: the data
+    gradient's epilogue keywords (the chain's EPI_SILU_BWD, Z, p, seed). Both wanted: ONE paired launch, unless
+    the caller (`pair`) or the GEMM policy (GEMM_NO_PAIR) asks for separate ones; else the data gradient, then
+    the weight gradient, one launch each."""
+    O, I = weight.shape
+    dspec = dict(a=g, a_kcontig=True, b=wsp, b_kcontig=False, M=rows, N=I, K=O, **dgrad)
+    if need_x and need_w and pair and _pairing():
+        kw = _wgrad_kw(weight, g, inp, rows)
+        gx, dW = _bwd_pair(dspec, kw)
+        return gx, _wgrad_result(weight, kw, dW)
+    gx = gemm_x3(**dspec) if need_x else None
+    return gx, (_wgrad_into(weight, g, inp, rows) if need_w else None)
 
 
 # Kernel policy of the split-bf16 GEMM calls (rq_gemm_desc.flags, RQ_GEMM_* in include/rqvae_hip.h; 0 = the
@@ -888,10 +902,9 @@ def _mlp_forward(a, wsp, rows: int, p: float, seeds, residual=None, p_out: float
 
 def _mlp_backward(gcur, x_in, wsp, zs, hs, rows: int, p: float, seeds, need_w, need_x: bool, weights):
     """The chain's backward from the output grad gcur (fp32 or Split): (dx fp32 or None, [dW]); a
-    weight grad added straight into its flat gradient bucket comes back as None (_wgrad_into)."""
+    weight grad added straight into its flat gradient bucket comes back as None (_wgrad_result)."""
     n = len(wsp)
     dws = [None] * n
-    dx = None
     # the weight gradients that share one grouped launch (gemm_x3_group) under group_wgrads() or
     # group_splits(): decided from the shapes alone, so a gradient returned to autograd and one added into
     # its flat bucket take the same path
@@ -903,45 +916,19 @@ def _mlp_backward(gcur, x_in, wsp, zs, hs, rows: int, p: float, seeds, need_w, n
         gs = gemm_group_choice([tuple(wsp[i].hi.shape) for i in cand], rows)
         grouped = {i: s_ for i, s_ in zip(cand, gs) if s_ > 0}
     for i in reversed(range(n)):
-        O, I = wsp[i].hi.shape
-        inp = x_in if i == 0 else hs[i - 1]
+        inp = x_in if i == 0 else hs[i - 1]   # dW_i = g^T h_{i-1}
+        own_w = need_w[i] and i not in grouped
         if i in grouped:   # its data gradient alone; the weight gradient waits for the group's last member
-            from . import dp
-            sink = dp.direct_grad(weights[i])
-            spec = dict(a=gcur, a_kcontig=False, b=inp, b_kcontig=False, M=O, N=I, K=rows,
-                        flags=_GEMM_POLICY["flags"] | gemm_split(grouped[i]))
-            if sink is not None:
-                spec.update(out=sink, accumulate=True, defer=dp.defer_ok(weights[i]))
-            gspecs.append((i, spec))
+            gspecs.append((i, _wgrad_kw(weights[i], gcur, inp, rows,
+                                        flags=_GEMM_POLICY["flags"] | gemm_split(grouped[i]))))
             if len(gspecs) == len(grouped):
                 for (j, sp), res in zip(gspecs, gemm_x3_group([sp for _, sp in gspecs])):
                     dws[j] = _wgrad_result(weights[j], sp, res)
-            if i > 0:
-                gcur = gemm_x3(a=gcur, a_kcontig=True, b=wsp[i], b_kcontig=False, M=rows, N=I, K=O,
-                               epilogue=EPI_SILU_BWD, Z=zs[i - 1], p=p, seed=seeds[i - 1])
-            elif need_x:
-                dx = gemm_x3(a=gcur, a_kcontig=True, b=wsp[0], b_kcontig=False, M=rows, N=I, K=O)
-            continue
-        if i > 0:
-            dspec = dict(a=gcur, a_kcontig=True, b=wsp[i], b_kcontig=False, M=rows, N=I, K=O, epilogue=EPI_SILU_BWD,
-                         Z=zs[i - 1], p=p, seed=seeds[i - 1])
-        elif need_x:
-            dspec = dict(a=gcur, a_kcontig=True, b=wsp[0], b_kcontig=False, M=rows, N=I, K=O)
-        else:
-            dspec = None
-        wspec = _wgrad_spec(weights[i], gcur, False, inp, False, O, I, rows) if need_w[i] else None
-        if dspec is not None and wspec is not None:   # dW = g^T h_{i-1} and the data grad in one launch
-            gnext, wres = _bwd_pair(dspec, wspec)
-            dws[i] = _wgrad_result(weights[i], wspec, wres)
-        else:
-            if need_w[i]:
-                dws[i] = _wgrad_into(weights[i], gcur, False, inp, False, O, I, rows)   # dW = g^T h_{i-1}
-            gnext = gemm_x3(**dspec) if dspec is not None else None
-        if i > 0:
-            gcur = gnext
-        elif need_x:
-            dx = gnext
-    return dx, dws
+        dgrad = dict(epilogue=EPI_SILU_BWD, Z=zs[i - 1], p=p, seed=seeds[i - 1]) if i > 0 else {}
+        gcur, dW = _linear_bwd(weights[i], wsp[i], gcur, inp, rows, i > 0 or need_x, own_w, **dgrad)
+        if own_w:
+            dws[i] = dW
+    return gcur, dws   # after layer 0 gcur is dx (None when not wanted)
 
 
 def _mlp_save(ctx, x_in, wsp, zs, hs):
@@ -950,24 +937,43 @@ def _mlp_save(ctx, x_in, wsp, zs, hs):
     return [*xs, *[t for s_ in wsp for t in s_], *zs, *[t for h in hs for t in h]]
 
 
-def _mlp_load(ctx, n: int, saved):
+def _mlp_load(ctx):
+    saved, n = ctx.saved_tensors, ctx.n
     k = 2 if ctx.x_split else 1
     x_in = Split(saved[0], saved[1]) if ctx.x_split else saved[0]
     wsp = [Split(saved[k + 2 * i], saved[k + 1 + 2 * i]) for i in range(n)]
     zs = list(saved[k + 2 * n:k + 2 * n + (n - 1)])
     hb = k + 2 * n + (n - 1)
     hs = [Split(saved[hb + 2 * i], saved[hb + 2 * i + 1]) for i in range(n - 1)]
-    return x_in, wsp, zs, hs, hb + 2 * (n - 1)
+    return x_in, wsp, zs, hs
 
 
-def _mlp_prologue(x, p: float, weights):
+def _mlp_prologue(ctx, x, p: float, weights):
+    """What every chain Function's forward starts with: the 2-D input (split up front where _presplit_input says
+    so), the weights' split planes, the hidden layers' dropout keys — and the bookkeeping its backward
+    (_mlp_epilogue) reads from ctx."""
     n = len(weights)
     x2 = x.reshape(-1, weights[0].shape[1]).contiguous()
     rows = x2.shape[0]
     wsp = split_weights(weights)
     seeds = [next_seed() if p > 0 else 0 for _ in range(n - 1)]
     x_in = split_bf16x3(x2) if _presplit_input(rows, weights, n) else x2
+    ctx.n, ctx.p, ctx.seeds, ctx.xshape, ctx.weights = n, float(p), seeds, x.shape, weights
     return x_in, rows, wsp, seeds
+
+
+def _mlp_epilogue(ctx, g, first_weight: int):
+    """What every chain Function's backward ends with: the chain's backward (_mlp_backward) from the output
+    grad g (fp32 of any shape, or Split) — (dx in the input's shape or None, [dW]). `first_weight`: where the
+    weights start among the Function's inputs."""
+    x_in, wsp, zs, hs = _mlp_load(ctx)
+    rows = (x_in.hi if ctx.x_split else x_in).shape[0]
+    if not isinstance(g, Split):
+        g = g.reshape(rows, -1).contiguous()
+    dx, dws = _mlp_backward(g, x_in, wsp, zs, hs, rows, ctx.p, ctx.seeds, ctx.needs_input_grad[first_weight:],
+                            ctx.needs_input_grad[0], ctx.weights)
+    ctx.weights = None
+    return (None if dx is None else dx.view(ctx.xshape)), dws
 
 
 class MLPFunction(torch.autograd.Function):
@@ -982,21 +988,15 @@ class MLPFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, p: float, *weights):
-        x_in, rows, wsp, seeds = _mlp_prologue(x, p, weights)
+        x_in, rows, wsp, seeds = _mlp_prologue(ctx, x, p, weights)
         out, zs, hs = _mlp_forward(x_in, wsp, rows, p, seeds)
-        ctx.n, ctx.p, ctx.seeds, ctx.xshape, ctx.weights = len(weights), float(p), seeds, x.shape, weights
         ctx.save_for_backward(*_mlp_save(ctx, x_in, wsp, zs, hs))
         return out.view(*x.shape[:-1], weights[-1].shape[0])
 
     @staticmethod
     def backward(ctx, g):
-        x_in, wsp, zs, hs, _ = _mlp_load(ctx, ctx.n, ctx.saved_tensors)
-        rows = (x_in.hi if ctx.x_split else x_in).shape[0]
-        gcur = g.reshape(rows, -1).contiguous()
-        dx, dws = _mlp_backward(gcur, x_in, wsp, zs, hs, rows, ctx.p, ctx.seeds, ctx.needs_input_grad[2:],
-                                ctx.needs_input_grad[0], ctx.weights)
-        ctx.weights = None
-        return (None if dx is None else dx.view(ctx.xshape), None, *dws)
+        dx, dws = _mlp_epilogue(ctx, g, 2)
+        return (dx, None, *dws)
 
 
 def mlp_chain(x: torch.Tensor, weights, p: float = 0.0) -> torch.Tensor:
@@ -1012,27 +1012,21 @@ class MLPResidualFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, h, p: float, p_out: float, *weights):
-        x_in, rows, wsp, seeds = _mlp_prologue(x, p, weights)
+        x_in, rows, wsp, seeds = _mlp_prologue(ctx, x, p, weights)
         seed_out = next_seed()
         out, zs, hs = _mlp_forward(x_in, wsp, rows, p, seeds, residual=h.reshape(rows, -1).contiguous(),
                                    p_out=p_out, seed_out=seed_out)
-        ctx.n, ctx.p, ctx.seeds, ctx.xshape, ctx.weights = len(weights), float(p), seeds, x.shape, weights
         ctx.p_out, ctx.seed_out = float(p_out), seed_out
         ctx.save_for_backward(*_mlp_save(ctx, x_in, wsp, zs, hs))
         return out.view(*x.shape[:-1], weights[-1].shape[0])
 
     @staticmethod
     def backward(ctx, g):
-        x_in, wsp, zs, hs, _ = _mlp_load(ctx, ctx.n, ctx.saved_tensors)
-        rows = (x_in.hi if ctx.x_split else x_in).shape[0]
-        g2 = g.reshape(rows, -1).contiguous()
+        g2 = g.reshape(-1, g.shape[-1]).contiguous()
         gy = torch.empty_like(g2)
         call("rq_dropout_bwd", ptr(g2), g2.numel(), ctx.p_out, ctx.seed_out, ptr(gy), stream_handle(g2.device))
-        dx, dws = _mlp_backward(gy, x_in, wsp, zs, hs, rows, ctx.p, ctx.seeds, ctx.needs_input_grad[4:],
-                                ctx.needs_input_grad[0], ctx.weights)
-        ctx.weights = None
-        gh = g if ctx.needs_input_grad[1] else None
-        return (None if dx is None else dx.view(ctx.xshape), gh, None, None, *dws)
+        dx, dws = _mlp_epilogue(ctx, gy, 4)
+        return (dx, g if ctx.needs_input_grad[1] else None, None, None, *dws)
 
 
 def mlp_chain_residual(x: torch.Tensor, weights, p: float, h: torch.Tensor, p_out: float) -> torch.Tensor:
@@ -1052,7 +1046,7 @@ class MLPL2ReconFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, e, x, p: float, grad_mode: bool, *weights):
-        x_in, rows, wsp, seeds = _mlp_prologue(e, p, weights)
+        x_in, rows, wsp, seeds = _mlp_prologue(ctx, e, p, weights)
         pre, zs, hs = _mlp_forward(x_in, wsp, rows, p, seeds)
         x2 = x.reshape(rows, -1).contiguous()
         C = pre.shape[1]
@@ -1069,14 +1063,12 @@ class MLPL2ReconFunction(torch.autograd.Function):
                  ptr(ctx.g.hi), ptr(ctx.g.lo), stream_handle(pre.device))
         else:
             call("rq_l2norm_recon_fwd", ptr(pre), ptr(x2), rows, C, ptr(recon), ptr(norms), stream_handle(pre.device))
-        ctx.n, ctx.p, ctx.seeds, ctx.eshape, ctx.weights = len(weights), float(p), seeds, e.shape, weights
         ctx.save_for_backward(*_mlp_save(ctx, x_in, wsp, zs, hs), pre, x2, norms)
         return recon.view(e.shape[:-1])
 
     @staticmethod
     def backward(ctx, g_recon):
-        x_in, wsp, zs, hs, k = _mlp_load(ctx, ctx.n, ctx.saved_tensors)
-        pre, x2, norms = ctx.saved_tensors[k:k + 3]
+        pre, x2, norms = ctx.saved_tensors[-3:]
         rows, C = pre.shape
         g_recon = g_recon.reshape(rows)
         if ctx.g is not None:   # the forward's planes, rows with another g_recon recomputed
@@ -1090,10 +1082,8 @@ class MLPL2ReconFunction(torch.autograd.Function):
                       torch.empty((rows, C), device=pre.device, dtype=torch.bfloat16))
             call("rq_l2norm_recon_bwd_split", ptr(pre), ptr(x2), ptr(norms), ptr(g_recon.contiguous()), rows, C,
                  ptr(g.hi), ptr(g.lo), stream_handle(pre.device))
-        de, dws = _mlp_backward(g, x_in, wsp, zs, hs, rows, ctx.p, ctx.seeds, ctx.needs_input_grad[4:],
-                                ctx.needs_input_grad[0], ctx.weights)
-        ctx.weights = None
-        return (None if de is None else de.view(ctx.eshape), None, None, None, *dws)
+        de, dws = _mlp_epilogue(ctx, g, 4)
+        return (de, None, None, None, *dws)
 
 
 def mlp_l2norm_recon(e: torch.Tensor, x: torch.Tensor, weights, p: float = 0.0) -> torch.Tensor:
@@ -1135,54 +1125,36 @@ class LinearFunction(torch.autograd.Function):
         O, I = weight.shape
         g2 = g.reshape(-1, O)
         gx = dW = db = None
+        need_x, need_w = ctx.needs_input_grad[:2]
+        need_b = ctx.has_bias and ctx.needs_input_grad[2]
         high = ctx.high and g2.shape[0] > 0
-        if (high and ctx.wsp is not None and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and
-                not ctx.has_bias):
-            wspec = _wgrad_spec(ctx.weight, g2.contiguous(), False, x.reshape(-1, I).contiguous(), False, O, I,
-                                g2.shape[0])
-            if wspec is not None:   # data and weight gradient in one launch
-                gx, wres = _bwd_pair(dict(a=g2, a_kcontig=True, b=ctx.wsp, b_kcontig=False, M=g2.shape[0], N=I,
-                                             K=O), wspec)
-                dW = _wgrad_result(ctx.weight, wspec, wres)
-                ctx.wsp = ctx.weight = None
-                return gx.view(x.shape), dW, None
-        if ctx.needs_input_grad[0]:
-            if high and ctx.wsp is not None:
-                gx = gemm_x3(g2, True, ctx.wsp, False, g2.shape[0], I, O).view(x.shape)
-            else:
-                gx = (linear_dgrad_high(g2, weight) if high else g2 @ weight).view(x.shape)
-        ctx.wsp = None
-        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            x2 = x.reshape(-1, I)
-            if high:
-                if ctx.needs_input_grad[1]:
-                    dW = _wgrad_into(ctx.weight, g2.contiguous(), False, x2.contiguous(), False, O, I, g2.shape[0])
-                db = g2.sum(0) if ctx.has_bias else None
-            elif _wgrad_choice(g2, x2, ctx.has_bias) == "hip":
-                dW, db = linear_wgrad(g2, x2, ctx.has_bias)
-            else:   # library GEMM: small row counts, or measured faster for this shape
-                dW = g2.t() @ x2
-                db = g2.sum(0) if ctx.has_bias else None
-        ctx.weight = None
-        return gx, dW, db if ctx.has_bias else None
+        if high and ctx.wsp is not None:   # a biased Linear keeps its two launches (pairing would re-split dW)
+            gx, dW = _linear_bwd(ctx.weight, ctx.wsp, g2, x, g2.shape[0], need_x, need_w, pair=not ctx.has_bias)
+            db = g2.sum(0) if ctx.has_bias and (need_w or need_b) else None
+        else:
+            if need_x:
+                gx = linear_dgrad_high(g2, weight) if high else g2 @ weight
+            if need_w or need_b:
+                x2 = x.reshape(-1, I)
+                if high:
+                    dW = _wgrad_into(ctx.weight, g2, x2, g2.shape[0]) if need_w else None
+                    db = g2.sum(0) if ctx.has_bias else None
+                elif _wgrad_choice(g2, x2, ctx.has_bias) == "hip":
+                    dW, db = linear_wgrad(g2, x2, ctx.has_bias)
+                else:   # library GEMM: small row counts, or measured faster for this shape
+                    dW = g2.t() @ x2
+                    db = g2.sum(0) if ctx.has_bias else None
+        ctx.wsp = ctx.weight = None
+        return (None if gx is None else gx.view(x.shape)), dW, db if ctx.has_bias else None
 
 
 def _linear_bwd_high(x, g, weight, wsp, need_x: bool, need_w: bool):
-    """(gx, dW) of y = x W^T at 'high' with W's split planes wsp: data and weight gradient in one paired launch
-    where both are needed (the weight gradient straight into its bucket: dW None), else one each."""
+    """(gx in x's shape, dW) of y = x W^T at 'high' with W's split planes wsp: _linear_bwd around the reshapes.
+    (There are rows: linear_pair_supported asks for x.numel() > 0.)"""
     O, I = weight.shape
     g2 = g.reshape(-1, O)
-    x2 = x.reshape(-1, I)
-    if g2.shape[0] == 0:
-        return (torch.zeros_like(x) if need_x else None), (torch.zeros_like(weight) if need_w else None)
-    if need_x and need_w:
-        wspec = _wgrad_spec(weight, g2.contiguous(), False, x2.contiguous(), False, O, I, g2.shape[0])
-        if wspec is not None:
-            gx, wres = _bwd_pair(dict(a=g2, a_kcontig=True, b=wsp, b_kcontig=False, M=g2.shape[0], N=I, K=O), wspec)
-            return gx.view(x.shape), _wgrad_result(weight, wspec, wres)
-    gx = gemm_x3(g2, True, wsp, False, g2.shape[0], I, O).view(x.shape) if need_x else None
-    dW = _wgrad_into(weight, g2.contiguous(), False, x2.contiguous(), False, O, I, g2.shape[0]) if need_w else None
-    return gx, dW
+    gx, dW = _linear_bwd(weight, wsp, g2, x.reshape(-1, I), g2.shape[0], need_x, need_w)
+    return (None if gx is None else gx.view(x.shape)), dW
 
 
 class LinearPairFunction(torch.autograd.Function):
@@ -1247,28 +1219,10 @@ class LinearAddFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, weight = ctx.saved_tensors
-        O, I = weight.shape
-        g2 = g.reshape(-1, O)
-        gx = dW = None
-        wspec = None
-        if ctx.needs_input_grad[0] and ctx.needs_input_grad[1]:
-            wspec = _wgrad_spec(ctx.weight, g2.contiguous(), False, x.reshape(-1, I).contiguous(), False, O, I,
-                                g2.shape[0])
-        if wspec is not None:   # data and weight gradient in one launch
-            gx, wres = _bwd_pair(dict(a=g2, a_kcontig=True, b=ctx.wsp, b_kcontig=False, M=g2.shape[0], N=I, K=O),
-                                    wspec)
-            gx = gx.view(x.shape)
-            dW = _wgrad_result(ctx.weight, wspec, wres)
-            ctx.wsp = ctx.weight = None
-            return gx, dW, g if ctx.needs_input_grad[2] else None
-        if ctx.needs_input_grad[0]:
-            gx = gemm_x3(g2, True, ctx.wsp, False, g2.shape[0], I, O).view(x.shape)
-        ctx.wsp = None
-        if ctx.needs_input_grad[1]:
-            dW = _wgrad_into(ctx.weight, g2.contiguous(), False, x.reshape(-1, I).contiguous(), False, O, I,
-                             g2.shape[0])
-        ctx.weight = None
-        return gx, dW, g if ctx.needs_input_grad[2] else None
+        g2 = g.reshape(-1, weight.shape[0])
+        gx, dW = _linear_bwd(ctx.weight, ctx.wsp, g2, x, g2.shape[0], *ctx.needs_input_grad[:2])
+        ctx.wsp = ctx.weight = None
+        return (None if gx is None else gx.view(x.shape)), dW, g if ctx.needs_input_grad[2] else None
 
 
 def linear_add(x: torch.Tensor, weight: torch.Tensor, r: torch.Tensor) -> torch.Tensor:
